@@ -2,18 +2,23 @@
 """bench.py — whole-job throughput of the viewport -> tile -> entropy hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload config3|config2|config4|config5]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (one C-ABI call: samples resident in HBM -> per-frame
 entropy + nearest-tile assignments in HBM) over one synthetic video per GPU.  N > 1 is launched
 by torch.distributed.run, one rank per GPU, one video per rank (weak scaling, no data-path
 collective); the per-video entropy series are collected on rank 0 with ONE RCCL gather per
-step.  Rank 0 prints one JSON line (contract in the task statement) carrying `roofline`
-(dominant kernel, hipEvent-timed on the launch stream inside the timed region) and, at N = 1,
-`cpu_baseline` (the C port of the reference path timed on this box's host cores on a bounded
-sample of the same workload), and `parity`: after the timed region every rank compares the series
-its timed steps produced with the C port's on the first frames of the same video (indices bit-exact,
-entropy within 1e-6) and runs one golden of the real reference through the HIP path; a violation
-prints no metric line and exits with status 3.
+step.  A plain run sets up, warms up, times K steps, writes the outputs of the last timed step
+(--dump-outputs) and prints one JSON line (metric, value, unit, ms_per_step, dtype, ...).
+
+--full adds what the headline does not need: `roofline` (dominant kernel, hipEvent-timed on the
+launch stream inside the timed region, and a device copy of the same bytes), per-rank attribution
+at N > 1 and, at N = 1, `cpu_baseline` (the C port of the reference path timed on this box's host
+cores on a bounded sample of the same workload), the nearest-tile / FP64-weights variants, the
+drop-in API timing, and `parity`: after the timed region every rank compares the series its timed
+steps produced with the C port's on the first frames of the same video (indices bit-exact, entropy
+within 1e-6) and runs one golden of the real reference through the HIP path; a violation prints no
+metric line and exits with status 3.
 """
 from __future__ import annotations
 
@@ -236,6 +241,35 @@ def parity_gate(eng, mode, tcs, weighted, W, H, mu_h, mv_h, ent_dev, idx_dev, po
             "indices": "nearest tile of tile_counts[0] per sample" if mode == "spatial" else "(prior, current) tile pairs of tile_counts[0]"}
 
 
+DUMP_INDEX_BYTES = 48 << 20      # --dump-outputs: cap of the index sample (float32); the entropy series are written whole
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, mode, ent_bufs, idx_bufs):
+    """--dump-outputs: what the caller of the timed path receives from its last step, one device buffer per video, as .npy:
+    entropy.npy — the per-frame entropy series, float64, [frames] (one video) or [videos, frames];
+    assign.npy (spatial, [rows, users]) / pairs.npy (transition, [rows, users, 2]) — the nearest-tile indices of
+    tile_counts[0] as float32 (exact: tile numbers < 2**24), every (video, frame) row when they fit DUMP_INDEX_BYTES,
+    else a fixed seeded sample of rows; <name>_rows.npy (float64) holds the row numbers, video * frames + frame."""
+    import torch
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    ent = np.stack([e.cpu().numpy() for e in ent_bufs])
+    np.save(out_dir / "entropy.npy", (ent[0] if len(ent_bufs) == 1 else ent).astype(np.float64))
+    rows, row_elems = idx_bufs[0].shape[0], idx_bufs[0][0].numel()
+    total = rows * len(idx_bufs)
+    keep = min(total, max(1, DUMP_INDEX_BYTES // (4 * row_elems)))
+    sel = np.arange(total) if keep == total else np.sort(np.random.default_rng(DUMP_SEED).choice(total, keep, replace=False))
+    parts = []
+    for v, buf in enumerate(idx_bufs):
+        r = sel[(sel >= v * rows) & (sel < (v + 1) * rows)] - v * rows
+        if len(r):
+            parts.append(buf[torch.from_numpy(r).to(buf.device)].cpu().numpy())
+    name = "assign" if mode == "spatial" else "pairs"
+    np.save(out_dir / f"{name}.npy", np.concatenate(parts).astype(np.float32))
+    np.save(out_dir / f"{name}_rows.npy", sel.astype(np.float64))
+
+
 def expected_step_ms(workload, mode, strong, world, U, T_total, kernel_ms_max, gather_ms_max, pipelined):
     """The model of an N-GPU step, printed beside the measurement.
     Weak scaling (one video per rank, BASELINE config 4): no data-path collective, every rank runs the 1-GPU kernel on its
@@ -270,7 +304,7 @@ def main():
                          "BASELINE.json scaling configs: `--gpus N --workload config4` (one video per GPU, one RCCL gather: weak "
                          "scaling) and `--gpus N --workload config5 --shard frames` (one video cut along the frame axis with a "
                          "one-frame halo: strong scaling); the N > 1 line carries per_rank step / kernel / gather times")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="config3", choices=sorted(WORKLOADS),
                     help="config2..config5 = BASELINE.json configs[1..4] (config3 = the single-GPU roofline config, the default); "
@@ -298,7 +332,19 @@ def main():
     ap.add_argument("--shard", default="videos", choices=["videos", "frames"],
                     help="N > 1: one video per GPU (weak scaling, default) or ONE video cut along the frame "
                          "axis with a 1-frame halo in transition mode (strong scaling, BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and per-kernel times, per-rank attribution, the parity "
+                         "gate, cpu_baseline, the nearest-tile / FP64-weights variants and the drop-in API timing "
+                         "(--no-cpu-baseline / --no-variants / --no-api / --parity-frames / --inject-fault apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: entropy "
+                         "(float64, every frame) and the nearest-tile indices of tile_counts[0] (float32, a fixed seeded "
+                         "sample of frames when the whole exceeds 48 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.inject_fault != "none" and not args.full:
+        ap.error("--inject-fault is a test hook of the parity gate, which runs with --full")
 
     # --gpus N without an outer launcher: start the N ranks ourselves, as a CHILD process and before
     # anything here touches torch or HIP (a process that has initialised the GPU must not exec).
@@ -456,27 +502,34 @@ def main():
     table_build_ms = None
     with torch.cuda.stream(run_stream):
         # the first call of a plan builds what it needs on the device (row statistics, weight table, per-direction
-        # records: k_row_stats + k_wtab + k_dirrec, hipEvent-timed by the engine); reported beside plan_build_ms
-        eng.profile_enable(True)
-        eng.profile_reset()
+        # records: k_row_stats + k_wtab + k_dirrec, hipEvent-timed by the engine under --full); reported beside plan_build_ms
+        if args.full:
+            eng.profile_enable(True)
+            eng.profile_reset()
         t_first = time.perf_counter()
         step()
         fence()
         first_step_ms = (time.perf_counter() - t_first) * 1e3
-        table_build_ms = eng.profile_get("k_wtab")[0]
+        if args.full:
+            table_build_ms = eng.profile_get("k_wtab")[0]
         for _ in range(max(args.warmup - 1, 0)):
             step()
         fence()
-        eng.profile_reset()
+        if args.full:
+            eng.profile_reset()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         fence()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything below reuses the output buffers (the --full variants write into `ent` / `idx`)
+        last_ent = ent_bufs[(step_no[0] - 1) & 1] if pipelined else ent
+        dump_outputs(args.dump_outputs, mode, ents if n_batch > 1 else [last_ent], idxs if n_batch > 1 else [idx])
     # ---- outside the timed region: what a step's time is made of on THIS rank (kernel time from the engine's
     # hipEvents above; the RCCL gather alone, hipEvents around an in-order gather of the step's series)
     gather_ms = None
-    if multi:
+    if multi and args.full:
         g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 5
         with torch.cuda.stream(run_stream):
@@ -491,7 +544,7 @@ def main():
     # the practical ceiling beside the 8 TB/s nominal: a device-to-device copy that moves the workload's algorithmic
     # bytes (read + write), timed once with hipEvents
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         alg_probe = int((16 + (4 if mode == "spatial" else 8)) * U * T + 8 * R)
         half = max(alg_probe // 2 // 8, 1)
         src_c = torch.empty(half, dtype=torch.float64, device=dev).fill_(1.0)
@@ -515,17 +568,21 @@ def main():
                        f"{plan.table_stride(0)} entries, {len(tcs)} lattice(s) fused in one launch)")
     else:
         formulation = f"k_spatial_w: brute-force FP64 sweep ({plan.last_formulation(0)})"
-    k_ms, k_n = eng.profile_get(kname)
-    fin_ms, fin_n = eng.profile_get("k_finalize")
-    eng.profile_enable(False)
+    k_ms, k_n, fin_ms = 0.0, 0, 0.0
+    if args.full:
+        k_ms, k_n = eng.profile_get(kname)
+        fin_ms, fin_n = eng.profile_get("k_finalize")
+        eng.profile_enable(False)
 
     per_rank = None
-    if multi:
+    if multi and args.full:
         # one small all_gather after the timed region: [step time, kernel time per step, gather alone] of every rank
         mine = torch.tensor([elapsed / args.steps * 1e3, (k_ms + fin_ms) / args.steps, gather_ms or 0.0], dtype=torch.float64, device=cdev)
         allr = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = torch.stack(allr).cpu().numpy()
+    if multi:
+        # the slowest rank's clock is the step time of the job
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
@@ -533,39 +590,40 @@ def main():
     e_host = (ents[-1] if n_batch > 1 else ent).cpu().numpy()
     assert np.isfinite(e_host).all()
 
-    # ---- parity gate, outside the timed region, on EVERY rank: the series of the timed steps against the
-    # C port on the first frames of this rank's video, and one reference golden through the HIP path
-    chk_ent, chk_idx = (ents[0], idxs[0]) if n_batch > 1 else (ent, idx)
-    chk_mu, chk_mv = (mu_h, mv_h) if (n_batch == 1 or rank == 0) else synth_video(U, T, args.seed, rank * n_batch, args.data)
-    if args.inject_fault == "assign":
-        chk_idx.view(-1)[U * 3 + 5] ^= 1
-    elif args.inject_fault == "entropy":
-        chk_ent[min(7, R - 1)] *= 1.0 + 3e-6
-    cpu_rec, port_out = None, None
-    if world == 1 and not args.no_cpu_baseline:
-        cpu_rec, port_out = cpu_baseline(mu_h, mv_h, tcs, mode, weighted, args.cpu_seconds, W, H)
-    parity = parity_gate(eng, mode, tcs, weighted, W, H, chk_mu, chk_mv, chk_ent, chk_idx, port_out, args.parity_frames)
-    if multi:
-        # one all_reduce joins the ranks' verdicts: [failed, index mismatches, max relative entropy error, frames]
-        flag = torch.tensor([0.0 if parity["ok"] else 1.0, float(parity["assign_mismatches"])], dtype=torch.float64, device=cdev)
-        worst = torch.tensor([parity["entropy_max_rel"], parity["golden_entropy_max_rel"]], dtype=torch.float64, device=cdev)
-        dist.all_reduce(flag, op=dist.ReduceOp.SUM)
-        dist.all_reduce(worst, op=dist.ReduceOp.MAX)
-        parity.update(ok=bool(flag[0].item() == 0), ranks_failed=int(flag[0].item()), assign_mismatches=int(flag[1].item()),
-                      entropy_max_rel=float(worst[0].item()), golden_entropy_max_rel=float(worst[1].item()),
-                      frames_per_rank=parity["frames"], ranks_checked=world)
-    if not parity["ok"]:
-        # a wrong result has no throughput: no metric line, the verdict on stderr, non-zero exit on every rank
-        if rank == 0:
-            print("PARITY GATE FAILED: " + json.dumps(parity), file=sys.stderr, flush=True)
-        plan.close()
+    # ---- parity gate (--full), outside the timed region, on EVERY rank: the series of the timed steps against
+    # the C port on the first frames of this rank's video, and one reference golden through the HIP path
+    cpu_rec, port_out, parity = None, None, None
+    if args.full:
+        chk_ent, chk_idx = (ents[0], idxs[0]) if n_batch > 1 else (ent, idx)
+        chk_mu, chk_mv = (mu_h, mv_h) if (n_batch == 1 or rank == 0) else synth_video(U, T, args.seed, rank * n_batch, args.data)
+        if args.inject_fault == "assign":
+            chk_idx.view(-1)[U * 3 + 5] ^= 1
+        elif args.inject_fault == "entropy":
+            chk_ent[min(7, R - 1)] *= 1.0 + 3e-6
+        if world == 1 and not args.no_cpu_baseline:
+            cpu_rec, port_out = cpu_baseline(mu_h, mv_h, tcs, mode, weighted, args.cpu_seconds, W, H)
+        parity = parity_gate(eng, mode, tcs, weighted, W, H, chk_mu, chk_mv, chk_ent, chk_idx, port_out, args.parity_frames)
         if multi:
-            dist.destroy_process_group()
-        raise SystemExit(3)
-    if pipelined:       # both buffers hold the same series (same input every step)
-        assert np.array_equal(ent_bufs[1].cpu().numpy(), e_host, equal_nan=True)
-        if rank == 0:
-            assert np.array_equal(gathered[0][:R].cpu().numpy(), e_host, equal_nan=True), "gathered series differs from the local one"
+            # one all_reduce joins the ranks' verdicts: [failed, index mismatches, max relative entropy error, frames]
+            flag = torch.tensor([0.0 if parity["ok"] else 1.0, float(parity["assign_mismatches"])], dtype=torch.float64, device=cdev)
+            worst = torch.tensor([parity["entropy_max_rel"], parity["golden_entropy_max_rel"]], dtype=torch.float64, device=cdev)
+            dist.all_reduce(flag, op=dist.ReduceOp.SUM)
+            dist.all_reduce(worst, op=dist.ReduceOp.MAX)
+            parity.update(ok=bool(flag[0].item() == 0), ranks_failed=int(flag[0].item()), assign_mismatches=int(flag[1].item()),
+                          entropy_max_rel=float(worst[0].item()), golden_entropy_max_rel=float(worst[1].item()),
+                          frames_per_rank=parity["frames"], ranks_checked=world)
+        if not parity["ok"]:
+            # a wrong result has no throughput: no metric line, the verdict on stderr, non-zero exit on every rank
+            if rank == 0:
+                print("PARITY GATE FAILED: " + json.dumps(parity), file=sys.stderr, flush=True)
+            plan.close()
+            if multi:
+                dist.destroy_process_group()
+            raise SystemExit(3)
+        if pipelined:       # both buffers hold the same series (same input every step)
+            assert np.array_equal(ent_bufs[1].cpu().numpy(), e_host, equal_nan=True)
+            if rank == 0:
+                assert np.array_equal(gathered[0][:R].cpu().numpy(), e_host, equal_nan=True), "gathered series differs from the local one"
 
     if rank == 0:
         samples_per_step = (U * T_total if strong else U * T * world) * n_batch
@@ -592,7 +650,7 @@ def main():
         # hash of the kernel sources it was measured on; a stale record is dropped, not replayed
         traffic, traffic_src = None, None
         tf = ROOT / "profiles" / "pmc_traffic.json"
-        if tf.exists() and args.data == "random_walk":
+        if args.full and tf.exists() and args.data == "random_walk":
             try:
                 rec = json.loads(tf.read_text()).get(args.workload, {})
                 if rec.get("kernel_src_sha") == kernel_src_sha():
@@ -613,30 +671,32 @@ def main():
                        "videos_per_gpu": n_batch, "batched_launch": bool(n_batch > 1 and not args.loop), "parallelism": (f"one video cut into {world} frame blocks" if strong
                                        else f"one video per GPU x{world}")},
             "frames_per_s": (T_total if strong else R * world) * n_batch / (ms_per_step * 1e-3),
-            "roofline": {"bound": bound, "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
-                         "frac_is": "algorithmic bytes / kernel time / HBM peak (the HBM roofline fraction), whatever `bound` says",
-                         "measured_copy_ceiling": {"GBps": copy_gbps, "what": "device-to-device copy moving the workload's "
-                                                   "algorithmic bytes (read + write), hipEvent-timed outside the timed region",
-                                                   "frac_of_copy": (achieved / copy_gbps) if (achieved and copy_gbps) else None},
-                         "traffic": traffic, "traffic_provenance": traffic_src,
-                         "algorithmic_bytes_per_launch": alg_bytes_launch,
-                         "avg_kernel_ms": avg_kernel_ms, "launches": k_n,
-                         "note": ("weighted FoV histogram: on top of the algorithmic bytes the gather moves 6 B per in-FoV "
-                                  "tile of every distinct direction of a frame from L2 / Infinity Cache and issues one "
-                                  "LDS atomic per entry; see `secondary` for that formulation's own speed of light "
-                                  "(DESIGN.md §5)") if (mode == "spatial" and weighted) else
-                                 ("transition mode: bytes are not the limiter (traffic = 1.14 x algorithmic); the per-row LDS "
-                                  "work of the five barrier-separated steps is: see `secondary`") if mode == "transition" else
-                                 "integer histogram stream: HBM-bound"},
-            "kernel_ms_per_step": {kname: k_ms / args.steps, "k_finalize": fin_ms / args.steps},
             "formulation": formulation,
-            "plan_build_ms": plan_ms,
-            # built inside the plan's first call (before the timed region): k_row_stats + k_wtab + k_dirrec, hipEvents
-            "table_build_ms": table_build_ms, "first_call_ms": first_step_ms,
-            "parity": parity,
+            "plan_build_ms": plan_ms, "first_call_ms": first_step_ms,
         }
-        if mode == "spatial" and weighted:
+        if args.full:
+            out["roofline"] = {
+                "bound": bound, "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
+                "frac_is": "algorithmic bytes / kernel time / HBM peak (the HBM roofline fraction), whatever `bound` says",
+                "measured_copy_ceiling": {"GBps": copy_gbps, "what": "device-to-device copy moving the workload's "
+                                          "algorithmic bytes (read + write), hipEvent-timed outside the timed region",
+                                          "frac_of_copy": (achieved / copy_gbps) if (achieved and copy_gbps) else None},
+                "traffic": traffic, "traffic_provenance": traffic_src,
+                "algorithmic_bytes_per_launch": alg_bytes_launch,
+                "avg_kernel_ms": avg_kernel_ms, "launches": k_n,
+                "note": ("weighted FoV histogram: on top of the algorithmic bytes the gather moves 6 B per in-FoV "
+                         "tile of every distinct direction of a frame from L2 / Infinity Cache and issues one "
+                         "LDS atomic per entry; see `secondary` for that formulation's own speed of light "
+                         "(DESIGN.md §5)") if (mode == "spatial" and weighted) else
+                        ("transition mode: bytes are not the limiter (traffic = 1.14 x algorithmic); the per-row LDS "
+                         "work of the five barrier-separated steps is: see `secondary`") if mode == "transition" else
+                        "integer histogram stream: HBM-bound"}
+            out["kernel_ms_per_step"] = {kname: k_ms / args.steps, "k_finalize": fin_ms / args.steps}
+            # built inside the plan's first call (before the timed region): k_row_stats + k_wtab + k_dirrec, hipEvents
+            out["table_build_ms"] = table_build_ms
+            out["parity"] = parity
+        if args.full and mode == "spatial" and weighted:
             # the arithmetic choice, auditable from this line: the proven worst-case |dH|/H of the integer formulations for
             # EVERY possible frame of this plan (vet_plan_error_bounds, k_row_stats), per lattice; the contract is 1e-6
             bounds = [plan.error_bounds(k) for k in range(len(tcs))]
@@ -673,7 +733,7 @@ def main():
             out["per_rank"]["expected"] = expected_step_ms(args.workload, mode, strong, world, U, T_total,
                                                             float(per_rank[:, 1].max()), float(per_rank[:, 2].max()), pipelined)
         # besides the HBM figure, say what the run formulation is really bound by
-        if mode == "spatial" and weighted and k_n:
+        if args.full and mode == "spatial" and weighted and k_n:
             n_lat = [2 * (tc // 2) + 1 for tc in tcs]
             cap = (1.0 - np.cos(np.radians(120.0 / 2.0))) / 2.0          # share of tiles inside the FoV cap
             if plan.last_formulation(0) == "table":
@@ -743,7 +803,7 @@ def main():
                 out["roofline"]["secondary"] = {
                     "bound": "fp64 valu (13.5 flop per tile and sample, SURVEY.md 8d)", "flop_per_launch": flop,
                     "achieved": flop / (avg_kernel_ms * 1e-3) / 1e12, "peak": 78.6, "unit": "TFLOP/s"}
-        if mode == "transition" and k_n:
+        if args.full and mode == "transition" and k_n:
             # Transition mode's own limiter: the per-row LDS work of k_transition_run (atomics on the per-tile words and the
             # bucket hash, five barrier-separated steps) — not bytes.  LDS wave instructions and LDS-busy cycles per launch
             # come from the SQ counter passes of tools/pmc_sq.sh (profiles/pmc_sq.json, valid for the kernel sources they
@@ -777,7 +837,7 @@ def main():
                     "reading": "the LDS is busy a third of the kernel: the row's dependent LDS round trips (a wave waits in "
                                "s_waitcnt for half of its life) bound it, not LDS throughput and not bytes"})
             out["roofline"]["secondary"] = sec
-        if world == 1 and mode == "spatial" and weighted and n_batch == 1 and not args.no_variants:
+        if args.full and world == 1 and mode == "spatial" and weighted and n_batch == 1 and not args.no_variants:
             # the same video with use_weight_distribution=False (every user counts 1 on its nearest
             # tile): the HBM-streaming formulation of the path, reported beside the headline
             plan_u = _native.Plan(eng, [_quantiser.lattice_xyz(tc) for tc in tcs], 120.0, 2.0, False, W, H)
@@ -805,7 +865,7 @@ def main():
                              "achieved": per_launch / (ku_ms / max(ku_n, 1) * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS,
                              "unit": "GB/s", "frac": per_launch / (ku_ms / max(ku_n, 1) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                              "avg_kernel_ms": ku_ms / max(ku_n, 1), "launches": ku_n}}
-        if world == 1 and mode == "spatial" and weighted and n_batch == 1 and not args.no_variants:
+        if args.full and world == 1 and mode == "spatial" and weighted and n_batch == 1 and not args.no_variants:
             # ---- what the same video costs with FP64 weights (the arithmetic the u32 table replaces), outside the timed region:
             # (a) exact FP64 weight rows summed per tile (the d_weights output: k_weights, calculate_tile_weights at the
             #     reference's precision, entropy_utils.py:131-136) on top of the entropy pass;
@@ -866,7 +926,7 @@ def main():
                                  "kernel_ms": km_s, "entropy_vs_timed_series_max_rel": float(d.max().item())}
                 plan.set_table_policy(args.policy)
             out["fp64_weights_variant"] = fp64
-        if world == 1 and n_batch == 1 and not args.no_api:
+        if args.full and world == 1 and n_batch == 1 and not args.no_api:
             # the drop-in API itself, from host arrays to the result DataFrame (PCIe inclusive; never `value`)
             import tempfile
             from viewport_entropy_toolkit import AnalyzerConfig, SpatialEntropyAnalyzer, TransitionEntropyAnalyzer

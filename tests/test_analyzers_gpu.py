@@ -204,7 +204,7 @@ def test_naive_analyzer_vs_reference(tmp_path, golden_dir, th, tw, flag):
         compute_naive_spatial_entropy({}, 10, 10, cfg.entropy_config)
 
 
-def test_naive_config3_size_vs_oracle():
+def test_naive_config3_size_vs_oracle(tmp_path):
     """Large video through the naive analyzer's engine path (persistent LDS-LUT stream kernel)."""
     from viewport_entropy_toolkit import NaiveSpatialEntropyAnalyzer
     from viewport_entropy_toolkit.config import NaiveAnalyzerConfig
@@ -215,7 +215,7 @@ def test_naive_config3_size_vs_oracle():
     mu[rng.random((T, U)) < 0.05] = np.nan
     mu[:, 0] = 0.5
     for flag in (True, False):
-        an = NaiveSpatialEntropyAnalyzer(NaiveAnalyzerConfig(output_dir="/tmp/vet_naive_out", tile_height=10, tile_width=20,
+        an = NaiveSpatialEntropyAnalyzer(NaiveAnalyzerConfig(output_dir=tmp_path, tile_height=10, tile_width=20,
                                                              entropy_config=EntropyConfig(use_weight_distribution=flag)))
         an.load_arrays(np.arange(T) * 0.1, mu, mv)
         ent = an.compute_entropy()["entropy"].to_numpy()

@@ -203,7 +203,7 @@ def test_bench_launches_its_own_ranks(workload, shard):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--workload", workload, "--shard", shard, "--no-cpu-baseline"],
+                          "--workload", workload, "--shard", shard, "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -236,7 +236,7 @@ def test_bench_rccl_pipelined_gather(workload):
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"),
                           "--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", workload, "--no-cpu-baseline",
-                          "--no-api"], env=env, capture_output=True, text=True, timeout=600)
+                          "--no-api", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["value"] > 0
@@ -288,7 +288,7 @@ def _run_bench(*extra, timeout=600):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "VET_BENCH_BACKEND"):
         env.pop(k, None)
     return subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--no-api", "--no-variants",
-                           *extra], env=env, capture_output=True, text=True, timeout=timeout)
+                           "--full", *extra], env=env, capture_output=True, text=True, timeout=timeout)
 
 
 @pytest.mark.parametrize("workload", ["config2", "config5", "config2x64"])
@@ -332,8 +332,58 @@ def test_bench_parity_violation_at_two_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload",
-                          "config2", "--no-cpu-baseline", "--no-api", "--no-variants", "--inject-fault", "entropy"],
+                          "config2", "--no-cpu-baseline", "--no-api", "--no-variants", "--inject-fault", "entropy", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0
     assert "PARITY GATE FAILED" in out.stderr and '"ranks_failed": 2' in out.stderr
     assert not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+
+
+def _run_plain_bench(*extra, timeout=600):
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "VET_BENCH_BACKEND"):
+        env.pop(k, None)
+    return subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *extra], env=env, capture_output=True,
+                          text=True, timeout=timeout)
+
+
+@pytest.mark.parametrize("workload", ["config2", "config5", "config2x64"])
+def test_plain_bench_line_and_dumped_outputs(tmp_path, workload):
+    """A plain run (no --full): the headline fields and none of the --full blocks; --steps sets the timed steps; and
+    --dump-outputs writes what the last timed step computed, identical from a second run with the same arguments and,
+    on the first frames of video 0, equal to the oracle (indices bit-exact, entropy within 1e-6)."""
+    _paths()
+    import bench
+    from oracle import vet_oracle as vo
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = _run_plain_bench("--workload", workload, "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["metric"] == "viewport samples/sec" and rec["unit"] == "samples/s" and rec["higher_is_better"] is True
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["dtype"].startswith("f64")
+        assert not {"roofline", "parity", "cpu_baseline", "nearest_tile_variant", "fp64_weights_variant", "drop_in_api"} & set(rec)
+        files = {f.name: np.load(f) for f in d.glob("*.npy")}
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name], equal_nan=True), name
+    U, T, tcs, mode, weighted = bench.WORKLOADS[workload]
+    n_batch = bench.BATCH.get(workload, 1)
+    R = T if mode == "spatial" else T - 1
+    name = "assign" if mode == "spatial" else "pairs"
+    ent, idx, rows = dumps[0]["entropy.npy"], dumps[0][f"{name}.npy"], dumps[0][f"{name}_rows.npy"].astype(np.int64)
+    assert ent.shape == ((R,) if n_batch == 1 else (n_batch, R))
+    assert idx.shape[1:] == ((U,) if mode == "spatial" else (U, 2)) and len(idx) == len(rows)
+    F = 8
+    mu, mv = bench.synth_video(U, T, 1234, 0)
+    if mode == "spatial":
+        ref_ent, ref_idx = vo.spatial_series(mu[:F], mv[:F], 100, 200, tcs, use_weight_distribution=weighted)[:2]
+    else:
+        ref_ent, ref_idx = vo.transition_series(mu[:F + 1], mv[:F + 1], 100, 200, tcs)
+    np.testing.assert_allclose(ent.reshape(n_batch, R)[0, :F], ref_ent, rtol=1e-6)
+    head = rows < F                                    # rows of video 0's first frames among the dumped ones
+    assert np.array_equal(idx[head], ref_idx[rows[head]].astype(np.float32))

@@ -353,6 +353,34 @@ def test_bench_parity_helpers():
         assert f"{tag}__entropy" in g.files and f"{tag}__columns" in g.files
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: entropy whole in float64, indices as float32 — every row when they fit the cap, else a
+    fixed seeded sample of (video, frame) rows whose numbers are written beside them; the same call writes the same files."""
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_INDEX_BYTES", 7 * 10 * 4)              # room for 7 rows of 10 users
+    ent = [torch.arange(20, dtype=torch.float64) + 100 * v for v in range(2)]
+    idx = [torch.arange(200, dtype=torch.int32).reshape(20, 10) + 1000 * v for v in range(2)]
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, "spatial", ent, idx)
+    e, a, rows = (np.load(tmp_path / "a" / f) for f in ("entropy.npy", "assign.npy", "assign_rows.npy"))
+    assert e.dtype == np.float64 and np.array_equal(e, np.stack([t.numpy() for t in ent]))
+    assert a.dtype == np.float32 and a.shape == (7, 10) and rows.dtype == np.float64 and rows.shape == (7,)
+    assert np.all(np.diff(rows) > 0) and rows.min() >= 0 and rows.max() < 40
+    for r, got in zip(rows.astype(np.int64), a):
+        v, f = divmod(int(r), 20)
+        assert np.array_equal(got, idx[v][f].numpy())
+    for f in ("entropy.npy", "assign.npy", "assign_rows.npy"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    # one transition video that fits: every row, in order
+    monkeypatch.setattr(bench, "DUMP_INDEX_BYTES", 19 * 10 * 2 * 4)
+    pairs = torch.arange(19 * 10 * 2, dtype=torch.int32).reshape(19, 10, 2)
+    bench.dump_outputs(tmp_path / "t", "transition", [ent[0][:19]], [pairs])
+    assert np.load(tmp_path / "t" / "entropy.npy").shape == (19,)
+    assert np.array_equal(np.load(tmp_path / "t" / "pairs.npy"), pairs.numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "t" / "pairs_rows.npy"), np.arange(19.0))
+
+
 def test_design_names_files_that_exist():
     """VERDICT r05 next #8: DESIGN.md is the current state (<= 30 KB) and every profile file it names is in the tree."""
     import re

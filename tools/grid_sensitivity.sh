@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"
 TAG=$1; O=gpurun_out/$TAG; mkdir -p $O
 row() { # name, bench args...
   local name=$1; shift
-  timeout -k 10 600 python3 bench.py --no-cpu-baseline --no-api --no-variants --steps 10 --warmup 2 "$@" > $O/grid_$name.json 2> $O/grid_$name.err || { echo "$name FAILED: $(tail -2 $O/grid_$name.err | tr '\n' ' ')" >> $O/grid_sensitivity.txt; return 0; }
+  timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --no-api --no-variants --steps 10 --warmup 2 "$@" > $O/grid_$name.json 2> $O/grid_$name.err || { echo "$name FAILED: $(tail -2 $O/grid_$name.err | tr '\n' ' ')" >> $O/grid_sensitivity.txt; return 0; }
   python3 - "$name" "$O/grid_$name.json" >> $O/grid_sensitivity.txt <<'PY'
 import json, sys
 name, f = sys.argv[1:3]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """kt.py [bench.py args] — one short bench run, prints step / per-kernel times (engine hipEvents)."""
 import json, subprocess, sys, os
-r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "..", "bench.py"), "--no-cpu-baseline", "--no-api",
+r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "..", "bench.py"), "--full", "--no-cpu-baseline", "--no-api",
                     "--no-variants", "--steps", "10"] + sys.argv[1:], capture_output=True, text=True)
 if r.returncode:
     print(r.stderr[-2000:]); sys.exit(1)

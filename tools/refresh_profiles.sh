@@ -8,8 +8,9 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"
 TAG=$1; PART=${2:-ab}
 mkdir -p gpurun_out/$TAG
-line() { # name, args...
+line() { # name, args...  (the records hold the --full blocks: roofline, parity, variants, cpu_baseline)
   local name=$1; shift
+  set -- --full "$@"
   timeout -k 10 300 python3 bench.py "$@" > gpurun_out/$TAG/bench_$name.json 2> gpurun_out/$TAG/bench_$name.err || { echo "bench $name failed"; tail -3 gpurun_out/$TAG/bench_$name.err; return 1; }
   echo "bench $name ok"
 }
