@@ -44,7 +44,8 @@ extern "C" {
 
 #define VET_VERSION 141 /* 0.1.4: tile_weights values at the reference's precision under every formulation
                            (+ vet_plan_set_raw_weights); batch descriptors in an event-guarded ring;
-                           0.1.4.1: vet_device_pci_bus_id */
+                           0.1.4.1: vet_device_pci_bus_id; vet_plan_set_fp64 (formulation 4, `dtable`) added
+                           without a new number: existing callers see no change */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -140,13 +141,20 @@ typedef struct vet_plan_desc {
 int vet_plan_create(vet_ctx *ctx, const vet_plan_desc *desc, vet_plan **out);
 int vet_plan_destroy(vet_plan *plan);
 int64_t vet_plan_n_dirs(const vet_plan *plan);
-/* Weighted spatial mode (calculate_tile_weights, entropy_utils.py:108-144) has three formulations:
+/* Weighted spatial mode (calculate_tile_weights, entropy_utils.py:108-144) has five formulations:
  *   0 table    direction weight table, built once per plan and gathered per distinct direction of a
  *              frame (memory bound); 32-bit block-floating-point weights, 64-bit integer histograms
  *   1 sweep    every sample sweeps every tile (FP64 VALU bound); 2^-52 fixed-point integer histograms
  *   2 precise  the sweep with the exact weights in FP64 histograms, in the reference's summation order
  *   3 ftable   the table with FP32 weights (2^-24 relative each, scaled by their row's exponent) in FP64
  *              histograms: |dH|/H <= 1.2e-7 for every frame whatever the weights' dynamic range
+ *   4 dtable   FP64 from start to end (plans with vet_plan_set_fp64 only): per frame, the users' exact FP64 weight rows
+ *              of every lattice (the rows the tile_weights pass gathers, built once per plan and lattice) summed in FP64
+ *              histograms in a fixed order — the users in column order within each of NW contiguous shares, the shares
+ *              in order, NW as for tile_weights —, then the reference's -sum q log2 q over the keys: bit-identical run
+ *              to run, under any frame split and between the ids and the grid entry points; lattice 0's sums ARE the
+ *              tile_weights values (the call that asks for both runs one pass).  Its NaN frames are the reference's
+ *              with no special case (a key whose sum is 0.0 gives 0 * log2 0)
  * The integer formulations (0, 1) are order independent (bit-identical run to run, under any user
  * permutation, frame split or GPU count).  They are only used where a bound computed from the plan's
  * own rows proves their deviation from exact arithmetic <= 1e-7 relative for EVERY possible frame
@@ -170,10 +178,16 @@ int64_t vet_plan_n_dirs(const vet_plan *plan);
  * plan's direction table, +1 = table whenever it is inside the contract and fits, -1 = never table.
  * vet_plan_table_stride: row length of lattice k's table (of the plan's fused table — one row per direction over
  * all lattices — where that is the one in use), 0 = not built (yet), -1 = does not fit.
+ * vet_plan_set_fp64: on != 0 restricts the plan's weighted Fibonacci lattices to FP64 arithmetic end to end: where the
+ * policy's rule asks for a table and lattice k's exact rows exist (they do not when the plan's rows would exceed 8 GB or a
+ * quarter of the free device memory, or under VET_NO_EXACT_ROWS), `dtable`; `precise` otherwise — never `table`, `sweep` or
+ * `ftable`.  Binned lattices and unweighted plans count integers and are unaffected.  The batch entry points run an fp64
+ * plan video by video through vet_spatial_entropy (no batched launch).  on = 0 restores the default choice.
  * vet_plan_last_formulation: formulation lattice k used in the plan's last weighted call (-1 none).
  * vet_plan_error_bounds: the proven relative entropy error bounds of lattice k for the table and the
  * sweep (at <= 1024 users) formulations; inf = a frame exists whose entropy no fixed point resolves. */
 int vet_plan_set_table_policy(vet_plan *plan, int policy);
+int vet_plan_set_fp64(vet_plan *plan, int on);
 /* tile_weights VALUES (the d_weights / h_weights outputs and the weight rows of a vet_result; calculate_tile_weights and
  * the accumulation of compute_spatial_entropy, utilities/entropy_utils.py:131-136, 190-192).  Whatever formulation
  * produces the entropy, they are the reference's: exact FP64 weights (ocml acos / pow), summed over the users in column
@@ -235,7 +249,7 @@ int vet_transition_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users
  * README.md:108-120); a batch shares one grid: the weighted table formulation (k_spatial_lut over the plan's fused
  * table), the nearest-tile / binned modes (k_spatial_u_lds, one launch per lattice) and transition mode
  * (k_transition_run, one launch per lattice, every video with its own workgroups).  Batches outside those kernels'
- * limits run video by video inside the call.  Lattice 0's tile weights / source counts are not produced by the
+ * limits, and plans with vet_plan_set_fp64 on, run video by video inside the call.  Lattice 0's tile weights / source counts are not produced by the
  * batched forms.  Asynchronous on ``stream`` like vet_spatial_entropy. */
 typedef struct vet_video {
     const double *d_mu, *d_mv;   /* [n_frames * n_users], frame-major */

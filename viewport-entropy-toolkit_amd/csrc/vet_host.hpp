@@ -172,6 +172,10 @@ struct Lattice {
     bool interleaved = false;      // well-filled row blocks are dealt by LDS bank class (k_wtab)
     bool binned = false;           // caller-supplied direction -> bin table (naive lat/lon tiling)
     int norm_n = 0;                // tile count used by the normaliser rule
+    // exact FP64 weight rows of this lattice for the `dtable` formulation (k_wexact; lattices k > 0 only — lattice 0's are
+    // the plan's WeightsCore::Exact, shared with device-resident results).  Rows use the plan's alias numbering (no alias
+    // copy); decided once per plan like lattice 0's (ensure_exact_rows)
+    WeightsCore::Exact ex;
 };
 
 }  // namespace vh
@@ -209,6 +213,8 @@ struct vet_plan {
     std::shared_ptr<vh::WeightsCore> wcore;   // owner of d_dir_unit and lat[0].d_tiles (shared with device-resident results)
     bool stats_all = false;        // k_row_stats has run for every weighted lattice
     bool ultra = false;            // some lattice has ultra-tiny in-FoV weights: FP64 formulations only (plan-wide)
+    bool fp64 = false;             // vet_plan_set_fp64: weighted Fibonacci lattices run `dtable` or `precise` only
+    size_t exact_bytes = 0;        // device bytes of the exact weight rows of all lattices (one cap for the plan)
 };
 
 namespace vh {
@@ -274,6 +280,9 @@ bool any_binned(const vet_plan* pl);
 int weights_pass_ids(const WeightsCore& w, const int32_t* d_ids, int U, int T, double* d_weights, hipStream_t s, vet_ctx* prof);
 // vet_plan.hip: the exact weight rows of lattice 0 (first use; synchronises once).  Leaves ex.state = -1 when they do not fit.
 int ensure_exact_weights(vet_plan* pl, hipStream_t s);
+// the same for lattice k (k = 0: ensure_exact_weights); exact_rows(pl, k) = its tables
+int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s);
+const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k);
 // (mu, mv) -> direction ids [n] (-1 absent or out of range) on the plan's pixel grid
 int sample_ids(const vet_plan* pl, const double* d_mu, const double* d_mv, long n, int32_t* d_out, hipStream_t s);
 

@@ -10,8 +10,8 @@
 //                       vet_weight_table.hpp   k_row_stats      exact rows -> error bounds of the integer formulations
 //                                              k_wtab           direction -> ELL row of (tile, FoV weight), ocml acos / pow
 //                                              k_fuse_shifts, k_dirrec   fused-row shifts, per-direction records
-//                                              k_wexact         direction -> ELL row of (tile, exact FP64 weight) of lattice 0:
-//                                                               the rows the weights pass gathers
+//                                              k_wexact         direction -> ELL row of (tile, exact FP64 weight) of lattice k:
+//                                                               the rows the weights pass (lattice 0) and k_spatial_dtable gather
 //                       vet_geometry.hpp       k_fb_boundaries  tile boundary edges of a Fibonacci tiling
 //   vet_spatial.hip     vet_spatial_lut.hpp    k_spatial_lut    table formulation: per frame, samples -> direction ids ->
 //                                                               gather of the users' rows into 64-bit integer (or FP64) LDS
@@ -22,6 +22,8 @@
 //                                                               per frame, the users' exact weight rows summed in column
 //                                                               order (off the hot path; k_spatial_w<PRECISE> in weights-only
 //                                                               mode where the exact rows do not fit the device)
+//                       vet_spatial_dtable.hpp k_spatial_dtable dtable formulation (fp64 plans): the weights pass's gather over the
+//                                                               exact FP64 rows of every lattice + the reference's entropy in FP64
 //                       vet_spatial_u.hpp      k_spatial_u_lds  nearest-tile (unweighted) and naive lat/lon-grid mode:
 //                                                               persistent stream with the nearest LUT in LDS (HBM-bound)
 //                                              k_spatial_u      generic fallback (LUT gathered from global memory)

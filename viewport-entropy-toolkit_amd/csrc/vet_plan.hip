@@ -237,14 +237,15 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     return VET_OK;
 }
 
-// Exact FP64 weight rows of lattice 0 for the weights pass (vet_host.hpp: WeightsCore::Exact).  Rows = the plan's
-// canonical directions (ensure_alias: a direction and its mirror image share a row; the dot products are identical bit
-// for bit, so are the weights).  10 bytes per entry; capped at a quarter of the free device memory and 8 GB.
-int ensure_exact_weights(vet_plan* pl, hipStream_t s) {
-    WeightsCore::Exact& X = pl->wcore->ex;
+// Exact FP64 weight rows of lattice k: lattice 0's for the weights pass (vet_host.hpp: WeightsCore::Exact) and the `dtable`
+// formulation, lattices k > 0 for `dtable` only.  Rows = the plan's canonical directions (ensure_alias: a direction and its
+// mirror image share a row; the dot products are identical bit for bit, so are the weights).  10 bytes per entry; the rows
+// of all lattices of a plan together are capped at a quarter of the free device memory and 8 GB.
+int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s) {
+    WeightsCore::Exact& X = k == 0 ? pl->wcore->ex : pl->lat[k].ex;
     if (X.state != 0) return VET_OK;
     vet_ctx* c = pl->ctx;
-    const Lattice& L = pl->lat[0];
+    const Lattice& L = pl->lat[k];
     if (!pl->weighted || L.binned || !L.d_tiles || c->tune.no_exact_rows) { X.state = -1; return VET_OK; }
     int rc = ensure_alias(pl);
     if (rc) return rc;
@@ -267,22 +268,25 @@ int ensure_exact_weights(vet_plan* pl, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(&longest, d_max.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const int stride = ((longest > 0 ? longest : 1) + 63) / 64 * 64;
-    const size_t D = (size_t)pl->n_dirs, entries = (size_t)R * stride, bytes = entries * 10 + (size_t)R * 4 + D * 4;
+    // lattice 0 keeps a copy of the alias table (results that share its rows may outlive the plan); the others use the plan's
+    const size_t D = k == 0 ? (size_t)pl->n_dirs : 0, entries = (size_t)R * stride, bytes = entries * 10 + (size_t)R * 4 + D * 4;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    if (bytes > ((size_t)8 << 30) || bytes > free_b / 4 || stride > 65535) { X.state = -1; return VET_OK; }
+    const size_t total = pl->exact_bytes + bytes;       // the plan's rows so far count against the cap as if still free
+    if (total > ((size_t)8 << 30) || total > (free_b + pl->exact_bytes) / 4 || stride > 65535) { X.state = -1; return VET_OK; }
     auto dev_free = [](void* q) { if (q) (void)hipFree(q); };
     auto dev_alloc = [&](size_t b) {
         void* q = nullptr;
         if (hipMalloc(&q, b ? b : 8) != hipSuccess) { (void)hipGetLastError(); q = nullptr; }
         return std::shared_ptr<void>(q, dev_free);
     };
-    auto alias = dev_alloc(D * 4), idx = dev_alloc(entries * 2), w = dev_alloc(entries * 8), len = dev_alloc((size_t)R * 4);
+    auto alias = k == 0 ? dev_alloc(D * 4) : std::shared_ptr<void>();
+    auto idx = dev_alloc(entries * 2), w = dev_alloc(entries * 8), len = dev_alloc((size_t)R * 4);
     // out of memory at the first request: decided ONCE for the plan, like "does not fit" above — the precise sweep serves
     // every later weights request and every result of this plan (a retry that succeeded later would switch paths between an
     // eager weights call and the fetch of the same frames: same values, different last bits)
-    if (!alias || !idx || !w || !len) { X.state = -1; return VET_OK; }
-    HIP_TRY(hipMemcpyAsync(alias.get(), pl->d_alias, D * 4, hipMemcpyDeviceToDevice, s));
+    if ((k == 0 && !alias) || !idx || !w || !len) { X.state = -1; return VET_OK; }
+    if (k == 0) HIP_TRY(hipMemcpyAsync(alias.get(), pl->d_alias, D * 4, hipMemcpyDeviceToDevice, s));
     vet::WexactParams q{};
     q.dir_unit = pl->d_dir_unit; q.canon = pl->d_canon; q.R = R; q.tiles = L.d_tiles; q.n = L.n;
     q.cos_cull = pl->cos_cull; q.wc = p.wc; q.stride = stride;
@@ -296,8 +300,13 @@ int ensure_exact_weights(vet_plan* pl, hipStream_t s) {
     X.alias = alias; X.idx = idx; X.w = w; X.len = len;
     X.stride = stride; X.n_rows = (int)R;
     X.state = 1;
+    pl->exact_bytes = total;
     return VET_OK;
 }
+
+int ensure_exact_weights(vet_plan* pl, hipStream_t s) { return ensure_exact_rows(pl, 0, s); }
+
+const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k) { return k == 0 ? pl->wcore->ex : pl->lat[k].ex; }
 
 bool any_binned(const vet_plan* pl) {
     for (const auto& L : pl->lat) if (L.binned) return true;
@@ -606,6 +615,12 @@ int64_t vet_plan_n_dirs(const vet_plan* pl) { return pl ? pl->n_dirs : 0; }
 int vet_plan_set_table_policy(vet_plan* pl, int policy) {
     if (!pl) return fail(VET_ERR_INVALID, "plan is NULL");
     pl->table_policy = policy > 0 ? 1 : (policy < 0 ? -1 : 0);
+    return VET_OK;
+}
+
+int vet_plan_set_fp64(vet_plan* pl, int on) {
+    if (!pl) return fail(VET_ERR_INVALID, "plan is NULL");
+    pl->fp64 = on != 0;
     return VET_OK;
 }
 

@@ -1,10 +1,11 @@
 // vet_spatial.hip — launch logic of the spatial-entropy kernels behind vet_spatial_entropy* (include/vet.h):
-// formulation choice (table / sweep / precise / FP table), launch geometry, single videos and batches.
+// formulation choice (table / sweep / precise / FP table / FP64 table), launch geometry, single videos and batches.
 // No CPU compute path; nothing here reads the environment (the context's Tuning was parsed in vet_create).
 #include "vet_host.hpp"
 #include "vet_finalize.hpp"
 #include "vet_spatial_sweep.hpp"
 #include "vet_weights_pass.hpp"
+#include "vet_spatial_dtable.hpp"
 #include "vet_spatial_lut.hpp"
 #include "vet_spatial_u.hpp"
 
@@ -151,7 +152,9 @@ int lut_frames_per_wg(int U, long total_frames, int n_cu, int n_sum) {
 //            sample is 4-10x cheaper than a swept one), if the table fits and its error bound is inside the contract;
 //   sweep    integer (2^-52) histogram, if its error bound is inside the contract;
 //   precise  FP64 histogram and exact weights otherwise.
-enum { F_TABLE = 0, F_SWEEP = 1, F_PRECISE = 2, F_FTABLE = 3 };
+// Plans with fp64 on (vet_plan_set_fp64) never run those: where the same rule asks for a table and the lattice's exact FP64
+// weight rows exist, `dtable` (k_spatial_dtable), `precise` otherwise.
+enum { F_TABLE = 0, F_SWEEP = 1, F_PRECISE = 2, F_FTABLE = 3, F_DTABLE = 4 };
 
 bool table_requested(const vet_plan* pl, long samples, int U) {
     if (!pl->weighted || pl->table_policy < 0 || any_binned(pl) || U >= 65536) return false;
@@ -172,6 +175,67 @@ int sweep_formulation(const vet_plan* pl, const Lattice& L, int U) {
     double step = std::ldexp(1.0, sweep_shift(U) - 52);
     if (weight_mode(pl) != 0 && step < 4e-14) step = 4e-14;
     return L.crit_base * step <= kContractMargin ? F_SWEEP : F_PRECISE;
+}
+
+// waves per workgroup of the weights pass over a lattice of n tiles (4, 2, 1: the FP64 histograms of all waves in LDS);
+// k_spatial_dtable runs lattice 0 at the same NW, so lattice 0's tile sums are the weights pass's bits
+int weights_nw(size_t lds_max, int n) {
+    int nw = 4;
+    while (nw > 1 && (size_t)nw * n * 8 > lds_max) nw /= 2;
+    return nw;
+}
+
+// formulation of lattice k of an fp64 plan: `dtable` where a table is requested and the lattice's exact rows exist (built on
+// first use) and fit the LDS at the weights pass's NW, `precise` otherwise
+int fp64_formulation(vet_plan* pl, int k, bool want_table, hipStream_t s, int* out) {
+    *out = F_PRECISE;
+    if (!want_table) return VET_OK;
+    int rc = ensure_exact_rows(pl, k, s);
+    if (rc) return rc;
+    const int n = pl->lat[k].n;
+    if (exact_rows(pl, k).state == 1 && vet::dtable_lds_bytes(weights_nw(pl->ctx->lds_max, n), n) <= pl->ctx->lds_max)
+        *out = F_DTABLE;
+    return VET_OK;
+}
+
+// one launch of k_spatial_dtable over lattices lat_idx[0..K) of the plan at NW waves per workgroup.  d_mean: the mean over the
+// K lattices (the launch holds the plan's lattices, K > 1); d_ent_k: K rows of per-lattice values.  Lattice 0's outputs
+// (assign, weights, present, status) only where lat_idx[0] == 0.
+template <bool FROM_IDS>
+int launch_dtable(vet_plan* pl, const int* lat_idx, int K, int nw, const vet::SampleSrc& src, int U, int T, double* d_mean,
+                  double* d_ent_k, int32_t* d_assign, double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    if (T <= 0) return VET_OK;
+    vet::DtableParams q{};
+    q.src = src; q.U = U; q.T = T;
+    q.alias = pl->d_alias; q.nearest = pl->lat[0].d_nearest;
+    q.K = K; q.n_sum = 0;
+    int max_stride = 0;
+    auto chunk_class = [](int stride) { const int c = stride / vet::WAVE; return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 0; };
+    for (int j = 0; j < K; ++j) {
+        const Lattice& L = pl->lat[lat_idx[j]];
+        const WeightsCore::Exact& X = exact_rows(pl, lat_idx[j]);
+        q.off[j] = q.n_sum; q.hmax[j] = L.hmax; q.chunk[j] = chunk_class(X.stride);
+        q.lat[j] = vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(), X.stride, L.n};
+        q.n_sum += L.n;
+        max_stride = std::max(max_stride, X.stride);
+    }
+    q.entropy = d_mean; q.ent_k = d_ent_k;
+    const bool first = lat_idx[0] == 0;
+    q.assign = first ? d_assign : nullptr; q.weights = first ? d_weights : nullptr;
+    q.present = first ? d_present : nullptr; q.status = first ? d_status : nullptr;
+    const size_t lds = vet::dtable_lds_bytes(nw, q.n_sum);
+    if (lds > c->lds_max) return fail(VET_ERR_UNSUPPORTED, "dtable: %zu B of LDS", lds);
+    // the instance of the longest row of the launch; each lattice picks its own row walk inside it (q.chunk)
+    const int cls = chunk_class(max_stride);
+    const void* fn = cls == 1 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 1>
+                   : cls == 2 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 2>
+                   : cls == 4 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 4> : (const void*)vet::k_spatial_dtable<FROM_IDS, 0>;
+    void* args[] = {(void*)&q};
+    ProfScope ps(c, s, KID_SPATIAL);
+    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)T), dim3(nw * vet::WAVE), args, lds, s));
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
 }
 
 // formulation of lattice k for a call; builds the statistics (and the table) on first use
@@ -420,8 +484,7 @@ int launch_weights_pass(const WeightsCore& w, const vet::SampleSrc& src, int U, 
     if (T <= 0) return VET_OK;
     if (w.ex.state == 1) {
         // the exact weight rows exist (ensure_exact_weights): gather them, one workgroup per frame
-        int nw = 4;
-        while (nw > 1 && (size_t)nw * w.n0 * 8 > w.lds_max) nw /= 2;
+        const int nw = weights_nw(w.lds_max, w.n0);
         if ((size_t)nw * w.n0 * 8 <= w.lds_max) {
             vet::WeightsGatherParams q{};
             q.src = src; q.U = U; q.T = T;
@@ -471,7 +534,8 @@ int launch_weights_pass(const WeightsCore& w, const vet::SampleSrc& src, int U, 
 
 template <bool FROM_IDS>
 int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, double* d_entropy, int32_t* d_assign,
-                        double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s);
+                        double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s, double* d_wexact = nullptr,
+                        bool* wrote_wexact = nullptr);
 
 // tile_weights VALUES carry the reference's precision under every formulation (utilities/entropy_utils.py:131-136,
 // 190-192).  The formulations' histograms hold block-floating-point, FP32-rounded or 2^-52 fixed-point weights, good for
@@ -479,22 +543,28 @@ int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, d
 // left to the weights pass over the same samples — ONE producer for every weights output (the eager d_weights and the
 // rows a device-resident result computes per fetched block are the same bits) and off the hot path: only calls that ask
 // for d_weights pay for it.  Unweighted / binned plans count users per tile: integers, exact, written by the main launch.
+// The one exception: where `dtable` ran lattice 0 (fp64 plans), its launch has summed the weights pass's own rows in the
+// weights pass's order and wrote d_weights itself — the same bits — and no weights pass runs.
 template <bool FROM_IDS>
 int launch_spatial(vet_plan* pl, const vet::SampleSrc& src, int U, int T, double* d_entropy, int32_t* d_assign,
                    double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s) {
     const bool exact = d_weights && pl->weighted && !pl->lat[0].binned && !pl->raw_weights;
-    int rc = launch_spatial_main<FROM_IDS>(pl, src, U, T, d_entropy, d_assign, exact ? nullptr : d_weights, d_present, d_status, s);
-    if (rc || !exact) return rc;
+    bool wrote = false;
+    int rc = launch_spatial_main<FROM_IDS>(pl, src, U, T, d_entropy, d_assign, exact ? nullptr : d_weights, d_present, d_status, s,
+                                           exact ? d_weights : nullptr, &wrote);
+    if (rc || !exact || wrote) return rc;
     rc = ensure_exact_weights(pl, s);          // first request for weights: the exact rows of lattice 0 (or not, if too large)
     if (rc) return rc;
     return launch_weights_pass<FROM_IDS>(*pl->wcore, src, U, T, d_weights, s, pl->ctx);
 }
 
 // d_weights: the formulation's own histogram of lattice 0 (unweighted / binned plans: the exact integer counts; weighted
-// plans only with vet_plan_set_raw_weights)
+// plans only with vet_plan_set_raw_weights).  d_wexact: the weights output at the reference's precision, written here only
+// where `dtable` runs lattice 0 (then *wrote_wexact = true; the caller runs the weights pass otherwise)
 template <bool FROM_IDS>
 int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, double* d_entropy, int32_t* d_assign,
-                        double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s) {
+                        double* d_weights, int32_t* d_present, int32_t* d_status, hipStream_t s, double* d_wexact,
+                        bool* wrote_wexact) {
     vet_ctx* c = pl->ctx;
     const int K = (int)pl->lat.size();
     double* ent_k = d_entropy;
@@ -502,9 +572,11 @@ int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, d
     int form[64];
     if (K > 64) return fail(VET_ERR_UNSUPPORTED, "more than 64 lattices in one plan");
     const bool want_table = table_requested(pl, (long)U * T, U);
+    const bool fp64 = pl->fp64 && pl->weighted;
+    double* const w0 = d_wexact ? d_wexact : d_weights;       // what `dtable` writes for lattice 0: its sums are exact
     // ---- weighted, integer table formulation over the plan's fused table (one row per distinct direction over all
     // lattices) where the plan allows (ensure_fused)
-    if (want_table && pl->weighted) {
+    if (want_table && pl->weighted && !fp64) {
         int rc = ensure_fused(pl, s);
         if (rc) return rc;
         if (pl->fused.state == 1) {
@@ -515,14 +587,29 @@ int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, d
             if (rc || launched) return rc;
         }
     }
-    bool all_table = pl->weighted != 0;
+    bool all_table = pl->weighted != 0 && !fp64, all_dtable = fp64;
+    int n_sum = 0;
     for (int k = 0; k < K; ++k) {
         form[k] = F_SWEEP;
         if (pl->weighted && !pl->lat[k].binned) {
-            int rc = choose_formulation(pl, k, want_table, U, s, &form[k]);
+            int rc = fp64 ? fp64_formulation(pl, k, want_table, s, &form[k]) : choose_formulation(pl, k, want_table, U, s, &form[k]);
             if (rc) return rc;
         }
         all_table = all_table && (form[k] == F_TABLE || form[k] == F_FTABLE) && form[k] == form[0];
+        all_dtable = all_dtable && form[k] == F_DTABLE;
+        n_sum += pl->lat[k].n;
+    }
+    // ---- fp64, every lattice from its exact rows: one launch where the histograms of all lattices fit the LDS at lattice 0's
+    // weights-pass NW; otherwise lattice 0 alone at that NW and the others in launches of their own (loop below)
+    if (all_dtable && K <= vet::MAX_LATTICES && vet::dtable_lds_bytes(weights_nw(c->lds_max, pl->lat[0].n), n_sum) <= c->lds_max) {
+        int idx[vet::MAX_LATTICES];
+        for (int k = 0; k < K; ++k) idx[k] = k;
+        int rc = launch_dtable<FROM_IDS>(pl, idx, K, weights_nw(c->lds_max, pl->lat[0].n), src, U, T, K > 1 ? d_entropy : nullptr,
+                                         K > 1 ? nullptr : d_entropy, d_assign, w0, d_present, d_status, s);
+        if (rc) return rc;
+        for (int k = 0; k < K; ++k) pl->lat[k].last_form = F_DTABLE;
+        if (wrote_wexact) *wrote_wexact = d_wexact != nullptr;
+        return VET_OK;
     }
     // ---- weighted, table formulation: every lattice in one launch
     if (all_table) {
@@ -551,6 +638,14 @@ int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, d
     }
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
+        if (form[k] == F_DTABLE) {
+            int rc = launch_dtable<FROM_IDS>(pl, &k, 1, weights_nw(c->lds_max, L.n), src, U, T, nullptr, ent_k + (size_t)k * T,
+                                             d_assign, w0, d_present, d_status, s);
+            if (rc) return rc;
+            pl->lat[k].last_form = F_DTABLE;
+            if (k == 0 && wrote_wexact) *wrote_wexact = d_wexact != nullptr;
+            continue;
+        }
         if (form[k] == F_TABLE || form[k] == F_FTABLE) {
             bool launched = false;
             uint32_t* d_list = nullptr;
@@ -688,6 +783,10 @@ int spatial_set_attrs(vet_ctx* c) {
     ATTR_TRY((vet::k_weights_gather<false, 1>), c->lds_max); ATTR_TRY((vet::k_weights_gather<true, 1>), c->lds_max);
     ATTR_TRY((vet::k_weights_gather<false, 2>), c->lds_max); ATTR_TRY((vet::k_weights_gather<true, 2>), c->lds_max);
     ATTR_TRY((vet::k_weights_gather<false, 4>), c->lds_max); ATTR_TRY((vet::k_weights_gather<true, 4>), c->lds_max);
+    ATTR_TRY((vet::k_spatial_dtable<false, 0>), c->lds_max); ATTR_TRY((vet::k_spatial_dtable<true, 0>), c->lds_max);
+    ATTR_TRY((vet::k_spatial_dtable<false, 1>), c->lds_max); ATTR_TRY((vet::k_spatial_dtable<true, 1>), c->lds_max);
+    ATTR_TRY((vet::k_spatial_dtable<false, 2>), c->lds_max); ATTR_TRY((vet::k_spatial_dtable<true, 2>), c->lds_max);
+    ATTR_TRY((vet::k_spatial_dtable<false, 4>), c->lds_max); ATTR_TRY((vet::k_spatial_dtable<true, 4>), c->lds_max);
     ATTR_TRY((vet::k_spatial_u_lds<false, true, true>), c->lds_max);
     ATTR_TRY((vet::k_spatial_u_lds<false, false, true>), c->lds_max);
     ATTR_TRY((vet::k_spatial_u_lds<false, true>), c->lds_max);
@@ -877,7 +976,8 @@ int vet_spatial_entropy_batch(vet_plan* pl, int n_videos, const vet_video* video
             if (rc || launched) return rc;
         }
     }
-    bool table = table_requested(pl, total, max_users);
+    // fp64 plans (vet_plan_set_fp64): video by video through the single-video path (`dtable` / `precise`), no batched launch
+    bool table = !(pl->fp64 && pl->weighted) && table_requested(pl, total, max_users);
     if (table) {
         // the plan's fused table: every video's frame blocks in one k_spatial_lut launch
         int rc = ensure_fused(pl, s);

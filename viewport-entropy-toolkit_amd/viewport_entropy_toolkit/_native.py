@@ -88,6 +88,7 @@ SIGNATURES = {
     "vet_plan_destroy": (_I, [_P]),
     "vet_plan_n_dirs": (_I64, [_P]),
     "vet_plan_set_table_policy": (_I, [_P, _I]),
+    "vet_plan_set_fp64": (_I, [_P, _I]),
     "vet_plan_set_raw_weights": (_I, [_P, _I]),
     "vet_plan_table_stride": (_I, [_P, _I]),
     "vet_plan_table_rows": (_I64, [_P]),
@@ -114,6 +115,9 @@ SIGNATURES = {
     "vet_csv_read_tracks": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(Track), _I]),
     "vet_csv_free_tracks": (None, [_I, C.POINTER(Track)]),
 }
+
+# vet_plan_last_formulation codes (include/vet.h)
+FORMULATIONS = {0: "table", 1: "sweep", 2: "precise", 3: "ftable", 4: "dtable"}
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -411,6 +415,11 @@ class Plan:
         """0 auto, 1 always use the direction weight table, -1 never (brute-force sweep)."""
         _check(self.lib, self.lib.vet_plan_set_table_policy(self.handle, int(policy)))
 
+    def set_fp64(self, on: bool = True):
+        """FP64 arithmetic end to end for the weighted Fibonacci lattices: the ``dtable`` formulation (exact FP64 weight rows,
+        FP64 histograms) where the table policy asks for a table, ``precise`` otherwise (include/vet.h: vet_plan_set_fp64)."""
+        _check(self.lib, self.lib.vet_plan_set_fp64(self.handle, 1 if on else 0))
+
     def set_raw_weights(self, on: bool = True):
         """Diagnostic: ``weights`` = the formulation's own histogram (table / sweep resolution) instead of the reference's
         values from the weights-only pass of the precise sweep (include/vet.h: vet_plan_set_raw_weights)."""
@@ -424,8 +433,8 @@ class Plan:
         return int(self.lib.vet_plan_table_rows(self.handle))
 
     def last_formulation(self, lattice: int = 0) -> str:
-        """'table' | 'sweep' | 'precise' | 'ftable' of the last weighted call ('' before any)."""
-        return {0: "table", 1: "sweep", 2: "precise", 3: "ftable"}.get(int(self.lib.vet_plan_last_formulation(self.handle, lattice)), "")
+        """'table' | 'sweep' | 'precise' | 'ftable' | 'dtable' of the last weighted call ('' before any)."""
+        return FORMULATIONS.get(int(self.lib.vet_plan_last_formulation(self.handle, lattice)), "")
 
     def error_bounds(self, lattice: int = 0):
         """(table bound, sweep bound): proven worst-case relative entropy error of the integer formulations."""

@@ -133,14 +133,17 @@ class _EntropyAnalyzerBase:
     # ------------------------------------------------------------------ engine
     def _get_plan(self, dir_table: Optional[np.ndarray] = None) -> "_native.Plan":
         ec = self.config.entropy_config
+        fp64 = getattr(self, "_fp64", False)        # SpatialEntropyAnalyzer(..., fp64=True)
         key = (tuple(self.config.tile_counts), self.config.video_width, self.config.video_height,
-               ec.fov_angle, ec.power_factor, ec.use_weight_distribution, dir_table is None)
+               ec.fov_angle, ec.power_factor, ec.use_weight_distribution, dir_table is None, fp64)
         if dir_table is not None or self._plan is None or self._plan_key != key:
             tiles = [np.array([[v.x, v.y, v.z] for v in self._fibonacci_vectors[c]], dtype=np.float64)
                      for c in self.config.tile_counts]
             plan = _native.Plan(_native.Engine.default(), tiles, ec.fov_angle, ec.power_factor,
                                 ec.use_weight_distribution, self.config.video_width, self.config.video_height,
                                 dir_table=dir_table)
+            if fp64:
+                plan.set_fp64(True)
             if dir_table is not None:
                 return plan
             self._plan, self._plan_key = plan, key

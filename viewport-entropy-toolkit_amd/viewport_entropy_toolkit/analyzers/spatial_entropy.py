@@ -6,10 +6,12 @@ from __future__ import annotations
 
 import logging
 import time
+from typing import Optional
 
 import pandas as pd
 
 from .. import _native
+from ..config import AnalyzerConfig
 from ..data_types import ValidationError
 from .._results import DeviceRows, FrameDictArray, TileAssignments, TileWeights
 from ._base import _EntropyAnalyzerBase
@@ -23,6 +25,13 @@ class SpatialEntropyAnalyzer(_EntropyAnalyzerBase):
     (``time``, ``entropy``, ``tile_weights``, ``tile_assignments``)."""
 
     _logger = logger
+
+    def __init__(self, config: Optional[AnalyzerConfig] = None, *, fp64: bool = False):
+        """``fp64=True``: the entropy in FP64 arithmetic from start to end (``Plan.set_fp64``: exact FP64 weights summed in
+        FP64, the reference's own arithmetic) instead of the engine's default formulations.  The tile weights are the same
+        values either way."""
+        super().__init__(config)
+        self._fp64 = bool(fp64)
 
     def compute_entropy(self) -> pd.DataFrame:
         kind, times, a, b, names = self._samples()
