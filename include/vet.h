@@ -217,8 +217,10 @@ int vet_plan_read_nearest(vet_plan *plan, int lattice, int32_t *h_nearest /* [n_
  *                      -0.0 = the tile is a key of the reference's dict with the value 0.0 (in some
  *                      user's FoV, weight underflowed), +0.0 = no key
  *   d_present [T]      users present per frame                              (nullable)
- *   d_status  [2]      {#samples outside [0,1], #frames without a user}; the call ADDS to
- *                      it, the caller zeroes it                             (nullable)   */
+ *   d_status  [2]      {bad, #frames without a user}; the call ADDS to it, the caller
+ *                      zeroes it                                            (nullable)
+ *                      bad: non-zero if and only if some sample is outside [0,1] (ids: at
+ *                      or beyond the direction table); not the number of such samples   */
 int vet_spatial_entropy(vet_plan *plan, const double *d_mu, const double *d_mv,
                         int n_users, int n_frames,
                         double *d_entropy, int32_t *d_assign, double *d_weights,
@@ -235,7 +237,8 @@ int vet_spatial_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, i
  *   d_pairs    [(T-1)*U*2]  (prior tile, current tile) of lattice 0, -1 if not in both (nullable)
  *   d_srccount [(T-1)*n_0]  users per source tile of lattice 0                          (nullable)
  *   d_common   [T-1]        users present in both frames                                (nullable)
- *   d_status   [2]          {#samples outside [0,1], #rows without a common user}       (nullable) */
+ *   d_status   [2]          {bad, #rows without a common user}                          (nullable)
+ *                           bad: as in vet_spatial_entropy                                        */
 int vet_transition_entropy(vet_plan *plan, const double *d_mu, const double *d_mv,
                            int n_users, int n_frames,
                            double *d_entropy, int32_t *d_pairs, int32_t *d_srccount,

@@ -5,8 +5,10 @@ sums are the weights pass's bits; deterministic; the default formulations are un
 import numpy as np
 import pandas as pd
 import pytest
+from hypothesis import HealthCheck, given, settings, strategies as st
 
 from oracle import vet_oracle as vo
+from tests._fp64 import fp64_form
 from tests._tol import W_RTOL, w_atol
 
 pytestmark = pytest.mark.gpu
@@ -27,8 +29,8 @@ def engine(native):
     return native.Engine.default()
 
 
-def make_plan(native, engine, tcs, fov=120.0, power=2.0, policy=0, fp64=True, dir_table=None):
-    plan = native.Plan(engine, [vo.fibonacci_lattice(tc) for tc in tcs], fov, power, True, W, H, dir_table=dir_table)
+def make_plan(native, engine, tcs, fov=120.0, power=2.0, policy=0, fp64=True, dir_table=None, grid=(W, H)):
+    plan = native.Plan(engine, [vo.fibonacci_lattice(tc) for tc in tcs], fov, power, True, *grid, dir_table=dir_table)
     plan.set_table_policy(policy)
     if fp64:
         plan.set_fp64(True)
@@ -321,3 +323,313 @@ def test_analyzer_fp64(tmp_path, golden_dir, tag, tcs):
     assert len(res) == len(ref)
     for i in range(len(res)):
         assert dict(res["tile_weights"][i]) == dict(ref["tile_weights"][i]), i
+
+
+# --------------------------------------------------------------------------- 9. the edge matrix under fp64
+def fp64_oracle(mu, mv, tcs, fov=120.0, power=2.0, grid=(W, H)):
+    """The oracle frame by frame (vo.spatial_entropy_frame: the reference's sums in user order, no table over the whole
+    pixel grid); a frame without a user: entropy NaN, assign -1, no keys."""
+    px, py, present, dirs_grid = vo.sample_directions(mu, mv, *grid)
+    flat = dirs_grid.reshape(-1, 3)
+    lattices = [vo.fibonacci_lattice(tc) for tc in tcs]
+    T = len(mu)
+    ent = np.full(T, np.nan)
+    assign = np.full(mu.shape, -1, dtype=np.int32)
+    weights = np.zeros((T, len(lattices[0])))
+    for t in range(T):
+        if not present[t].any():
+            continue
+        dirs = flat[(py[t] * (grid[0] + 1) + px[t])[present[t]]]
+        s = 0.0
+        for k, L in enumerate(lattices):
+            e, hist, near = vo.spatial_entropy_frame(dirs, L, fov, power)
+            s += e
+            if k == 0:
+                weights[t], assign[t][present[t]] = hist, near
+        ent[t] = s / len(lattices)
+    return ent, assign, weights
+
+
+def max_rel(got, ref):
+    ok = ~np.isnan(ref) & (ref != 0)
+    return float(np.max(np.abs(got[ok] - ref[ok]) / np.abs(ref[ok]))) if ok.any() else 0.0
+
+
+def profiled(engine, fn):
+    engine.profile_enable(True)
+    try:
+        engine.profile_reset()
+        out = fn()
+        counts = tuple(engine.profile_get(k)[1] for k in ("k_spatial", "k_finalize", "k_weights"))
+    finally:
+        engine.profile_enable(False)
+    return out, counts
+
+
+# Fibonacci lattices have an odd number of tiles, at most 6783 (the plan's LDS tile cache: 24 bytes a tile), so every one fits
+# `dtable` at the weights pass's NW.  What leaves a lattice to `precise` under a table request is the plan-wide cap on the exact
+# rows (8 GB): at 640 x 480 pixels and fov 360, 6001 tiles need about 9 GB of rows, 51 tiles 0.1 GB.
+BIG = dict(grid=(640, 480), fov=360.0)
+MIXED_PLANS = [
+    # tcs, plan keywords, per-lattice formulation, (k_spatial, k_finalize, k_weights) launches
+    ([5000], {}, ["dtable"], (1, 0, 0)),                       # 5001 tiles: NW = 2
+    ([6000], {}, ["dtable"], (1, 0, 0)),                       # 6001 tiles: NW = 1
+    ([50, 5000], {}, ["dtable", "dtable"], (2, 1, 0)),         # 4 waves x 5052 tiles do not fit: a launch per lattice
+    ([50, 6000], BIG, ["dtable", "precise"], (2, 1, 0)),       # lattice 1 without exact rows: `precise`
+    ([6000, 50], BIG, ["precise", "dtable"], (2, 1, 1)),       # lattice 0 `precise`: the weights pass writes the weights
+]
+
+
+@pytest.mark.parametrize("tcs,kw,forms,launches", MIXED_PLANS)
+def test_weights_pass_wave_counts_and_mixed_plans(native, engine, tcs, kw, forms, launches):
+    """Lattices at the weights pass's 2 and 1 waves, and plans that mix `dtable` with `precise` (the per-lattice launches,
+    then k_finalize): against the oracle on sampled frames; the weights are the fp64-off plan's weights-pass bits; the mean
+    is k_finalize's (0.0 + e0 + e1) / 2 of single-lattice plans, bit for bit."""
+    from viewport_entropy_toolkit import _quantiser
+    U, T = 300, 16                                             # not a multiple of 64 * NW
+    mu, mv = video(U, T, 31)
+    plan = make_plan(native, engine, tcs, policy=1, **kw)
+    plan.spatial(mu=mu, mv=mv)                                 # builds the rows
+    res, counts = profiled(engine, lambda: plan.spatial(mu=mu, mv=mv, want_weights=True))
+    assert [plan.last_formulation(k) for k in range(len(tcs))] == forms
+    assert counts == launches, counts
+    fr = np.array([0, 3, 7, 11, T - 1])
+    ent, assign, weights = fp64_oracle(mu[fr], mv[fr], tcs, kw.get("fov", 120.0), grid=kw.get("grid", (W, H)))
+    assert np.array_equal(res["assign"][fr], assign)
+    print(f"fp64 {tcs} {kw} {U}x{T} vs oracle: max relative difference {max_rel(res['entropy'][fr], ent):.3e}")
+    np.testing.assert_allclose(res["entropy"][fr], ent, rtol=RTOL)
+    np.testing.assert_allclose(res["weights"][fr], weights, rtol=W_RTOL, atol=w_atol(U))
+    off = make_plan(native, engine, tcs, policy=-1, fp64=False, **kw)
+    ref = off.spatial(mu=mu, mv=mv, want_weights=True)
+    off.close()
+    assert np.array_equal(bits(res["weights"]), bits(ref["weights"]))
+    singles = []
+    for tc, form in zip(tcs, forms):
+        one = make_plan(native, engine, [tc], policy=1, **kw)
+        r = one.spatial(mu=mu, mv=mv, want_weights=True)
+        assert one.last_formulation(0) == form
+        singles.append(r["entropy"])
+        if form == "dtable":                                   # entropy = the entropy of the call's own weights
+            w = r["weights"]
+            keys = w.view(np.uint64) != 0
+            v = np.where(keys, np.abs(w), 0.0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                q = v / v.sum(axis=1, keepdims=True)
+                h = -np.where(keys, q * np.log2(q), 0.0).sum(axis=1)
+            np.testing.assert_allclose(r["entropy"], h / _quantiser.max_entropy(tc + 1), rtol=1e-12, equal_nan=True)
+        one.close()
+    if len(tcs) == 1:
+        assert np.array_equal(bits(res["entropy"]), bits(singles[0]))
+    else:
+        assert np.array_equal(bits(res["entropy"]), bits((0.0 + singles[0] + singles[1]) / 2.0))
+    plan.close()
+
+
+U_BOUNDARIES = [63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513]
+fp64_problem = st.fixed_dictionaries(dict(
+    U=st.one_of(st.integers(1, 300), st.sampled_from(U_BOUNDARIES)), T=st.integers(1, 12), seed=st.integers(0, 2 ** 31 - 1),
+    p_absent=st.sampled_from([0.0, 0.1, 0.5]), empty_frame=st.booleans(),
+    tcs=st.lists(st.sampled_from([1, 2, 3, 20, 50, 64, 65, 100, 129, 250, 500, 1000]), min_size=1, max_size=3),
+    fov=st.sampled_from([0.5, 30.0, 90.0, 120.0, 150.0, 360.0]), power=st.sampled_from([0.01, 0.5, 1.0, 2.0, 3.0, 100.0]),
+    policy=st.sampled_from([1, 0, -1]), ids=st.booleans(), edge=st.booleans()))
+
+
+@settings(max_examples=80, deadline=None, derandomize=True, suppress_health_check=[HealthCheck.function_scoped_fixture])
+@given(fp64_problem)
+def test_fp64_matches_oracle(native, engine, pr):
+    """fp64 plans on small random problems: user counts around the 64-user steps of every wave count, 1-12 frames, the
+    property test's lattices, empty cones (fov 0.5), an underflowing power (100: the reference's NaN frames), exact pixel
+    corners, absent users and frames without a user, grid samples or direction ids, every table policy."""
+    rng = np.random.default_rng(pr["seed"])
+    U, T, tcs = pr["U"], pr["T"], pr["tcs"]
+    if pr["edge"]:
+        mu = rng.integers(0, W + 1, (T, U)) / W
+        mv = rng.integers(0, H + 1, (T, U)) / H
+    else:
+        mu, mv = rng.random((T, U)), rng.random((T, U))
+    gone = rng.random((T, U)) < pr["p_absent"]
+    gone[:, 0] = False
+    if pr["empty_frame"]:
+        gone[rng.integers(0, T)] = True
+    mu[gone] = np.nan
+    mv[gone] = np.nan
+    plan = make_plan(native, engine, tcs, pr["fov"], pr["power"], policy=pr["policy"])
+    try:
+        call = (lambda a, b: plan.spatial(ids=grid_ids(a, b), want_weights=True, check=False)) if pr["ids"] else \
+               (lambda a, b: plan.spatial(mu=a, mv=b, want_weights=True, check=False))
+        res = call(mu, mv)
+        table_asked = pr["policy"] > 0       # policy 0: fewer samples than VET_TABLE_SAMPLES_PER_DIRECTION per direction
+        assert [plan.last_formulation(k) for k in range(len(tcs))] == [fp64_form(tc + 1, table_asked) for tc in tcs]
+        empty = gone.all(axis=1)
+        assert res["code"] == (native.VET_ERR_EMPTY if empty.any() else native.VET_OK)
+        assert np.array_equal(res["present"], (~gone).sum(axis=1))
+        ent, assign, weights = fp64_oracle(mu, mv, tcs, pr["fov"], pr["power"])
+        assert np.array_equal(res["assign"], assign)
+        assert np.array_equal(np.isnan(res["entropy"]), np.isnan(ent))
+        ok = ~np.isnan(ent)
+        np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=RTOL, atol=1e-15)
+        np.testing.assert_allclose(res["weights"], weights, rtol=W_RTOL, atol=w_atol(U, pr["power"]))
+        assert np.array_equal(bits(res["weights"][empty]), bits(np.zeros_like(weights[empty])))   # no keys
+        if T >= 2:                                             # bit-identical under a split of the frame axis
+            h = T // 2
+            lo, hi = call(mu[:h], mv[:h]), call(mu[h:], mv[h:])
+            assert np.array_equal(bits(np.concatenate([lo["entropy"], hi["entropy"]])), bits(res["entropy"]))
+            assert np.array_equal(bits(np.concatenate([lo["weights"], hi["weights"]])), bits(res["weights"]))
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("policy", [1, -1])
+def test_explicit_direction_table_ids(native, engine, policy):
+    """The *_ids entry points of an fp64 plan over arbitrary Vectors (no mirror sharing in the alias table), frame by frame
+    against the oracle."""
+    rng = np.random.default_rng(9)
+    table = vo.vector_from_spherical(np.round(rng.uniform(-180, 180, 300), 1), np.round(rng.uniform(-90, 90, 300), 1))
+    ids = rng.integers(0, 300, (50, 24)).astype(np.int32)
+    ids[rng.random(ids.shape) < 0.1] = -1
+    ids[:, 0] = np.abs(ids[:, 0])
+    L = vo.fibonacci_lattice(100)
+    plan = make_plan(native, engine, [100], policy=policy, dir_table=table)
+    res = plan.spatial(ids=ids, want_weights=True)
+    assert plan.last_formulation(0) == ("dtable" if policy > 0 else "precise")
+    for t in range(len(ids)):
+        e, hist, near = vo.spatial_entropy_frame(table[ids[t][ids[t] >= 0]], L)
+        np.testing.assert_allclose(res["entropy"][t], e, rtol=RTOL)
+        np.testing.assert_allclose(res["weights"][t], hist, rtol=W_RTOL, atol=w_atol(ids.shape[1]))
+        assert np.array_equal(res["assign"][t][ids[t] >= 0], near)
+    assert np.array_equal(res["present"], (ids >= 0).sum(1))
+    plan.close()
+
+
+@pytest.mark.parametrize("policy", [1, -1])
+def test_ids_with_several_lattices(native, engine, policy):
+    rng = np.random.default_rng(12)
+    table = vo.vector_from_spherical(np.round(rng.uniform(-180, 180, 500), 1), np.round(rng.uniform(-90, 90, 500), 1))
+    ids = rng.integers(0, 500, (30, 70)).astype(np.int32)
+    ids[rng.random(ids.shape) < 0.2] = -1
+    ids[:, 3] = 7
+    tcs = [100, 20, 250]
+    plan = make_plan(native, engine, tcs, policy=policy, dir_table=table)
+    res = plan.spatial(ids=ids, want_weights=True)
+    assert [plan.last_formulation(k) for k in range(3)] == ["dtable" if policy > 0 else "precise"] * 3
+    ref = np.zeros(len(ids))
+    for k, tc in enumerate(tcs):
+        L = vo.fibonacci_lattice(tc)
+        for t, r in enumerate(ids):
+            e, hist, _ = vo.spatial_entropy_frame(table[r[r >= 0]], L)
+            ref[t] += e
+            if k == 0:
+                np.testing.assert_allclose(res["weights"][t], hist, rtol=W_RTOL, atol=w_atol(ids.shape[1]))
+    np.testing.assert_allclose(res["entropy"], ref / len(tcs), rtol=RTOL)
+    assert np.array_equal(res["present"], (ids >= 0).sum(1))
+    plan.close()
+
+
+USER_SHARE_U = [1, 2, 3, 5, 63, 64, 65, 255, 256, 257, 2049, 4097]
+
+
+@pytest.mark.parametrize("tc,nw", [(500, 4), (4000, 2), (6000, 1)])
+def test_user_share_edges(native, engine, tc, nw):
+    """Users cut into NW contiguous shares: fewer users than waves (empty shares), partial 64-user steps, thousands of
+    users (many steps per wave).  dtable's weights are the weights pass's bits, against the oracle; a frame without a
+    user is NaN with no keys (VET_ERR_EMPTY); out-of-range samples and ids are VET_ERR_RANGE and count as absent."""
+    from tests._fp64 import weights_nw
+    assert weights_nw(tc + 1) == nw
+    plan = make_plan(native, engine, [tc], policy=1)
+    off = make_plan(native, engine, [tc], policy=-1, fp64=False)
+    worst = 0.0
+    for U in USER_SHARE_U:
+        mu, mv = video(U, 3, 1000 + U)
+        mu, mv = np.concatenate([mu, np.full((1, U), np.nan)]), np.concatenate([mv, np.full((1, U), np.nan)])
+        res = plan.spatial(mu=mu, mv=mv, want_weights=True, check=False)
+        assert plan.last_formulation(0) == "dtable"
+        assert res["code"] == native.VET_ERR_EMPTY
+        present = ~np.isnan(mu)
+        assert np.array_equal(res["present"], present.sum(1))
+        ref = off.spatial(mu=mu, mv=mv, want_weights=True, check=False)
+        assert np.array_equal(bits(res["weights"]), bits(ref["weights"])), U
+        ent, assign, weights = fp64_oracle(mu, mv, [tc])
+        assert np.array_equal(res["assign"], assign)
+        assert np.isnan(res["entropy"][3]) and np.array_equal(np.isnan(res["entropy"]), np.isnan(ent))
+        worst = max(worst, max_rel(res["entropy"], ent))
+        ok = ~np.isnan(ent)
+        np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=RTOL, err_msg=str(U))
+        np.testing.assert_allclose(res["weights"], weights, rtol=W_RTOL, atol=w_atol(U), err_msg=str(U))
+        assert np.array_equal(bits(res["weights"][3]), bits(np.zeros(tc + 1)))
+        # out of range: flagged, treated as absent
+        bad_mu, bad_mv = mu[:1].copy(), mv[:1].copy()
+        bad_mu[0, U // 2], bad_mv[0, U // 2] = 1.5, 0.5
+        r = plan.spatial(mu=bad_mu, mv=bad_mv, check=False)
+        assert r["code"] == native.VET_ERR_RANGE
+        assert r["present"][0] == present[0].sum() - (1 if present[0, U // 2] else 0)
+        ids = grid_ids(mu[:1], mv[:1])
+        ids[0, U - 1] = (W + 1) * (H + 1)
+        r = plan.spatial(ids=ids, want_weights=True, check=False)
+        assert r["code"] == native.VET_ERR_RANGE
+        assert r["present"][0] == present[0].sum() - (1 if present[0, U - 1] else 0)
+    print(f"dtable at NW = {nw}, U = {USER_SHARE_U}: max relative difference to the oracle {worst:.3e}")
+    off.close()
+    plan.close()
+
+
+@pytest.mark.parametrize("policy", [1, 0])
+def test_batch_shapes_equal_single_calls_and_the_oracle(native, engine, policy):
+    shapes = [(1, 5), (33, 7), (3000, 4), (64, 100)]
+    vids = [video(u, t, 50 + i) for i, (u, t) in enumerate(shapes)]
+    tcs = [50, 100]
+    plan = make_plan(native, engine, tcs, policy=policy)
+    batch = plan.spatial_batch(vids, want_assign=True)
+    for (mu, mv), got in zip(vids, batch):
+        one = plan.spatial(mu=mu, mv=mv)
+        assert np.array_equal(bits(got["entropy"]), bits(one["entropy"]))
+        assert np.array_equal(got["assign"], one["assign"]) and np.array_equal(got["present"], one["present"])
+        ent, assign, _ = vo.spatial_series(mu, mv, W, H, tcs)
+        assert np.array_equal(got["assign"], assign)
+        np.testing.assert_allclose(got["entropy"], ent, rtol=RTOL)
+    plan.close()
+
+
+NO_ROWS_CASES = (("k2", [100, 20], 70, 40), ("k1", [500], 130, 12))
+
+
+def _no_exact_rows_worker(q, env):
+    """Child process: fp64 plans with / without the exact weight rows (the knob is read at engine creation)."""
+    import os
+    os.environ.update(env)
+    from viewport_entropy_toolkit import _native
+    eng = _native.Engine(0)
+    out = {}
+    for name, tcs, U, T in NO_ROWS_CASES:
+        mu, mv = video(U, T, U + T)
+        plan = _native.Plan(eng, [vo.fibonacci_lattice(tc) for tc in tcs], 120.0, 2.0, True, W, H)
+        plan.set_table_policy(1)
+        plan.set_fp64(True)
+        eager = plan.spatial(mu=mu, mv=mv, want_weights=True)
+        forms = [plan.last_formulation(k) for k in range(len(tcs))]
+        lazy = plan.spatial_resident(mu=mu, mv=mv)
+        out[name] = (eager["entropy"], eager["assign"], eager["weights"], lazy["result"].rows(1, 3, T - 5), forms)
+        lazy["result"].close()
+        plan.close()
+    q.put(out)
+
+
+def test_fp64_plans_without_the_exact_rows():
+    """VET_NO_EXACT_ROWS=1 (as if the rows did not fit the device): every lattice of an fp64 plan runs `precise`, the
+    weights come from the precise sweep; oracle parity, eager weights == fetched weights."""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_no_exact_rows_worker, args=(q, {"VET_NO_EXACT_ROWS": "1"}))
+    p.start()
+    out = q.get(timeout=600)
+    p.join(60)
+    assert p.exitcode == 0
+    for name, tcs, U, T in NO_ROWS_CASES:
+        e, a, w, fetched, forms = out[name]
+        assert forms == ["precise"] * len(tcs)
+        mu, mv = video(U, T, U + T)
+        ent, assign, weights = vo.spatial_series(mu, mv, W, H, tcs, want_weights=True)
+        assert np.array_equal(a, assign)
+        np.testing.assert_allclose(e, ent, rtol=RTOL)
+        np.testing.assert_allclose(w, weights, rtol=W_RTOL, atol=w_atol(U))
+        assert np.array_equal(bits(fetched), bits(w[3:T - 2]))

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import vet_oracle as vo
+from tests._fp64 import fp64_form
 from tests._tol import W_RTOL, w_atol
 
 pytestmark = pytest.mark.gpu
@@ -64,35 +65,70 @@ def oracle_for(tcs, fov, power, name, mu, mv):
     return _ORACLE[key]
 
 
+def case_weights(rows, name, perm, near):
+    """Lattice 0's tile_weights of a contract case: the users' FP64 weight rows added in column order."""
+    if name == "one user":
+        return rows
+    return rows + rows[perm if name == "two users, random pair" else near]
+
+
 @pytest.mark.parametrize("tcs,fov,power", EXTREME + UNDERFLOW + [([500], 120.0, 2.0), ([20, 50], 120.0, 2.0)])
 @pytest.mark.parametrize("policy", [1, -1, 0])
-def test_single_and_two_user_frames_over_all_directions(native, engine, tcs, fov, power, policy):
+def test_single_and_two_user_frames_over_all_directions(native, engine, tcs, fov, power, policy, fp64=False):
+    """fp64 plans (vet_plan_set_fp64): `dtable` where a table is asked for, `precise` otherwise; entropy within 1e-9 of
+    the oracle, the NaN frames exactly, and lattice 0's tile_weights against the FP64 weight rows."""
     cases = contract_cases()
     plan = native.Plan(engine, [vo.fibonacci_lattice(tc) for tc in tcs], fov, power, True, W, H)
     plan.set_table_policy(policy)
+    if fp64:
+        plan.set_fp64(True)
+        rows = vo.tile_weight_rows(vo.direction_grid(W, H).reshape(-1, 3), vo.fibonacci_lattice(tcs[0]), fov, power)
+        rng = np.random.default_rng(20301)
+        perm = rng.permutation(len(rows))
+        near = (np.arange(len(rows)) + 1) % len(rows)
     tab_bound, sweep_bound = plan.error_bounds(0)
     for name, (mu, mv) in cases.items():
-        res = plan.spatial(mu=mu, mv=mv)
-        form = plan.last_formulation(0)
+        res = plan.spatial(mu=mu, mv=mv, want_weights=fp64)
         # an integer formulation only where the plan's own bound puts it inside the contract
         table_asked = policy > 0 or (policy == 0 and mu.size >= native.TABLE_SAMPLES_PER_DIRECTION * (W + 1) * (H + 1))
-        want = ("table" if tab_bound <= 1e-7 else "ftable") if table_asked else ("sweep" if sweep_bound <= 1e-7 else "precise")
-        assert form == want, (name, form, tab_bound, sweep_bound)
+        if fp64:
+            forms = [plan.last_formulation(k) for k in range(len(tcs))]
+            assert forms == [fp64_form(tc + 1, table_asked) for tc in tcs], (name, forms)
+            form = forms[0]
+        else:
+            form = plan.last_formulation(0)
+            want = ("table" if tab_bound <= 1e-7 else "ftable") if table_asked else ("sweep" if sweep_bound <= 1e-7 else "precise")
+            assert form == want, (name, form, tab_bound, sweep_bound)
         ent, assign = oracle_for(tcs, fov, power, name, mu, mv)
         assert np.array_equal(res["assign"], assign), name
         assert np.array_equal(np.isnan(res["entropy"]), np.isnan(ent)), name
         ok = ~np.isnan(ent)
-        np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=1e-6, atol=ATOL, err_msg=f"{name} [{form}]")
+        np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=1e-9 if fp64 else 1e-6, atol=ATOL,
+                                   err_msg=f"{name} [{form}]")
+        if fp64:
+            d, big = np.abs(res["entropy"][ok] - ent[ok]), np.abs(ent[ok]) >= 1e-6
+            print(f"fp64 {tcs} fov {fov} p {power} policy {policy} {name} [{form}]: max relative difference "
+                  f"{(d[big] / np.abs(ent[ok][big])).max(initial=0):.3e} (entropy >= 1e-6), "
+                  f"max absolute difference {d[~big].max(initial=0):.3e} below")
+            np.testing.assert_allclose(res["weights"], case_weights(rows, name, perm, near), rtol=W_RTOL,
+                                       atol=w_atol(mu.shape[1], power), err_msg=name)
     plan.close()
+
+
+@pytest.mark.parametrize("tcs,fov,power", EXTREME + UNDERFLOW + [([500], 120.0, 2.0), ([20, 50], 120.0, 2.0)])
+@pytest.mark.parametrize("policy", [1, -1, 0])
+def test_single_and_two_user_frames_over_all_directions_fp64(native, engine, tcs, fov, power, policy):
+    """The same on fp64 plans (vet_plan_set_fp64): `dtable` or `precise`, entropy within 1e-9."""
+    test_single_and_two_user_frames_over_all_directions(native, engine, tcs, fov, power, policy, fp64=True)
 
 
 @pytest.mark.parametrize("tcs", [[1], [2], [3], [1, 3], [3, 50], [50, 3]])
 @pytest.mark.parametrize("policy", [1, -1, 0])
 @pytest.mark.parametrize("fov,power", [(120.0, 2.0), (30.0, 0.5), (360.0, 1.0)])
-def test_degenerate_lattices(native, engine, tcs, policy, fov, power):
+def test_degenerate_lattices(native, engine, tcs, policy, fov, power, fp64=False):
     """1-, 3- and 3-tile lattices (tile_count 1, 2, 3 -> n = 1, 3, 3): frames whose users weigh on one tile
     only, frames where nobody has a tile in the FoV, the 0 / -0.0 normaliser of a one-tile lattice; the
-    nan / 0.0 pattern must be the reference's."""
+    nan / 0.0 pattern must be the reference's.  fp64 plans: `dtable` or `precise` by the table rule, 1e-9."""
     rng = np.random.default_rng(sum(tcs) * 7 + int(fov))
     U, T = 61, 48
     mu, mv = rng.random((T, U)), rng.random((T, U))
@@ -104,15 +140,28 @@ def test_degenerate_lattices(native, engine, tcs, policy, fov, power):
     mv[:8, 1:] = np.nan
     plan = native.Plan(engine, [vo.fibonacci_lattice(tc) for tc in tcs], fov, power, True, W, H)
     plan.set_table_policy(policy)
+    if fp64:
+        plan.set_fp64(True)
     res = plan.spatial(mu=mu, mv=mv, want_weights=True)
+    if fp64:
+        table_asked = policy > 0 or (policy == 0 and mu.size >= native.TABLE_SAMPLES_PER_DIRECTION * (W + 1) * (H + 1))
+        assert [plan.last_formulation(k) for k in range(len(tcs))] == [fp64_form(tc + 1, table_asked) for tc in tcs]
     ent, assign, weights = vo.spatial_series(mu, mv, W, H, tcs, fov_angle=fov, power_factor=power, want_weights=True)
     assert np.array_equal(res["assign"], assign)
     assert np.array_equal(np.isnan(res["entropy"]), np.isnan(ent)), (res["entropy"][:10], ent[:10])
     ok = ~np.isnan(ent)
-    np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=1e-6, atol=ATOL)
+    np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=1e-9 if fp64 else 1e-6, atol=ATOL)
     # tile_weights values: the reference's under every formulation (tests/_tol.py)
     np.testing.assert_allclose(res["weights"], weights, rtol=W_RTOL, atol=w_atol(U, power))
     plan.close()
+
+
+@pytest.mark.parametrize("tcs", [[1], [2], [3], [1, 3], [3, 50], [50, 3]])
+@pytest.mark.parametrize("policy", [1, -1, 0])
+@pytest.mark.parametrize("fov,power", [(120.0, 2.0), (30.0, 0.5), (360.0, 1.0)])
+def test_degenerate_lattices_fp64(native, engine, tcs, policy, fov, power):
+    """The same on fp64 plans (vet_plan_set_fp64): `dtable` or `precise`, entropy within 1e-9."""
+    test_degenerate_lattices(native, engine, tcs, policy, fov, power, fp64=True)
 
 
 @pytest.mark.parametrize("policy", [1, -1, 0])
@@ -207,11 +256,12 @@ def test_fp_table_is_bit_reproducible(native, engine, tcs, fov, power):
 
 @pytest.mark.parametrize("tcs,fov,power", [([50], 120.0, 50.0), ([50], 120.0, 20.0)])
 @pytest.mark.parametrize("policy", [1, -1])
-def test_tiny_entropies_against_extended_precision(native, engine, tcs, fov, power, policy):
+def test_tiny_entropies_against_extended_precision(native, engine, tcs, fov, power, policy, fp64=False):
     """Where the 1e-6 relative contract meets the FP64 rounding floor of the reference's own -p*log2(p) (single-user
     frames whose entropy is 1e-9 ... 4e-12: the ATOL term of the tests above), the comparison is made against the
     entropy evaluated in extended precision (numpy longdouble) from the same FP64 tile weights: the engine must be
-    within 1e-6 relative of it, or at most twice as far from it as the FP64 reference path itself gets."""
+    within 1e-6 relative of it, or at most twice as far from it as the FP64 reference path itself gets.  `dtable`
+    (fp64 plans asking for a table) computes the reference's own FP64 arithmetic: within 1e-9 relative, or that floor."""
     if np.finfo(np.longdouble).eps > 1e-18:
         pytest.skip("no extended precision on this host")
     L = vo.fibonacci_lattice(tcs[0])
@@ -226,15 +276,31 @@ def test_tiny_entropies_against_extended_precision(native, engine, tcs, fov, pow
     ref64, _ = oracle_for(tcs, fov, power, "one user", mu[:, None], mv[:, None])
     plan = native.Plan(engine, [L], fov, power, True, W, H)
     plan.set_table_policy(policy)
+    if fp64:
+        plan.set_fp64(True)
     got = plan.spatial(mu=mu[:, None], mv=mv[:, None], want_assign=False)["entropy"]
+    form = plan.last_formulation(0)
     plan.close()
+    if fp64:
+        assert form == ("dtable" if policy > 0 else "precise")
+    rtol, tiny_h = (1e-9, 2e-6) if form == "dtable" else (1e-6, 1e-8)
     ok = np.isfinite(ref64) & (h_ld > 0)
     err_eng = np.abs(got.astype(np.longdouble) - h_ld)[ok]
     err_ref = np.abs(ref64.astype(np.longdouble) - h_ld)[ok]
-    rel_ok = err_eng <= 1e-6 * h_ld[ok]
+    rel_ok = err_eng <= rtol * h_ld[ok]
     tiny = ~rel_ok
-    # the frames outside 1e-6 relative are exactly the ones where FP64 itself cannot do better
+    if fp64:
+        print(f"fp64 {tcs} fov {fov} p {power} [{form}]: max rel diff to longdouble {float((err_eng / h_ld[ok]).max()):.3e}, "
+              f"{int(tiny.sum())} frames at the FP64 floor")
+    # the frames outside `rtol` relative are exactly the ones where FP64 itself cannot do better
     floor = float(err_ref.max())
     assert floor < 1e-15
     assert np.all(err_eng[tiny] <= 2 * floor + 1e-22), (int(tiny.sum()), float(err_eng[tiny].max()), floor)
-    assert np.all(h_ld[ok][tiny] < 1e-8)
+    assert np.all(h_ld[ok][tiny] < tiny_h)
+
+
+@pytest.mark.parametrize("tcs,fov,power", [([50], 120.0, 50.0), ([50], 120.0, 20.0)])
+@pytest.mark.parametrize("policy", [1, -1])
+def test_tiny_entropies_against_extended_precision_fp64(native, engine, tcs, fov, power, policy):
+    """The same on fp64 plans (vet_plan_set_fp64): `dtable` or `precise`, entropy within 1e-9."""
+    test_tiny_entropies_against_extended_precision(native, engine, tcs, fov, power, policy, fp64=True)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import vet_oracle as vo
+from tests._fp64 import fp64_form
 from tests._tol import W_RTOL, w_atol
 
 pytestmark = pytest.mark.gpu
@@ -406,15 +407,22 @@ def test_table_formulation_on_a_larger_grid(native, engine):
     plan.close()
 
 
-@pytest.mark.parametrize("fov,power", [(180.0, 2.0), (360.0, 1.0), (0.5, 2.0), (120.0, 50.0), (120.0, 0.01),
-                                       (119.999, 2.0), (120.001, 2.0), (60.0, 1.0), (300.0, 0.3)])
+EXTREME_CONFIGS = [(180.0, 2.0), (360.0, 1.0), (0.5, 2.0), (120.0, 50.0), (120.0, 0.01), (119.999, 2.0), (120.001, 2.0),
+                   (60.0, 1.0), (300.0, 0.3)]
+
+
+@pytest.mark.parametrize("fov,power", EXTREME_CONFIGS)
 @pytest.mark.parametrize("policy", [-1, 1])
-def test_extreme_entropy_configs(native, engine, fov, power, policy):
+def test_extreme_entropy_configs(native, engine, fov, power, policy, fp64=False):
     """Cone edges (fov 180 / 360 / sub-degree), the fast-acos boundary at 120 degrees, and very
-    large / small power factors, in both weighted formulations."""
+    large / small power factors, in both weighted formulations; fp64 plans: `dtable` / `precise` within 1e-9."""
     mu, mv = video(60, 40, seed=int(fov * 10 + power))
     plan = plan_for(native, engine, [100, 20], policy=policy, fov=fov, power=power)
+    if fp64:
+        plan.set_fp64(True)
     res = plan.spatial(mu=mu, mv=mv, want_weights=True)
+    if fp64:
+        assert [plan.last_formulation(k) for k in range(2)] == [fp64_form(n, policy > 0) for n in (101, 21)]
     ent, assign, weights = vo.spatial_series(mu, mv, 100, 200, [100, 20], fov_angle=fov, power_factor=power,
                                              want_weights=True)
     assert np.array_equal(res["assign"], assign)
@@ -423,8 +431,15 @@ def test_extreme_entropy_configs(native, engine, fov, power, policy):
     assert np.array_equal(np.isnan(res["entropy"]), np.isnan(ent))
     ok = np.isfinite(ent)
     fp = "ftable" in (plan.last_formulation(0), plan.last_formulation(1))       # FP32 table weights: |dH|/H <= 1.2e-7
-    np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=2e-7 if fp else 1e-8, atol=1e-15)
+    np.testing.assert_allclose(res["entropy"][ok], ent[ok], rtol=1e-9 if fp64 else 2e-7 if fp else 1e-8, atol=1e-15)
     plan.close()
+
+
+@pytest.mark.parametrize("fov,power", EXTREME_CONFIGS)
+@pytest.mark.parametrize("policy", [-1, 1])
+def test_extreme_entropy_configs_fp64(native, engine, fov, power, policy):
+    """The same on fp64 plans (vet_plan_set_fp64): `dtable` or `precise`, entropy within 1e-9."""
+    test_extreme_entropy_configs(native, engine, fov, power, policy, fp64=True)
 
 
 def test_cabi_argument_validation(native, engine):
@@ -451,21 +466,111 @@ def test_cabi_argument_validation(native, engine):
     plan.close()
 
 
+STATUS_CASES = (("table", True, 1, False), ("sweep", True, -1, False), ("dtable", True, 1, True),
+                ("precise", True, -1, True), ("unweighted", False, 0, False))
+
+
+def _status_worker(q):
+    """Child process (torch owns the device buffers): d_status of the device-pointer entry points with many bad samples
+    per thread, and of the same call with those samples made valid."""
+    import torch
+    from viewport_entropy_toolkit import _native
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    eng = _native.Engine(0)
+    mu, mv, bad = _status_video()
+    clean_mu, clean_mv = np.where(bad, 0.5, mu), np.where(bad, 0.5, mv)
+    T, U = mu.shape
+    out = {}
+    for name, weighted, policy, fp64 in STATUS_CASES:
+        plan = _native.Plan(eng, [vo.fibonacci_lattice(tc) for tc in (50, 100)], 120.0, 2.0, weighted, 100, 200)
+        plan.set_table_policy(policy)
+        if fp64:
+            plan.set_fp64(True)
+        for tag, (a, b) in (("bad", (mu, mv)), ("clean", (clean_mu, clean_mv))):
+            d_mu, d_mv = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+            ent = torch.empty(T, dtype=torch.float64, device=dev)
+            tr = torch.empty(T - 1, dtype=torch.float64, device=dev)
+            st = torch.zeros(2, dtype=torch.int32, device=dev)
+            st_tr = torch.zeros(2, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            plan.spatial_device(d_mu.data_ptr(), d_mv.data_ptr(), U, T, ent.data_ptr(), d_status=st.data_ptr())
+            form = plan.last_formulation(0)
+            if policy == 0:
+                plan.transition_device(d_mu.data_ptr(), d_mv.data_ptr(), U, T, tr.data_ptr(), d_status=st_tr.data_ptr())
+            eng.synchronize()
+            out[(name, tag)] = (form, st.cpu().numpy().tolist(), st_tr.cpu().numpy().tolist(), ent.cpu().numpy())
+        plan.close()
+    q.put(out)
+
+
+def _status_video():
+    """1000 users x 6 frames: frame 1 wholly out of range, half of frame 3 out of range, frame 4 without a user.  Every
+    thread of every formulation meets several samples of a frame (1000 users over at most 256 threads)."""
+    rng = np.random.default_rng(3)
+    T, U = 6, 1000
+    mu, mv = rng.random((T, U)), rng.random((T, U))
+    bad = np.zeros((T, U), dtype=bool)
+    bad[1] = True
+    bad[3, ::2] = True
+    mu[1] = 1.5
+    mv[3, ::2] = -0.25
+    mu[4] = np.nan
+    mv[4] = np.nan
+    return mu, mv, bad
+
+
+def test_status_words_with_several_bad_samples_per_thread():
+    """include/vet.h, d_status of vet_spatial_entropy / vet_transition_entropy: word 0 is non-zero if and only if some
+    sample is outside [0,1] (each thread flags whether it met one; it is not their number), word 1 counts the frames
+    (rows) without a user exactly; out-of-range samples count as absent."""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_status_worker, args=(q,))
+    p.start()
+    out = q.get(timeout=600)
+    p.join(60)
+    assert p.exitcode == 0
+    for name, weighted, policy, fp64 in STATUS_CASES:
+        form_bad, st_bad, tr_bad, ent_bad = out[(name, "bad")]
+        form_clean, st_clean, tr_clean, ent_clean = out[(name, "clean")]
+        if weighted:
+            assert form_bad == form_clean == name
+        assert st_bad[0] > 0 and st_bad[1] == 2, (name, st_bad)              # frame 1 has no valid sample: no user
+        assert st_clean == [0, 1], (name, st_clean)
+        assert np.array_equal(np.isnan(ent_bad), np.arange(6) % 3 == 1)      # frames 1 and 4
+        if policy == 0:
+            assert tr_bad[0] > 0 and tr_bad[1] == 4, (name, tr_bad)          # rows 0, 1, 3, 4
+            assert tr_clean == [0, 2], (name, tr_clean)
+
+
 @pytest.mark.parametrize("policy", [-1, 1])
-def test_very_large_lattice(native, engine, policy):
-    """tile_count = 5000 (5001 tiles): more tile groups than waves in the sweep, long table rows."""
+def test_very_large_lattice(native, engine, policy, fp64=False):
+    """tile_count = 5000 (5001 tiles): more tile groups than waves in the sweep, long table rows; fp64 plans run
+    `dtable` at 2 waves (the weights pass's wave count for 5001 tiles) or `precise`."""
     mu, mv = video(50, 12, seed=5)
     plan = plan_for(native, engine, [5000], policy=policy)
+    if fp64:
+        plan.set_fp64(True)
     res = plan.spatial(mu=mu, mv=mv, want_weights=True)
+    if fp64:
+        assert plan.last_formulation(0) == ("dtable" if policy > 0 else "precise")
     ent, assign, weights = vo.spatial_series(mu, mv, 100, 200, [5000], want_weights=True)
     assert np.array_equal(res["assign"], assign)
-    np.testing.assert_allclose(res["entropy"], ent, rtol=1e-8)
+    np.testing.assert_allclose(res["entropy"], ent, rtol=1e-9 if fp64 else 1e-8)
     np.testing.assert_allclose(res["weights"], weights, rtol=W_RTOL, atol=w_atol(50))
     tr = plan.transition(mu=mu, mv=mv)
     e2, pairs = vo.transition_series(mu, mv, 100, 200, [5000])
     assert np.array_equal(tr["pairs"], pairs)
     np.testing.assert_allclose(tr["entropy"], e2, rtol=1e-9, equal_nan=True)
     plan.close()
+
+
+@pytest.mark.parametrize("policy", [-1, 1])
+def test_very_large_lattice_fp64(native, engine, policy):
+    """The same on fp64 plans (vet_plan_set_fp64): `dtable` or `precise`, entropy within 1e-9."""
+    test_very_large_lattice(native, engine, policy, fp64=True)
 
 
 @pytest.mark.parametrize("policy", [-1, 1])

@@ -127,7 +127,7 @@ static int run_host(vet_plan* pl, bool transition, const double* h_mu, const dou
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (keep) { *keep = res; guard.r = nullptr; }       // outputs are written also when a status word is set
-    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1 (%d samples)", status[0]);
+    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
     if (status[1])
         return fail(VET_ERR_EMPTY, transition ? "%d frame pair(s) without a user present in both frames"
                                               : "%d frame(s) without any user (Empty vector dictionary)", status[1]);
@@ -239,7 +239,7 @@ int vet_spatial_entropy_batch_host(vet_plan* pl, int n_videos, const int* n_user
     if (h_present) HIP_TRY(hipMemcpyAsync(h_present, pr, R * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(status, st, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1 (%d samples)", status[0]);
+    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
     if (status[1]) return fail(VET_ERR_EMPTY, "%d frame(s) without any user (Empty vector dictionary)", status[1]);
     return VET_OK;
 }
@@ -289,7 +289,7 @@ int vet_transition_entropy_batch_host(vet_plan* pl, int n_videos, const int* n_u
     if (h_common) HIP_TRY(hipMemcpyAsync(h_common, cm, R * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(status, st, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1 (%d samples)", status[0]);
+    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
     if (status[1]) return fail(VET_ERR_EMPTY, "%d frame pair(s) without a user present in both frames", status[1]);
     return VET_OK;
 }

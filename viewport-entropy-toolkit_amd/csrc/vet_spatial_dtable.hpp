@@ -39,7 +39,7 @@ struct DtableParams {
     int32_t* assign;                 // [T*U] nearest tile of lattice 0, -1 absent, or null
     double* weights;                 // [T*n_0] tile weight sums of lattice j = 0 (the launch starts at lattice 0), or null
     int32_t* present;                // [T] or null
-    int32_t* status;                 // [2] or null: {samples outside [0,1], frames without a user}
+    int32_t* status;                 // [2] or null: {non-zero iff a sample is outside [0,1], frames without a user}
 };
 
 __host__ __device__ constexpr size_t dtable_lds_bytes(int NW, int n_sum) {
