@@ -45,7 +45,8 @@ extern "C" {
 #define VET_VERSION 141 /* 0.1.4: tile_weights values at the reference's precision under every formulation
                            (+ vet_plan_set_raw_weights); batch descriptors in an event-guarded ring;
                            0.1.4.1: vet_device_pci_bus_id; vet_plan_set_fp64 (formulation 4, `dtable`) added
-                           without a new number: existing callers see no change */
+                           without a new number: existing callers see no change; the vet_heatmap_* entry points
+                           (per-frame tile-attention heatmaps) added the same way */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -328,6 +329,40 @@ int vet_angular_distances(vet_ctx *ctx, const double *h_vectors, int64_t n_vecto
  * (get_tile_corners :530-575, compute_spherical_polygon_area :657-678) stay on the host. */
 int vet_fb_tile_boundaries(vet_ctx *ctx, const double *h_tiles, int n_tiles, int max_edges,
                            double *h_edges, int32_t *h_count);
+
+/* ---- per-frame tile-attention heatmaps -------------------------------------------------------
+ * The reference's tile-attention animation (PlotManager.update_frame / _get_color_from_intensity, create_animation,
+ * utilities/visualization_utils.py:99-247) as uint8 RGB frames [n][H][W][3], C-contiguous, equirectangular: column c
+ * covers longitude [-180 + 360c/W, -180 + 360(c+1)/W), row 0 is the top (lat +90), as video pixel coordinates.
+ *   pixel -> tile: the nearest tile of the lattice (find_nearest_tile's first minimum, k_nearest_lut's arithmetic) to the
+ *     unrounded Vector.from_spherical direction of the pixel centre; built once, by vet_heatmap_create;
+ *   colour of a tile in frame t: _get_color_from_intensity(w / n) in FP64, w = tile_weights[t][tile] (+-0.0 = grey),
+ *     n = users present (intensity 0 when n == 0): clip to [0, 1], red = i * (1 - 0.8) + 0.8, green = blue = 0.8 - i * 0.8,
+ *     byte = floor(v * 255 + 0.5);
+ *   markers (when samples are given): every present user paints a black square of side 2 * marker_radius + 1 centred on
+ *     (row, col) = (min(py * H / video_height, H - 1), min(px * W / video_width, W - 1)), px = int(mu * video_width),
+ *     py = int(mv * video_height) (integer division); columns wrap modulo W, rows clamp to [0, H); NaN = absent; a sample
+ *     outside [0, 1] draws nothing and raises no error.
+ * A heatmap belongs to its context (destroy it first) and, like the context, is used from one thread on one stream at a
+ * time.  VET_ERR_INVALID: bad sizes, marker_radius outside [0, 16], a transition result, a result of another device or
+ * lattice size; VET_ERR_UNSUPPORTED: a lattice larger than the map kernel's LDS tile cache (6783 tiles, the plans' own
+ * limit). */
+typedef struct vet_heatmap vet_heatmap;   /* W x H pixel -> tile map of one lattice, on one context's device */
+int vet_heatmap_create(vet_ctx *ctx, const double *h_tiles /* [n_tiles*3] lattice Vectors */, int n_tiles, int width,
+                       int height, int video_width, int video_height, int marker_radius, vet_heatmap **out);
+int vet_heatmap_destroy(vet_heatmap *hm);
+int vet_heatmap_read_map(vet_heatmap *hm, int32_t *h_map /* [H*W] */);
+/* device pointers, asynchronous on `stream` (same stream convention as every other entry); d_rgb 4-byte aligned */
+int vet_heatmap_render(vet_heatmap *hm, const double *d_weights /* [T][n_tiles] */, const int32_t *d_present /* [T] */,
+                       const double *d_mu, const double *d_mv /* [T][U] or both NULL: no markers */,
+                       int n_users, int n_frames, uint8_t *d_rgb /* [T][H][W][3] */, void *stream);
+/* frames [row0, row0+n_rows) of a spatial vet_result -> host; synchronous.  The weight rows never leave the device (stored
+ * rows are read in place; lazy ones are computed into the result's staging buffer); sub-blocks of frames alternate
+ * between two pinned staging buffers so that the copy of one overlaps the kernels of the next: device memory does not
+ * grow with n_rows. */
+int vet_heatmap_render_result(vet_heatmap *hm, vet_result *r, const int32_t *h_present /* [n_rows] */,
+                              const double *h_mu, const double *h_mv /* [n_rows][U] or NULL */, int n_users,
+                              int64_t row0, int64_t n_rows, uint8_t *h_rgb);
 
 /* ---- host-side track loader (no GPU involved) -------------------------------------------
  * Replaces the per-file `pd.read_csv(filepath)` + column selection of process_viewport_data

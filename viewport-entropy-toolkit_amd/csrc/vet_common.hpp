@@ -62,6 +62,31 @@ __device__ __forceinline__ void nt_store(int2* p, int2 v) {
 __device__ __forceinline__ double round6(double v) { return rint(v * 1e6) / 1e6; }
 
 
+__device__ __forceinline__ double clip_unit(double c) {        // np.clip(c, -1, 1): NaN stays NaN
+    return c != c ? c : fmin(fmax(c, -1.0), 1.0);
+}
+
+// find_nearest_tile (entropy_utils.py:89-106) of the unit vector (x, y, z) over n unit tile centres (xyz, typically in
+// LDS): np.argmin over arccos(clip(dot)) — the FIRST minimum.  arccos is monotone, so the arg-max of the cosine ('>'
+// keeps the lowest index on exact ties) finds a tile of minimal distance; where the cosines of two tiles differ by a few
+// ulp, arccos may map them to one double, and the reference then keeps the lower index: the second pass applies that
+// rule literally to the (rare) tiles of lower index within 8 ulp of the best cosine.  k_nearest_lut, k_heatmap_map.
+__device__ __forceinline__ int nearest_tile(double x, double y, double z, const double* tiles, int n) {
+    double best = -2.0;
+    int bi = 0;
+    for (int t = 0; t < n; ++t) {
+        const double c = fma(z, tiles[3 * t + 2], fma(y, tiles[3 * t + 1], x * tiles[3 * t]));
+        if (c > best) { best = c; bi = t; }
+    }
+    const double near = best - 8.0 * 2.220446049250313e-16, dbest = acos(clip_unit(best));
+    for (int t = 0; t < bi; ++t) {
+        const double c = fma(z, tiles[3 * t + 2], fma(y, tiles[3 * t + 1], x * tiles[3 * t]));
+        if (c >= near && acos(clip_unit(c)) <= dbest) { bi = t; break; }
+    }
+    return bi;
+}
+
+
 // ------------------------------------------------------------------------------------------
 // sample -> direction id
 // ------------------------------------------------------------------------------------------

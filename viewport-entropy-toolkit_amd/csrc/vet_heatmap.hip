@@ -1,0 +1,183 @@
+// vet_heatmap.hip — per-frame tile-attention heatmaps (the reference's tile-attention animation,
+// utilities/visualization_utils.py:99-204, as an equirectangular RGB raster): the kernels and their launch logic.
+// The C-ABI entry points (vet_heatmap_*) and the render pipeline of a device-resident result live in vet_hostapi.hip.
+//
+//   k_heatmap_map      pixel -> nearest tile of the lattice (find_nearest_tile over the pixel centre's direction)
+//   k_heatmap_palette  per frame and tile: _get_color_from_intensity(tile_weights / users present) as packed RGB
+//   k_heatmap_fill     the hot path: RGB[t][q] = palette[t][map[q]], a streamed store of n x H x W x 3 bytes
+//   k_heatmap_markers  per (frame, user): a black square centred on the user's viewport pixel
+// Reference citations are relative to /root/reference/src/viewport_entropy_toolkit/.
+#include "vet_host.hpp"
+#include "vet_common.hpp"
+
+namespace vet {
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_map: pixel (r, c) of a W x H equirectangular frame -> nearest tile.  The pixel centre's direction is
+// Vector.from_spherical (data_types.py:204-216) in FP64 without its 6-decimal rounding, at
+//   lon = (c + 0.5) / W * 360 - 180,   lat = 90 - (r + 0.5) / H * 180   (row 0 = lat +90, as pixel_to_spherical),
+// normalised as vector_angle_distance does (entropy_utils.py:55-58); the tile is nearest_tile's first minimum over the
+// lattice's unit centres in LDS — k_nearest_lut's arithmetic.  One thread per pixel.
+// ------------------------------------------------------------------------------------------
+__global__ void k_heatmap_map(const double* __restrict__ tiles, int n, int W, int H, uint16_t* __restrict__ map) {
+    extern __shared__ double s_tiles[];
+    for (int i = threadIdx.x; i < 3 * n; i += blockDim.x) s_tiles[i] = tiles[i];
+    __syncthreads();
+    const long HW = (long)W * H;
+    constexpr double kRad = 3.141592653589793 / 180.0;             // np.radians: x * (pi / 180)
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < HW; q += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(q / W), c = (int)(q - (long)r * W);
+        const double lon = ((double)c + 0.5) / (double)W * 360.0 - 180.0;
+        const double lat = 90.0 - ((double)r + 0.5) / (double)H * 180.0;
+        const double theta = lon * kRad, phi = (90.0 - lat) * kRad;
+        const double sp = sin(phi);
+        const double x = sp * cos(theta), y = sp * sin(theta), z = cos(phi);
+        const double len = sqrt(x * x + y * y + z * z);
+        map[q] = (uint16_t)nearest_tile(x / len, y / len, z / len, s_tiles, n);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_palette: PlotManager._get_color_from_intensity (utilities/visualization_utils.py:187-204) of every tile of
+// every frame, in FP64 and in the reference's operation order (the library builds with -ffp-contract=off: no FMA here):
+//   i = w / n (0 when no user is present), clip to [0, 1], red = i * (1 - 0.8) + 0.8, green = blue = 0.8 - i * 0.8,
+//   byte = floor(v * 255 + 0.5);  packed R | G << 8 | B << 16.
+// w = tile_weights[t][tile] (a non-key is +0.0, a zero-valued key -0.0: both give grey).  A NaN intensity clips to 0.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t colour_byte(double v) { return (uint32_t)floor(v * 255.0 + 0.5); }
+
+__global__ void k_heatmap_palette(const double* __restrict__ weights, const int32_t* __restrict__ present, long T, int n,
+                                  uint32_t* __restrict__ pal) {
+    const long total = T * (long)n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int users = present[i / n];
+        double v = users > 0 ? weights[i] / (double)users : 0.0;
+        v = fmin(fmax(v, 0.0), 1.0);
+        const double red = v * 0.19999999999999996 + 0.8;
+        const double gb = 0.8 - v * 0.8;
+        const uint32_t g = colour_byte(gb);
+        pal[i] = colour_byte(red) | g << 8 | g << 16;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_fill: RGB[p] = palette[t][map[q]] over the flat pixel space p = t * HW + q of the block's n frames.  Thread i
+// takes pixels 4i .. 4i+3: its 12 bytes start at a multiple of 4 whatever HW is and leave as ONE non-temporal dwordx3
+// store (the frames are streamed once and not reread; cdna_hip_programming.md, stores).  The map (HW u16, L2-resident)
+// and the palette rows (n_tiles u32 per frame) are the only loads.  QUAD: HW % 4 == 0, so the four pixels share a frame
+// and their map entries are one 8-byte load.  Grid-stride; (t, q) of the first quad from one division, then stepped by
+// the stride's (frames, pixels).  The last N % 4 pixels of the block are written byte-wise by the first threads.
+// ------------------------------------------------------------------------------------------
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
+
+struct FillParams {
+    const uint16_t* map;   // [HW]
+    const uint32_t* pal;   // [T][n]
+    int n;
+    long HW, N;            // pixels per frame, pixels of the block (T * HW)
+    long step_t, step_q;   // the grid stride (4 * threads) as whole frames + pixels
+    uint8_t* out;          // [N][3], 4-byte aligned
+};
+
+template <bool QUAD>
+__global__ __launch_bounds__(256) void k_heatmap_fill(const FillParams p) {
+    const long quads = p.N >> 2;
+    long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    long t = (i << 2) / p.HW, q = (i << 2) - t * p.HW;
+    const long istep = (long)gridDim.x * blockDim.x;
+    for (; i < quads; i += istep) {
+        uint32_t c[4];
+        if (QUAD) {
+            const ushort4 m = *(const ushort4*)(p.map + q);
+            const uint32_t* row = p.pal + t * p.n;
+            c[0] = row[m.x]; c[1] = row[m.y]; c[2] = row[m.z]; c[3] = row[m.w];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                long tk = t, qk = q + k;
+                while (qk >= p.HW) { qk -= p.HW; ++tk; }
+                c[k] = p.pal[tk * p.n + p.map[qk]];
+            }
+        }
+        const u32x3 v = {c[0] | c[1] << 24, c[1] >> 8 | c[2] << 16, c[2] >> 16 | c[3] << 8};
+        __builtin_nontemporal_store(v, (u32x3_a4*)(p.out + 12 * i));
+        t += p.step_t; q += p.step_q;
+        if (q >= p.HW) { q -= p.HW; ++t; }
+    }
+    const int tail = (int)(p.N & 3);
+    if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+        const long px = (quads << 2) + threadIdx.x;
+        const long tk = px / p.HW, qk = px - tk * p.HW;
+        const uint32_t c = p.pal[tk * p.n + p.map[qk]];
+        uint8_t* o = p.out + 3 * px;
+        o[0] = (uint8_t)c; o[1] = (uint8_t)(c >> 8); o[2] = (uint8_t)(c >> 16);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_markers: one thread per (frame, user) of the block, after the fill on the same stream.  The viewport pixel
+// is the engine's own quantiser (grid_dir: normalize_to_pixel, data_utils.py:243-261, px = int(mu * video_width)); a
+// NaN sample is absent and a sample outside [0, 1] draws nothing (the run that produced the weights reported it).
+//   col = min(px * W / video_width, W - 1), row = min(py * H / video_height, H - 1)   (integer division)
+// A (2 radius + 1)^2 black square around (row, col): columns wrap modulo W (longitude is periodic), rows clamp to
+// [0, H).  Overlapping squares write the same bytes, so the result does not depend on the order.
+// ------------------------------------------------------------------------------------------
+__global__ void k_heatmap_markers(const double* __restrict__ mu, const double* __restrict__ mv, int U, long T, int VW,
+                                  int VH, int W, int H, int radius, uint8_t* __restrict__ out) {
+    const long total = T * (long)U;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        bool bad = false;
+        const int id = grid_dir(mu[i], mv[i], VW, VH, bad);
+        if (id < 0) continue;
+        const long f = i / U;
+        const long py = id / (VW + 1), px = id - py * (VW + 1);
+        const long col = min(px * W / VW, (long)W - 1), row = min(py * H / VH, (long)H - 1);
+        for (long rr = max(row - radius, 0L); rr <= min(row + radius, (long)H - 1); ++rr) {
+            uint8_t* line = out + (f * H + rr) * (long)W * 3;
+            for (long dc = -radius; dc <= radius; ++dc) {
+                long cc = (col + dc) % W;
+                if (cc < 0) cc += W;
+                uint8_t* o = line + 3 * cc;
+                o[0] = 0; o[1] = 0; o[2] = 0;
+            }
+        }
+    }
+}
+
+}  // namespace vet
+
+namespace vh {
+
+int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uint16_t* d_map, hipStream_t s) {
+    const size_t lds = (size_t)n * 3 * sizeof(double);
+    if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void*)vet::k_heatmap_map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(vet::k_heatmap_map, dim3(grid_for((long)W * H, 256, c->n_cu)), dim3(256), lds, s, d_unit_tiles, n,
+                       W, H, d_map);
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
+
+int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, const int32_t* d_present, const double* d_mu,
+                   const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
+    const long HW = (long)g.W * g.H, N = HW * T;
+    hipLaunchKernelGGL(vet::k_heatmap_palette, dim3(grid_for((long)T * g.n, 256, c->n_cu)), dim3(256), 0, s, d_weights,
+                       d_present, (long)T, g.n, d_pal);
+    HIP_TRY(hipGetLastError());
+    const long quads = N >> 2;
+    const int grid = grid_for(quads > 0 ? quads : 1, 256, c->n_cu);
+    const long stride = 4L * grid * 256;
+    const vet::FillParams fp{g.d_map, d_pal, g.n, HW, N, stride / HW, stride % HW, d_rgb};
+    if (HW % 4 == 0) hipLaunchKernelGGL(vet::k_heatmap_fill<true>, dim3(grid), dim3(256), 0, s, fp);
+    else hipLaunchKernelGGL(vet::k_heatmap_fill<false>, dim3(grid), dim3(256), 0, s, fp);
+    HIP_TRY(hipGetLastError());
+    if (d_mu && d_mv && U > 0) {
+        hipLaunchKernelGGL(vet::k_heatmap_markers, dim3(grid_for((long)T * U, 256, c->n_cu)), dim3(256), 0, s, d_mu, d_mv,
+                           U, (long)T, g.VW, g.VH, g.W, g.H, g.radius, d_rgb);
+        HIP_TRY(hipGetLastError());
+    }
+    return VET_OK;
+}
+
+}  // namespace vh

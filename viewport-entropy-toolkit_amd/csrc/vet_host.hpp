@@ -5,7 +5,8 @@
 //                       error bounds; parity read-back hooks; angular distances; tile boundary geometry
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
-//   vet_hostapi.hip     host-buffer entry points and device-resident results (no kernels of their own)
+//   vet_heatmap.hip     the heatmap kernels (pixel -> tile map, palette, fill, markers) and their launch logic
+//   vet_hostapi.hip     host-buffer entry points, device-resident results and heatmaps (no kernels of their own)
 // Every kernel header is included by exactly one of them.  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
@@ -285,6 +286,18 @@ int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s);
 const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k);
 // (mu, mv) -> direction ids [n] (-1 absent or out of range) on the plan's pixel grid
 int sample_ids(const vet_plan* pl, const double* d_mu, const double* d_mv, long n, int32_t* d_out, hipStream_t s);
+
+// vet_heatmap.hip: per-frame tile-attention heatmaps.  heatmap_map: W x H pixel -> nearest tile of the n unit centres
+// d_unit_tiles (k_heatmap_map).  heatmap_render: frames [0, T) -> d_rgb [T][H][W][3] (k_heatmap_palette into d_pal
+// [T][n], k_heatmap_fill, then k_heatmap_markers when d_mu / d_mv are given), enqueued on s.
+struct HeatmapGeom {
+    const uint16_t* d_map = nullptr;   // [H][W] tile index
+    int n = 0, W = 0, H = 0;           // lattice size, frame size
+    int VW = 0, VH = 0, radius = 0;    // video size of the samples (marker quantiser), marker half-width
+};
+int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uint16_t* d_map, hipStream_t s);
+int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, const int32_t* d_present, const double* d_mu,
+                   const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s);
 
 // dynamic-LDS limits of the run kernels (once per context, from vet_plan_create)
 int spatial_set_attrs(vet_ctx* c);

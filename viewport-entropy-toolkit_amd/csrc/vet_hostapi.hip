@@ -1,8 +1,12 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h): stage through the context's grow-only device
-// buffers, run the device-pointer entry points, copy back (synchronous); device-resident results (vet_result).
+// buffers, run the device-pointer entry points, copy back (synchronous); device-resident results (vet_result); heatmaps
+// (vet_heatmap: the map and the render pipeline; the kernels are vet_heatmap.hip's).
 // No kernels of its own and no CPU compute path.
 #include "vet_host.hpp"
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -14,6 +18,7 @@ extern "C" {
 
 struct vet_result {
     int device = 0;                      // the result may outlive its context: only the device id is kept
+    bool transition = false;
     void* d[2] = {nullptr, nullptr};     // 0: assign / pairs, 1: weights / srccount (null when the weights are lazy)
     size_t row_bytes[2] = {0, 0};
     int64_t rows = 0;
@@ -67,6 +72,7 @@ static int run_host(vet_plan* pl, bool transition, const double* h_mu, const dou
         *keep = nullptr;
         res = new vet_result();
         res->device = c->device;
+        res->transition = transition;
         res->rows = R > 0 ? R : 0;
         res->row_bytes[0] = transition ? (size_t)U * 2 * 4 : (size_t)U * 4;
         res->row_bytes[1] = transition ? (size_t)n0 * 4 : (size_t)n0 * 8;
@@ -291,6 +297,229 @@ int vet_transition_entropy_batch_host(vet_plan* pl, int n_videos, const int* n_u
     HIP_TRY(hipStreamSynchronize(s));
     if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
     if (status[1]) return fail(VET_ERR_EMPTY, "%d frame pair(s) without a user present in both frames", status[1]);
+    return VET_OK;
+}
+
+
+// ---- per-frame tile-attention heatmaps (include/vet.h) ----------------------------------------------------------------
+struct vet_heatmap {
+    vet_ctx* ctx = nullptr;
+    int device = 0;
+    HeatmapGeom g;
+    uint16_t* d_map = nullptr;           // [H][W]
+    uint32_t* d_pal = nullptr;           // grow-only palette [T][n] (both render entries)
+    size_t pal_cap = 0;
+    // vet_heatmap_render_result: sub-blocks of B frames; everything but the RGB buffers is consumed in stream order on the
+    // context's stream, so one copy suffices; the RGB buffers alternate, and so do the pinned buffers the copy stream fills
+    int B = 0, U = -1;
+    hipStream_t copy = nullptr;
+    hipEvent_t computed[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
+    uint8_t* d_rgb[2] = {nullptr, nullptr};
+    uint8_t* h_pin[2] = {nullptr, nullptr};
+    int32_t* d_present = nullptr;
+    double *d_mu = nullptr, *d_mv = nullptr;
+};
+
+static void heatmap_release_staging(vet_heatmap* hm) {
+    for (int i = 0; i < 2; ++i) {
+        if (hm->d_rgb[i]) (void)hipFree(hm->d_rgb[i]);
+        if (hm->h_pin[i]) (void)hipHostFree(hm->h_pin[i]);
+        hm->d_rgb[i] = nullptr; hm->h_pin[i] = nullptr;
+    }
+    if (hm->d_present) (void)hipFree(hm->d_present);
+    if (hm->d_mu) (void)hipFree(hm->d_mu);
+    if (hm->d_mv) (void)hipFree(hm->d_mv);
+    hm->d_present = nullptr; hm->d_mu = hm->d_mv = nullptr;
+    hm->B = 0; hm->U = -1;
+}
+
+static int heatmap_palette(vet_heatmap* hm, int T, hipStream_t s) {
+    const size_t bytes = (size_t)T * hm->g.n * 4;
+    if (hm->pal_cap >= bytes) return VET_OK;
+    if (hm->d_pal) {
+        HIP_TRY(hipStreamSynchronize(s));      // a pending render of the same heatmap may still read it
+        HIP_TRY(hipFree(hm->d_pal));
+        hm->d_pal = nullptr; hm->pal_cap = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&hm->d_pal, bytes));
+    hm->pal_cap = bytes;
+    return VET_OK;
+}
+
+int vet_heatmap_create(vet_ctx* c, const double* h_tiles, int n, int W, int H, int VW, int VH, int radius,
+                       vet_heatmap** out) {
+    if (!c || !h_tiles || !out) return fail(VET_ERR_INVALID, "ctx, tiles or out is NULL");
+    *out = nullptr;
+    if (n <= 0 || W <= 0 || H <= 0 || VW <= 0 || VH <= 0)
+        return fail(VET_ERR_INVALID, "need n_tiles, width, height, video_width, video_height > 0");
+    if ((int64_t)W * H > ((int64_t)1 << 31) / 3) return fail(VET_ERR_INVALID, "frame of %d x %d pixels is too large", W, H);
+    if (radius < 0 || radius > 16) return fail(VET_ERR_INVALID, "marker_radius %d outside [0, 16]", radius);
+    if ((size_t)n * 3 * sizeof(double) > 160 * 1024 - 1024)
+        return fail(VET_ERR_UNSUPPORTED, "lattice of %d tiles exceeds the LDS tile cache of k_heatmap_map", n);
+    std::vector<double> unit((size_t)n * 3);
+    for (int t = 0; t < n; ++t) {            // as vet_plan_create normalises its lattices
+        const double x = h_tiles[3 * t], y = h_tiles[3 * t + 1], z = h_tiles[3 * t + 2];
+        const double len = std::sqrt(x * x + y * y + z * z);
+        if (!(len > 0.0)) return fail(VET_ERR_INVALID, "Vector cannot have zero length (tile %d)", t);
+        unit[3 * t] = x / len; unit[3 * t + 1] = y / len; unit[3 * t + 2] = z / len;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevBuf tiles;
+    HIP_TRY(tiles.alloc(unit.size() * sizeof(double)));
+    auto* hm = new vet_heatmap();
+    struct Guard { vet_heatmap* h; ~Guard() { if (h) vet_heatmap_destroy(h); } } guard{hm};
+    hm->ctx = c; hm->device = c->device;
+    hm->g.n = n; hm->g.W = W; hm->g.H = H; hm->g.VW = VW; hm->g.VH = VH; hm->g.radius = radius;
+    HIP_TRY(hipMalloc((void**)&hm->d_map, (size_t)W * H * sizeof(uint16_t)));
+    hm->g.d_map = hm->d_map;
+    HIP_TRY(hipMemcpyAsync(tiles.p, unit.data(), unit.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    int rc = heatmap_map(c, (const double*)tiles.p, n, W, H, hm->d_map, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_TRY(hipStreamSynchronize(s));         // 'unit' and 'tiles' go out of scope
+    *out = hm;
+    guard.h = nullptr;
+    return VET_OK;
+}
+
+int vet_heatmap_destroy(vet_heatmap* hm) {
+    if (!hm) return VET_OK;
+    (void)hipSetDevice(hm->device);
+    if (hm->ctx) (void)hipStreamSynchronize(hm->ctx->stream);
+    if (hm->copy) (void)hipStreamSynchronize(hm->copy);
+    heatmap_release_staging(hm);
+    for (int i = 0; i < 2; ++i) {
+        if (hm->computed[i]) (void)hipEventDestroy(hm->computed[i]);
+        if (hm->copied[i]) (void)hipEventDestroy(hm->copied[i]);
+    }
+    if (hm->copy) (void)hipStreamDestroy(hm->copy);
+    if (hm->d_pal) (void)hipFree(hm->d_pal);
+    if (hm->d_map) (void)hipFree(hm->d_map);
+    delete hm;
+    return VET_OK;
+}
+
+int vet_heatmap_read_map(vet_heatmap* hm, int32_t* h_map) {
+    if (!hm || !h_map) return fail(VET_ERR_INVALID, "heatmap or output is NULL");
+    HIP_TRY(hipSetDevice(hm->device));
+    std::vector<uint16_t> tmp((size_t)hm->g.W * hm->g.H);
+    HIP_TRY(hipMemcpy(tmp.data(), hm->d_map, tmp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tmp.size(); ++i) h_map[i] = tmp[i];
+    return VET_OK;
+}
+
+int vet_heatmap_render(vet_heatmap* hm, const double* d_weights, const int32_t* d_present, const double* d_mu,
+                       const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
+    if (!hm || !d_weights || !d_present || !d_rgb) return fail(VET_ERR_INVALID, "heatmap, weights, present or rgb is NULL");
+    if (T < 0) return fail(VET_ERR_INVALID, "n_frames must be >= 0 (got %d)", T);
+    if (!d_mu != !d_mv) return fail(VET_ERR_INVALID, "pass both d_mu and d_mv, or neither");
+    if (d_mu && U <= 0) return fail(VET_ERR_INVALID, "n_users must be positive with samples (got %d)", U);
+    if ((uintptr_t)d_rgb % 4) return fail(VET_ERR_INVALID, "d_rgb must be 4-byte aligned");
+    if (T == 0) return VET_OK;
+    HIP_TRY(hipSetDevice(hm->device));
+    hipStream_t s = stream ? (hipStream_t)stream : hm->ctx->stream;
+    int rc = heatmap_palette(hm, T, s);
+    if (rc) return rc;
+    return heatmap_render(hm->ctx, hm->g, d_weights, d_present, d_mu, d_mv, U, T, hm->d_pal, d_rgb, s);
+}
+
+int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_present, const double* h_mu,
+                              const double* h_mv, int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb) {
+    if (!hm || !r || !h_present || !h_rgb) return fail(VET_ERR_INVALID, "heatmap, result, present or rgb is NULL");
+    if (r->transition) return fail(VET_ERR_INVALID, "a transition result has no tile weights to render");
+    if (r->device != hm->device)
+        return fail(VET_ERR_INVALID, "result on device %d, heatmap on device %d", r->device, hm->device);
+    const int n = hm->g.n;
+    if (r->row_bytes[1] != (size_t)n * 8)
+        return fail(VET_ERR_INVALID, "the result's lattice 0 has %zu tiles, the heatmap's lattice %d", r->row_bytes[1] / 8, n);
+    if (row0 < 0 || n_rows < 0 || row0 + n_rows > r->rows)
+        return fail(VET_ERR_INVALID, "rows [%lld, %lld) outside the result's %lld rows", (long long)row0,
+                    (long long)(row0 + n_rows), (long long)r->rows);
+    if (!h_mu != !h_mv) return fail(VET_ERR_INVALID, "pass both h_mu and h_mv, or neither");
+    const int RU = (int)(r->row_bytes[0] / 4);
+    if (h_mu && U != RU) return fail(VET_ERR_INVALID, "n_users %d, the result has %d", U, RU);
+    if (n_rows == 0) return VET_OK;
+    HIP_TRY(hipSetDevice(hm->device));
+    vet_ctx* c = hm->ctx;
+    hipStream_t s = c->stream;
+    const size_t frame = (size_t)hm->g.W * hm->g.H * 3;
+    const int B = (int)std::max<size_t>(1, std::min<size_t>((size_t)32 << 20, (size_t)n_rows * frame) / frame);
+    if (hm->B < B || (h_mu && hm->U < U)) {                 // grow-only staging
+        HIP_TRY(hipStreamSynchronize(s));
+        if (hm->copy) HIP_TRY(hipStreamSynchronize(hm->copy));
+        heatmap_release_staging(hm);
+        if (!hm->copy) {
+            HIP_TRY(hipStreamCreateWithFlags(&hm->copy, hipStreamNonBlocking));
+            for (int i = 0; i < 2; ++i) {
+                HIP_TRY(hipEventCreateWithFlags(&hm->computed[i], hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(&hm->copied[i], hipEventDisableTiming));
+            }
+        }
+        const int UU = h_mu ? U : 0;
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(hipMalloc((void**)&hm->d_rgb[i], (size_t)B * frame));
+            HIP_TRY(hipHostMalloc((void**)&hm->h_pin[i], (size_t)B * frame, hipHostMallocDefault));
+        }
+        HIP_TRY(hipMalloc((void**)&hm->d_present, (size_t)B * 4));
+        HIP_TRY(hipMalloc((void**)&hm->d_mu, (size_t)B * std::max(UU, 1) * 8));
+        HIP_TRY(hipMalloc((void**)&hm->d_mv, (size_t)B * std::max(UU, 1) * 8));
+        hm->B = B; hm->U = UU;
+    }
+    int rc = heatmap_palette(hm, B, s);
+    if (rc) return rc;
+    // lazy weight rows: the weights pass of each block into the result's staging buffer, under its fetch lock
+    std::unique_lock<std::mutex> lock(r->fetch_mu, std::defer_lock);
+    if (r->lazy_weights) {
+        lock.lock();
+        const size_t wb = (size_t)B * r->row_bytes[1];
+        if (r->tmp_cap < wb) {
+            if (r->d_tmp) { HIP_TRY(hipFree(r->d_tmp)); r->d_tmp = nullptr; r->tmp_cap = 0; }
+            HIP_TRY(hipMalloc(&r->d_tmp, wb));
+            r->tmp_cap = wb;
+        }
+    }
+    auto drain = [&](int code) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamSynchronize(hm->copy);
+        return code;
+    };
+    const int64_t nb = (n_rows + B - 1) / B;
+    auto rows_of = [&](int64_t k) { return (int)std::min<int64_t>(B, n_rows - k * B); };
+    for (int64_t k = 0; k < nb; ++k) {
+        const int st = (int)(k & 1), b = rows_of(k);
+        const int64_t f0 = row0 + k * B;
+        if (k >= 2 && hipStreamWaitEvent(s, hm->copied[st], 0) != hipSuccess)     // the copy of block k-2 has left d_rgb[st]
+            return drain(fail(VET_ERR_DEVICE, "hipStreamWaitEvent failed"));
+        if (hipMemcpyAsync(hm->d_present, h_present + k * B, (size_t)b * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+            return drain(fail(VET_ERR_DEVICE, "upload of the user counts failed"));
+        if (h_mu && (hipMemcpyAsync(hm->d_mu, h_mu + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+                     hipMemcpyAsync(hm->d_mv, h_mv + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess))
+            return drain(fail(VET_ERR_DEVICE, "upload of the samples failed"));
+        const double* w;
+        if (r->lazy_weights) {
+            rc = weights_pass_ids(*r->core, r->d_ids + (size_t)f0 * r->U, r->U, b, (double*)r->d_tmp, s, nullptr);
+            if (rc) return drain(rc);
+            w = (const double*)r->d_tmp;
+        } else {
+            w = (const double*)r->d[1] + (size_t)f0 * n;
+        }
+        rc = heatmap_render(c, hm->g, w, hm->d_present, h_mu ? hm->d_mu : nullptr, h_mu ? hm->d_mv : nullptr, U, b, hm->d_pal,
+                            hm->d_rgb[st], s);
+        if (rc) return drain(rc);
+        if (hipEventRecord(hm->computed[st], s) != hipSuccess || hipStreamWaitEvent(hm->copy, hm->computed[st], 0) != hipSuccess ||
+            hipMemcpyAsync(hm->h_pin[st], hm->d_rgb[st], (size_t)b * frame, hipMemcpyDeviceToHost, hm->copy) != hipSuccess ||
+            hipEventRecord(hm->copied[st], hm->copy) != hipSuccess)
+            return drain(fail(VET_ERR_DEVICE, "download of block %lld failed", (long long)k));
+        if (k >= 1) {                                       // block k-1 to the caller while block k runs
+            const int ps = (int)((k - 1) & 1);
+            if (hipEventSynchronize(hm->copied[ps]) != hipSuccess) return drain(fail(VET_ERR_DEVICE, "hipEventSynchronize failed"));
+            std::memcpy(h_rgb + (size_t)(k - 1) * B * frame, hm->h_pin[ps], (size_t)rows_of(k - 1) * frame);
+        }
+    }
+    const int ls = (int)((nb - 1) & 1);
+    if (hipEventSynchronize(hm->copied[ls]) != hipSuccess) return drain(fail(VET_ERR_DEVICE, "hipEventSynchronize failed"));
+    std::memcpy(h_rgb + (size_t)(nb - 1) * B * frame, hm->h_pin[ls], (size_t)rows_of(nb - 1) * frame);
+    HIP_TRY(hipStreamSynchronize(s));
     return VET_OK;
 }
 

@@ -32,6 +32,10 @@
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into
 //                                                               ranges of source tiles whose buckets fit it
 //                                              k_transition_any fallback for lattices of thousands of tiles (hash in global scratch)
+//   vet_heatmap.hip     (in the unit)          k_heatmap_map    pixel -> nearest tile of a lattice (nearest_tile, as k_nearest_lut)
+//                                              k_heatmap_palette, k_heatmap_fill, k_heatmap_markers   per-frame tile-attention
+//                                                               RGB frames: palette per (frame, tile), streamed gather-store
+//                                                               of the pixels, viewport markers
 //   (several units)     vet_finalize.hpp       k_log2_table, k_finalize*   log2(k) table; mean over a plan's lattices
 // Shared, kernel-free headers: vet_layout.hpp (table / histogram layout constants), vet_common.hpp (wave helpers, the
 // sample -> direction-id quantiser), vet_weights.hpp (FoV weight, weighted frame entropy), vet_host.hpp (host state).

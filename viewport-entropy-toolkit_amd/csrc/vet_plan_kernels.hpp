@@ -194,35 +194,16 @@ __global__ void k_alias_rows(const uint32_t* __restrict__ alias, long D, const u
 // ------------------------------------------------------------------------------------------
 // k_nearest_lut: find_nearest_tile (entropy_utils.py:89-106) for every direction of the table:
 // np.argmin over arccos(clip(dot)) — the FIRST minimum, i.e. the lowest index among the tiles whose
-// distance VALUE is the smallest.  arccos is monotone, so the arg-max of the cosine ('>' keeps the
-// lowest index on exact ties) finds a tile of minimal distance; where the cosines of two tiles differ by
-// a few ulp, arccos may map them to one double, and the reference then keeps the lower index: the second
-// pass applies that rule literally to the (rare) tiles of lower index within 8 ulp of the best cosine.
-// lane = direction, the tiles walk through LDS (broadcast).
+// distance VALUE is the smallest (nearest_tile, vet_common.hpp).  lane = direction, the tiles walk through
+// LDS (broadcast).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double clip_unit(double c) {        // np.clip(c, -1, 1): NaN stays NaN
-    return c != c ? c : fmin(fmax(c, -1.0), 1.0);
-}
-
 __global__ void k_nearest_lut(const double* __restrict__ unit, long D, const double* __restrict__ tiles,
                               int n, uint16_t* __restrict__ nearest) {
     extern __shared__ double s_tiles[];
     for (int i = threadIdx.x; i < 3 * n; i += blockDim.x) s_tiles[i] = tiles[i];
     __syncthreads();
     for (long d = blockIdx.x * (long)blockDim.x + threadIdx.x; d < D; d += (long)gridDim.x * blockDim.x) {
-        const double x = unit[3 * d], y = unit[3 * d + 1], z = unit[3 * d + 2];
-        double best = -2.0;
-        int bi = 0;
-        for (int t = 0; t < n; ++t) {
-            const double c = fma(z, s_tiles[3 * t + 2], fma(y, s_tiles[3 * t + 1], x * s_tiles[3 * t]));
-            if (c > best) { best = c; bi = t; }
-        }
-        const double near = best - 8.0 * 2.220446049250313e-16, dbest = acos(clip_unit(best));
-        for (int t = 0; t < bi; ++t) {
-            const double c = fma(z, s_tiles[3 * t + 2], fma(y, s_tiles[3 * t + 1], x * s_tiles[3 * t]));
-            if (c >= near && acos(clip_unit(c)) <= dbest) { bi = t; break; }
-        }
-        nearest[d] = (uint16_t)bi;
+        nearest[d] = (uint16_t)nearest_tile(unit[3 * d], unit[3 * d + 1], unit[3 * d + 2], s_tiles, n);
     }
 }
 

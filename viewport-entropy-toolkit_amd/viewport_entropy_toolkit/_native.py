@@ -112,6 +112,11 @@ SIGNATURES = {
     "vet_result_free": (_I, [_P]),
     "vet_fb_tile_boundaries": (_I, [_P, _P, _I, _I, _P, _P]),
     "vet_angular_distances": (_I, [_P, _P, _I64, _P, _I, _P]),
+    "vet_heatmap_create": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "vet_heatmap_destroy": (_I, [_P]),
+    "vet_heatmap_read_map": (_I, [_P, _P]),
+    "vet_heatmap_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "vet_heatmap_render_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
     "vet_csv_read_tracks": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(Track), _I]),
     "vet_csv_free_tracks": (None, [_I, C.POINTER(Track)]),
 }
@@ -596,3 +601,71 @@ class Plan:
         _check(self.lib, self.lib.vet_transition_entropy(self.handle, d_mu, d_mv, n_users, n_frames, d_entropy,
                                                          d_pairs or None, d_srccount or None, d_common or None,
                                                          d_status or None, _stream(stream)))
+
+
+class Heatmap:
+    """Per-frame tile-attention heatmaps of one lattice (include/vet.h: vet_heatmap): ``width`` x ``height`` uint8 RGB
+    frames, equirectangular (row 0 = latitude +90), every pixel coloured by its nearest tile's
+    ``tile_weights / users present`` as the reference's animation colours tiles, with black viewport markers of side
+    ``2 * marker_radius + 1``.  The pixel -> tile map is built on the device once, here."""
+
+    def __init__(self, engine: Engine, tiles: np.ndarray, width: int, height: int, video_width: int, video_height: int,
+                 marker_radius: int = 2):
+        self.engine, self.lib = engine, engine.lib
+        tiles = np.ascontiguousarray(tiles, dtype=np.float64).reshape(-1, 3)
+        self.n_tiles, self.width, self.height = len(tiles), int(width), int(height)
+        self.video_width, self.video_height, self.marker_radius = int(video_width), int(video_height), int(marker_radius)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.vet_heatmap_create(engine.handle, _ptr(tiles), self.n_tiles, self.width, self.height,
+                                                     self.video_width, self.video_height, self.marker_radius, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.vet_heatmap_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def map(self) -> np.ndarray:
+        """int32 [height, width]: the tile of every pixel."""
+        out = np.empty((self.height, self.width), dtype=np.int32)
+        _check(self.lib, self.lib.vet_heatmap_read_map(self.handle, _ptr(out)))
+        return out
+
+    def render_device(self, d_weights: int, d_present: int, n_frames: int, d_rgb: int, d_mu: int = 0, d_mv: int = 0,
+                      n_users: int = 0, stream=None):
+        """Frames [0, n_frames) from device pointers (weights f64 [T, n_tiles], present i32 [T], optional samples f64
+        [T, U]) into ``d_rgb`` (uint8 [T, H, W, 3], 4-byte aligned); asynchronous on ``stream`` as ``Plan.spatial_device``."""
+        _check(self.lib, self.lib.vet_heatmap_render(self.handle, d_weights, d_present, d_mu or None, d_mv or None,
+                                                     int(n_users), int(n_frames), d_rgb, _stream(stream)))
+
+    def render_result(self, result: "DeviceResult", present: np.ndarray, mu: Optional[np.ndarray] = None,
+                      mv: Optional[np.ndarray] = None, row0: int = 0, n: Optional[int] = None,
+                      out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Frames [row0, row0 + n) of a spatial ``DeviceResult`` -> uint8 [n, H, W, 3] (into ``out`` when given: a
+        C-contiguous uint8 array of that shape).  ``present``, ``mu``, ``mv`` hold those frames' rows only; without
+        ``mu`` / ``mv`` no markers are drawn.  The weight rows stay on the device."""
+        n = result.n_rows - row0 if n is None else int(n)
+        present = np.ascontiguousarray(present, dtype=np.int32).reshape(-1)
+        if len(present) != n:
+            raise ValueError(f"present holds {len(present)} rows, expected {n}")
+        U = 0
+        if mu is not None:
+            mu = np.ascontiguousarray(mu, dtype=np.float64)
+            mv = np.ascontiguousarray(mv, dtype=np.float64)
+            if mu.ndim != 2 or mu.shape != mv.shape or len(mu) != n:
+                raise ValueError(f"mu and mv must be [{n}, n_users] arrays of equal shape")
+            U = mu.shape[1]
+        shape = (n, self.height, self.width, 3)
+        if out is None:
+            out = np.empty(shape, dtype=np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        _check(self.lib, self.lib.vet_heatmap_render_result(self.handle, result.handle, _ptr(present), _ptr(mu), _ptr(mv),
+                                                            U, int(row0), n, _ptr(out)))
+        return out

@@ -172,8 +172,8 @@ class _EntropyAnalyzerBase:
     def create_visualization(self, base_name: str) -> None:
         """Writes ``{base_name}_graph.png`` and ``{base_name}.csv`` (columns time, entropy).
 
-        The per-frame scatter animation / mp4 of the reference is host matplotlib + ffmpeg
-        work outside this engine and is not produced."""
+        The reference's per-frame scatter animation / mp4 is not produced here; its GPU-rendered
+        counterpart is opt-in: ``SpatialEntropyAnalyzer.render_heatmaps`` / ``save_heatmaps``."""
         if self._entropy_results is None:
             raise ValidationError("No entropy results. Call compute_entropy first.")
         try:

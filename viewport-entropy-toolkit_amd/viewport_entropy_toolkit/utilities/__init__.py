@@ -2,7 +2,8 @@
 
 The operator-level functions keep the reference's names and signatures and run on the HIP
 engine; the ingest helpers are vectorised host code; visualisation is reduced to the
-configuration object and the entropy-over-time graph (rendering is outside the engine).
+configuration object and the entropy-over-time graph (the per-frame heatmaps are rendered by
+``SpatialEntropyAnalyzer.render_heatmaps``; the reference's matplotlib / pyvista renderers raise).
 """
 
 from . import data_utils as _data, entropy_utils as _entropy, visualization_utils as _viz
@@ -17,7 +18,9 @@ _PUBLIC = {
     _entropy: ("EntropyConfig", "vector_angle_distance", "find_angular_distances", "find_nearest_tile", "calculate_tile_weights", "compute_spatial_entropy",
                "compute_transition_entropy", "calculate_naive_tile_weights", "find_naive_tile_index",
                "compute_naive_spatial_entropy"),
-    _viz: ("VisualizationConfig", "save_graph"),
+    _viz: ("VisualizationConfig", "save_graph", "PlotManager", "create_animation", "save_video",
+           "save_fb_tiling_visualization_image", "save_fb_tiling_visualization_video", "save_tiling_visualization_image",
+           "save_tiling_visualization_video"),
 }
 for _module, _names in _PUBLIC.items():
     for _name in _names:

@@ -1,9 +1,11 @@
 """Visualisation configuration and the entropy-over-time graph.
 
-Rendering is outside the MI355X hot path: only the configuration
-dataclass that ``AnalyzerConfig`` embeds (reference visualization_utils.py:32-60) and the
-plain matplotlib line graph are provided; the per-frame scatter animation, the ffmpeg video
-writer and the pyvista sphere renderers are not part of this engine.
+The configuration dataclass that ``AnalyzerConfig`` embeds (reference visualization_utils.py:32-60)
+and the plain matplotlib line graph are provided here.  The per-frame tile-attention animation is
+rendered on the GPU by ``SpatialEntropyAnalyzer.render_heatmaps`` / ``save_heatmaps``; the
+reference's matplotlib names for it (``PlotManager``, ``create_animation``, ``save_video``) and its
+pyvista sphere renderers exist so that code importing them loads, and raise ``RuntimeError`` when
+called.
 """
 
 from __future__ import annotations
@@ -51,3 +53,31 @@ def save_graph(entropy_values: Sequence[float], time_values: Sequence[float], ou
     plt.grid(True)
     plt.savefig(output_path)
     plt.close(fig)
+
+
+_USE_HEATMAPS = ("{name}: the matplotlib scatter animation is not part of this engine; render the per-frame tile-attention "
+                 "frames on the GPU with SpatialEntropyAnalyzer.render_heatmaps / save_heatmaps (.npy, a PNG directory or .mp4)")
+_NO_PYVISTA = "{name}: 3-D tiling renders need pyvista and are not part of this engine"
+
+
+class PlotManager:
+    """Reference name (matplotlib scatter animation, visualization_utils.py:63-204); raises ``RuntimeError``."""
+
+    def __init__(self, *args, **kwargs):
+        raise RuntimeError(_USE_HEATMAPS.format(name="PlotManager"))
+
+
+def _unavailable(name: str, message: str):
+    def stub(*args, **kwargs):
+        raise RuntimeError(message.format(name=name))
+    stub.__name__ = stub.__qualname__ = name
+    stub.__doc__ = f"Reference name; raises ``RuntimeError``: {message.format(name=name)}."
+    return stub
+
+
+create_animation = _unavailable("create_animation", _USE_HEATMAPS)
+save_video = _unavailable("save_video", _USE_HEATMAPS)
+save_fb_tiling_visualization_image = _unavailable("save_fb_tiling_visualization_image", _NO_PYVISTA)
+save_fb_tiling_visualization_video = _unavailable("save_fb_tiling_visualization_video", _NO_PYVISTA)
+save_tiling_visualization_image = _unavailable("save_tiling_visualization_image", _NO_PYVISTA)
+save_tiling_visualization_video = _unavailable("save_tiling_visualization_video", _NO_PYVISTA)
