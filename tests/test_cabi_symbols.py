@@ -101,6 +101,10 @@ def test_environment_is_read_in_one_place_only():
         if f.name != "vet_context.hip":
             assert "getenv" not in code, f"{f.name} reads the environment"
         assert "experiments/" not in code and "k_spatial_rows" not in code and "k_spatial_walk" not in code, f.name
+    # the switches vet_create reads are the test and development ones (vet_host.hpp: Tuning), no tuning knobs
+    ctx = (csrc / "vet_context.hip").read_text()
+    read = set(re.findall(r"\b(?:getenv|env_[a-z]+)\(\s*\"(VET_[A-Z0-9_]+)\"", ctx))
+    assert read == {"VET_NO_FUSED", "VET_FUSED", "VET_T_GLOBAL", "VET_NO_EXACT_ROWS", "VET_LUT_TIMELINE"}, sorted(read)
     mk = (csrc / "Makefile").read_text()
     assert "experiments" not in mk
     # timing-only switches (wrong results by design) live in tools/experiments/ as a patch, not in the product sources

@@ -1,5 +1,5 @@
 // vet_context.hip — library, context, profiling and device-memory entry points of the C-ABI (include/vet.h), the
-// grow-only scratch of a context and the tuning knobs (environment read once, in vet_create).
+// grow-only scratch of a context and the test and development switches (environment read once, in vet_create).
 // There is no CPU compute path here: without a HIP device vet_create fails.
 #include "vet_host.hpp"
 #include "vet_finalize.hpp"
@@ -16,19 +16,6 @@ thread_local std::string g_err;
 const char* const kKernelNames[KID_COUNT] = {"k_grid_dirs", "k_nearest_lut", "k_spatial", "k_transition",
                                              "k_finalize", "k_wtab", "k_weights"};
 
-// a value outside [lo, hi] (or not a number) is ignored
-int env_int(const char* name, int lo, int hi, int fallback) {
-    const char* e = getenv(name);
-    if (!e || !*e) return fallback;
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end == e || *end != '\0' || v < lo || v > hi) return fallback;
-    return (int)v;
-}
-int env_threads(const char* name, int fallback) {       // workgroup size: whole waves, at most 1024 threads
-    const int v = env_int(name, 64, 1024, fallback);
-    return v % 64 == 0 ? v : fallback;
-}
 int env_flag(const char* name) { return getenv(name) ? 1 : 0; }
 }  // namespace
 
@@ -44,31 +31,9 @@ int fail(int code, const char* fmt, ...) {
 const char* last_error() { return g_err.c_str(); }
 
 void Tuning::from_environment() {
-    gs_log2 = env_int("VET_GS_LOG2", 1, 4, 0);
-    tab_interleave = env_int("VET_TAB_INTERLEAVE", 0, 1, 1);
-    lut_threads = env_threads("VET_LUT_THREADS", 256);
-    if (lut_threads > 256) lut_threads = 256;              // __launch_bounds__(256)
-    lut_fpw = env_int("VET_LUT_FPW", 1, 16, 0);
-    stride_align = (env_int("VET_STRIDE_ALIGN", 64, 1024, 64) + 63) / 64 * 64;   // whole 64-entry blocks: the walk reads whole blocks
-    no_dedup = env_flag("VET_NO_DEDUP");
-    dedup_min_users = env_int("VET_DEDUP_MIN_USERS", 1, 1 << 20, 128);
-    no_mirror = env_flag("VET_NO_MIRROR");
-    u_wgs_per_cu = env_int("VET_U_WGS_PER_CU", 1, 8, 2);
-    u_no_lds = env_flag("VET_U_NO_LDS");
-    u_fpw = env_int("VET_U_FPW", 1, 64, 0);
-    u_waves = env_int("VET_U_WAVES", 1, 16, 4);
-    t_threads = env_threads("VET_T_THREADS", 0);
-    // powers of two only: the launch logic doubles the workgroup until it covers the users (192 -> 1536 would exceed 1024
-    // threads and the 16 wave slots of the cell sums)
-    if (t_threads & (t_threads - 1)) t_threads = 0;
-    t_wgs_per_cu = env_int("VET_T_WGS_PER_CU", 1, 16, 0);
-    t_global = env_flag("VET_T_GLOBAL");
-    t_hs_pct = env_int("VET_T_HS_PCT", 100, 400, 200);     // bucket-hash slots per 100 users (100: no gain, 43.3 vs 43.7 us)
     no_fused = env_flag("VET_NO_FUSED");
     fused_single = env_flag("VET_FUSED");
-    lut_occ8 = env_int("VET_LUT_OCC8", 0, 1, -1);
-    fused_narrow = env_int("VET_FUSED_NARROW", 0, 1, 1);
-    narrow_deal = env_int("VET_NARROW_DEAL", 0, 1, 1);
+    t_global = env_flag("VET_T_GLOBAL");
     if (const char* e = getenv("VET_LUT_TIMELINE")) lut_timeline = e;
     no_exact_rows = env_flag("VET_NO_EXACT_ROWS");
 }

@@ -1,6 +1,6 @@
 // vet_host.hpp — host-side state shared by the translation units of libvet_hip.so (not part of the C-ABI).
 //
-//   vet_context.hip     library / context / profiling / device-memory helpers, the tuning knobs (parsed once)
+//   vet_context.hip     library / context / profiling / device-memory helpers, the test / development switches (parsed once)
 //   vet_plan.hip        device tables of a plan: direction table, lattices, nearest-tile LUTs, alias and weight tables,
 //                       error bounds; parity read-back hooks; angular distances; tile boundary geometry
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
@@ -84,33 +84,19 @@ struct BatchStage {
 };
 constexpr int kBatchStages = 4;
 
-// Tuning knobs.  The environment is read ONCE, in vet_create; nothing between a C-ABI entry point and
-// its kernel launches calls getenv.  A value outside its range is ignored (the built-in default stays).
+// Test and development switches.  The environment is read ONCE, in vet_create; nothing between a C-ABI entry point and
+// its kernel launches calls getenv.  Each forces a path that real inputs can also reach, or (VET_LUT_TIMELINE) adds
+// output to a development build: none changes a result.
 struct Tuning {
-    int gs_log2 = 0;            // VET_GS_LOG2 1..4: lanes per gather group (0: by row length)
-    int tab_interleave = 1;     // VET_TAB_INTERLEAVE
-    int lut_threads = 256;      // VET_LUT_THREADS
-    int lut_fpw = 0;            // VET_LUT_FPW (0: by shape)
-    int stride_align = 64;      // VET_STRIDE_ALIGN
-    int no_dedup = 0;           // VET_NO_DEDUP
-    int dedup_min_users = 128;  // VET_DEDUP_MIN_USERS
-    int no_mirror = 0;          // VET_NO_MIRROR
-    int u_wgs_per_cu = 2;       // VET_U_WGS_PER_CU
-    int u_no_lds = 0;           // VET_U_NO_LDS
-    int u_fpw = 0;              // VET_U_FPW (0: by shape)
-    int u_waves = 4;            // VET_U_WAVES
-    int t_threads = 0;          // VET_T_THREADS (0: by shape)
-    int t_wgs_per_cu = 0;       // VET_T_WGS_PER_CU (0: by LDS)
-    int t_global = 0;           // VET_T_GLOBAL
-    int t_hs_pct = 200;         // VET_T_HS_PCT
-    int no_fused = 0;           // VET_NO_FUSED
-    int fused_single = 0;       // VET_FUSED: fused table also for one-lattice plans
-    int lut_occ8 = -1;          // VET_LUT_OCC8 (fused table kernel: -1 by shape)
-    int fused_narrow = 1;       // VET_FUSED_NARROW: 8-lane rows for fused rows of 65..96 entries
-    int narrow_deal = 1;        // VET_NARROW_DEAL: class-dealt blocks for those 8-lane rows (0: plain order, round 4)
-    std::string lut_timeline;   // VET_LUT_TIMELINE=path (development builds only): per-workgroup wall-clock timeline of the fused table kernel
+    int no_fused = 0;           // VET_NO_FUSED: per-lattice tables instead of the fused one (test_fused_table_kernels_agree)
+    int fused_single = 0;       // VET_FUSED: fused table also for one-lattice plans (test_fused_table_kernels_agree)
+    int t_global = 0;           // VET_T_GLOBAL: transition through k_transition_any whatever the shape
+                                // (test_transition_global_hash_variant_on_small_frames)
+    std::string lut_timeline;   // VET_LUT_TIMELINE=path (make DEV=1 builds only): per-workgroup wall-clock timeline of the
+                                // fused table kernel, read by tools/timeline_summary.py
     int no_exact_rows = 0;      // VET_NO_EXACT_ROWS: the weights pass never builds the exact weight rows (as if they did not fit
                                 // the device): the precise sweep in weights-only mode serves — the fallback's test switch
+                                // (include/vet.h; test_fp64_formulation.py, test_hip_shapes.py)
     void from_environment();
 };
 

@@ -15,6 +15,7 @@ constexpr uint32_t MARKER_BITS = 0x80000000u;            // -0.0f: FP-table entr
 constexpr int ROW_BITS = 19;                             // set key = row (19 bits) | mirror flag; slot = key << 12 | count
 constexpr uint32_t ROW_MASK = (1u << ROW_BITS) - 1;
 constexpr unsigned DEDUP_MAX_DIRS = (1u << ROW_BITS) - 1;
+constexpr int DEDUP_MIN_USERS = 128;                     // frames of fewer users run the table kernel without the set (LutParams)
 
 // ------------------------------------------------------------------------------------------
 // Fused histogram layout.  The plan's K lattices (analyzers/spatial_entropy.py:142-156 loops over

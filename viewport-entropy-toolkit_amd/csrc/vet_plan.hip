@@ -29,7 +29,7 @@ int ensure_alias(vet_plan* pl) {
     const long D = (long)pl->n_dirs;
     if (D <= 0 || D >= (long)0x7FFFFFFF) return fail(VET_ERR_UNSUPPORTED, "direction table of %ld entries", D);
     // mirror symmetry of every lattice, bit for bit on the unit vectors the kernels use (host: a few thousand values)
-    bool mirror = !c->tune.no_mirror && pl->weighted;
+    bool mirror = pl->weighted;
     for (const auto& L : pl->lat) {
         if (L.binned || L.h_unit.empty()) { mirror = false; break; }
         for (int i = 0; i < L.n && mirror; ++i) {
@@ -179,8 +179,7 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(VET_ERR_DEVICE, "k_wtab<count> failed: %s", hipGetErrorString(e));
     // rows start on 128-byte lines (u16 tile rows) / 256 bytes (u32 weight rows); whole 64-entry blocks
-    const int align = c->tune.stride_align;
-    int stride = ((longest > 0 ? longest : 1) + align - 1) / align * align;
+    const int stride = ((longest > 0 ? longest : 1) + 63) / 64 * 64;
     const size_t rows = (size_t)R + 1;            // one extra, all-zero row (index n_rows) for the gather's idle lanes
     const size_t bytes = rows * stride * 6 + rows * 4;
     size_t free_b = 0, total_b = 0;
@@ -209,9 +208,8 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     // lattices do not idle most of a group
     L.gs_log2 = 1;
     while (L.gs_log2 < 4 && (4 << L.gs_log2) < longest) ++L.gs_log2;
-    if (c->tune.gs_log2) L.gs_log2 = c->tune.gs_log2;
     // 16-lane rows with at least one block that is 3/4 full get the class-dealt layout (k_wtab)
-    L.interleaved = L.gs_log2 == 4 && stride % 64 == 0 && 4 * longest >= 3 * 64 && c->tune.tab_interleave != 0;
+    L.interleaved = L.gs_log2 == 4 && stride % 64 == 0 && 4 * longest >= 3 * 64;
     p.stride = stride; p.w = L.d_tab_w; p.idx = L.d_tab_i; p.meta = L.d_tab_meta; p.maxcount = nullptr;
     p.markers = L.fp_table ? d_max + 1 : nullptr;
     p.gs_log2 = L.interleaved ? L.gs_log2 : -1;
@@ -420,11 +418,9 @@ int ensure_fused(vet_plan* pl, hipStream_t s) {
     while (F.gs_log2 < 4 && (4 << F.gs_log2) < longest) ++F.gs_log2;
     // rows of 65..96 entries: three 32-entry blocks of an 8-lane group instead of two 64-entry blocks, the second mostly
     // empty (config 4: 88-94 entries: 128 -> 96 slots per row walk)
-    if (longest > 64 && longest <= 96 && c->tune.fused_narrow) F.gs_log2 = 3;
-    if (c->tune.gs_log2) F.gs_log2 = c->tune.gs_log2;
+    if (longest > 64 && longest <= 96) F.gs_log2 = 3;
     // class-dealt blocks (k_wtab): 16-lane rows with a block of 64 at least 3/4 full, 8-lane rows with one of 32
-    F.interleaved = ((F.gs_log2 == 4 && 4 * longest >= 3 * 64) || (F.gs_log2 == 3 && 4 * longest >= 3 * 32 && c->tune.narrow_deal)) &&
-                    c->tune.tab_interleave != 0;
+    F.interleaved = (F.gs_log2 == 4 && 4 * longest >= 3 * 64) || (F.gs_log2 == 3 && 4 * longest >= 3 * 32);
     p.stride = stride; p.w = F.d_w; p.idx = F.d_i; p.meta = F.d_meta; p.maxcount = nullptr;
     p.gs_log2 = F.interleaved ? F.gs_log2 : -1;
     {

@@ -50,9 +50,8 @@ int spatial_geometry(const vet_ctx* c, int n, int U, bool weighted, Geometry* g,
     if (!weighted) {
         // k_spatial_u: one wave per frame in the entropy phase; keep >= 2048 samples per workgroup
         g->R = 1; g->G = 1; g->UC = 0;
-        g->NW = c->tune.u_waves;
+        g->NW = 4;
         g->FPW = U >= 2048 ? 2 : (U >= 512 ? 4 : (U >= 128 ? 8 : 32));
-        if (c->tune.u_fpw) g->FPW = c->tune.u_fpw;
         while ((size_t)g->FPW * n * 4 > c->lds_max && g->FPW > 1) g->FPW /= 2;
         g->lds = (size_t)g->FPW * n * 4;
         if (g->lds > c->lds_max)
@@ -60,6 +59,28 @@ int spatial_geometry(const vet_ctx* c, int n, int U, bool weighted, Geometry* g,
         return VET_OK;
     }
     return sweep_geometry(c->lds_max, n, U, g, one_frame);
+}
+
+// k_spatial_u_lds, the persistent nearest-tile kernel with the nearest LUT in LDS: 1024 threads, a round is 4096 users = fb
+// frames of up to U users over a lattice of up to n tiles (2048 pairs with 16-byte loads when U is even, 4096 single users
+// otherwise).  LDS bytes of one workgroup:
+constexpr int kULdsThreads = 1024;
+size_t u_lds_bytes(const vet_plan* pl, int U, int n, int fb) {
+    return (((size_t)pl->n_dirs * 2 + 15) & ~(size_t)15) + (size_t)(U + 1) * 8 +
+           ((((size_t)fb * n + 1) & ~(size_t)1) * 4) + (size_t)fb * (kULdsThreads / 64) * 8 + fb * 4 + 16;
+}
+// frames per round: fb, halved while the LDS does not fit (few users x many tiles); 1 may still not fit
+int u_lds_frames(const vet_plan* pl, int U, int n, int fb) {
+    while (fb > 1 && u_lds_bytes(pl, U, n, fb) > pl->ctx->lds_max) fb /= 2;
+    return fb;
+}
+// persistent grid over n_blocks frame blocks, 2 workgroups per CU; even rounds: every workgroup walks the same number of
+// blocks (no tail)
+long u_lds_grid(const vet_ctx* c, long n_blocks) {
+    long grid = (long)c->n_cu * 2;
+    if (grid > n_blocks) grid = n_blocks;
+    const long rounds = (n_blocks + grid - 1) / grid;
+    return (n_blocks + rounds - 1) / rounds;
 }
 
 // weight-evaluation variant of k_spatial_w (see fov_weight_fx)
@@ -81,26 +102,25 @@ const void* spatial_w_kernel(int wmode, int R, bool precise = false) {
 
 // fused rows are short (config 4: 94 entries = 2 blocks): four rows in flight per lane group and 7 workgroups per CU
 // (72 VGPRs, one spilled register) measured 3-5 % faster than two rows and 8 workgroups (config 4 0.165 -> 0.160 ms, 64 x config 2
-// 0.907 -> 0.882, defaults 0.531 -> 0.519); single-lattice tables keep two (profiles/r01/v3_*)
-#ifndef VET_FUSED_UN
-#define VET_FUSED_UN 4
-#endif
-// k_spatial_lut<FUSED, UN == 2> IS the narrow (8-lane rows) kernel: the row width of the class-dealt layout is inferred from
-// UN there (GSL_IL), so the 16-lane fused kernel must not be built with two rows in flight
-static_assert(VET_FUSED_UN != 2, "VET_FUSED_UN=2 would alias the 16-lane fused kernel onto the 8-lane (narrow) instantiation");
+// 0.907 -> 0.882, defaults 0.531 -> 0.519); single-lattice tables keep two (profiles/r01/v3_*).  (k_spatial_lut<FUSED, UN == 2>
+// IS the narrow, 8-lane kernel: the row width of the class-dealt layout is inferred from UN there (GSL_IL), so a 16-lane fused
+// kernel with two rows in flight would share its instantiation.)
+// occ8 (8 workgroups per CU) only on the narrow kernel with the set of distinct rows (launch_lut_fused): the other combinations
+// are not built.
 template <bool FROM_IDS>
 const void* lut_kernel_fused(bool il, bool occ8, bool dedup, bool narrow = false) {
     // narrow: rows of 8-lane groups (32-entry blocks; fused rows of 65..96 entries fill three of them instead of two half-empty
     // 64-entry ones): two rows in flight per lane group keep a wave at 16 rows per step, as four do with 16-lane groups
     if (narrow) {
 #define VET_PICKN(I, O, D) if (il == I && occ8 == O && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, I, O, D, false, true>
-        VET_PICKN(false, false, false); VET_PICKN(false, true, false); VET_PICKN(false, false, true); VET_PICKN(false, true, true);
-        VET_PICKN(true, false, false); VET_PICKN(true, true, false); VET_PICKN(true, false, true); VET_PICKN(true, true, true);
+        VET_PICKN(false, false, false); VET_PICKN(false, false, true); VET_PICKN(false, true, true);
+        VET_PICKN(true, false, false); VET_PICKN(true, false, true); VET_PICKN(true, true, true);
 #undef VET_PICKN
+        return nullptr;
     }
-#define VET_PICK(I, O, D) if (il == I && occ8 == O && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, VET_FUSED_UN, I, O, D, false, true>
-    VET_PICK(false, false, false); VET_PICK(false, true, false); VET_PICK(true, false, false); VET_PICK(true, true, false);
-    VET_PICK(false, false, true); VET_PICK(false, true, true); VET_PICK(true, false, true); VET_PICK(true, true, true);
+    if (occ8) return nullptr;
+#define VET_PICK(I, D) if (il == I && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 4, I, false, D, false, true>
+    VET_PICK(false, false); VET_PICK(true, false); VET_PICK(false, true); VET_PICK(true, true);
 #undef VET_PICK
     return nullptr;
 }
@@ -252,6 +272,15 @@ int choose_formulation(vet_plan* pl, int k, bool want_table, int U, hipStream_t 
     return VET_OK;
 }
 
+// The per-frame set of distinct rows pays for itself from ~128 users per frame on (measured: config 2, 64 users, 0.0332 ms
+// without vs 0.0366 ms with; config 4, 256 users, equal; config 3, 1024 users, 1.60 -> 1.53 ms).  users: of the video, or the
+// most of any video of a batch.  The fused table always has its direction records (ensure_fused refuses larger plans); the
+// per-lattice tables have them where the plan's rows fit the set's key.
+bool dedup_fused(int users) { return users >= vet::DEDUP_MIN_USERS; }
+bool dedup_lattices(const vet_plan* pl, int users) {
+    return (uint64_t)pl->n_rows <= vet::DEDUP_MAX_DIRS && pl->d_dirrec && dedup_fused(users);
+}
+
 // one launch of the table kernel over lattices lat_idx[0..K) of the plan (single video or a batch)
 template <bool FROM_IDS>
 int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& src, int U, int T,
@@ -262,7 +291,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     *launched = false;
     vet::LutParams q{};
     q.resolve = d_resolve;
-    q.dedup_min_users = c->tune.dedup_min_users;
+    q.dedup_min_users = vet::DEDUP_MIN_USERS;
     q.videos = d_videos; q.n_videos = n_videos;
     q.src = src; q.U = U; q.T = T;
     q.nearest = pl->lat[lat_idx[0]].d_nearest;
@@ -284,20 +313,16 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     }
     q.entropy = d_entropy; q.assign = d_assign; q.weights = d_weights; q.present = d_present;
     q.status = d_status;
-    // the per-frame set of distinct rows pays for itself from ~128 users per frame on (measured: config 2, 64
-    // users, 0.0332 ms without vs 0.0366 ms with; config 4, 256 users, equal; config 3, 1024 users, 1.60 -> 1.53 ms)
-    const bool dedup = (uint64_t)pl->n_rows <= vet::DEDUP_MAX_DIRS && pl->d_dirrec && !c->tune.no_dedup &&
-                       (d_videos ? batch_max_users : U) >= c->tune.dedup_min_users;
-    int blocks = blocks_batch, threads = 256;
+    const bool dedup = dedup_lattices(pl, d_videos ? batch_max_users : U);
+    int blocks = blocks_batch;
+    const int threads = 256;     // __launch_bounds__(256); the FP table's row sort counts on 256 threads
     size_t lds = lds_batch;
     bool occ8 = true;
     // FP table: canonical row order through a bitmap over (row, mirrored) where that is small (<= 8 KB of LDS)
     q.sort_words = (fpt && dedup && 2 * pl->n_rows <= 65536) ? (int)((2 * pl->n_rows + 31) / 32) : 0;
     if (!d_videos) {
         q.UC = U < 2048 ? U : 2048;
-        threads = fpt ? 256 : c->tune.lut_threads;     // the FP table's row sort counts on 256 threads
         int fpw = lut_frames_per_wg(U, T, c->n_cu, q.n_sum);
-        if (c->tune.lut_fpw) fpw = c->tune.lut_fpw;
         for (;; fpw /= 2) {
             lds = vet::lut_lds_bytes(U, q.UC, fpw, q.n_sum, dedup, d_resolve != nullptr, fpt ? threads / 64 : 1, q.sort_words);
             if (lds <= c->lds_max || fpw == 1) break;
@@ -305,7 +330,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
         if (lds > c->lds_max) return VET_OK;      // not launched: caller falls back to the sweep
         q.FPW = fpw;
         blocks = (T + fpw - 1) / fpw;
-        occ8 = K == 1 && threads == 256;
+        occ8 = K == 1;
     } else {
         q.FPW = 1; q.UC = 1;
     }
@@ -327,7 +352,7 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
     const auto& F = pl->fused;
     *launched = false;
     vet::LutParams q{};
-    q.dedup_min_users = c->tune.dedup_min_users;
+    q.dedup_min_users = vet::DEDUP_MIN_USERS;
     q.videos = d_videos; q.n_videos = n_videos;
     q.src = src; q.U = U; q.T = T;
     q.nearest = pl->lat[0].d_nearest; q.alias = nullptr; q.dirrec = F.d_dirrec; q.rec_meta = 1;
@@ -337,13 +362,12 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
     q.lat[0].n = F.lay.N; q.lat[0].hmax = 0.0; q.lat[0].zrow = (uint32_t)F.R;
     q.lay = F.lay;
     q.entropy = d_entropy; q.assign = d_assign; q.weights = d_weights; q.present = d_present; q.status = d_status;
-    const bool dedup = !c->tune.no_dedup && (d_videos ? batch_max_users : U) >= c->tune.dedup_min_users;
+    const bool dedup = dedup_fused(d_videos ? batch_max_users : U);
     int blocks = blocks_batch, threads = 256;
     size_t lds = lds_batch;
     if (!d_videos) {
         q.UC = U < 2048 ? U : 2048;
         int fpw = lut_frames_per_wg(U, T, c->n_cu, q.n_sum);
-        if (c->tune.lut_fpw) fpw = c->tune.lut_fpw;
         for (;; fpw /= 2) {
             lds = vet::lut_lds_bytes(U, q.UC, fpw, q.n_sum, dedup);
             if (lds <= c->lds_max || fpw == 1) break;
@@ -357,7 +381,7 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
     // 8 workgroups per CU (64 VGPRs) pay for the narrow kernel on a single video of many users (two rows in flight: few
     // registers; config 4 0.146 -> 0.142 ms), not for the 16-lane kernel with four rows in flight (defaults +5 %), for
     // batches (+1 %) or for frames without the set (config 2 +2 %)
-    const bool occ8 = c->tune.lut_occ8 >= 0 ? c->tune.lut_occ8 != 0 : (F.gs_log2 == 3 && !d_videos && dedup);
+    const bool occ8 = F.gs_log2 == 3 && !d_videos && dedup;
 #if VET_STAGE_CYCLES
     DevBuf dbg, tl;                           // development builds: cycles per stage (thread 0 of every workgroup), synchronous
     HIP_TRY(dbg.alloc(64));
@@ -690,33 +714,20 @@ int launch_spatial_main(vet_plan* pl, const vet::SampleSrc& src, int U, int T, d
         p.full_norm = (L.binned && pl->weighted) ? 1 : 0;
         p.norm_n = L.norm_n;
         p.frame_list = nullptr;
-        if (!hist_weighted && !FROM_IDS && U <= 4096 && !c->tune.u_no_lds) {
-            // persistent variant with the nearest LUT in LDS: a round is 4096 users = FB frames
-            // (2048 pairs with 16-byte loads when U is even, 4096 single users otherwise)
-            constexpr int THREADS = 1024;
+        if (!hist_weighted && !FROM_IDS && U <= 4096) {
+            // the persistent variant (k_spatial_u_lds): a round is 4096 users
             const bool pairs = (U & 1) == 0;
-            int FB = 4096 / U;
-            if (FB > 64) FB = 64;
-            auto lds_of = [&](int fb) {
-                return (((size_t)pl->n_dirs * 2 + 15) & ~(size_t)15) + (size_t)(U + 1) * 8 +
-                       ((((size_t)fb * L.n + 1) & ~(size_t)1) * 4) + (size_t)fb * (THREADS / 64) * 8 + fb * 4 + 16;
-            };
-            while (FB > 1 && lds_of(FB) > c->lds_max) FB /= 2;      // few users x many tiles: fewer frames per round
-            const size_t lds = lds_of(FB);
+            const int FB = u_lds_frames(pl, U, L.n, std::min(4096 / U, 64));
+            const size_t lds = u_lds_bytes(pl, U, L.n, FB);
             if (lds <= c->lds_max) {
                 vet::SpatialParams q = p;
                 q.FPW = FB;
-                const long nblk = ((long)T + FB - 1) / FB;
-                long grid = (long)c->n_cu * c->tune.u_wgs_per_cu;
-                if (grid > nblk) grid = nblk;
-                // even rounds: every persistent workgroup walks the same number of blocks (no tail)
-                const long rounds = (nblk + grid - 1) / grid;
-                grid = (nblk + rounds - 1) / rounds;
+                const long grid = u_lds_grid(c, ((long)T + FB - 1) / FB);
                 ProfScope ps(c, s, KID_SPATIAL);
                 const void* fn = q.weights ? (pairs ? (const void*)vet::k_spatial_u_lds<true, true> : (const void*)vet::k_spatial_u_lds<true, false>)
                                            : (pairs ? (const void*)vet::k_spatial_u_lds<false, true> : (const void*)vet::k_spatial_u_lds<false, false>);
                 void* args[] = {(void*)&q};
-                HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(THREADS), args, lds, s));
+                HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(kULdsThreads), args, lds, s));
                 HIP_TRY(hipGetLastError());
                 continue;
             }
@@ -768,10 +779,14 @@ int spatial_set_attrs(vet_ctx* c) {
         ATTR_TRY(spatial_w_kernel<true>(0, R, true), c->lds_max);
     }
     for (int v = 0; v < 8; ++v) {
-        ATTR_TRY(lut_kernel_fused<false>(v & 1, v & 2, v & 4), c->lds_max);
-        ATTR_TRY(lut_kernel_fused<true>(v & 1, v & 2, v & 4), c->lds_max);
-        ATTR_TRY(lut_kernel_fused<false>(v & 1, v & 2, v & 4, true), c->lds_max);
-        ATTR_TRY(lut_kernel_fused<true>(v & 1, v & 2, v & 4, true), c->lds_max);
+        if (!(v & 2)) {                 // the fused kernels that are built (lut_kernel_fused)
+            ATTR_TRY(lut_kernel_fused<false>(v & 1, false, v & 4), c->lds_max);
+            ATTR_TRY(lut_kernel_fused<true>(v & 1, false, v & 4), c->lds_max);
+        }
+        if (!(v & 2) || (v & 4)) {
+            ATTR_TRY(lut_kernel_fused<false>(v & 1, v & 2, v & 4, true), c->lds_max);
+            ATTR_TRY(lut_kernel_fused<true>(v & 1, v & 2, v & 4, true), c->lds_max);
+        }
         ATTR_TRY(lut_kernel<false>(v & 1, v & 2, v & 4), c->lds_max);
         ATTR_TRY(lut_kernel<true>(v & 1, v & 2, v & 4), c->lds_max);
         if (!(v & 2)) {
@@ -848,7 +863,6 @@ static int batch_unweighted(vet_plan* pl, int n_videos, const vet_video* videos,
     *launched = false;
     vet_ctx* c = pl->ctx;
     const int K = (int)pl->lat.size();
-    if (c->tune.u_no_lds) return VET_OK;
     int max_users = 0;
     bool pairs = true;
     long frames = 0;
@@ -858,18 +872,12 @@ static int batch_unweighted(vet_plan* pl, int n_videos, const vet_video* videos,
         frames += videos[v].n_frames;
     }
     if (max_users > 4096) return VET_OK;
-    constexpr int THREADS = 1024;
     std::vector<vet::VideoDesc> desc((size_t)n_videos * K);
     std::vector<long> frame0((size_t)n_videos + 1);
     std::vector<double*> outs(n_videos);
     int n_max = 0;
     for (const auto& L : pl->lat) n_max = std::max(n_max, L.n);
-    auto lds_of = [&](int fb) {
-        return (((size_t)pl->n_dirs * 2 + 15) & ~(size_t)15) + (size_t)(max_users + 1) * 8 +
-               ((((size_t)fb * n_max + 1) & ~(size_t)1) * 4) + (size_t)fb * (THREADS / 64) * 8 + fb * 4 + 16;
-    };
-    int fb_cap = 64;
-    while (fb_cap > 1 && lds_of(fb_cap) > c->lds_max) fb_cap /= 2;
+    const int fb_cap = u_lds_frames(pl, max_users, n_max, 64);
     int fb_max = 1, block = 0;
     for (int v = 0; v < n_videos; ++v) {
         const vet_video& x = videos[v];
@@ -886,7 +894,7 @@ static int batch_unweighted(vet_plan* pl, int n_videos, const vet_video* videos,
         block += (x.n_frames + fb - 1) / fb;
     }
     frame0[n_videos] = frames;
-    const size_t lds = lds_of(fb_max);
+    const size_t lds = u_lds_bytes(pl, max_users, n_max, fb_max);
     if (lds > c->lds_max) return VET_OK;
     double* ws = nullptr;
     if (K > 1) {
@@ -929,14 +937,11 @@ static int batch_unweighted(vet_plan* pl, int n_videos, const vet_video* videos,
         q.norm_n = L.norm_n;
         q.videos = (const vet::VideoDesc*)base + (size_t)k * n_videos;
         q.n_videos = n_videos; q.n_blocks = block;
-        long grid = (long)c->n_cu * c->tune.u_wgs_per_cu;
-        if (grid > block) grid = block;
-        const long rounds = (block + grid - 1) / grid;
-        grid = (block + rounds - 1) / rounds;
+        const long grid = u_lds_grid(c, block);
         ProfScope ps(c, s, KID_SPATIAL);
         const void* fn = pairs ? (const void*)vet::k_spatial_u_lds<false, true, true> : (const void*)vet::k_spatial_u_lds<false, false, true>;
         void* args[] = {(void*)&q};
-        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(THREADS), args, lds, s));
+        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(kULdsThreads), args, lds, s));
         HIP_TRY(hipGetLastError());
     }
     if (K > 1) {
@@ -984,7 +989,7 @@ int vet_spatial_entropy_batch(vet_plan* pl, int n_videos, const vet_video* video
         if (rc) return rc;
         if (pl->fused.state == 1) {
             const int N = pl->fused.lay.N;
-            const bool dedup = !c->tune.no_dedup && max_users >= c->tune.dedup_min_users;
+            const bool dedup = dedup_fused(max_users);
             std::vector<vet::VideoDesc> desc(n_videos);
             int block = 0;
             size_t lds_max = 0;
@@ -1028,8 +1033,7 @@ int vet_spatial_entropy_batch(vet_plan* pl, int n_videos, const vet_video* video
     std::vector<vet::VideoDesc> desc;
     size_t lds_max = 0;
     if (table) {
-        const bool dedup = (uint64_t)pl->n_rows <= vet::DEDUP_MAX_DIRS && pl->d_dirrec && !c->tune.no_dedup &&
-                           max_users >= c->tune.dedup_min_users;
+        const bool dedup = dedup_lattices(pl, max_users);
         desc.resize(n_videos);
         int block = 0;
         for (int v = 0; v < n_videos && table; ++v) {

@@ -12,19 +12,55 @@ namespace vh {
 
 namespace {
 
+// Shape of the transition kernels for up to U users per frame over a lattice of n tiles (single videos: the video's users;
+// batches: the most of any video, and the largest lattice for the decision, each lattice's own n for its launch)
+constexpr size_t kTransLdsCap = 160 * 1024 - 512;     // a single workgroup may take the whole LDS
+struct TransGeometry {
+    int HS, lg;             // bucket-hash slots (a power of two >= 2 U, at least 64) and their log2
+    size_t lds_tiles;       // LDS of every transition kernel
+    size_t lds_run;         // k_transition_run: + the bucket hash + log2(k), k <= U
+    bool run;               // k_transition_run holds the frame (U <= 4096 and lds_run fits); the fields below only then
+    // k_transition_run: persistent workgroups over contiguous runs of rows; users per thread 1, 2 or 4 — two waves per row up
+    // to 512 users (measured: 46 us vs 51 us with four, profiles/r02); workgroups per CU by LDS and wave slots, 1..8
+    int threads, upt;
+    long per_cu;
+};
+TransGeometry trans_geometry(int U, int n) {
+    TransGeometry g{};
+    g.HS = 64; g.lg = 6;
+    while ((long)g.HS < 2L * U) { g.HS <<= 1; ++g.lg; }
+    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
+    g.lds_tiles = 2 * 20 * 8 + 4 * n4 * 4;
+    g.lds_run = g.lds_tiles + (size_t)3 * g.HS * 4 + ((size_t)U + 2) * 8;
+    g.run = U <= 4096 && g.lds_run <= kTransLdsCap;
+    if (!g.run) return g;
+    g.threads = U <= 512 ? 128 : (U <= 2048 ? 512 : 1024);
+    g.upt = (U + g.threads - 1) / g.threads;
+    g.upt = g.upt <= 1 ? 1 : (g.upt <= 2 ? 2 : 4);          // at most 4: U <= 4096, and threads * upt >= U
+    g.per_cu = (long)(kTransLdsCap / g.lds_run);
+    const long by_waves = 32 / (g.threads / 64);
+    if (g.per_cu > by_waves) g.per_cu = by_waves;
+    g.per_cu = g.per_cu > 8 ? 8 : (g.per_cu < 1 ? 1 : g.per_cu);
+    return g;
+}
+
+// the shapes trans_geometry gives: 128 threads (up to 512 users: the size is compiled in) with 1, 2 or 4 users per thread;
+// 512 or 1024 threads (more than 512 users) with 2 or 4
 template <bool FROM_IDS>
 const void* transition_run_kernel(int upt, bool exact, int threads) {
-    // the default workgroup of up to 512 users (128 threads) has its size compiled in
-#define VET_PICK(N) if (upt == N) return threads == 128 ? (exact ? (const void*)vet::k_transition_run<FROM_IDS, N, true, 128> : (const void*)vet::k_transition_run<FROM_IDS, N, false, 128>) \
-                                                        : (exact ? (const void*)vet::k_transition_run<FROM_IDS, N, true, 0> : (const void*)vet::k_transition_run<FROM_IDS, N, false, 0>)
-    VET_PICK(1); VET_PICK(2); VET_PICK(4); VET_PICK(8);
+#define VET_PICK(N, TH) if (upt == N) return exact ? (const void*)vet::k_transition_run<FROM_IDS, N, true, TH> : (const void*)vet::k_transition_run<FROM_IDS, N, false, TH>
+    if (threads == 128) {
+        VET_PICK(1, 128); VET_PICK(2, 128); VET_PICK(4, 128);
+    } else {
+        VET_PICK(2, 0); VET_PICK(4, 0);
+    }
 #undef VET_PICK
     return nullptr;
 }
 
 const void* transition_batch_kernel(int upt, bool exact) {       // batched launches: the workgroup size is read from blockDim
 #define VET_PICK(N) if (upt == N) return exact ? (const void*)vet::k_transition_run<false, N, true, 0, true> : (const void*)vet::k_transition_run<false, N, false, 0, true>
-    VET_PICK(1); VET_PICK(2); VET_PICK(4); VET_PICK(8);
+    VET_PICK(1); VET_PICK(2); VET_PICK(4);
 #undef VET_PICK
     return nullptr;
 }
@@ -42,18 +78,12 @@ int launch_transition(vet_plan* pl, const vet::SampleSrc& src, int U, int T, dou
         if (rc) return rc;
         ent_k = (double*)c->ws;
     }
-    int HS = 64, lg = 6;
-    const int hs_pct = c->tune.t_hs_pct;      // bucket-hash slots per 100 users
-    while ((long)HS * 100 < (long)hs_pct * U) { HS <<= 1; ++lg; }
     const size_t U4 = ((size_t)U + 3) & ~(size_t)3;
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
-        const size_t n4 = ((size_t)L.n + 3) & ~(size_t)3;
-        const size_t lds_tiles = 2 * 20 * 8 + 4 * n4 * 4;
-        const size_t lds_run = lds_tiles + (size_t)3 * HS * 4 + ((size_t)U + 2) * 8;     // + log2(k), k <= U
-        const size_t lds_cap = 160 * 1024 - 512;     // a single workgroup may take the whole LDS
-        if (lds_tiles > lds_cap)
-            return fail(VET_ERR_UNSUPPORTED, "transition kernel: %d tiles need %zu B of LDS (max %zu)", L.n, lds_tiles, lds_cap);
+        const TransGeometry g = trans_geometry(U, L.n);
+        if (g.lds_tiles > kTransLdsCap)
+            return fail(VET_ERR_UNSUPPORTED, "transition kernel: %d tiles need %zu B of LDS (max %zu)", L.n, g.lds_tiles, kTransLdsCap);
         vet::TransParams p{};
         p.src = src;
         p.U = U; p.T = T;
@@ -65,29 +95,18 @@ int launch_transition(vet_plan* pl, const vet::SampleSrc& src, int U, int T, dou
         p.srccount = k == 0 ? d_srccount : nullptr;
         p.common = k == 0 ? d_common : nullptr;
         p.status = k == 0 ? d_status : nullptr;
-        p.HS = HS; p.hs_shift = 32 - lg;
+        p.HS = g.HS; p.hs_shift = 32 - g.lg;
         p.log2_tab = c->d_log2;
         p.scratch = nullptr;
         p.run_q = 0; p.run_r = 0;
         ProfScope ps(c, s, KID_TRANSITION);
-        if (U <= 4096 && lds_run <= lds_cap && !c->tune.t_global) {
-            // persistent workgroups over contiguous runs of rows (k_transition_run); users per thread 1, 2, 4 or 8:
-            // two waves per row up to 512 users (measured: 46 us vs 51 us with four, profiles/r02)
-            int threads = U <= 512 ? 128 : (U <= 2048 ? 512 : 1024);
-            if (c->tune.t_threads) threads = c->tune.t_threads;
-            int upt = (U + threads - 1) / threads;
-            upt = upt <= 1 ? 1 : (upt <= 2 ? 2 : (upt <= 4 ? 4 : 8));
-            while ((long)upt * threads < U) threads *= 2;
-            long per_cu = (long)(lds_cap / lds_run);
-            const long by_waves = 32 / (threads / 64);
-            if (per_cu > by_waves) per_cu = by_waves;
-            per_cu = c->tune.t_wgs_per_cu ? c->tune.t_wgs_per_cu : (per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu));
-            long grid = (long)c->n_cu * per_cu;
+        if (g.run && !c->tune.t_global) {
+            long grid = (long)c->n_cu * g.per_cu;
             if (grid > R) grid = R;
             p.run_q = (int)(R / grid); p.run_r = (int)(R % grid);
-            const void* fn = transition_run_kernel<FROM_IDS>(upt, (long)upt * threads == U, threads);
+            const void* fn = transition_run_kernel<FROM_IDS>(g.upt, (long)g.upt * g.threads == U, g.threads);
             void* args[] = {(void*)&p};
-            HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, lds_run, s));
+            HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(g.threads), args, g.lds_run, s));
         } else if (U < (1 << 19) && L.n <= vet::TRANS_BIG_MAX_TILES && !c->tune.t_global) {
             // more users than the register kernel holds: the bucket hash stays in LDS, the row is cut into ranges of
             // source tiles whose buckets fit it (k_transition_big); one persistent workgroup per CU
@@ -103,7 +122,7 @@ int launch_transition(vet_plan* pl, const vet::SampleSrc& src, int U, int T, dou
         } else {
             // lattices of thousands of tiles (or 2^19 users): bucket hash and per-user words in global scratch, one slice
             // per persistent workgroup (the reference accepts any number of users, entropy_utils.py:259-332)
-            const size_t slice = ((size_t)3 * HS + 2 * U4) * 4;
+            const size_t slice = ((size_t)3 * g.HS + 2 * U4) * 4;
             long grid = (long)c->n_cu * 2;
             if (grid > R) grid = R;
             while (grid > 1 && slice * (size_t)grid > ((size_t)2 << 30)) grid /= 2;
@@ -111,7 +130,7 @@ int launch_transition(vet_plan* pl, const vet::SampleSrc& src, int U, int T, dou
             int rc = pooled(c, 8, slice * (size_t)grid, &scratch);
             if (rc) return rc;
             p.scratch = (uint32_t*)scratch;
-            hipLaunchKernelGGL((vet::k_transition_any<FROM_IDS>), dim3((unsigned)grid), dim3(1024), lds_tiles, s, p);
+            hipLaunchKernelGGL((vet::k_transition_any<FROM_IDS>), dim3((unsigned)grid), dim3(1024), g.lds_tiles, s, p);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -129,14 +148,15 @@ int launch_transition(vet_plan* pl, const vet::SampleSrc& src, int U, int T, dou
 int transition_set_attrs(vet_ctx* c) {
     std::vector<const void*> tk = {(const void*)vet::k_transition_any<false>, (const void*)vet::k_transition_any<true>,
                                    (const void*)vet::k_transition_big<false>, (const void*)vet::k_transition_big<true>};
-    for (int upt : {1, 2, 4, 8})
-        for (int ex = 0; ex < 2; ++ex)
-            for (int threads : {128, 0}) {
+    for (int upt : {1, 2, 4})
+        for (int ex = 0; ex < 2; ++ex) {
+            for (int threads : {128, 512}) {
+                if (upt == 1 && threads != 128) continue;           // not built (transition_run_kernel)
                 tk.push_back(transition_run_kernel<false>(upt, ex != 0, threads));
                 tk.push_back(transition_run_kernel<true>(upt, ex != 0, threads));
             }
-    for (int upt : {1, 2, 4, 8})
-        for (int ex = 0; ex < 2; ++ex) tk.push_back(transition_batch_kernel(upt, ex != 0));
+            tk.push_back(transition_batch_kernel(upt, ex != 0));
+        }
     for (const void* f : tk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWholeLds));
     return VET_OK;
 }
@@ -190,13 +210,10 @@ int vet_transition_entropy_batch(vet_plan* pl, int n_videos, const vet_video* vi
         min_users = std::min(min_users, x.n_users);
         rows += x.n_frames > 1 ? x.n_frames - 1 : 0;
     }
-    int HS = 64, lg = 6;
-    while (HS < 2 * max_users) { HS <<= 1; ++lg; }
-    size_t n4_max = 0;
-    for (const auto& L : pl->lat) n4_max = std::max(n4_max, ((size_t)L.n + 3) & ~(size_t)3);
-    const size_t lds_cap = 160 * 1024 - 512;
-    const size_t lds_run = 2 * 20 * 8 + 4 * n4_max * 4 + (size_t)3 * HS * 4 + ((size_t)max_users + 2) * 8;
-    bool one_launch = rows > 0 && max_users <= 4096 && lds_run <= lds_cap && !c->tune.t_global;
+    int n_max = 0;
+    for (const auto& L : pl->lat) n_max = std::max(n_max, L.n);
+    const TransGeometry g = trans_geometry(max_users, n_max);
+    bool one_launch = rows > 0 && g.run && !c->tune.t_global;
     for (int v = 0; v < n_videos; ++v) one_launch = one_launch && videos[v].n_frames > 1;
     if (!one_launch) {
         for (int v = 0; v < n_videos; ++v) {
@@ -207,16 +224,7 @@ int vet_transition_entropy_batch(vet_plan* pl, int n_videos, const vet_video* vi
         }
         return VET_OK;
     }
-    int threads = max_users <= 512 ? 128 : (max_users <= 2048 ? 512 : 1024);
-    if (c->tune.t_threads) threads = c->tune.t_threads;
-    int upt = (max_users + threads - 1) / threads;
-    upt = upt <= 1 ? 1 : (upt <= 2 ? 2 : (upt <= 4 ? 4 : 8));
-    while ((long)upt * threads < max_users) threads *= 2;
-    long per_cu = (long)(lds_cap / lds_run);
-    const long by_waves = 32 / (threads / 64);
-    if (per_cu > by_waves) per_cu = by_waves;
-    per_cu = c->tune.t_wgs_per_cu ? c->tune.t_wgs_per_cu : (per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu));
-    long grid_want = (long)c->n_cu * per_cu;
+    long grid_want = (long)c->n_cu * g.per_cu;
     if (grid_want > rows) grid_want = rows;
     if (grid_want < n_videos) grid_want = n_videos;
     std::vector<vet::TransVideo> tv((size_t)n_videos * K);
@@ -265,7 +273,7 @@ int vet_transition_entropy_batch(vet_plan* pl, int n_videos, const vet_video* vi
     double** d_outs = (double**)(base + tv_b + r0_b);
     rc = blob.upload(s);
     if (rc) return rc;
-    const bool exact = min_users == max_users && (long)upt * threads == max_users;
+    const bool exact = min_users == max_users && (long)g.upt * g.threads == max_users;
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
         vet::TransParams p{};
@@ -273,15 +281,13 @@ int vet_transition_entropy_batch(vet_plan* pl, int n_videos, const vet_video* vi
         p.U = max_users; p.T = 0;
         p.nearest = L.d_nearest; p.n = L.n; p.hmax = L.hmax;
         p.status = k == 0 ? d_status : nullptr;
-        p.HS = HS; p.hs_shift = 32 - lg;
+        p.HS = g.HS; p.hs_shift = 32 - g.lg;
         p.log2_tab = c->d_log2;
         p.videos = (const vet::TransVideo*)base + (size_t)k * n_videos; p.n_videos = n_videos;
-        const size_t n4 = ((size_t)L.n + 3) & ~(size_t)3;
-        const size_t lds = 2 * 20 * 8 + 4 * n4 * 4 + (size_t)3 * HS * 4 + ((size_t)max_users + 2) * 8;
         ProfScope ps(c, s, KID_TRANSITION);
-        const void* fn = transition_batch_kernel(upt, exact);
+        const void* fn = transition_batch_kernel(g.upt, exact);
         void* args[] = {(void*)&p};
-        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)wg), dim3(threads), args, lds, s));
+        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)wg), dim3(g.threads), args, trans_geometry(max_users, L.n).lds_run, s));
         HIP_TRY(hipGetLastError());
     }
     if (K > 1) {
