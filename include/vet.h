@@ -46,7 +46,8 @@ extern "C" {
                            (+ vet_plan_set_raw_weights); batch descriptors in an event-guarded ring;
                            0.1.4.1: vet_device_pci_bus_id; vet_plan_set_fp64 (formulation 4, `dtable`) added
                            without a new number: existing callers see no change; the vet_heatmap_* entry points
-                           (per-frame tile-attention heatmaps) added the same way */
+                           (per-frame tile-attention heatmaps) and the vet_tiling_* entry points
+                           (tilings drawn on the unit sphere) added the same way */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -363,6 +364,40 @@ int vet_heatmap_render(vet_heatmap *hm, const double *d_weights /* [T][n_tiles] 
 int vet_heatmap_render_result(vet_heatmap *hm, vet_result *r, const int32_t *h_present /* [n_rows] */,
                               const double *h_mu, const double *h_mv /* [n_rows][U] or NULL */, int n_users,
                               int64_t row0, int64_t n_rows, uint8_t *h_rgb);
+
+/* ---- tilings drawn on the unit sphere --------------------------------------------------------
+ * The scenes of the reference's pyvista tiling renders (save_*tiling_visualization_*, utilities/visualization_utils.py:
+ * 306-674) as uint8 RGB frames [n][H][W][3], C-contiguous, row 0 at the top; pixel (row, col) has its centre at image
+ * coordinates (X, Y) = (col + 0.5, row + 0.5).  All arithmetic is FP64.  This is the library's own frame definition (no
+ * lighting, anti-aliasing or axes; not a pixel match of pyvista); tests/_tiling_oracle.py implements it in numpy.
+ *   arcs: each (a, b) is drawn as the 49 chords between the spherical_interpolation points of a / |a| and b / |b| at
+ *     t = np.linspace(0, 1, 50); an arc with coincident or antipodal ends (sin(theta) == 0 or clip(â.b̂) == -1: sin(pi) is
+ *     1.2e-16 in FP64) draws nothing, and so does a chord with a non-finite end.  Duplicate arcs are allowed;
+ *   camera (P, U, F) per frame: dist = |P - F|, d = (F - P) / dist, r = normalise(d x U), u = r x d, pixel size
+ *     s = 2 dist sin(15 deg) / H (a parallel projection of a 30-degree view angle); X(p) = W/2 + (p - F).r / s,
+ *     Y(p) = H/2 - (p - F).u / s; p is in front iff p.(-d) > 0.  dist == 0 or d x U == 0: VET_ERR_INVALID;
+ *   line: the pixel centre is within distance <= 1 of a projected chord AB; tau = clamp((q - A).(B - A) / |B - A|^2, 0, 1)
+ *     (0 when A == B), and the chord point P_i + tau (P_i+1 - P_i) decides front-line / back-line;
+ *   point (centres): |X(c) - X_q| < 5 and |Y(c) - Y_q| < 5; c.(-d) > 0 decides front-point / back-point;
+ *   disc: ((X_q - X0)^2 + (Y_q - Y0)^2) s^2 <= 1, (X0, Y0) the projection of the origin (the unit sphere);
+ *   colour: under = back-point ? red : back-line ? black : background; pixel = front-point ? red : front-line ? black :
+ *     disc ? blend(under) : under, blend(x) = floor(0.3 * 128 + 0.7 x + 0.5) per channel (grey 128 at opacity 0.3).
+ * Frames are rendered in blocks of B = min(64, max(4, 32 MiB / (3 W H)) rounded down to a multiple of 4) frames, so device
+ * memory does not grow with n_frames.  A tiling belongs to its context (destroy it first) and, like the context, is used
+ * from one thread on one stream at a time.  VET_ERR_INVALID: a NULL argument, n_arcs, width, height or n_frames <= 0,
+ * n_centres < 0, width or height > 16384, more than 2^22 arcs or 2^26 centres, an invalid camera. */
+typedef struct vet_tiling vet_tiling;     /* the chord points (and centres) of one scene, on one context's device */
+int vet_tiling_create(vet_ctx *ctx, const double *h_arcs /* [n_arcs][2][3] */, int n_arcs,
+                      const double *h_centres /* [n_centres][3] or NULL */, int n_centres, int width, int height,
+                      vet_tiling **out);
+int vet_tiling_destroy(vet_tiling *tl);
+/* h_cameras [n_frames][9] = (P, U, F) per frame, background [3] (RGB).  d_rgb: device, 4-byte aligned, [n][H][W][3];
+ * asynchronous on `stream` (same stream convention as every other entry); the cameras are checked before any device work */
+int vet_tiling_render(vet_tiling *tl, const double *h_cameras, int n_frames, const uint8_t *background, uint8_t *d_rgb,
+                      void *stream);
+/* the same frames to host memory h_rgb [n][H][W][3], synchronous, through two pinned staging blocks */
+int vet_tiling_render_host(vet_tiling *tl, const double *h_cameras, int n_frames, const uint8_t *background,
+                           uint8_t *h_rgb);
 
 /* ---- host-side track loader (no GPU involved) -------------------------------------------
  * Replaces the per-file `pd.read_csv(filepath)` + column selection of process_viewport_data

@@ -58,6 +58,10 @@ __device__ __forceinline__ void nt_store(int2* p, int2 v) {
     __builtin_nontemporal_store(v.y, &p->y);
 }
 
+// 12 bytes = 4 RGB pixels, stored as one dwordx3 at any 4-byte-aligned address (k_heatmap_fill, k_tiling_compose)
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
+
 // numpy-scalar round(v, 6) == rint(v * 1e6) / 1e6   (data_types.py:213-215)
 __device__ __forceinline__ double round6(double v) { return rint(v * 1e6) / 1e6; }
 

@@ -68,9 +68,6 @@ __global__ void k_heatmap_palette(const double* __restrict__ weights, const int3
 // and their map entries are one 8-byte load.  Grid-stride; (t, q) of the first quad from one division, then stepped by
 // the stride's (frames, pixels).  The last N % 4 pixels of the block are written byte-wise by the first threads.
 // ------------------------------------------------------------------------------------------
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
-
 struct FillParams {
     const uint16_t* map;   // [HW]
     const uint32_t* pal;   // [T][n]

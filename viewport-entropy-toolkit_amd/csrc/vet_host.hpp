@@ -6,7 +6,8 @@
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile map, palette, fill, markers) and their launch logic
-//   vet_hostapi.hip     host-buffer entry points, device-resident results and heatmaps (no kernels of their own)
+//   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
+//   vet_hostapi.hip     host-buffer entry points, device-resident results, heatmaps and tilings (no kernels of their own)
 // Every kernel header is included by exactly one of them.  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
@@ -284,6 +285,25 @@ struct HeatmapGeom {
 int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uint16_t* d_map, hipStream_t s);
 int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, const int32_t* d_present, const double* d_mu,
                    const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s);
+
+// vet_tiling.hip: tilings drawn on the unit sphere.  tiling_chords: arcs [n][2][3] -> 50 slerp points per arc
+// (k_tiling_chords).  tiling_render: frames [0, T) -> d_rgb [T][H][W][3]: clear d_flags [T][H][W], k_tiling_splat,
+// k_tiling_compose, enqueued on s.  The cameras are computed on the host (vet_hostapi.hip).
+struct TilingCam {
+    double F[3], r[3], u[3], nd[3];    // focal point; right, up and -view direction (unit vectors)
+    double s;                          // world size of a pixel
+    double X0, Y0;                     // image position of the origin (the sphere's centre)
+};
+struct TilingGeom {
+    const double* d_pts = nullptr;     // [n_arcs][50][3] slerp points (NaN: the arc draws nothing)
+    const double* d_centres = nullptr; // [n_centres][3]
+    long n_arcs = 0, n_centres = 0;
+    int W = 0, H = 0;
+    uint32_t colour[6] = {};           // packed RGB: background, red, black, then each blended with the sphere
+};
+int tiling_chords(vet_ctx* c, const double* d_arcs, long n_arcs, double* d_pts, hipStream_t s);
+int tiling_render(vet_ctx* c, const TilingGeom& g, const TilingCam* d_cam, int T, uint32_t* d_flags, uint8_t* d_rgb,
+                  hipStream_t s);
 
 // dynamic-LDS limits of the run kernels (once per context, from vet_plan_create)
 int spatial_set_attrs(vet_ctx* c);

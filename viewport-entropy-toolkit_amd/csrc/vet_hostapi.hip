@@ -1,6 +1,7 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h): stage through the context's grow-only device
 // buffers, run the device-pointer entry points, copy back (synchronous); device-resident results (vet_result); heatmaps
-// (vet_heatmap: the map and the render pipeline; the kernels are vet_heatmap.hip's).
+// (vet_heatmap: the map and the render pipeline; the kernels are vet_heatmap.hip's); tilings (vet_tiling: the cameras and
+// the block loop; the kernels are vet_tiling.hip's).
 // No kernels of its own and no CPU compute path.
 #include "vet_host.hpp"
 
@@ -519,6 +520,202 @@ int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_p
     const int ls = (int)((nb - 1) & 1);
     if (hipEventSynchronize(hm->copied[ls]) != hipSuccess) return drain(fail(VET_ERR_DEVICE, "hipEventSynchronize failed"));
     std::memcpy(h_rgb + (size_t)(nb - 1) * B * frame, hm->h_pin[ls], (size_t)rows_of(nb - 1) * frame);
+    HIP_TRY(hipStreamSynchronize(s));
+    return VET_OK;
+}
+
+
+
+// ---- tilings on the unit sphere (include/vet.h) -----------------------------------------------------------------------
+struct vet_tiling {
+    vet_ctx* ctx = nullptr;
+    int device = 0;
+    TilingGeom g;
+    double* d_pts = nullptr;             // [n_arcs][50][3]
+    double* d_centres = nullptr;         // [n_centres][3] (null without centres)
+    int B = 0;                           // frames per block: the flags of one block are B * H * W * 4 bytes
+    uint32_t* d_flags = nullptr;         // [B][H][W]
+    // cameras of a call, computed on the host: pinned copy (reused once the event says its upload has left) -> device
+    TilingCam* h_cam = nullptr;
+    TilingCam* d_cam = nullptr;
+    int cam_cap = 0;
+    hipEvent_t cam_up = nullptr;
+    // vet_tiling_render_host: two RGB blocks and their pinned copies
+    uint8_t* d_rgb[2] = {nullptr, nullptr};
+    uint8_t* h_pin[2] = {nullptr, nullptr};
+    hipEvent_t copied[2] = {nullptr, nullptr};
+};
+
+static constexpr double kSin15 = 0.25881904510252074;      // sin(15 degrees): half of the 30-degree view angle
+static constexpr size_t kTilingBlockBytes = (size_t)32 << 20;
+
+// Camera of one frame (P, U, F) as include/vet.h defines it; false for dist == 0, d x U == 0 or a non-finite value.
+static bool tiling_camera(const double* c9, int W, int H, TilingCam& o) {
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(c9[k])) return false;
+    const double *P = c9, *U = c9 + 3, *F = c9 + 6;
+    const double vx = P[0] - F[0], vy = P[1] - F[1], vz = P[2] - F[2];
+    const double dist = std::sqrt(vx * vx + vy * vy + vz * vz);
+    if (!(dist > 0.0)) return false;
+    const double d[3] = {(F[0] - P[0]) / dist, (F[1] - P[1]) / dist, (F[2] - P[2]) / dist};
+    const double x[3] = {d[1] * U[2] - d[2] * U[1], d[2] * U[0] - d[0] * U[2], d[0] * U[1] - d[1] * U[0]};
+    const double xl = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    if (!(xl > 0.0)) return false;
+    for (int k = 0; k < 3; ++k) { o.F[k] = F[k]; o.r[k] = x[k] / xl; o.nd[k] = -d[k]; }
+    o.u[0] = o.r[1] * d[2] - o.r[2] * d[1];
+    o.u[1] = o.r[2] * d[0] - o.r[0] * d[2];
+    o.u[2] = o.r[0] * d[1] - o.r[1] * d[0];
+    o.s = 2.0 * dist * kSin15 / (double)H;
+    if (!(o.s > 0.0) || !std::isfinite(o.s)) return false;
+    const double ox = 0.0 - F[0], oy = 0.0 - F[1], oz = 0.0 - F[2];
+    o.X0 = (double)W / 2.0 + (ox * o.r[0] + oy * o.r[1] + oz * o.r[2]) / o.s;
+    o.Y0 = (double)H / 2.0 - (ox * o.u[0] + oy * o.u[1] + oz * o.u[2]) / o.s;
+    return true;
+}
+
+static uint32_t tiling_blend(uint32_t rgb) {                 // floor(0.3 * 128 + 0.7 x + 0.5) per channel
+    uint32_t out = 0;
+    for (int k = 0; k < 3; ++k) {
+        const double x = (double)((rgb >> (8 * k)) & 0xFF);
+        out |= (uint32_t)std::floor(0.3 * 128.0 + 0.7 * x + 0.5) << (8 * k);
+    }
+    return out;
+}
+
+// Checks the arguments of a render, computes its cameras and stages them on the device (stream-ordered on s).
+static int tiling_begin(vet_tiling* tl, const double* h_cameras, int T, const uint8_t* bg, hipStream_t s) {
+    std::vector<TilingCam> cams((size_t)T);
+    for (int f = 0; f < T; ++f)
+        if (!tiling_camera(h_cameras + 9 * (size_t)f, tl->g.W, tl->g.H, cams[f]))
+            return fail(VET_ERR_INVALID, "camera %d: the position equals the focal point, the view-up is parallel to the view "
+                                         "direction, or a value is not finite", f);
+    const uint32_t base[3] = {(uint32_t)bg[0] | (uint32_t)bg[1] << 8 | (uint32_t)bg[2] << 16, 0x0000FFu, 0u};
+    for (int k = 0; k < 3; ++k) { tl->g.colour[k] = base[k]; tl->g.colour[3 + k] = tiling_blend(base[k]); }
+    HIP_TRY(hipSetDevice(tl->device));
+    if (tl->cam_cap < T) {                                   // grow-only
+        HIP_TRY(hipStreamSynchronize(s));                    // a pending render may still read them
+        if (tl->cam_up) HIP_TRY(hipEventSynchronize(tl->cam_up));
+        if (tl->h_cam) HIP_TRY(hipHostFree(tl->h_cam));
+        if (tl->d_cam) HIP_TRY(hipFree(tl->d_cam));
+        tl->h_cam = nullptr; tl->d_cam = nullptr; tl->cam_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&tl->h_cam, (size_t)T * sizeof(TilingCam), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void**)&tl->d_cam, (size_t)T * sizeof(TilingCam)));
+        tl->cam_cap = T;
+    }
+    if (!tl->cam_up) HIP_TRY(hipEventCreateWithFlags(&tl->cam_up, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(tl->cam_up));                // the previous upload has left the pinned copy
+    std::memcpy(tl->h_cam, cams.data(), (size_t)T * sizeof(TilingCam));
+    HIP_TRY(hipMemcpyAsync(tl->d_cam, tl->h_cam, (size_t)T * sizeof(TilingCam), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(tl->cam_up, s));
+    return VET_OK;
+}
+
+int vet_tiling_create(vet_ctx* c, const double* h_arcs, int n_arcs, const double* h_centres, int n_centres, int W, int H,
+                      vet_tiling** out) {
+    if (!c || !h_arcs || !out) return fail(VET_ERR_INVALID, "ctx, arcs or out is NULL");
+    *out = nullptr;
+    if (n_arcs <= 0 || n_centres < 0 || W <= 0 || H <= 0)
+        return fail(VET_ERR_INVALID, "need n_arcs, width, height > 0 and n_centres >= 0");
+    if (n_centres > 0 && !h_centres) return fail(VET_ERR_INVALID, "n_centres is %d but centres is NULL", n_centres);
+    if (W > 16384 || H > 16384) return fail(VET_ERR_INVALID, "frame of %d x %d pixels: at most 16384 each way", W, H);
+    if (n_arcs > (1 << 22) || n_centres > (1 << 26))
+        return fail(VET_ERR_INVALID, "too many arcs (%d, at most 2^22) or centres (%d, at most 2^26)", n_arcs, n_centres);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevBuf arcs;
+    HIP_TRY(arcs.alloc((size_t)n_arcs * 6 * sizeof(double)));
+    auto* tl = new vet_tiling();
+    struct Guard { vet_tiling* t; ~Guard() { if (t) vet_tiling_destroy(t); } } guard{tl};
+    tl->ctx = c; tl->device = c->device;
+    tl->g.W = W; tl->g.H = H; tl->g.n_arcs = n_arcs; tl->g.n_centres = n_centres;
+    const size_t frame = (size_t)W * H;
+    tl->B = (int)std::min<size_t>(64, std::max<size_t>(4, kTilingBlockBytes / (frame * 3)) / 4 * 4);
+    HIP_TRY(hipMalloc((void**)&tl->d_pts, (size_t)n_arcs * 50 * 3 * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&tl->d_flags, (size_t)tl->B * frame * 4));
+    tl->g.d_pts = tl->d_pts;
+    if (n_centres > 0) {
+        HIP_TRY(hipMalloc((void**)&tl->d_centres, (size_t)n_centres * 3 * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(tl->d_centres, h_centres, (size_t)n_centres * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        tl->g.d_centres = tl->d_centres;
+    }
+    HIP_TRY(hipMemcpyAsync(arcs.p, h_arcs, (size_t)n_arcs * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    int rc = tiling_chords(c, (const double*)arcs.p, n_arcs, tl->d_pts, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_TRY(hipStreamSynchronize(s));                        // 'arcs' goes out of scope; the caller's arrays are free
+    *out = tl;
+    guard.t = nullptr;
+    return VET_OK;
+}
+
+int vet_tiling_destroy(vet_tiling* tl) {
+    if (!tl) return VET_OK;
+    (void)hipSetDevice(tl->device);
+    if (tl->ctx) (void)hipStreamSynchronize(tl->ctx->stream);
+    if (tl->cam_up) { (void)hipEventSynchronize(tl->cam_up); (void)hipEventDestroy(tl->cam_up); }
+    for (int i = 0; i < 2; ++i) {
+        if (tl->copied[i]) { (void)hipEventSynchronize(tl->copied[i]); (void)hipEventDestroy(tl->copied[i]); }
+        if (tl->d_rgb[i]) (void)hipFree(tl->d_rgb[i]);
+        if (tl->h_pin[i]) (void)hipHostFree(tl->h_pin[i]);
+    }
+    if (tl->h_cam) (void)hipHostFree(tl->h_cam);
+    if (tl->d_cam) (void)hipFree(tl->d_cam);
+    if (tl->d_flags) (void)hipFree(tl->d_flags);
+    if (tl->d_centres) (void)hipFree(tl->d_centres);
+    if (tl->d_pts) (void)hipFree(tl->d_pts);
+    delete tl;
+    return VET_OK;
+}
+
+int vet_tiling_render(vet_tiling* tl, const double* h_cameras, int T, const uint8_t* background, uint8_t* d_rgb,
+                      void* stream) {
+    if (!tl || !h_cameras || !background || !d_rgb) return fail(VET_ERR_INVALID, "tiling, cameras, background or rgb is NULL");
+    if (T <= 0) return fail(VET_ERR_INVALID, "n_frames must be > 0 (got %d)", T);
+    if ((uintptr_t)d_rgb % 4) return fail(VET_ERR_INVALID, "d_rgb must be 4-byte aligned");
+    hipStream_t s = stream ? (hipStream_t)stream : tl->ctx->stream;
+    int rc = tiling_begin(tl, h_cameras, T, background, s);
+    if (rc) return rc;
+    const size_t frame = (size_t)tl->g.W * tl->g.H * 3;
+    for (int f0 = 0; f0 < T; f0 += tl->B) {                  // B % 4 == 0: every block starts 4-byte aligned
+        rc = tiling_render(tl->ctx, tl->g, tl->d_cam + f0, std::min(tl->B, T - f0), tl->d_flags, d_rgb + (size_t)f0 * frame, s);
+        if (rc) return rc;
+    }
+    return VET_OK;
+}
+
+int vet_tiling_render_host(vet_tiling* tl, const double* h_cameras, int T, const uint8_t* background, uint8_t* h_rgb) {
+    if (!tl || !h_cameras || !background || !h_rgb) return fail(VET_ERR_INVALID, "tiling, cameras, background or rgb is NULL");
+    if (T <= 0) return fail(VET_ERR_INVALID, "n_frames must be > 0 (got %d)", T);
+    hipStream_t s = tl->ctx->stream;
+    int rc = tiling_begin(tl, h_cameras, T, background, s);
+    if (rc) return rc;
+    const int B = tl->B;
+    const size_t frame = (size_t)tl->g.W * tl->g.H * 3;
+    for (int i = 0; i < 2; ++i) {                            // first host render: the staging pair
+        if (!tl->d_rgb[i]) HIP_TRY(hipMalloc((void**)&tl->d_rgb[i], (size_t)B * frame));
+        if (!tl->h_pin[i]) HIP_TRY(hipHostMalloc((void**)&tl->h_pin[i], (size_t)B * frame, hipHostMallocDefault));
+        if (!tl->copied[i]) HIP_TRY(hipEventCreateWithFlags(&tl->copied[i], hipEventDisableTiming));
+    }
+    auto drain = [&](int code) { (void)hipStreamSynchronize(s); return code; };
+    // block k renders into d_rgb[k & 1] and is copied to h_pin[k & 1] on the same stream; the host copies block k - 1 out
+    // of its pinned buffer while block k runs.  Stream order keeps d_rgb[k & 1] until its copy has left, and h_pin[k & 1]
+    // is refilled (block k + 2) only after the host has read it (at block k + 1).
+    const int nb = (T + B - 1) / B;
+    auto frames_of = [&](int k) { return std::min(B, T - k * B); };
+    for (int k = 0; k <= nb; ++k) {
+        if (k < nb) {
+            const int st = k & 1, b = frames_of(k);
+            rc = tiling_render(tl->ctx, tl->g, tl->d_cam + (size_t)k * B, b, tl->d_flags, tl->d_rgb[st], s);
+            if (rc) return drain(rc);
+            if (hipMemcpyAsync(tl->h_pin[st], tl->d_rgb[st], (size_t)b * frame, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipEventRecord(tl->copied[st], s) != hipSuccess)
+                return drain(fail(VET_ERR_DEVICE, "download of block %d failed", k));
+        }
+        if (k >= 1) {
+            const int ps = (k - 1) & 1;
+            if (hipEventSynchronize(tl->copied[ps]) != hipSuccess) return drain(fail(VET_ERR_DEVICE, "hipEventSynchronize failed"));
+            std::memcpy(h_rgb + (size_t)(k - 1) * B * frame, tl->h_pin[ps], (size_t)frames_of(k - 1) * frame);
+        }
+    }
     HIP_TRY(hipStreamSynchronize(s));
     return VET_OK;
 }

@@ -36,6 +36,9 @@
 //                                              k_heatmap_palette, k_heatmap_fill, k_heatmap_markers   per-frame tile-attention
 //                                                               RGB frames: palette per (frame, tile), streamed gather-store
 //                                                               of the pixels, viewport markers
+//   vet_tiling.hip      (in the unit)          k_tiling_chords, k_tiling_splat, k_tiling_compose   a tiling drawn on the unit
+//                                                               sphere: arcs -> slerp points, per-pixel line / point flags,
+//                                                               streamed RGB compose
 //   (several units)     vet_finalize.hpp       k_log2_table, k_finalize*   log2(k) table; mean over a plan's lattices
 // Shared, kernel-free headers: vet_layout.hpp (table / histogram layout constants), vet_common.hpp (wave helpers, the
 // sample -> direction-id quantiser), vet_weights.hpp (FoV weight, weighted frame entropy), vet_host.hpp (host state).

@@ -117,6 +117,10 @@ SIGNATURES = {
     "vet_heatmap_read_map": (_I, [_P, _P]),
     "vet_heatmap_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "vet_heatmap_render_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
+    "vet_tiling_create": (_I, [_P, _P, _I, _P, _I, _I, _I, C.POINTER(_P)]),
+    "vet_tiling_destroy": (_I, [_P]),
+    "vet_tiling_render": (_I, [_P, _P, _I, _P, _P, _P]),
+    "vet_tiling_render_host": (_I, [_P, _P, _I, _P, _P]),
     "vet_csv_read_tracks": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(Track), _I]),
     "vet_csv_free_tracks": (None, [_I, C.POINTER(Track)]),
 }
@@ -669,3 +673,58 @@ class Heatmap:
         _check(self.lib, self.lib.vet_heatmap_render_result(self.handle, result.handle, _ptr(present), _ptr(mu), _ptr(mv),
                                                             U, int(row0), n, _ptr(out)))
         return out
+
+
+class Tiling:
+    """A tiling drawn on the unit sphere (include/vet.h: vet_tiling): ``arcs`` [n, 2, 3] great-circle arcs, each drawn as 49
+    black chords, optional ``centres`` [m, 3] drawn as red squares, over a translucent grey unit sphere, seen through a
+    parallel projection.  The chord points are computed on the device once, here; every render takes one camera (P, U, F)
+    per frame."""
+
+    def __init__(self, engine: Engine, arcs: np.ndarray, centres: Optional[np.ndarray], width: int, height: int):
+        self.engine, self.lib = engine, engine.lib
+        arcs = np.ascontiguousarray(arcs, dtype=np.float64).reshape(-1, 2, 3)
+        centres = None if centres is None else np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+        self.n_arcs, self.n_centres = len(arcs), 0 if centres is None else len(centres)
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.vet_tiling_create(engine.handle, _ptr(arcs), self.n_arcs,
+                                                    _ptr(centres) if self.n_centres else None, self.n_centres,
+                                                    self.width, self.height, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.vet_tiling_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    @staticmethod
+    def _inputs(cameras, background):
+        cameras = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 9)
+        bg = np.ascontiguousarray(background, dtype=np.uint8).reshape(3)
+        return cameras, bg
+
+    def render(self, cameras: np.ndarray, background=(255, 255, 255), out: Optional[np.ndarray] = None) -> np.ndarray:
+        """cameras [n, 3, 3] (P, U, F per frame) -> uint8 [n, H, W, 3] on the host (into ``out`` when given: a C-contiguous
+        uint8 array of that shape); synchronous."""
+        cameras, bg = self._inputs(cameras, background)
+        shape = (len(cameras), self.height, self.width, 3)
+        if out is None:
+            out = np.empty(shape, dtype=np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        _check(self.lib, self.lib.vet_tiling_render_host(self.handle, _ptr(cameras), len(cameras), _ptr(bg), _ptr(out)))
+        return out
+
+    def render_device(self, cameras: np.ndarray, d_rgb: int, background=(255, 255, 255), stream=None):
+        """The frames of ``cameras`` [n, 3, 3] into ``d_rgb`` (device, uint8 [n, H, W, 3], 4-byte aligned); asynchronous on
+        ``stream`` as ``Plan.spatial_device``."""
+        cameras, bg = self._inputs(cameras, background)
+        _check(self.lib, self.lib.vet_tiling_render(self.handle, _ptr(cameras), len(cameras), _ptr(bg), d_rgb,
+                                                    _stream(stream)))

@@ -3,7 +3,8 @@
 The operator-level functions keep the reference's names and signatures and run on the HIP
 engine; the ingest helpers are vectorised host code; visualisation is reduced to the
 configuration object and the entropy-over-time graph (the per-frame heatmaps are rendered by
-``SpatialEntropyAnalyzer.render_heatmaps``; the reference's matplotlib / pyvista renderers raise).
+``SpatialEntropyAnalyzer.render_heatmaps``, tilings on the sphere by ``render_tiling`` and the
+``write_*tiling_*`` writers; the reference's matplotlib / pyvista renderers raise).
 """
 
 from . import data_utils as _data, entropy_utils as _entropy, visualization_utils as _viz
@@ -20,7 +21,8 @@ _PUBLIC = {
                "compute_naive_spatial_entropy"),
     _viz: ("VisualizationConfig", "save_graph", "PlotManager", "create_animation", "save_video",
            "save_fb_tiling_visualization_image", "save_fb_tiling_visualization_video", "save_tiling_visualization_image",
-           "save_tiling_visualization_video"),
+           "save_tiling_visualization_video", "render_tiling", "tiling_orbit_cameras", "write_tiling_image",
+           "write_tiling_video", "write_fb_tiling_image", "write_fb_tiling_video"),
 }
 for _module, _names in _PUBLIC.items():
     for _name in _names:
