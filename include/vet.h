@@ -46,8 +46,10 @@ extern "C" {
                            (+ vet_plan_set_raw_weights); batch descriptors in an event-guarded ring;
                            0.1.4.1: vet_device_pci_bus_id; vet_plan_set_fp64 (formulation 4, `dtable`) added
                            without a new number: existing callers see no change; the vet_heatmap_* entry points
-                           (per-frame tile-attention heatmaps) and the vet_tiling_* entry points
-                           (tilings drawn on the unit sphere) added the same way */
+                           (per-frame tile-attention heatmaps), the vet_tiling_* entry points
+                           (tilings drawn on the unit sphere) and vet_heatmap_render_counts /
+                           vet_heatmap_render_transition_result (heatmaps of transition results) added the
+                           same way */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -345,8 +347,8 @@ int vet_fb_tile_boundaries(vet_ctx *ctx, const double *h_tiles, int n_tiles, int
  *     py = int(mv * video_height) (integer division); columns wrap modulo W, rows clamp to [0, H); NaN = absent; a sample
  *     outside [0, 1] draws nothing and raises no error.
  * A heatmap belongs to its context (destroy it first) and, like the context, is used from one thread on one stream at a
- * time.  VET_ERR_INVALID: bad sizes, marker_radius outside [0, 16], a transition result, a result of another device or
- * lattice size; VET_ERR_UNSUPPORTED: a lattice larger than the map kernel's LDS tile cache (6783 tiles, the plans' own
+ * time.  VET_ERR_INVALID: bad sizes, marker_radius outside [0, 16], a result of the other kind for the entry (spatial /
+ * transition), a result of another device or lattice size; VET_ERR_UNSUPPORTED: a lattice larger than the map kernel's LDS tile cache (6783 tiles, the plans' own
  * limit). */
 typedef struct vet_heatmap vet_heatmap;   /* W x H pixel -> tile map of one lattice, on one context's device */
 int vet_heatmap_create(vet_ctx *ctx, const double *h_tiles /* [n_tiles*3] lattice Vectors */, int n_tiles, int width,
@@ -364,6 +366,20 @@ int vet_heatmap_render(vet_heatmap *hm, const double *d_weights /* [T][n_tiles] 
 int vet_heatmap_render_result(vet_heatmap *hm, vet_result *r, const int32_t *h_present /* [n_rows] */,
                               const double *h_mu, const double *h_mv /* [n_rows][U] or NULL */, int n_users,
                               int64_t row0, int64_t n_rows, uint8_t *h_rgb);
+/* Transition results (the reference's TransitionEntropyAnalyzer animation): frame r of the T-1 result rows is the pair
+ * r -> r+1, coloured by _get_color_from_intensity(c / n) with c = srccount[r][tile] (the users present in both frames whose
+ * frame-r nearest tile is this one; exact in FP64) and n = the users present in frame r (not the common-user count: a
+ * user who leaves at r+1 counts in n and not in c); markers are the frame-r samples.  Same rules otherwise.
+ * vet_heatmap_render_counts: device pointers, asynchronous on `stream`, as vet_heatmap_render. */
+int vet_heatmap_render_counts(vet_heatmap *hm, const int32_t *d_counts /* [T][n_tiles] */, const int32_t *d_present /* [T] */,
+                              const double *d_mu, const double *d_mv /* [T][U] or both NULL: no markers */,
+                              int n_users, int n_frames, uint8_t *d_rgb /* [T][H][W][3] */, void *stream);
+/* rows [row0, row0+n_rows) of a transition vet_result -> host; synchronous; the stored srccount rows are read in place,
+ * through vet_heatmap_render_result's two-buffer pipeline.  h_present / h_mu / h_mv: frame r's users present and samples
+ * for every row r of the range (the frame table's rows row0 .. row0+n_rows-1). */
+int vet_heatmap_render_transition_result(vet_heatmap *hm, vet_result *r, const int32_t *h_present /* [n_rows] */,
+                                         const double *h_mu, const double *h_mv /* [n_rows][U] or NULL */, int n_users,
+                                         int64_t row0, int64_t n_rows, uint8_t *h_rgb);
 
 /* ---- tilings drawn on the unit sphere --------------------------------------------------------
  * The scenes of the reference's pyvista tiling renders (save_*tiling_visualization_*, utilities/visualization_utils.py:

@@ -4,6 +4,7 @@
 //
 //   k_heatmap_map      pixel -> nearest tile of the lattice (find_nearest_tile over the pixel centre's direction)
 //   k_heatmap_palette  per frame and tile: _get_color_from_intensity(tile_weights / users present) as packed RGB
+//                      (f64 spatial weights, or the i32 source-tile counts of a transition result)
 //   k_heatmap_fill     the hot path: RGB[t][q] = palette[t][map[q]], a streamed store of n x H x W x 3 bytes
 //   k_heatmap_markers  per (frame, user): a black square centred on the user's viewport pixel
 // Reference citations are relative to /root/reference/src/viewport_entropy_toolkit/.
@@ -43,15 +44,18 @@ __global__ void k_heatmap_map(const double* __restrict__ tiles, int n, int W, in
 //   i = w / n (0 when no user is present), clip to [0, 1], red = i * (1 - 0.8) + 0.8, green = blue = 0.8 - i * 0.8,
 //   byte = floor(v * 255 + 0.5);  packed R | G << 8 | B << 16.
 // w = tile_weights[t][tile] (a non-key is +0.0, a zero-valued key -0.0: both give grey).  A NaN intensity clips to 0.
+// Wt = double: spatial tile_weights.  Wt = int32_t: a transition result's srccount rows (the users counted per source tile,
+// weight_per_tile, utilities/entropy_utils.py:289-292), converted exactly to double before the same arithmetic.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t colour_byte(double v) { return (uint32_t)floor(v * 255.0 + 0.5); }
 
-__global__ void k_heatmap_palette(const double* __restrict__ weights, const int32_t* __restrict__ present, long T, int n,
+template <typename Wt>
+__global__ void k_heatmap_palette(const Wt* __restrict__ weights, const int32_t* __restrict__ present, long T, int n,
                                   uint32_t* __restrict__ pal) {
     const long total = T * (long)n;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int users = present[i / n];
-        double v = users > 0 ? weights[i] / (double)users : 0.0;
+        double v = users > 0 ? (double)weights[i] / (double)users : 0.0;
         v = fmin(fmax(v, 0.0), 1.0);
         const double red = v * 0.19999999999999996 + 0.8;
         const double gb = 0.8 - v * 0.8;
@@ -156,10 +160,11 @@ int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uin
     return VET_OK;
 }
 
-int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, const int32_t* d_present, const double* d_mu,
+template <typename Wt>
+int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
                    const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
     const long HW = (long)g.W * g.H, N = HW * T;
-    hipLaunchKernelGGL(vet::k_heatmap_palette, dim3(grid_for((long)T * g.n, 256, c->n_cu)), dim3(256), 0, s, d_weights,
+    hipLaunchKernelGGL(vet::k_heatmap_palette<Wt>, dim3(grid_for((long)T * g.n, 256, c->n_cu)), dim3(256), 0, s, d_weights,
                        d_present, (long)T, g.n, d_pal);
     HIP_TRY(hipGetLastError());
     const long quads = N >> 2;
@@ -176,5 +181,10 @@ int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, co
     }
     return VET_OK;
 }
+
+template int heatmap_render<double>(vet_ctx*, const HeatmapGeom&, const double*, const int32_t*, const double*,
+                                    const double*, int, int, uint32_t*, uint8_t*, hipStream_t);
+template int heatmap_render<int32_t>(vet_ctx*, const HeatmapGeom&, const int32_t*, const int32_t*, const double*,
+                                     const double*, int, int, uint32_t*, uint8_t*, hipStream_t);
 
 }  // namespace vh

@@ -276,14 +276,16 @@ int sample_ids(const vet_plan* pl, const double* d_mu, const double* d_mv, long 
 
 // vet_heatmap.hip: per-frame tile-attention heatmaps.  heatmap_map: W x H pixel -> nearest tile of the n unit centres
 // d_unit_tiles (k_heatmap_map).  heatmap_render: frames [0, T) -> d_rgb [T][H][W][3] (k_heatmap_palette into d_pal
-// [T][n], k_heatmap_fill, then k_heatmap_markers when d_mu / d_mv are given), enqueued on s.
+// [T][n], k_heatmap_fill, then k_heatmap_markers when d_mu / d_mv are given), enqueued on s.  Wt = double (tile_weights
+// [T][n]) or int32_t (a transition result's source-tile counts [T][n]); both are instantiated in vet_heatmap.hip.
 struct HeatmapGeom {
     const uint16_t* d_map = nullptr;   // [H][W] tile index
     int n = 0, W = 0, H = 0;           // lattice size, frame size
     int VW = 0, VH = 0, radius = 0;    // video size of the samples (marker quantiser), marker half-width
 };
 int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uint16_t* d_map, hipStream_t s);
-int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const double* d_weights, const int32_t* d_present, const double* d_mu,
+template <typename Wt>
+int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
                    const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s);
 
 // vet_tiling.hip: tilings drawn on the unit sphere.  tiling_chords: arcs [n][2][3] -> 50 slerp points per arc

@@ -409,8 +409,12 @@ int vet_heatmap_read_map(vet_heatmap* hm, int32_t* h_map) {
     return VET_OK;
 }
 
-int vet_heatmap_render(vet_heatmap* hm, const double* d_weights, const int32_t* d_present, const double* d_mu,
-                       const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
+}  // extern "C"
+
+// both device-pointer entries: checks first, then the palette, fill and markers of frames [0, T) on `stream`
+template <typename Wt>
+static int heatmap_render_device(vet_heatmap* hm, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
+                                 const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
     if (!hm || !d_weights || !d_present || !d_rgb) return fail(VET_ERR_INVALID, "heatmap, weights, present or rgb is NULL");
     if (T < 0) return fail(VET_ERR_INVALID, "n_frames must be >= 0 (got %d)", T);
     if (!d_mu != !d_mv) return fail(VET_ERR_INVALID, "pass both d_mu and d_mv, or neither");
@@ -424,27 +428,53 @@ int vet_heatmap_render(vet_heatmap* hm, const double* d_weights, const int32_t* 
     return heatmap_render(hm->ctx, hm->g, d_weights, d_present, d_mu, d_mv, U, T, hm->d_pal, d_rgb, s);
 }
 
-int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_present, const double* h_mu,
-                              const double* h_mv, int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb) {
-    if (!hm || !r || !h_present || !h_rgb) return fail(VET_ERR_INVALID, "heatmap, result, present or rgb is NULL");
-    if (r->transition) return fail(VET_ERR_INVALID, "a transition result has no tile weights to render");
+extern "C" {
+
+int vet_heatmap_render(vet_heatmap* hm, const double* d_weights, const int32_t* d_present, const double* d_mu,
+                       const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
+    return heatmap_render_device(hm, d_weights, d_present, d_mu, d_mv, U, T, d_rgb, stream);
+}
+
+int vet_heatmap_render_counts(vet_heatmap* hm, const int32_t* d_counts, const int32_t* d_present, const double* d_mu,
+                              const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
+    return heatmap_render_device(hm, d_counts, d_present, d_mu, d_mv, U, T, d_rgb, stream);
+}
+
+// The checks both result entries share, after the NULL and result-kind checks: device, lattice size (w_bytes per count or
+// weight), row range, samples (u_bytes per user in a row of output 0: 4 for assignments, 8 for pairs).
+static int heatmap_result_checks(vet_heatmap* hm, vet_result* r, size_t w_bytes, size_t u_bytes, const double* h_mu,
+                                 const double* h_mv, int U, int64_t row0, int64_t n_rows) {
     if (r->device != hm->device)
         return fail(VET_ERR_INVALID, "result on device %d, heatmap on device %d", r->device, hm->device);
     const int n = hm->g.n;
-    if (r->row_bytes[1] != (size_t)n * 8)
-        return fail(VET_ERR_INVALID, "the result's lattice 0 has %zu tiles, the heatmap's lattice %d", r->row_bytes[1] / 8, n);
+    if (r->row_bytes[1] != (size_t)n * w_bytes)
+        return fail(VET_ERR_INVALID, "the result's lattice 0 has %zu tiles, the heatmap's lattice %d", r->row_bytes[1] / w_bytes, n);
     if (row0 < 0 || n_rows < 0 || row0 + n_rows > r->rows)
         return fail(VET_ERR_INVALID, "rows [%lld, %lld) outside the result's %lld rows", (long long)row0,
                     (long long)(row0 + n_rows), (long long)r->rows);
     if (!h_mu != !h_mv) return fail(VET_ERR_INVALID, "pass both h_mu and h_mv, or neither");
-    const int RU = (int)(r->row_bytes[0] / 4);
+    const int RU = (int)(r->row_bytes[0] / u_bytes);
     if (h_mu && U != RU) return fail(VET_ERR_INVALID, "n_users %d, the result has %d", U, RU);
-    if (n_rows == 0) return VET_OK;
-    HIP_TRY(hipSetDevice(hm->device));
+    return VET_OK;
+}
+
+// Frames per sub-block of the result entries: at most 32 MiB of RGB, at least one frame.
+static int heatmap_block_frames(const vet_heatmap* hm, int64_t n_rows) {
+    const size_t frame = (size_t)hm->g.W * hm->g.H * 3;
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)32 << 20, (size_t)n_rows * frame) / frame);
+}
+
+}  // extern "C"
+
+// The render pipeline of both result entries: frames [row0, row0 + n_rows) in sub-blocks of B frames into the alternating
+// RGB and pinned buffers, the copy of one block overlapping the kernels of the next.  rows_of_block(f0, b, &w) yields the
+// device rows of frames [f0, f0 + b) (Wt [b][n]), enqueued on the context's stream.
+template <typename Wt, typename Rows>
+static int heatmap_render_blocks(vet_heatmap* hm, int B, const int32_t* h_present, const double* h_mu, const double* h_mv,
+                                 int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb, Rows rows_of_block) {
     vet_ctx* c = hm->ctx;
     hipStream_t s = c->stream;
     const size_t frame = (size_t)hm->g.W * hm->g.H * 3;
-    const int B = (int)std::max<size_t>(1, std::min<size_t>((size_t)32 << 20, (size_t)n_rows * frame) / frame);
     if (hm->B < B || (h_mu && hm->U < U)) {                 // grow-only staging
         HIP_TRY(hipStreamSynchronize(s));
         if (hm->copy) HIP_TRY(hipStreamSynchronize(hm->copy));
@@ -468,17 +498,6 @@ int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_p
     }
     int rc = heatmap_palette(hm, B, s);
     if (rc) return rc;
-    // lazy weight rows: the weights pass of each block into the result's staging buffer, under its fetch lock
-    std::unique_lock<std::mutex> lock(r->fetch_mu, std::defer_lock);
-    if (r->lazy_weights) {
-        lock.lock();
-        const size_t wb = (size_t)B * r->row_bytes[1];
-        if (r->tmp_cap < wb) {
-            if (r->d_tmp) { HIP_TRY(hipFree(r->d_tmp)); r->d_tmp = nullptr; r->tmp_cap = 0; }
-            HIP_TRY(hipMalloc(&r->d_tmp, wb));
-            r->tmp_cap = wb;
-        }
-    }
     auto drain = [&](int code) {
         (void)hipStreamSynchronize(s);
         (void)hipStreamSynchronize(hm->copy);
@@ -496,14 +515,9 @@ int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_p
         if (h_mu && (hipMemcpyAsync(hm->d_mu, h_mu + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
                      hipMemcpyAsync(hm->d_mv, h_mv + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess))
             return drain(fail(VET_ERR_DEVICE, "upload of the samples failed"));
-        const double* w;
-        if (r->lazy_weights) {
-            rc = weights_pass_ids(*r->core, r->d_ids + (size_t)f0 * r->U, r->U, b, (double*)r->d_tmp, s, nullptr);
-            if (rc) return drain(rc);
-            w = (const double*)r->d_tmp;
-        } else {
-            w = (const double*)r->d[1] + (size_t)f0 * n;
-        }
+        const Wt* w = nullptr;
+        rc = rows_of_block(f0, b, &w);
+        if (rc) return drain(rc);
         rc = heatmap_render(c, hm->g, w, hm->d_present, h_mu ? hm->d_mu : nullptr, h_mu ? hm->d_mv : nullptr, U, b, hm->d_pal,
                             hm->d_rgb[st], s);
         if (rc) return drain(rc);
@@ -522,6 +536,56 @@ int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_p
     std::memcpy(h_rgb + (size_t)(nb - 1) * B * frame, hm->h_pin[ls], (size_t)rows_of(nb - 1) * frame);
     HIP_TRY(hipStreamSynchronize(s));
     return VET_OK;
+}
+
+extern "C" {
+
+int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_present, const double* h_mu,
+                              const double* h_mv, int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb) {
+    if (!hm || !r || !h_present || !h_rgb) return fail(VET_ERR_INVALID, "heatmap, result, present or rgb is NULL");
+    if (r->transition) return fail(VET_ERR_INVALID, "a transition result has no tile weights to render");
+    int rc = heatmap_result_checks(hm, r, 8, 4, h_mu, h_mv, U, row0, n_rows);
+    if (rc || n_rows == 0) return rc;
+    HIP_TRY(hipSetDevice(hm->device));
+    const int B = heatmap_block_frames(hm, n_rows);
+    // lazy weight rows: the weights pass of each block into the result's staging buffer, under its fetch lock
+    std::unique_lock<std::mutex> lock(r->fetch_mu, std::defer_lock);
+    if (r->lazy_weights) {
+        lock.lock();
+        const size_t wb = (size_t)B * r->row_bytes[1];
+        if (r->tmp_cap < wb) {
+            if (r->d_tmp) { HIP_TRY(hipFree(r->d_tmp)); r->d_tmp = nullptr; r->tmp_cap = 0; }
+            HIP_TRY(hipMalloc(&r->d_tmp, wb));
+            r->tmp_cap = wb;
+        }
+    }
+    const int n = hm->g.n;
+    hipStream_t s = hm->ctx->stream;
+    return heatmap_render_blocks<double>(hm, B, h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
+                                         [&](int64_t f0, int b, const double** w) -> int {
+        if (!r->lazy_weights) {
+            *w = (const double*)r->d[1] + (size_t)f0 * n;
+            return VET_OK;
+        }
+        *w = (const double*)r->d_tmp;
+        return weights_pass_ids(*r->core, r->d_ids + (size_t)f0 * r->U, r->U, b, (double*)r->d_tmp, s, nullptr);
+    });
+}
+
+int vet_heatmap_render_transition_result(vet_heatmap* hm, vet_result* r, const int32_t* h_present, const double* h_mu,
+                                         const double* h_mv, int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb) {
+    if (!hm || !r || !h_present || !h_rgb) return fail(VET_ERR_INVALID, "heatmap, result, present or rgb is NULL");
+    if (!r->transition)
+        return fail(VET_ERR_INVALID, "a spatial result has no source-tile counts to render");
+    int rc = heatmap_result_checks(hm, r, 4, 8, h_mu, h_mv, U, row0, n_rows);
+    if (rc || n_rows == 0) return rc;
+    HIP_TRY(hipSetDevice(hm->device));
+    const int n = hm->g.n;
+    return heatmap_render_blocks<int32_t>(hm, heatmap_block_frames(hm, n_rows), h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
+                                          [&](int64_t f0, int, const int32_t** w) -> int {
+        *w = (const int32_t*)r->d[1] + (size_t)f0 * n;
+        return VET_OK;
+    });
 }
 
 

@@ -117,6 +117,8 @@ SIGNATURES = {
     "vet_heatmap_read_map": (_I, [_P, _P]),
     "vet_heatmap_render": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "vet_heatmap_render_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
+    "vet_heatmap_render_counts": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "vet_heatmap_render_transition_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
     "vet_tiling_create": (_I, [_P, _P, _I, _P, _I, _I, _I, C.POINTER(_P)]),
     "vet_tiling_destroy": (_I, [_P]),
     "vet_tiling_render": (_I, [_P, _P, _I, _P, _P, _P]),
@@ -648,12 +650,14 @@ class Heatmap:
         _check(self.lib, self.lib.vet_heatmap_render(self.handle, d_weights, d_present, d_mu or None, d_mv or None,
                                                      int(n_users), int(n_frames), d_rgb, _stream(stream)))
 
-    def render_result(self, result: "DeviceResult", present: np.ndarray, mu: Optional[np.ndarray] = None,
-                      mv: Optional[np.ndarray] = None, row0: int = 0, n: Optional[int] = None,
-                      out: Optional[np.ndarray] = None) -> np.ndarray:
-        """Frames [row0, row0 + n) of a spatial ``DeviceResult`` -> uint8 [n, H, W, 3] (into ``out`` when given: a
-        C-contiguous uint8 array of that shape).  ``present``, ``mu``, ``mv`` hold those frames' rows only; without
-        ``mu`` / ``mv`` no markers are drawn.  The weight rows stay on the device."""
+    def render_counts_device(self, d_counts: int, d_present: int, n_frames: int, d_rgb: int, d_mu: int = 0, d_mv: int = 0,
+                             n_users: int = 0, stream=None):
+        """``render_device`` with i32 user counts per tile [T, n_tiles] (a transition result's source-tile counts) in
+        place of the f64 weights; ``present`` and the samples are those of each row's prior frame."""
+        _check(self.lib, self.lib.vet_heatmap_render_counts(self.handle, d_counts, d_present, d_mu or None, d_mv or None,
+                                                            int(n_users), int(n_frames), d_rgb, _stream(stream)))
+
+    def _render_rows(self, entry, result, present, mu, mv, row0, n, out) -> np.ndarray:
         n = result.n_rows - row0 if n is None else int(n)
         present = np.ascontiguousarray(present, dtype=np.int32).reshape(-1)
         if len(present) != n:
@@ -670,9 +674,25 @@ class Heatmap:
             out = np.empty(shape, dtype=np.uint8)
         elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
-        _check(self.lib, self.lib.vet_heatmap_render_result(self.handle, result.handle, _ptr(present), _ptr(mu), _ptr(mv),
-                                                            U, int(row0), n, _ptr(out)))
+        _check(self.lib, entry(self.handle, result.handle, _ptr(present), _ptr(mu), _ptr(mv), U, int(row0), n, _ptr(out)))
         return out
+
+    def render_result(self, result: "DeviceResult", present: np.ndarray, mu: Optional[np.ndarray] = None,
+                      mv: Optional[np.ndarray] = None, row0: int = 0, n: Optional[int] = None,
+                      out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Frames [row0, row0 + n) of a spatial ``DeviceResult`` -> uint8 [n, H, W, 3] (into ``out`` when given: a
+        C-contiguous uint8 array of that shape).  ``present``, ``mu``, ``mv`` hold those frames' rows only; without
+        ``mu`` / ``mv`` no markers are drawn.  The weight rows stay on the device."""
+        return self._render_rows(self.lib.vet_heatmap_render_result, result, present, mu, mv, row0, n, out)
+
+    def render_transition_result(self, result: "DeviceResult", present: np.ndarray, mu: Optional[np.ndarray] = None,
+                                 mv: Optional[np.ndarray] = None, row0: int = 0, n: Optional[int] = None,
+                                 out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Rows [row0, row0 + n) of a transition ``DeviceResult`` (row r: the pair of frames r -> r+1) -> uint8
+        [n, H, W, 3], as ``render_result``.  Row r's colours are its source-tile counts over ``present[r]``, the users
+        present in frame r (not the common users), and its markers are frame r's samples: ``present``, ``mu``, ``mv`` are
+        the frame table's rows row0 .. row0 + n - 1.  The count rows stay on the device."""
+        return self._render_rows(self.lib.vet_heatmap_render_transition_result, result, present, mu, mv, row0, n, out)
 
 
 class Tiling:

@@ -173,7 +173,8 @@ class _EntropyAnalyzerBase:
         """Writes ``{base_name}_graph.png`` and ``{base_name}.csv`` (columns time, entropy).
 
         The reference's per-frame scatter animation / mp4 is not produced here; its GPU-rendered
-        counterpart is opt-in: ``SpatialEntropyAnalyzer.render_heatmaps`` / ``save_heatmaps``."""
+        counterpart is opt-in: ``render_heatmaps`` / ``save_heatmaps`` of ``SpatialEntropyAnalyzer`` and
+        ``TransitionEntropyAnalyzer``."""
         if self._entropy_results is None:
             raise ValidationError("No entropy results. Call compute_entropy first.")
         try:

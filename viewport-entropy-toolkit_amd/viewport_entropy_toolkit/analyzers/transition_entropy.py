@@ -8,29 +8,43 @@ from __future__ import annotations
 import logging
 import time
 
+import numpy as np
 import pandas as pd
 
 from .. import _native
 from ..data_types import ValidationError
 from .._results import DeviceRows, FrameDictArray, TilePairs, TileWeights
 from ._base import _EntropyAnalyzerBase
+from ._heatmaps import _HeatmapMixin
 
 logger = logging.getLogger(__name__)
 
 
-class TransitionEntropyAnalyzer(_EntropyAnalyzerBase):
+class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
     """Drop-in analyzer with the reference's result schema; ``tile_weights`` holds the user
     count per source tile and ``tile_assignments`` the (prior, current) tile index pairs."""
 
     _logger = logger
+    _heatmap_entry = "render_transition_result"
 
     @staticmethod
-    def _empty_row_error(kind, a, b) -> Exception:
+    def _presence(kind, a, b) -> np.ndarray:
+        """bool [T, U]: user u has a sample in frame t (grid: (mu, mv) not NaN; ids: a direction id)."""
+        return (a >= 0) if kind != "grid" else ~(np.isnan(a) | np.isnan(b))
+
+    @classmethod
+    def _prior_frame_present(cls, kind, a, b) -> np.ndarray:
+        """int32 [T-1]: the users present in frame r for every result row r (the pair r -> r+1) — the denominator of the
+        reference's animation colours, len(points_list) of points_data.iloc[r] (utilities/visualization_utils.py:124-
+        152), which counts a user who leaves at r+1 and is not the common-user count."""
+        return cls._presence(kind, a, b)[:-1].sum(axis=1, dtype=np.int32)
+
+    @classmethod
+    def _empty_row_error(cls, kind, a, b) -> Exception:
         """The exception the reference raises at the FIRST frame pair without a common user: a frame whose dict is
         empty -> ValidationError("Empty vector dictionary") (utilities/entropy_utils.py:239-240); both frames have users
         but nobody is in both -> the division by the zero total weight (:322-327)."""
-        import numpy as np
-        present = (a >= 0) if kind != "grid" else ~(np.isnan(a) | np.isnan(b))
+        present = cls._presence(kind, a, b)
         common = (present[:-1] & present[1:]).any(axis=1)
         r = int(np.argmin(common))                 # first row without a common user
         if not present[r].any() or not present[r + 1].any():
@@ -59,6 +73,10 @@ class TransitionEntropyAnalyzer(_EntropyAnalyzerBase):
         tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
         R = len(res["entropy"])
         self._device_result = res["result"]
+        # heatmaps: the presence of each row's prior frame is counted on the first render, from these references
+        self._present = None
+        self._present_samples = (kind, a, b if kind == "grid" else None)
+        self._marker_samples = (a, b) if kind == "grid" else None
         self._entropy_results = pd.DataFrame({
             "time": times[1:],
             "entropy": res["entropy"],
@@ -66,3 +84,8 @@ class TransitionEntropyAnalyzer(_EntropyAnalyzerBase):
             "tile_assignments": FrameDictArray(DeviceRows(res["result"], 0, R), lambda row: TilePairs(names, row)),
         })
         return self._entropy_results
+
+    def _frame_present(self) -> np.ndarray:
+        if self._present is None:
+            self._present = self._prior_frame_present(*self._present_samples)
+        return self._present
