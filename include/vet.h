@@ -48,8 +48,9 @@ extern "C" {
                            without a new number: existing callers see no change; the vet_heatmap_* entry points
                            (per-frame tile-attention heatmaps), the vet_tiling_* entry points
                            (tilings drawn on the unit sphere) and vet_heatmap_render_counts /
-                           vet_heatmap_render_transition_result (heatmaps of transition results) added the
-                           same way */
+                           vet_heatmap_render_transition_result (heatmaps of transition results) and
+                           vet_heatmap_create_latlon / vet_heatmap_render_binned(_host) (lat/lon cell
+                           heatmaps of naive plans) added the same way */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -380,6 +381,36 @@ int vet_heatmap_render_counts(vet_heatmap *hm, const int32_t *d_counts /* [T][n_
 int vet_heatmap_render_transition_result(vet_heatmap *hm, vet_result *r, const int32_t *h_present /* [n_rows] */,
                                          const double *h_mu, const double *h_mv /* [n_rows][U] or NULL */, int n_users,
                                          int64_t row0, int64_t n_rows, uint8_t *h_rgb);
+/* Lat/lon cell heatmaps of a naive plan (the reference's NaiveSpatialEntropyAnalyzer; its own animation is commented out):
+ * the same frames, colour rule, markers and marker radius, with these parts replaced:
+ *   pixel -> cell: find_naive_tile_index (utilities/entropy_utils.py:362-381) of the pixel centre, FP64, C truncation:
+ *     lon = (c + 0.5) / W * 360 - 180, lat = 90 - (r + 0.5) / H * 180,
+ *     cell = (int)((lon + 180) / tile_width) * n_lat + (int)((lat + 90) / tile_height),  n_lat = 180 / tile_height + 1,
+ *     out of (360 / tile_width + 1) * n_lat cells: the bin numbering (li * n_lat + lj) of the naive plan's LUT;
+ *   colour of a cell in frame t: _get_color_from_intensity(count / present), count = the users whose sample falls in the
+ *     cell through the plan's own quantiser (grid_dir) and LUT (the counts the frame's entropy is computed from), present
+ *     = the users with a sample in frame t (intensity 0 when present == 0).  As the plan quantises: a sample at px = 0 has
+ *     lon 0 (it counts in the lon-0 column, its marker is drawn at column 0); one at py = 0 (lat 90) or px = W (lon 180)
+ *     counts in a cell of the extra row / column that no pixel centre maps to, so it dims the other cells and shows in
+ *     none.  NaN = absent; a sample outside [0, 1] counts in neither count nor present and draws no marker (no error).
+ * vet_heatmap_create_latlon: the cell map, built once; VET_ERR_INVALID for tile sizes <= 0 or not dividing 180 / 360 (the
+ * rules of compute_naive_spatial_entropy) and the frame checks of vet_heatmap_create.  vet_heatmap_read_map gives its cells
+ * (the device keeps slot lj * n_lon + li per pixel, so that a pixel row reads consecutive palette entries).
+ * The binned entries take the samples [T][U] (frame-major, as every sample array) and a plan whose lattice 0 is binned on
+ * a pixel grid, with the heatmap's cell count and video size (VET_ERR_INVALID otherwise, and for a heatmap of
+ * vet_heatmap_create; the other render entries refuse a lat/lon heatmap).  Per frame one workgroup builds the cell histogram in
+ * LDS, two 16-bit counts per word while n_users <= 65535, one u32 per cell above that: VET_ERR_UNSUPPORTED when those do
+ * not fit the LDS (n_users > 65535 on grids of more than about 40 800 cells).  markers != 0: draw the viewport markers.
+ * Frames run in chunks whose palette (n_cells u32 per frame) stays within 64 MiB.
+ * vet_heatmap_render_binned: device pointers, asynchronous on `stream`; d_rgb 4-byte aligned.
+ * vet_heatmap_render_binned_host: synchronous, through vet_heatmap_render_result's two-buffer pipeline, each block's
+ * samples uploaded in it: device memory does not grow with n_frames. */
+int vet_heatmap_create_latlon(vet_ctx *ctx, int tile_width, int tile_height, int width, int height, int video_width,
+                              int video_height, int marker_radius, vet_heatmap **out);
+int vet_heatmap_render_binned(vet_heatmap *hm, vet_plan *plan, const double *d_mu, const double *d_mv /* [T][U] */,
+                              int n_users, int n_frames, int markers, uint8_t *d_rgb /* [T][H][W][3] */, void *stream);
+int vet_heatmap_render_binned_host(vet_heatmap *hm, vet_plan *plan, const double *h_mu, const double *h_mv /* [T][U] */,
+                                   int n_users, int n_frames, int markers, uint8_t *h_rgb /* [T][H][W][3] */);
 
 /* ---- tilings drawn on the unit sphere --------------------------------------------------------
  * The scenes of the reference's pyvista tiling renders (save_*tiling_visualization_*, utilities/visualization_utils.py:

@@ -3,8 +3,10 @@
 // The C-ABI entry points (vet_heatmap_*) and the render pipeline of a device-resident result live in vet_hostapi.hip.
 //
 //   k_heatmap_map      pixel -> nearest tile of the lattice (find_nearest_tile over the pixel centre's direction)
+//   k_heatmap_map_latlon  pixel -> lat/lon cell of a naive tiling (find_naive_tile_index over the pixel centre)
 //   k_heatmap_palette  per frame and tile: _get_color_from_intensity(tile_weights / users present) as packed RGB
 //                      (f64 spatial weights, or the i32 source-tile counts of a transition result)
+//   k_heatmap_bin_palette  per frame: the lat/lon cell histogram of its samples in LDS, then its palette row (naive plans)
 //   k_heatmap_fill     the hot path: RGB[t][q] = palette[t][map[q]], a streamed store of n x H x W x 3 bytes
 //   k_heatmap_markers  per (frame, user): a black square centred on the user's viewport pixel
 // Reference citations are relative to /root/reference/src/viewport_entropy_toolkit/.
@@ -49,19 +51,122 @@ __global__ void k_heatmap_map(const double* __restrict__ tiles, int n, int W, in
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t colour_byte(double v) { return (uint32_t)floor(v * 255.0 + 0.5); }
 
+// the packed colour of weight w over `users` present (the palette arithmetic of every heatmap kind)
+__device__ __forceinline__ uint32_t heatmap_colour(double w, int users) {
+    double v = users > 0 ? w / (double)users : 0.0;
+    v = fmin(fmax(v, 0.0), 1.0);
+    const double red = v * 0.19999999999999996 + 0.8;
+    const double gb = 0.8 - v * 0.8;
+    const uint32_t g = colour_byte(gb);
+    return colour_byte(red) | g << 8 | g << 16;
+}
+
 template <typename Wt>
 __global__ void k_heatmap_palette(const Wt* __restrict__ weights, const int32_t* __restrict__ present, long T, int n,
                                   uint32_t* __restrict__ pal) {
     const long total = T * (long)n;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int users = present[i / n];
-        double v = users > 0 ? (double)weights[i] / (double)users : 0.0;
-        v = fmin(fmax(v, 0.0), 1.0);
-        const double red = v * 0.19999999999999996 + 0.8;
-        const double gb = 0.8 - v * 0.8;
-        const uint32_t g = colour_byte(gb);
-        pal[i] = colour_byte(red) | g << 8 | g << 16;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        pal[i] = heatmap_colour((double)weights[i], present[i / n]);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_map_latlon: pixel (r, c) -> lat/lon cell, find_naive_tile_index (utilities/entropy_utils.py:362-381) of the
+// pixel centre in FP64 with C truncation:
+//   lon = (c + 0.5) / W * 360 - 180,   lat = 90 - (r + 0.5) / H * 180,
+//   li = (int)((lon + 180) / tile_width),  lj = (int)((lat + 90) / tile_height)
+// — cell li * n_lat + lj in the numbering of the naive plan's direction -> bin LUT.  The map holds the cell's SLOT
+// lj * n_lon + li instead (the palette rows of lat/lon heatmaps are slot-ordered): a pixel row then reads consecutive
+// palette entries, where the cell numbering would put neighbouring columns n_lat entries apart (1x1-degree cells: 724 B,
+// one cache line per pixel of the fill).  vet_heatmap_read_map turns slots back into cells.  One thread per pixel.
+// ------------------------------------------------------------------------------------------
+__global__ void k_heatmap_map_latlon(int W, int H, double tw, double th, int n_lon, uint16_t* __restrict__ map) {
+    const long HW = (long)W * H;
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < HW; q += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(q / W), c = (int)(q - (long)r * W);
+        const double lon = ((double)c + 0.5) / (double)W * 360.0 - 180.0;
+        const double lat = 90.0 - ((double)r + 0.5) / (double)H * 180.0;
+        map[q] = (uint16_t)((int)((lat + 90.0) / th) * n_lon + (int)((lon + 180.0) / tw));
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_heatmap_bin_palette: the palette rows of a block of frames straight from their samples, for a binned (lat/lon) plan.
+// Workgroup g takes frames [g * FPW, g * FPW + FPW).  Pass 1: every sample (16 B in: mu, mv, non-temporal) goes through
+// the plan's own quantiser (grid_dir) and direction -> bin LUT into the frame's LDS histogram (ds_add), and every present
+// user into the frame's LDS `present` counter; a NaN is absent, a sample outside [0, 1] counts in neither.  The histogram
+// and the palette rows are slot-ordered (bin li * n_lat + lj -> slot lj * n_lon + li, as k_heatmap_map_latlon).  Pass 2:
+// palette[t][slot] = heatmap_colour(count, present) over the flat (frame, slot) range of the workgroup, which is
+// contiguous in the [T][n] palette; zero counts take the grey of heatmap_colour(0, 0) without the FP64 division.
+// PACK: two 16-bit counts per LDS word (slot b adds 1 << 16 (b & 1) to word b >> 1; exact while U <= 65535, so no carry
+// reaches the neighbour): 1x1-degree cells, 65 341 bins, take 128 KiB.  !PACK: one u32 per bin, for U > 65535 on grids
+// whose bins fit the LDS as u32 (the host refuses the rest).
+// LDS: present u32 [FPW rounded up to 4] | cnt u32 [FPW][words] (rounded up to 4)
+// ------------------------------------------------------------------------------------------
+struct BinParams {
+    const double* mu;      // [T][U]
+    const double* mv;
+    const uint16_t* lut;   // the plan's direction -> bin table of lattice 0
+    int U, T, VW, VH;      // users, frames, video size (the plan's pixel grid)
+    int n, words, FPW;     // bins, LDS words per frame, frames per workgroup
+    int n_lat, n_lon;      // bins per lon column, per lat row
+    uint32_t* pal;         // [T][n]
+};
+
+template <bool PACK>
+__global__ __launch_bounds__(1024) void k_heatmap_bin_palette(const BinParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* present = (uint32_t*)smem;
+    uint32_t* cnt = present + ((p.FPW + 3) & ~3);
+    const long f0 = (long)blockIdx.x * p.FPW;
+    const int nf = (int)min((long)p.FPW, (long)p.T - f0);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int zq = (nf * p.words + 3) >> 2;                      // 16-byte stores (the layout rounds the counts up to 4)
+    for (int i = tid; i < zq; i += nt) ((uint4*)cnt)[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = tid; i < nf; i += nt) present[i] = 0u;
+    __syncthreads();
+    const double* mu = p.mu + f0 * (long)p.U;
+    const double* mv = p.mv + f0 * (long)p.U;
+    const int total = nf * p.U;                                  // < 2^31 (host)
+    for (int i = tid; i < total; i += nt) {
+        bool bad = false;
+        const int id = grid_dir(__builtin_nontemporal_load(mu + i), __builtin_nontemporal_load(mv + i), p.VW, p.VH, bad);
+        if (id < 0) continue;
+        const int fl = nf == 1 ? 0 : (int)((unsigned)i / (unsigned)p.U);
+        const unsigned bin = p.lut[id], li = bin / (unsigned)p.n_lat;
+        const int slot = (int)((bin - li * p.n_lat) * p.n_lon + li);
+        atomicAdd(&present[fl], 1u);
+        if (PACK) atomicAdd(&cnt[fl * p.words + (slot >> 1)], 1u << ((slot & 1) << 4));
+        else atomicAdd(&cnt[fl * p.words + slot], 1u);
+    }
+    __syncthreads();
+    // the workgroup's span of the palette, [f0 * n, (f0 + nf) * n): a head up to 16-byte alignment (the palette itself is
+    // 16-byte aligned), 16-byte stores of 4 entries per thread, a tail
+    const uint32_t grey = heatmap_colour(0.0, 0);
+    uint32_t* out = p.pal + f0 * (long)p.n;
+    const int span = nf * p.n;
+    const int head = min((int)((4 - ((f0 * p.n) & 3)) & 3), span);
+    const int body = head + ((span - head) & ~3);
+    auto colour_at = [&](int fl, int b) {
+        const uint32_t* row = cnt + fl * p.words;
+        const uint32_t c = PACK ? (row[b >> 1] >> ((b & 1) << 4)) & 0xffffu : row[b];
+        return c ? heatmap_colour((double)c, (int)present[fl]) : grey;
+    };
+    auto single = [&](int j) {
+        const int fl = nf == 1 ? 0 : (int)((unsigned)j / (unsigned)p.n);
+        out[j] = colour_at(fl, j - fl * p.n);
+    };
+    if (tid < head) single(tid);
+    for (int j = head + 4 * tid; j < body; j += 4 * nt) {
+        int fl = nf == 1 ? 0 : (int)((unsigned)j / (unsigned)p.n), b = j - fl * p.n;
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = colour_at(fl, b);
+            if (++b == p.n) { b = 0; ++fl; }
+        }
+        *(uint4*)(out + j) = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+    if (tid < span - body) single(body + tid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -160,13 +265,17 @@ int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uin
     return VET_OK;
 }
 
-template <typename Wt>
-int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
-                   const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
-    const long HW = (long)g.W * g.H, N = HW * T;
-    hipLaunchKernelGGL(vet::k_heatmap_palette<Wt>, dim3(grid_for((long)T * g.n, 256, c->n_cu)), dim3(256), 0, s, d_weights,
-                       d_present, (long)T, g.n, d_pal);
+int heatmap_map_latlon(vet_ctx* c, int tile_width, int tile_height, int W, int H, uint16_t* d_map, hipStream_t s) {
+    hipLaunchKernelGGL(vet::k_heatmap_map_latlon, dim3(grid_for((long)W * H, 256, c->n_cu)), dim3(256), 0, s, W, H,
+                       (double)tile_width, (double)tile_height, 360 / tile_width + 1, d_map);
     HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
+
+// The fill of frames [0, T) from their palette rows, then the markers when d_mu / d_mv are given.
+static int heatmap_fill(vet_ctx* c, const HeatmapGeom& g, const double* d_mu, const double* d_mv, int U, int T,
+                        const uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
+    const long HW = (long)g.W * g.H, N = HW * T;
     const long quads = N >> 2;
     const int grid = grid_for(quads > 0 ? quads : 1, 256, c->n_cu);
     const long stride = 4L * grid * 256;
@@ -178,6 +287,63 @@ int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const 
         hipLaunchKernelGGL(vet::k_heatmap_markers, dim3(grid_for((long)T * U, 256, c->n_cu)), dim3(256), 0, s, d_mu, d_mv,
                            U, (long)T, g.VW, g.VH, g.W, g.H, g.radius, d_rgb);
         HIP_TRY(hipGetLastError());
+    }
+    return VET_OK;
+}
+
+template <typename Wt>
+int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
+                   const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
+    hipLaunchKernelGGL(vet::k_heatmap_palette<Wt>, dim3(grid_for((long)T * g.n, 256, c->n_cu)), dim3(256), 0, s, d_weights,
+                       d_present, (long)T, g.n, d_pal);
+    HIP_TRY(hipGetLastError());
+    return heatmap_fill(c, g, d_mu, d_mv, U, T, d_pal, d_rgb, s);
+}
+
+BinLayout heatmap_bin_layout(int n, int U) {
+    BinLayout L;
+    if (U <= 0 || (long)U > (1L << 30)) return L;
+    L.pack = U <= 65535;
+    L.words = L.pack ? (n + 1) / 2 : n;
+    const size_t frame = (size_t)L.words * 4;
+    if (16 + ((frame + 15) & ~(size_t)15) > kWholeLds) return L;   // u32 counts of this many bins do not fit
+    // frames per workgroup: about 4096 samples each (small U), within 32 KiB of counts so that several workgroups share
+    // a CU; one frame when a frame's counts alone are larger
+    long fpw = std::max(1, 4096 / U);
+    fpw = std::min<long>(fpw, std::max<size_t>(1, ((size_t)32 << 10) / frame));
+    fpw = std::min<long>(fpw, ((1L << 31) - 1024) / U);
+    L.FPW = (int)std::max(1L, fpw);
+    L.lds = (size_t)((L.FPW + 3) & ~3) * 4 + (((size_t)L.FPW * frame + 15) & ~(size_t)15);
+    L.ok = true;
+    return L;
+}
+
+// Frames per bin-palette + fill launch pair: at most 64 MiB of palette, so that the fill gathers a chunk's rows from the
+// Infinity Cache right after k_heatmap_bin_palette wrote them.  1x1-degree cells (261 KB per frame, 535 MB for 2 048
+// frames) would otherwise leave the fill gathering from HBM.  Measured on one MI355X, 2 048 frames of 1 024 users at
+// 1200 x 600 (bin-palette + fill): 1.95 / 1.51 / 1.30 / 1.31 ms in chunks of 16 / 32 / 64 / 128 MiB, 2.2 ms in one
+// (tools/naive_heatmap_timing.py).  Grids up to 10x10-degree cells (703 bins) run in one chunk.
+int heatmap_bin_chunk(int n) { return (int)std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)n * 4)); }
+
+int heatmap_render_binned(vet_ctx* c, const HeatmapGeom& g, int n_lat, const uint16_t* d_lut, const double* d_mu,
+                          const double* d_mv, int U, int T, bool markers, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s) {
+    const BinLayout L = heatmap_bin_layout(g.n, U);
+    if (!L.ok) return fail(VET_ERR_UNSUPPORTED, "%d users over %d cells exceed the LDS histogram of k_heatmap_bin_palette", U, g.n);
+    const void* fn = L.pack ? (const void*)vet::k_heatmap_bin_palette<true> : (const void*)vet::k_heatmap_bin_palette<false>;
+    if (L.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    const int C = heatmap_bin_chunk(g.n);
+    const size_t frame = (size_t)g.W * g.H * 3;
+    for (int f0 = 0; f0 < T; f0 += C) {
+        const int b = std::min(C, T - f0);
+        const size_t off = (size_t)f0 * U;
+        const vet::BinParams bp{d_mu + off, d_mv + off, d_lut, U, b, g.VW, g.VH, g.n, L.words, L.FPW, n_lat, g.n / n_lat, d_pal};
+        const dim3 grid((unsigned)((b + (long)L.FPW - 1) / L.FPW));
+        if (L.pack) hipLaunchKernelGGL(vet::k_heatmap_bin_palette<true>, grid, dim3(1024), L.lds, s, bp);
+        else hipLaunchKernelGGL(vet::k_heatmap_bin_palette<false>, grid, dim3(1024), L.lds, s, bp);
+        HIP_TRY(hipGetLastError());
+        int rc = heatmap_fill(c, g, markers ? d_mu + off : nullptr, markers ? d_mv + off : nullptr, U, b, d_pal,
+                              d_rgb + (size_t)f0 * frame, s);
+        if (rc) return rc;
     }
     return VET_OK;
 }

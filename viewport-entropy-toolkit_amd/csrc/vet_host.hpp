@@ -5,7 +5,7 @@
 //                       error bounds; parity read-back hooks; angular distances; tile boundary geometry
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
-//   vet_heatmap.hip     the heatmap kernels (pixel -> tile map, palette, fill, markers) and their launch logic
+//   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points, device-resident results, heatmaps and tilings (no kernels of their own)
 // Every kernel header is included by exactly one of them.  There is no CPU compute path anywhere.
@@ -287,6 +287,21 @@ int heatmap_map(vet_ctx* c, const double* d_unit_tiles, int n, int W, int H, uin
 template <typename Wt>
 int heatmap_render(vet_ctx* c, const HeatmapGeom& g, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
                    const double* d_mv, int U, int T, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s);
+// Lat/lon cells of a naive tiling (n_lat cells per lon column).  heatmap_map_latlon: W x H pixel -> the slot lj * n_lon + li
+// of its cell li * n_lat + lj (k_heatmap_map_latlon).  heatmap_render_binned: frames [0, T) of the samples d_mu / d_mv
+// [T][U] -> d_rgb: k_heatmap_bin_palette (the cell counts of each frame through the plan's LUT d_lut, straight into the
+// slot-ordered d_pal [T][n]), k_heatmap_fill, then k_heatmap_markers when `markers`.
+// heatmap_bin_layout: the LDS histogram of U users over n cells (ok = false: it does not fit, VET_ERR_UNSUPPORTED).
+struct BinLayout {
+    bool ok = false, pack = false;     // pack: two 16-bit counts per LDS word (U <= 65535)
+    int words = 0, FPW = 0;            // LDS words per frame, frames per workgroup
+    size_t lds = 0;                    // dynamic LDS bytes of a workgroup
+};
+BinLayout heatmap_bin_layout(int n, int U);
+int heatmap_map_latlon(vet_ctx* c, int tile_width, int tile_height, int W, int H, uint16_t* d_map, hipStream_t s);
+int heatmap_bin_chunk(int n);
+int heatmap_render_binned(vet_ctx* c, const HeatmapGeom& g, int n_lat, const uint16_t* d_lut, const double* d_mu,
+                          const double* d_mv, int U, int T, bool markers, uint32_t* d_pal, uint8_t* d_rgb, hipStream_t s);
 
 // vet_tiling.hip: tilings drawn on the unit sphere.  tiling_chords: arcs [n][2][3] -> 50 slerp points per arc
 // (k_tiling_chords).  tiling_render: frames [0, T) -> d_rgb [T][H][W][3]: clear d_flags [T][H][W], k_tiling_splat,

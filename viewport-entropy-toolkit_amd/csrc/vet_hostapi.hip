@@ -307,6 +307,8 @@ struct vet_heatmap {
     vet_ctx* ctx = nullptr;
     int device = 0;
     HeatmapGeom g;
+    bool latlon = false;                 // lat/lon cells of a naive tiling (vet_heatmap_create_latlon), not a lattice's tiles
+    int n_lat = 0;                       // lat/lon: cells per lon column (the map holds slots lj * n_lon + li)
     uint16_t* d_map = nullptr;           // [H][W]
     uint32_t* d_pal = nullptr;           // grow-only palette [T][n] (both render entries)
     size_t pal_cap = 0;
@@ -347,14 +349,21 @@ static int heatmap_palette(vet_heatmap* hm, int T, hipStream_t s) {
     return VET_OK;
 }
 
+// The frame checks of both create entries.
+static int heatmap_frame_checks(int W, int H, int VW, int VH, int radius) {
+    if (W <= 0 || H <= 0 || VW <= 0 || VH <= 0) return fail(VET_ERR_INVALID, "need width, height, video_width, video_height > 0");
+    if ((int64_t)W * H > ((int64_t)1 << 31) / 3) return fail(VET_ERR_INVALID, "frame of %d x %d pixels is too large", W, H);
+    if (radius < 0 || radius > 16) return fail(VET_ERR_INVALID, "marker_radius %d outside [0, 16]", radius);
+    return VET_OK;
+}
+
 int vet_heatmap_create(vet_ctx* c, const double* h_tiles, int n, int W, int H, int VW, int VH, int radius,
                        vet_heatmap** out) {
     if (!c || !h_tiles || !out) return fail(VET_ERR_INVALID, "ctx, tiles or out is NULL");
     *out = nullptr;
     if (n <= 0 || W <= 0 || H <= 0 || VW <= 0 || VH <= 0)
         return fail(VET_ERR_INVALID, "need n_tiles, width, height, video_width, video_height > 0");
-    if ((int64_t)W * H > ((int64_t)1 << 31) / 3) return fail(VET_ERR_INVALID, "frame of %d x %d pixels is too large", W, H);
-    if (radius < 0 || radius > 16) return fail(VET_ERR_INVALID, "marker_radius %d outside [0, 16]", radius);
+    if (int rc = heatmap_frame_checks(W, H, VW, VH, radius)) return rc;
     if ((size_t)n * 3 * sizeof(double) > 160 * 1024 - 1024)
         return fail(VET_ERR_UNSUPPORTED, "lattice of %d tiles exceeds the LDS tile cache of k_heatmap_map", n);
     std::vector<double> unit((size_t)n * 3);
@@ -383,6 +392,32 @@ int vet_heatmap_create(vet_ctx* c, const double* h_tiles, int n, int W, int H, i
     return VET_OK;
 }
 
+int vet_heatmap_create_latlon(vet_ctx* c, int tile_width, int tile_height, int W, int H, int VW, int VH, int radius,
+                              vet_heatmap** out) {
+    if (!c || !out) return fail(VET_ERR_INVALID, "ctx or out is NULL");
+    *out = nullptr;
+    if (tile_height <= 0 || tile_width <= 0) return fail(VET_ERR_INVALID, "No tile dimensions provided");
+    if (180 % tile_height != 0) return fail(VET_ERR_INVALID, "Tile height must divide 180!");
+    if (360 % tile_width != 0) return fail(VET_ERR_INVALID, "Tile width must divide 360!");
+    if (int rc = heatmap_frame_checks(W, H, VW, VH, radius)) return rc;
+    const int n = (360 / tile_width + 1) * (180 / tile_height + 1);   // the naive plan's bins: lon 180 and lat 90 open a cell
+    if (n > 65535) return fail(VET_ERR_INVALID, "%d cells exceed 65535", n);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    auto* hm = new vet_heatmap();
+    struct Guard { vet_heatmap* h; ~Guard() { if (h) vet_heatmap_destroy(h); } } guard{hm};
+    hm->ctx = c; hm->device = c->device; hm->latlon = true; hm->n_lat = 180 / tile_height + 1;
+    hm->g.n = n; hm->g.W = W; hm->g.H = H; hm->g.VW = VW; hm->g.VH = VH; hm->g.radius = radius;
+    HIP_TRY(hipMalloc((void**)&hm->d_map, (size_t)W * H * sizeof(uint16_t)));
+    hm->g.d_map = hm->d_map;
+    int rc = heatmap_map_latlon(c, tile_width, tile_height, W, H, hm->d_map, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = hm;
+    guard.h = nullptr;
+    return VET_OK;
+}
+
 int vet_heatmap_destroy(vet_heatmap* hm) {
     if (!hm) return VET_OK;
     (void)hipSetDevice(hm->device);
@@ -405,7 +440,9 @@ int vet_heatmap_read_map(vet_heatmap* hm, int32_t* h_map) {
     HIP_TRY(hipSetDevice(hm->device));
     std::vector<uint16_t> tmp((size_t)hm->g.W * hm->g.H);
     HIP_TRY(hipMemcpy(tmp.data(), hm->d_map, tmp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tmp.size(); ++i) h_map[i] = tmp[i];
+    const int n_lat = hm->n_lat, n_lon = hm->latlon ? hm->g.n / n_lat : 0;
+    for (size_t i = 0; i < tmp.size(); ++i)                 // lat/lon: slot lj * n_lon + li -> cell li * n_lat + lj
+        h_map[i] = hm->latlon ? (tmp[i] % n_lon) * n_lat + tmp[i] / n_lon : tmp[i];
     return VET_OK;
 }
 
@@ -416,6 +453,7 @@ template <typename Wt>
 static int heatmap_render_device(vet_heatmap* hm, const Wt* d_weights, const int32_t* d_present, const double* d_mu,
                                  const double* d_mv, int U, int T, uint8_t* d_rgb, void* stream) {
     if (!hm || !d_weights || !d_present || !d_rgb) return fail(VET_ERR_INVALID, "heatmap, weights, present or rgb is NULL");
+    if (hm->latlon) return fail(VET_ERR_INVALID, "a lat/lon heatmap renders samples (vet_heatmap_render_binned*)");
     if (T < 0) return fail(VET_ERR_INVALID, "n_frames must be >= 0 (got %d)", T);
     if (!d_mu != !d_mv) return fail(VET_ERR_INVALID, "pass both d_mu and d_mv, or neither");
     if (d_mu && U <= 0) return fail(VET_ERR_INVALID, "n_users must be positive with samples (got %d)", U);
@@ -444,6 +482,7 @@ int vet_heatmap_render_counts(vet_heatmap* hm, const int32_t* d_counts, const in
 // weight), row range, samples (u_bytes per user in a row of output 0: 4 for assignments, 8 for pairs).
 static int heatmap_result_checks(vet_heatmap* hm, vet_result* r, size_t w_bytes, size_t u_bytes, const double* h_mu,
                                  const double* h_mv, int U, int64_t row0, int64_t n_rows) {
+    if (hm->latlon) return fail(VET_ERR_INVALID, "a lat/lon heatmap renders samples (vet_heatmap_render_binned*), not a result");
     if (r->device != hm->device)
         return fail(VET_ERR_INVALID, "result on device %d, heatmap on device %d", r->device, hm->device);
     const int n = hm->g.n;
@@ -466,14 +505,15 @@ static int heatmap_block_frames(const vet_heatmap* hm, int64_t n_rows) {
 
 }  // extern "C"
 
-// The render pipeline of both result entries: frames [row0, row0 + n_rows) in sub-blocks of B frames into the alternating
-// RGB and pinned buffers, the copy of one block overlapping the kernels of the next.  rows_of_block(f0, b, &w) yields the
-// device rows of frames [f0, f0 + b) (Wt [b][n]), enqueued on the context's stream.
-template <typename Wt, typename Rows>
-static int heatmap_render_blocks(vet_heatmap* hm, int B, const int32_t* h_present, const double* h_mu, const double* h_mv,
-                                 int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb, Rows rows_of_block) {
-    vet_ctx* c = hm->ctx;
-    hipStream_t s = c->stream;
+// The render pipeline of the host entries: frames [row0, row0 + n_rows) in sub-blocks of B frames into the alternating
+// RGB and pinned buffers, the copy of one block overlapping the kernels of the next.  Each block's h_present (when given)
+// and samples are uploaded first; render_block(f0, b, d_mu, d_mv, d_rgb) then enqueues frames [f0, f0 + b) on the
+// context's stream (d_mu / d_mv: the block's samples, or null without h_mu).  The palette holds pal_frames frames.
+template <typename Render>
+static int heatmap_render_blocks(vet_heatmap* hm, int B, int pal_frames, const int32_t* h_present, const double* h_mu,
+                                 const double* h_mv, int U, int64_t row0, int64_t n_rows, uint8_t* h_rgb,
+                                 Render render_block) {
+    hipStream_t s = hm->ctx->stream;
     const size_t frame = (size_t)hm->g.W * hm->g.H * 3;
     if (hm->B < B || (h_mu && hm->U < U)) {                 // grow-only staging
         HIP_TRY(hipStreamSynchronize(s));
@@ -496,7 +536,7 @@ static int heatmap_render_blocks(vet_heatmap* hm, int B, const int32_t* h_presen
         HIP_TRY(hipMalloc((void**)&hm->d_mv, (size_t)B * std::max(UU, 1) * 8));
         hm->B = B; hm->U = UU;
     }
-    int rc = heatmap_palette(hm, B, s);
+    int rc = heatmap_palette(hm, pal_frames, s);
     if (rc) return rc;
     auto drain = [&](int code) {
         (void)hipStreamSynchronize(s);
@@ -510,16 +550,12 @@ static int heatmap_render_blocks(vet_heatmap* hm, int B, const int32_t* h_presen
         const int64_t f0 = row0 + k * B;
         if (k >= 2 && hipStreamWaitEvent(s, hm->copied[st], 0) != hipSuccess)     // the copy of block k-2 has left d_rgb[st]
             return drain(fail(VET_ERR_DEVICE, "hipStreamWaitEvent failed"));
-        if (hipMemcpyAsync(hm->d_present, h_present + k * B, (size_t)b * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        if (h_present && hipMemcpyAsync(hm->d_present, h_present + k * B, (size_t)b * 4, hipMemcpyHostToDevice, s) != hipSuccess)
             return drain(fail(VET_ERR_DEVICE, "upload of the user counts failed"));
         if (h_mu && (hipMemcpyAsync(hm->d_mu, h_mu + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
                      hipMemcpyAsync(hm->d_mv, h_mv + k * B * (int64_t)U, (size_t)b * U * 8, hipMemcpyHostToDevice, s) != hipSuccess))
             return drain(fail(VET_ERR_DEVICE, "upload of the samples failed"));
-        const Wt* w = nullptr;
-        rc = rows_of_block(f0, b, &w);
-        if (rc) return drain(rc);
-        rc = heatmap_render(c, hm->g, w, hm->d_present, h_mu ? hm->d_mu : nullptr, h_mu ? hm->d_mv : nullptr, U, b, hm->d_pal,
-                            hm->d_rgb[st], s);
+        rc = render_block(f0, b, h_mu ? hm->d_mu : nullptr, h_mu ? hm->d_mv : nullptr, hm->d_rgb[st]);
         if (rc) return drain(rc);
         if (hipEventRecord(hm->computed[st], s) != hipSuccess || hipStreamWaitEvent(hm->copy, hm->computed[st], 0) != hipSuccess ||
             hipMemcpyAsync(hm->h_pin[st], hm->d_rgb[st], (size_t)b * frame, hipMemcpyDeviceToHost, hm->copy) != hipSuccess ||
@@ -561,14 +597,15 @@ int vet_heatmap_render_result(vet_heatmap* hm, vet_result* r, const int32_t* h_p
     }
     const int n = hm->g.n;
     hipStream_t s = hm->ctx->stream;
-    return heatmap_render_blocks<double>(hm, B, h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
-                                         [&](int64_t f0, int b, const double** w) -> int {
-        if (!r->lazy_weights) {
-            *w = (const double*)r->d[1] + (size_t)f0 * n;
-            return VET_OK;
+    return heatmap_render_blocks(hm, B, B, h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
+                                 [&](int64_t f0, int b, const double* d_mu, const double* d_mv, uint8_t* d_rgb) -> int {
+        const double* w = (const double*)r->d[1] + (size_t)f0 * n;
+        if (r->lazy_weights) {
+            w = (const double*)r->d_tmp;
+            int rc = weights_pass_ids(*r->core, r->d_ids + (size_t)f0 * r->U, r->U, b, (double*)r->d_tmp, s, nullptr);
+            if (rc) return rc;
         }
-        *w = (const double*)r->d_tmp;
-        return weights_pass_ids(*r->core, r->d_ids + (size_t)f0 * r->U, r->U, b, (double*)r->d_tmp, s, nullptr);
+        return heatmap_render(hm->ctx, hm->g, w, hm->d_present, d_mu, d_mv, U, b, hm->d_pal, d_rgb, s);
     });
 }
 
@@ -581,10 +618,58 @@ int vet_heatmap_render_transition_result(vet_heatmap* hm, vet_result* r, const i
     if (rc || n_rows == 0) return rc;
     HIP_TRY(hipSetDevice(hm->device));
     const int n = hm->g.n;
-    return heatmap_render_blocks<int32_t>(hm, heatmap_block_frames(hm, n_rows), h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
-                                          [&](int64_t f0, int, const int32_t** w) -> int {
-        *w = (const int32_t*)r->d[1] + (size_t)f0 * n;
-        return VET_OK;
+    const int B = heatmap_block_frames(hm, n_rows);
+    return heatmap_render_blocks(hm, B, B, h_present, h_mu, h_mv, U, row0, n_rows, h_rgb,
+                                 [&](int64_t f0, int b, const double* d_mu, const double* d_mv, uint8_t* d_rgb) -> int {
+        return heatmap_render(hm->ctx, hm->g, (const int32_t*)r->d[1] + (size_t)f0 * n, hm->d_present, d_mu, d_mv, U, b,
+                              hm->d_pal, d_rgb, hm->ctx->stream);
+    });
+}
+
+// The checks both binned entries share, after the NULL checks: heatmap kind, the plan's lattice 0, cell count, video size
+// and device; the users' LDS histogram.
+static int heatmap_binned_checks(vet_heatmap* hm, vet_plan* pl, int U, int T) {
+    if (T < 0) return fail(VET_ERR_INVALID, "n_frames must be >= 0 (got %d)", T);
+    if (U <= 0) return fail(VET_ERR_INVALID, "n_users must be positive (got %d)", U);
+    if (!hm->latlon) return fail(VET_ERR_INVALID, "a lattice heatmap has no lat/lon cells (vet_heatmap_create_latlon)");
+    if (pl->lat.empty() || !pl->lat[0].binned || !pl->grid)
+        return fail(VET_ERR_INVALID, "the plan's lattice 0 is not binned on a pixel grid");
+    if (pl->lat[0].n != hm->g.n)
+        return fail(VET_ERR_INVALID, "the plan's lattice 0 has %d bins, the heatmap %d cells", pl->lat[0].n, hm->g.n);
+    if (pl->W != hm->g.VW || pl->H != hm->g.VH)
+        return fail(VET_ERR_INVALID, "the plan's video is %d x %d, the heatmap's %d x %d", pl->W, pl->H, hm->g.VW, hm->g.VH);
+    if (pl->ctx->device != hm->device)
+        return fail(VET_ERR_INVALID, "plan on device %d, heatmap on device %d", pl->ctx->device, hm->device);
+    if (!heatmap_bin_layout(hm->g.n, U).ok)
+        return fail(VET_ERR_UNSUPPORTED, "%d users over %d cells exceed the LDS histogram of k_heatmap_bin_palette", U, hm->g.n);
+    return VET_OK;
+}
+
+int vet_heatmap_render_binned(vet_heatmap* hm, vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T,
+                              int markers, uint8_t* d_rgb, void* stream) {
+    if (!hm || !pl || !d_mu || !d_mv || !d_rgb) return fail(VET_ERR_INVALID, "heatmap, plan, samples or rgb is NULL");
+    if (int rc = heatmap_binned_checks(hm, pl, U, T)) return rc;
+    if ((uintptr_t)d_rgb % 4) return fail(VET_ERR_INVALID, "d_rgb must be 4-byte aligned");
+    if (T == 0) return VET_OK;
+    HIP_TRY(hipSetDevice(hm->device));
+    hipStream_t s = stream ? (hipStream_t)stream : hm->ctx->stream;
+    int rc = heatmap_palette(hm, std::min(T, heatmap_bin_chunk(hm->g.n)), s);
+    if (rc) return rc;
+    return heatmap_render_binned(hm->ctx, hm->g, hm->n_lat, pl->lat[0].d_nearest, d_mu, d_mv, U, T, markers != 0, hm->d_pal,
+                                 d_rgb, s);
+}
+
+int vet_heatmap_render_binned_host(vet_heatmap* hm, vet_plan* pl, const double* h_mu, const double* h_mv, int U, int T,
+                                   int markers, uint8_t* h_rgb) {
+    if (!hm || !pl || !h_mu || !h_mv || !h_rgb) return fail(VET_ERR_INVALID, "heatmap, plan, samples or rgb is NULL");
+    if (int rc = heatmap_binned_checks(hm, pl, U, T)) return rc;
+    if (T == 0) return VET_OK;
+    HIP_TRY(hipSetDevice(hm->device));
+    const int B = heatmap_block_frames(hm, T);
+    return heatmap_render_blocks(hm, B, std::min(B, heatmap_bin_chunk(hm->g.n)), nullptr, h_mu, h_mv, U, 0, T, h_rgb,
+                                 [&](int64_t, int b, const double* d_mu, const double* d_mv, uint8_t* d_rgb) -> int {
+        return heatmap_render_binned(hm->ctx, hm->g, hm->n_lat, pl->lat[0].d_nearest, d_mu, d_mv, U, b, markers != 0,
+                                     hm->d_pal, d_rgb, hm->ctx->stream);
     });
 }
 

@@ -119,6 +119,9 @@ SIGNATURES = {
     "vet_heatmap_render_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
     "vet_heatmap_render_counts": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "vet_heatmap_render_transition_result": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P]),
+    "vet_heatmap_create_latlon": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "vet_heatmap_render_binned": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "vet_heatmap_render_binned_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "vet_tiling_create": (_I, [_P, _P, _I, _P, _I, _I, _I, C.POINTER(_P)]),
     "vet_tiling_destroy": (_I, [_P]),
     "vet_tiling_render": (_I, [_P, _P, _I, _P, _P, _P]),
@@ -626,6 +629,25 @@ class Heatmap:
                                                      self.video_width, self.video_height, self.marker_radius, C.byref(h)))
         self.handle = h
 
+    @classmethod
+    def latlon(cls, engine: Engine, tile_width: int, tile_height: int, width: int, height: int, video_width: int,
+               video_height: int, marker_radius: int = 2) -> "Heatmap":
+        """The heatmap of a naive plan's ``tile_height`` x ``tile_width`` degree lat/lon cells
+        (include/vet.h: vet_heatmap_create_latlon): every pixel centre's cell, find_naive_tile_index's arithmetic, in the
+        plan's bin numbering ((360 / tile_width + 1) * (180 / tile_height + 1) cells).  Render it with ``render_binned``."""
+        self = cls.__new__(cls)
+        self.engine, self.lib = engine, engine.lib
+        self.tile_width, self.tile_height = int(tile_width), int(tile_height)
+        self.width, self.height = int(width), int(height)
+        self.video_width, self.video_height, self.marker_radius = int(video_width), int(video_height), int(marker_radius)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.vet_heatmap_create_latlon(engine.handle, self.tile_width, self.tile_height, self.width,
+                                                            self.height, self.video_width, self.video_height,
+                                                            self.marker_radius, C.byref(h)))
+        self.handle = h
+        self.n_tiles = (360 // self.tile_width + 1) * (180 // self.tile_height + 1)
+        return self
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.vet_heatmap_destroy(self.handle)
@@ -657,6 +679,42 @@ class Heatmap:
         _check(self.lib, self.lib.vet_heatmap_render_counts(self.handle, d_counts, d_present, d_mu or None, d_mv or None,
                                                             int(n_users), int(n_frames), d_rgb, _stream(stream)))
 
+    def render_binned_device(self, plan: "Plan", d_mu: int, d_mv: int, n_users: int, n_frames: int, d_rgb: int,
+                             markers: bool = True, stream=None):
+        """Frames [0, n_frames) of a lat/lon heatmap from device samples (f64 [T, U] each) through ``plan``'s binned
+        lattice 0 into ``d_rgb`` (uint8 [T, H, W, 3], 4-byte aligned); asynchronous on ``stream`` as
+        ``Plan.spatial_device``."""
+        _check(self.lib, self.lib.vet_heatmap_render_binned(self.handle, plan.handle, d_mu, d_mv, int(n_users),
+                                                            int(n_frames), int(bool(markers)), d_rgb, _stream(stream)))
+
+    def _out(self, n: int, out: Optional[np.ndarray]) -> np.ndarray:
+        shape = (n, self.height, self.width, 3)
+        if out is None:
+            return np.empty(shape, dtype=np.uint8)
+        if out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        return out
+
+    def render_binned(self, plan: "Plan", mu: np.ndarray, mv: np.ndarray, row0: int = 0, n: Optional[int] = None,
+                      markers: bool = True, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Frames [row0, row0 + n) of the samples ``mu`` / ``mv`` (f64 [T, U], NaN = absent) of a lat/lon heatmap ->
+        uint8 [n, H, W, 3] (into ``out`` when given).  Each cell's colour is its users (through ``plan``'s own quantiser
+        and LUT) over the users present in the frame; ``markers=False`` draws no viewport markers."""
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        mv = np.ascontiguousarray(mv, dtype=np.float64)
+        if mu.ndim != 2 or mu.shape != mv.shape:
+            raise ValueError("mu and mv must be [n_frames, n_users] arrays of equal shape")
+        T, U = mu.shape
+        row0 = int(row0)
+        n = T - row0 if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > T:
+            raise ValueError(f"frames [{row0}, {row0 + n}) outside the samples' {T} frames")
+        out = self._out(n, out)
+        _check(self.lib, self.lib.vet_heatmap_render_binned_host(self.handle, plan.handle, _ptr(mu[row0:row0 + n]),
+                                                                 _ptr(mv[row0:row0 + n]), U, n, int(bool(markers)),
+                                                                 _ptr(out)))
+        return out
+
     def _render_rows(self, entry, result, present, mu, mv, row0, n, out) -> np.ndarray:
         n = result.n_rows - row0 if n is None else int(n)
         present = np.ascontiguousarray(present, dtype=np.int32).reshape(-1)
@@ -669,11 +727,7 @@ class Heatmap:
             if mu.ndim != 2 or mu.shape != mv.shape or len(mu) != n:
                 raise ValueError(f"mu and mv must be [{n}, n_users] arrays of equal shape")
             U = mu.shape[1]
-        shape = (n, self.height, self.width, 3)
-        if out is None:
-            out = np.empty(shape, dtype=np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous uint8 array of shape {shape}")
+        out = self._out(n, out)
         _check(self.lib, entry(self.handle, result.handle, _ptr(present), _ptr(mu), _ptr(mv), U, int(row0), n, _ptr(out)))
         return out
 

@@ -5,7 +5,8 @@ utilities/entropy_utils.py:383-452), on the HIP engine's integer histogram kerne
 The cell of a sample depends only on its pixel direction, so the host turns the two axis tables
 (lon per px, lat per py) into a direction -> cell table once and the device path is the same
 16-B-in / 4-B-out stream as the unweighted Fibonacci mode.  As in the reference the result frame
-carries ``None`` in ``tile_weights`` / ``tile_assignments``."""
+carries ``None`` in ``tile_weights`` / ``tile_assignments``.  ``render_heatmaps`` / ``save_heatmaps`` count the
+cells of each frame again on the GPU, from the samples of the last ``compute_entropy``."""
 
 from __future__ import annotations
 
@@ -21,12 +22,15 @@ from ..config import NaiveAnalyzerConfig
 from ..data_types import ValidationError
 from ..utilities.entropy_utils import naive_tile_count
 from ._base import _EntropyAnalyzerBase
+from ._heatmaps import _HeatmapMixin
 
 logger = logging.getLogger(__name__)
 
 
-class NaiveSpatialEntropyAnalyzer(_EntropyAnalyzerBase):
-    """Drop-in analyzer for the lat/lon-cut tiling; ``config`` is a ``NaiveAnalyzerConfig``."""
+class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
+    """Drop-in analyzer for the lat/lon-cut tiling; ``config`` is a ``NaiveAnalyzerConfig``.  The heatmap methods are the
+    mixin's, over lat/lon cells: ``_heatmap`` and ``_render_block`` render the samples of the last ``compute_entropy``
+    through its plan (include/vet.h: vet_heatmap_render_binned_host); no result stays on the device."""
 
     _logger = logger
 
@@ -40,6 +44,8 @@ class NaiveSpatialEntropyAnalyzer(_EntropyAnalyzerBase):
         self._plan = None
         self._plan_key = None
         self.last_timing = {}
+        self._heatmaps = {}
+        self._heatmap_source = None   # (plan, mu, mv, tile_width, tile_height) of the last compute_entropy
 
     def _naive_plan(self) -> "_native.Plan":
         cfg = self.config
@@ -73,7 +79,8 @@ class NaiveSpatialEntropyAnalyzer(_EntropyAnalyzerBase):
         times, mu, mv, _ = self._dense
         t_start = time.perf_counter()
         try:
-            res = self._naive_plan().spatial(mu=mu, mv=mv, want_assign=False, want_weights=False)
+            plan = self._naive_plan()
+            res = plan.spatial(mu=mu, mv=mv, want_assign=False, want_weights=False)
         except _native.NativeError as e:
             if e.code == _native.VET_ERR_RANGE:
                 raise ValidationError(str(e))
@@ -87,4 +94,23 @@ class NaiveSpatialEntropyAnalyzer(_EntropyAnalyzerBase):
             "tile_weights": [None] * len(times),
             "tile_assignments": [None] * len(times),
         })
+        self._heatmap_source = (plan, mu, mv, self.config.tile_width, self.config.tile_height)
         return self._entropy_results
+
+    # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
+    def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
+        plan, _, _, tw, th = self._heatmap_source
+        key = (tw, th, width, height, plan.width, plan.height, marker_radius)
+        if key not in self._heatmaps:
+            try:
+                self._heatmaps[key] = _native.Heatmap.latlon(_native.Engine.default(), tw, th, width, height, plan.width,
+                                                             plan.height, marker_radius)
+            except _native.NativeError as e:
+                if e.code == _native.VET_ERR_INVALID:
+                    raise ValidationError(str(e))
+                raise
+        return self._heatmaps[key]
+
+    def _render_block(self, hm, row0: int, n: int, markers: bool, out=None) -> np.ndarray:
+        plan, mu, mv, _, _ = self._heatmap_source
+        return hm.render_binned(plan, mu, mv, row0, n, markers, out=out)
