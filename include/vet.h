@@ -50,7 +50,8 @@ extern "C" {
                            (tilings drawn on the unit sphere) and vet_heatmap_render_counts /
                            vet_heatmap_render_transition_result (heatmaps of transition results) and
                            vet_heatmap_create_latlon / vet_heatmap_render_binned(_host) (lat/lon cell
-                           heatmaps of naive plans) added the same way */
+                           heatmaps of naive plans) added the same way; so were vet_window_rows and the
+                           vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -234,6 +235,59 @@ int vet_spatial_entropy(vet_plan *plan, const double *d_mu, const double *d_mv,
 int vet_spatial_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames,
                             double *d_entropy, int32_t *d_assign, double *d_weights,
                             int32_t *d_present, int32_t *d_status, void *stream);
+
+/* ---- sliding-window spatial entropy: the frames of a window pooled into one histogram -----------
+ * For window = w >= 1, stride = s >= 1 and n_frames = T >= w there are R = (T - w) / s + 1 rows (integer division;
+ * vet_window_rows, < 0 for illegal arguments); row r covers frames [r*s, r*s + w).  Row r is, for every lattice of the plan,
+ * what compute_spatial_entropy (utilities/entropy_utils.py:147-211; naive plans: compute_naive_spatial_entropy, :383-452)
+ * returns for ONE dict that holds every present (frame, user) sample of those frames, frame-major then user order, then the
+ * mean over the lattices as compute_entropy takes it (analyzers/spatial_entropy.py:142-156).  So, with `samples` = the present
+ * samples of the window (not users):
+ *   weighted: the keys are the tiles with distance < fov/2 of some sample of the window, the normaliser is log2(n); a key
+ *     whose weights are all 0.0 makes the row NaN (0 * log2 0);
+ *   unweighted and binned (naive) lattices: every sample adds 1 to its tile / bin; the normaliser is log2(n) if
+ *     use_weight_distribution or samples > n, else log2(samples); one sample in the window gives the reference's NaN (0 / 0);
+ *   a window without any present sample: NaN in d_entropy, 0 in d_samples and d_status[1] += 1 — what vet_spatial_entropy
+ *     does with a frame without a user; the _host entry then returns VET_ERR_EMPTY (outputs are still written).
+ * window = 1, stride = 1 is the per-frame series.
+ *   d_entropy [R]
+ *   d_weights [R*n_0]  lattice 0's pooled histogram, encoded and toleranced as vet_spatial_entropy's d_weights  (nullable)
+ *   d_samples [R]      present samples of the window                                                            (nullable)
+ *   d_status  [2]      {bad, #rows without a sample}; as vet_spatial_entropy: the call ADDS, the caller zeroes   (nullable)
+ * Two stages; every frame's histogram is built once, whatever the overlap of the windows:
+ *   1 per frame: weighted Fibonacci lattices — the `dtable` arithmetic: the users' exact FP64 weight rows (k_weights_gather,
+ *     built once per plan and lattice) summed per frame in `dtable`'s order (above), [T][n_k] f64 per lattice; there is no
+ *     other formulation, no error bound to check and no NaN hand-over: where a lattice's exact rows do not fit the device
+ *     (vet_plan_set_fp64's rule) the call fails with VET_ERR_UNSUPPORTED.  Unweighted and binned lattices — the tile / bin
+ *     of every sample, [T][U] i32 per lattice (k_window_tiles).  The call's scratch (those arrays, T * 4 bytes of frame
+ *     counts and K * R * 8 bytes of per-lattice rows) is the context's grow-only workspace: no allocation in steady state;
+ *   2 per row and lattice (k_window_entropy): weighted — the window's w frame histograms ADDED IN ASCENDING FRAME ORDER from
+ *     the window's first frame, for every row anew (never a running sum with subtractions), then `dtable`'s epilogue in one
+ *     wave; integer counts — a wave owns a run of consecutive rows, keeps the window's counts in LDS, adds the frames that
+ *     enter and subtracts those that leave (exact), then the per-frame kernel's epilogue in one wave.
+ * A row is therefore a pure function of the plan and the samples of its w frames: the same bits whatever stride selected
+ * it, wherever its frames lie in the call, from run to run, and between the ids and the grid entry points.  With window = 1
+ * a weighted plan gives the bits of the same plan under vet_plan_set_fp64 where that call runs `dtable`, and an unweighted /
+ * binned plan gives the bits of vet_spatial_entropy where that runs k_spatial_u_lds (grid samples, n_users <= 4096, the
+ * nearest-tile table in LDS; the other per-frame kernel takes log2(v / N) directly: same value within an ulp or two).
+ * Limits: an integer-count lattice keeps one u32 per bin in LDS, so binned lattices of more than lds / 4 bins (40 832 on
+ * gfx950; naive 1 x 1 degree cells have 65 341) are refused with VET_ERR_UNSUPPORTED.
+ * VET_ERR_INVALID: window < 1, stride < 1, window > n_frames (and what vet_spatial_entropy refuses).
+ * The kernels have no profile id of their own: stage 1 is charged to k_weights (weighted) / k_spatial (k_window_tiles),
+ * stage 2 to k_finalize.  Asynchronous on `stream` like vet_spatial_entropy. */
+int64_t vet_window_rows(int n_frames, int window, int stride);
+int vet_spatial_entropy_windowed(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames,
+                                 int window, int stride, double *d_entropy, double *d_weights, int32_t *d_samples,
+                                 int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_spatial_entropy_windowed_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                                     double *d_entropy, double *d_weights, int32_t *d_samples, int32_t *d_status,
+                                     void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE / VET_ERR_EMPTY when the status words are non-zero (outputs are
+ * still written).  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_spatial_entropy_windowed_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
+                                      int n_users, int n_frames, int window, int stride, double *h_entropy,
+                                      double *h_weights, int32_t *h_samples);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

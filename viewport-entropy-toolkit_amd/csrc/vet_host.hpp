@@ -5,6 +5,7 @@
 //                       error bounds; parity read-back hooks; angular distances; tile boundary geometry
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
+//   vet_window.hip      the sliding-window spatial-entropy kernels (pooled histograms of frame windows) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points, device-resident results, heatmaps and tilings (no kernels of their own)
@@ -271,6 +272,10 @@ int ensure_exact_weights(vet_plan* pl, hipStream_t s);
 // the same for lattice k (k = 0: ensure_exact_weights); exact_rows(pl, k) = its tables
 int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s);
 const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k);
+// vet_spatial.hip: per-frame tile sums of weighted lattice k from its exact rows (which must exist), [T][n_k] in the dense
+// tile_weights encoding, `dtable`'s bits — stage 1 of the windowed entry points (samples as d_mu / d_mv, or d_ids)
+int exact_frame_rows(vet_plan* pl, int k, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, double* out,
+                     hipStream_t s);
 // (mu, mv) -> direction ids [n] (-1 absent or out of range) on the plan's pixel grid
 int sample_ids(const vet_plan* pl, const double* d_mu, const double* d_mv, long n, int32_t* d_out, hipStream_t s);
 
@@ -325,5 +330,6 @@ int tiling_render(vet_ctx* c, const TilingGeom& g, const TilingCam* d_cam, int T
 // dynamic-LDS limits of the run kernels (once per context, from vet_plan_create)
 int spatial_set_attrs(vet_ctx* c);
 int transition_set_attrs(vet_ctx* c);
+int window_set_attrs(vet_ctx* c);
 
 }  // namespace vh

@@ -202,6 +202,53 @@ int vet_transition_entropy_host(vet_plan* pl, const double* h_mu, const double* 
     return run_host(pl, true, h_mu, h_mv, h_ids, U, T, h_entropy, h_pairs, h_srccount, h_common);
 }
 
+// Sliding-window spatial entropy with host buffers (include/vet.h): staged like run_host, R = vet_window_rows output rows
+int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
+                                      int window, int stride, double* h_entropy, double* h_weights, int32_t* h_samples) {
+    int rc = check_run_args(pl, U, T, h_entropy);
+    if (rc) return rc;
+    const bool ids = h_ids != nullptr;
+    if (!ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");
+    if (!ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const int64_t R = vet_window_rows(T, window, stride);
+    if (R < 0)
+        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
+                    stride, T);
+    vet_ctx* c = pl->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t S = (size_t)U * T, w_bytes = (size_t)R * pl->lat[0].n * 8;
+    void *mu = nullptr, *mv = nullptr, *id = nullptr, *ent = nullptr, *wt = nullptr, *cnt = nullptr, *st = nullptr;
+    if (ids) {
+        POOL(0, S * 4, id);
+        HIP_TRY(hipMemcpyAsync(id, h_ids, S * 4, hipMemcpyHostToDevice, s));
+    } else {
+        POOL(0, S * 8, mu);
+        POOL(1, S * 8, mv);
+        HIP_TRY(hipMemcpyAsync(mu, h_mu, S * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(mv, h_mv, S * 8, hipMemcpyHostToDevice, s));
+    }
+    POOL(2, (size_t)R * 8, ent);
+    if (h_weights) POOL(4, w_bytes, wt);
+    POOL(5, (size_t)R * 4, cnt);
+    POOL(6, 8, st);
+    HIP_TRY(hipMemsetAsync(st, 0, 8, s));
+    rc = ids ? vet_spatial_entropy_windowed_ids(pl, (const int32_t*)id, U, T, window, stride, (double*)ent, (double*)wt,
+                                                (int32_t*)cnt, (int32_t*)st, s)
+             : vet_spatial_entropy_windowed(pl, (const double*)mu, (const double*)mv, U, T, window, stride, (double*)ent,
+                                            (double*)wt, (int32_t*)cnt, (int32_t*)st, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    int32_t status[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_entropy, ent, (size_t)R * 8, hipMemcpyDeviceToHost, s));
+    if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, wt, w_bytes, hipMemcpyDeviceToHost, s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status, st, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
+    if (status[1]) return fail(VET_ERR_EMPTY, "%d window(s) without any sample (Empty vector dictionary)", status[1]);
+    return VET_OK;
+}
+
 // Concatenated host buffers: video v's samples start at element sum_{w<v} U_w*T_w of h_mu / h_mv /
 // h_assign and its entropies at sum_{w<v} T_w of h_entropy / h_present.  Two H2D copies, one launch
 // (when the table formulation applies), two or three D2H copies.

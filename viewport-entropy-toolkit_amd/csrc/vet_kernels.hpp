@@ -27,6 +27,11 @@
 //                       vet_spatial_u.hpp      k_spatial_u_lds  nearest-tile (unweighted) and naive lat/lon-grid mode:
 //                                                               persistent stream with the nearest LUT in LDS (HBM-bound)
 //                                              k_spatial_u      generic fallback (LUT gathered from global memory)
+//   vet_window.hip      (in the unit)          k_window_tiles   per frame: tile / bin of every sample, present count
+//                                              k_window_entropy_w, k_window_entropy_c   sliding windows of frames pooled into one
+//                                                               histogram per row (weighted: the frames' exact FP64 sums added in
+//                                                               frame order; counts: add entering, subtract leaving frames) ->
+//                                                               the reference's entropy of the pooled histogram
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

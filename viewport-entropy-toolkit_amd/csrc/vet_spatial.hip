@@ -761,6 +761,40 @@ int weights_pass_ids(const WeightsCore& w, const int32_t* d_ids, int U, int T, d
     return launch_weights_pass<true>(w, src, U, T, d_weights, s, prof);
 }
 
+// Per-frame tile sums of weighted lattice k, frames [0, T) -> out [T][n_k] in the dense tile_weights encoding: k_weights_gather
+// over the lattice's exact FP64 weight rows (the caller has checked that they exist) at the NW `dtable` runs this lattice at,
+// so the sums are `dtable`'s bit for bit (stage 1 of the windowed entry points, vet_window.hip)
+int exact_frame_rows(vet_plan* pl, int k, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, double* out,
+                     hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const int K = (int)pl->lat.size(), n = pl->lat[k].n;
+    const WeightsCore::Exact& X = exact_rows(pl, k);
+    if (X.state != 1) return fail(VET_ERR_UNSUPPORTED, "lattice %d has no exact weight rows", k);
+    int n_sum = 0;
+    for (const auto& L : pl->lat) n_sum += L.n;
+    // launch_spatial_main: one `dtable` launch at lattice 0's NW where all histograms fit, else every lattice at its own
+    const int nw0 = weights_nw(c->lds_max, pl->lat[0].n);
+    const bool one_launch = K <= vet::MAX_LATTICES && vet::dtable_lds_bytes(nw0, n_sum) <= c->lds_max;
+    const int nw = one_launch ? nw0 : weights_nw(c->lds_max, n);
+    const size_t lds = (size_t)nw * n * 8;
+    if (lds > c->lds_max) return fail(VET_ERR_UNSUPPORTED, "lattice of %d tiles does not fit the LDS histogram (%zu B)", n, lds);
+    vet::WeightsGatherParams q{};
+    q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    q.U = U; q.T = T;
+    q.alias = pl->d_alias; q.idx = (const uint16_t*)X.idx.get(); q.w = (const double*)X.w.get(); q.len = (const uint32_t*)X.len.get();
+    q.stride = X.stride; q.n = n; q.out = out;
+    const int chunks = X.stride / vet::WAVE;
+    const bool ids = d_ids != nullptr;
+#define VET_GATHER(S) (ids ? (const void*)vet::k_weights_gather<true, S> : (const void*)vet::k_weights_gather<false, S>)
+    const void* fn = chunks <= 1 ? VET_GATHER(1) : chunks <= 2 ? VET_GATHER(2) : chunks <= 4 ? VET_GATHER(4) : VET_GATHER(0);
+#undef VET_GATHER
+    void* args[] = {(void*)&q};
+    ProfScope ps(c, s, KID_WEIGHTS);
+    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)T), dim3(nw * vet::WAVE), args, lds, s));
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
+
 int sample_ids(const vet_plan* pl, const double* d_mu, const double* d_mv, long n, int32_t* d_out, hipStream_t s) {
     const vet::SampleSrc src{d_mu, d_mv, nullptr, pl->W, pl->H, (long)pl->n_dirs};
     hipLaunchKernelGGL(k_sample_ids, dim3(grid_for(n, 256, pl->ctx->n_cu)), dim3(256), 0, s, src, n, d_out);

@@ -1,0 +1,358 @@
+// vet_window.hip — sliding-window spatial entropy behind vet_spatial_entropy_windowed* (include/vet.h): the kernels and
+// their launch logic.  Row r pools the samples of frames [r * stride, r * stride + window) into ONE histogram per lattice
+// and takes the reference's normalised entropy of it (compute_spatial_entropy on one dict that holds every sample of the
+// window, utilities/entropy_utils.py:147-211), then the mean over the lattices (k_finalize).
+// Two stages, every frame's histogram built once whatever the overlap of the windows:
+//   1  per frame and lattice, in the context's workspace:
+//        weighted Fibonacci lattices   [T][n_k] f64 tile sums: k_weights_gather over the lattice's exact FP64 weight rows
+//                                      (vet_spatial.hip: exact_frame_rows), `dtable`'s sums bit for bit
+//        unweighted / binned lattices  [T][U] i32 tile of every sample, -1 absent (k_window_tiles)
+//        present samples per frame [T] and the range status word (k_window_tiles)
+//   2  k_window_entropy_w / k_window_entropy_c: the window's histogram in LDS and the reference's epilogue over it.
+// A row is a pure function of the plan and of its frames' samples: the FP64 sums are re-added from the window's first frame
+// in ascending frame order for every row (never a running sum with subtractions), the integer counts are exact under add
+// and subtract, and every reduction runs in one wave in fixed lane order.
+// No CPU compute path; nothing here reads the environment.
+#include "vet_host.hpp"
+#include "vet_common.hpp"
+#include "vet_finalize.hpp"
+
+#include <algorithm>
+
+namespace vet {
+
+// -0.0 = "no key" in an FP64 histogram (vet_spatial_sweep.hpp: NO_KEY_BITS; this unit does not include the sweep kernels)
+constexpr unsigned long long WIN_NO_KEY_BITS = 0x8000000000000000ull;
+
+// ------------------------------------------------------------------------------------------
+// k_window_tiles — stage 1 of the integer-count lattices and the per-frame bookkeeping of every plan: one wave per frame;
+// tiles[f][u] = nearest tile / bin of the sample (LUT gather), -1 absent; present[f] = samples of the frame; status[0] is
+// raised by samples outside [0, 1] (ids: at or beyond the direction table) exactly as vet_spatial_entropy raises it.
+// ------------------------------------------------------------------------------------------
+struct WindowTilesParams {
+    SampleSrc src;
+    int U, T;
+    const uint16_t* nearest;     // [n_dirs] direction -> tile / bin of this lattice, or null (bookkeeping only)
+    int32_t* tiles;              // [T][U] or null
+    int32_t* present;            // [T] or null
+    int32_t* status;             // [2] or null
+};
+
+template <bool FROM_IDS>
+__global__ __launch_bounds__(256) void k_window_tiles(const WindowTilesParams p) {
+    const int lane = lane_id();
+    const long f = (long)blockIdx.x * (blockDim.x >> 6) + wave_id();
+    bool bad = false;
+    if (f < p.T) {
+        int np = 0;
+        for (int u = lane; u < p.U; u += WAVE) {
+            const long idx = f * (long)p.U + u;
+            const int id = sample_dir<FROM_IDS>(p.src, idx, bad);
+            if (p.tiles) p.tiles[idx] = id >= 0 ? (int)p.nearest[id] : -1;
+            np += id >= 0 ? 1 : 0;
+        }
+        np = wave_sum(np);
+        if (lane == 0 && p.present) p.present[f] = np;
+    }
+    if (p.status) {
+        const unsigned long long anybad = __ballot(bad);
+        if (anybad && lane == 0) atomicAdd(&p.status[0], (int)__popcll(anybad));
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_window_entropy_w — stage 2 of a weighted Fibonacci lattice.  One wave per row, NW rows per workgroup, no barriers.
+// hist[f][t] is the dense tile_weights encoding of frame f (include/vet.h): -0.0 = key of the reference's dict with the
+// value 0.0, +0.0 = no key.  Tile t of the row = the window's frames added in ascending frame order onto "no key" (-0.0):
+// a frame without the key adds -0.0 (no change), a zero-valued key adds +0.0 (-0.0 + +0.0 = +0.0: key with the value 0.0),
+// so one frame (window = 1) gives back k_spatial_dtable's own LDS value.  Lane l owns tiles l, l + 64, ...: the loads of a
+// frame row are coalesced, four frames are in flight per tile, and a frame row is read from L2 by the window / stride rows
+// that share it.  The epilogue is k_spatial_dtable's: total and -sum q log2 q over the keys in lane order, wave_sum's
+// butterfly, / hmax; NaN for a window without a sample (and status[1] += 1).
+// LDS: f64 [NW][n] (a wave reads back only what its own lanes wrote).
+// ------------------------------------------------------------------------------------------
+struct WindowWParams {
+    const double* hist;          // [T][n]
+    const int32_t* present;      // [T]
+    int n;
+    double hmax;
+    int window, stride;
+    long R;
+    double* ent;                 // [R]
+    double* weights;             // [R][n] or null
+    int32_t* samples;            // [R] or null
+    int32_t* status;             // [2] or null
+};
+
+__device__ __forceinline__ double window_term(double v) { return v == 0.0 ? -v : v; }   // dense encoding -> histogram value
+
+__global__ __launch_bounds__(256) void k_window_entropy_w(const WindowWParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int NW = blockDim.x >> 6, lane = lane_id(), wv = wave_id();
+    const long r = (long)blockIdx.x * NW + wv;
+    if (r >= p.R) return;
+    double* h = (double*)smem + (size_t)wv * p.n;
+    const long f0 = r * (long)p.stride;
+    int np = 0;
+    for (int j = lane; j < p.window; j += WAVE) np += p.present[f0 + j];
+    np = wave_sum(np);
+    double tot = 0.0;
+    for (int t = lane; t < p.n; t += WAVE) {
+        const double* col = p.hist + f0 * (long)p.n + t;
+        double acc = __longlong_as_double((long long)WIN_NO_KEY_BITS);
+        int j = 0;
+        for (; j + 4 <= p.window; j += 4) {
+            const double v0 = col[(long)j * p.n], v1 = col[(long)(j + 1) * p.n], v2 = col[(long)(j + 2) * p.n],
+                         v3 = col[(long)(j + 3) * p.n];
+            acc += window_term(v0); acc += window_term(v1); acc += window_term(v2); acc += window_term(v3);
+        }
+        for (; j < p.window; ++j) acc += window_term(col[(long)j * p.n]);
+        h[t] = acc;
+        const bool key = (unsigned long long)__double_as_longlong(acc) != WIN_NO_KEY_BITS;
+        if (key) tot += acc;
+        if (p.weights) __builtin_nontemporal_store(key ? (acc == 0.0 ? -0.0 : acc) : 0.0, p.weights + r * (long)p.n + t);
+    }
+    tot = wave_sum(tot);
+    double hh = 0.0;
+    for (int t = lane; t < p.n; t += WAVE) {
+        const double v = h[t];
+        if ((unsigned long long)__double_as_longlong(v) != WIN_NO_KEY_BITS) {
+            const double q = v / tot;
+            hh -= q * log2(q);
+        }
+    }
+    hh = wave_sum(hh);
+    if (lane == 0) {
+        p.ent[r] = np == 0 ? __builtin_nan("") : hh / p.hmax;
+        if (p.samples) p.samples[r] = np;
+        if (p.status && np == 0) atomicAdd(&p.status[1], 1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_window_entropy_c — stage 2 of an integer-count lattice (unweighted nearest tile, naive lat/lon bins).  One wave per
+// workgroup owns rows [blockIdx * rpw, + rpw): the window's counts live in LDS; the first row adds its `window` frames, every
+// later row (stride < window; the host gives rpw = 1 otherwise) subtracts the `stride` frames that leave and adds the
+// `stride` frames that enter — integers, exact in any order.  The epilogue is k_spatial_u_lds's, operation for operation
+// (log2 taken directly where that kernel reads its log2 table: the same ocml values): samples = histogram total,
+// h -= (v / N) * (log2 v - log2 N) in lane order, the normaliser log2(n) if full_norm or N > norm_n, else log2(N)
+// (entropy_utils.py:201-206; one sample gives the reference's 0 / 0), NaN and status[1] += 1 for an empty window.
+// LDS: u32 [n].
+// ------------------------------------------------------------------------------------------
+struct WindowCParams {
+    const int32_t* tiles;        // [T][U]
+    int U, n;
+    double hmax;
+    int norm_n, full_norm;
+    int window, stride, rpw;
+    long R;
+    double* ent;                 // [R]
+    double* weights;             // [R][n] or null
+    int32_t* samples;            // [R] or null
+    int32_t* status;             // [2] or null
+};
+
+__device__ __forceinline__ void window_count(unsigned* cnt, int n, const int32_t* tiles, int U, long fa, long fb, unsigned delta) {
+    const int32_t* q = tiles + fa * (long)U;
+    const long m = (fb - fa) * (long)U;
+    for (long i = lane_id(); i < m; i += WAVE) {
+        const int t = q[i];
+        if ((unsigned)t < (unsigned)n) atomicAdd(&cnt[t], delta);      // -1 = absent
+    }
+}
+
+__global__ __launch_bounds__(64) void k_window_entropy_c(const WindowCParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned* cnt = (unsigned*)smem;
+    const int lane = lane_id();
+    for (int t = lane; t < p.n; t += WAVE) cnt[t] = 0u;
+    __syncthreads();
+    const long r0 = (long)blockIdx.x * p.rpw, r1 = min(p.R, r0 + (long)p.rpw);
+    for (long r = r0; r < r1; ++r) {
+        const long f0 = r * (long)p.stride;
+        if (r == r0) {
+            window_count(cnt, p.n, p.tiles, p.U, f0, f0 + p.window, 1u);
+        } else {
+            window_count(cnt, p.n, p.tiles, p.U, f0 - p.stride, f0, ~0u);                              // - 1 (mod 2^32)
+            window_count(cnt, p.n, p.tiles, p.U, f0 - p.stride + p.window, f0 + p.window, 1u);
+        }
+        __syncthreads();
+        int np = 0;
+        for (int t = lane; t < p.n; t += WAVE) np += (int)cnt[t];
+        np = wave_sum(np);
+        const double tw = (double)np, lgn = np ? log2(tw) : 0.0, inv_tw = 1.0 / tw;
+        double h = 0.0;
+        for (int t = lane; t < p.n; t += WAVE) {
+            const unsigned v = cnt[t];
+            if (v) h -= ((double)v * inv_tw) * (log2((double)v) - lgn);
+            if (p.weights) __builtin_nontemporal_store((double)v, p.weights + r * (long)p.n + t);
+        }
+        h = wave_sum(h);
+        if (lane == 0) {
+            double hmax = p.hmax;
+            if (!(tw > (double)p.norm_n) && !p.full_norm) hmax = -tw * (1.0 / tw) * -lgn;
+            double e = h / hmax;
+            if (np == 0) {
+                e = __builtin_nan("");
+                if (p.status) atomicAdd(&p.status[1], 1);
+            }
+            p.ent[r] = e;
+            if (p.samples) p.samples[r] = np;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace vet
+
+namespace vh {
+
+namespace {
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+bool counts_lattice(const vet_plan* pl, int k) { return !pl->weighted || pl->lat[k].binned; }
+
+template <bool FROM_IDS>
+int launch_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
+                    int stride, double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const int K = (int)pl->lat.size();
+    if (K > 64) return fail(VET_ERR_UNSUPPORTED, "more than 64 lattices in one plan");
+    const long R = (long)vet_window_rows(T, window, stride);
+    const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    // ---- what stage 1 leaves per lattice, and whether this plan can run windowed at all
+    size_t off[64], bytes = pad16(K > 1 ? (size_t)K * R * sizeof(double) : 0);
+    const size_t present_off = bytes;
+    bytes += pad16((size_t)T * sizeof(int32_t));
+    for (int k = 0; k < K; ++k) {
+        const Lattice& L = pl->lat[k];
+        off[k] = bytes;
+        if (counts_lattice(pl, k)) {
+            if ((size_t)L.n * 4 > c->lds_max)
+                return fail(VET_ERR_UNSUPPORTED, "windowed: %d bins do not fit the LDS histogram of a window (at most %zu)", L.n,
+                            c->lds_max / 4);
+            bytes += pad16((size_t)T * U * sizeof(int32_t));
+        } else {
+            int rc = ensure_exact_rows(pl, k, s);
+            if (rc) return rc;
+            if (exact_rows(pl, k).state != 1)
+                return fail(VET_ERR_UNSUPPORTED, "windowed: the exact FP64 weight rows of lattice %d are not on the device "
+                            "(too large for it); the windowed call has no other formulation", k);
+            bytes += pad16((size_t)T * L.n * sizeof(double));
+        }
+    }
+    int rc = ensure_ws(c, bytes);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    int32_t* d_frame_present = (int32_t*)(ws + present_off);
+    double* ent_k = K > 1 ? (double*)ws : d_entropy;
+    // ---- stage 1
+    {
+        const int frames_per_wg = 4;
+        const dim3 grid((unsigned)((T + frames_per_wg - 1) / frames_per_wg)), block(frames_per_wg * vet::WAVE);
+        bool booked = false;
+        for (int k = 0; k < K || !booked; ++k) {
+            if (k < K && !counts_lattice(pl, k)) continue;
+            vet::WindowTilesParams q{};
+            q.src = src; q.U = U; q.T = T;
+            q.nearest = k < K ? pl->lat[k].d_nearest : nullptr;
+            q.tiles = k < K ? (int32_t*)(ws + off[k]) : nullptr;
+            q.present = booked ? nullptr : d_frame_present;
+            q.status = booked ? nullptr : d_status;
+            booked = true;
+            ProfScope ps(c, s, KID_SPATIAL);
+            hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, grid, block, 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int k = 0; k < K; ++k) {
+            if (counts_lattice(pl, k)) continue;
+            rc = exact_frame_rows(pl, k, d_mu, d_mv, d_ids, U, T, (double*)(ws + off[k]), s);
+            if (rc) return rc;
+        }
+    }
+    // ---- stage 2, charged to the k_finalize scope (include/vet.h)
+    for (int k = 0; k < K; ++k) {
+        const Lattice& L = pl->lat[k];
+        ProfScope ps(c, s, KID_FINALIZE);
+        if (counts_lattice(pl, k)) {
+            vet::WindowCParams q{};
+            q.tiles = (const int32_t*)(ws + off[k]); q.U = U; q.n = L.n; q.hmax = L.hmax;
+            q.norm_n = L.norm_n; q.full_norm = (L.binned && pl->weighted) ? 1 : 0;
+            q.window = window; q.stride = stride; q.R = R;
+            // overlapping windows: a run of rows per wave, at least ~8 waves per CU in the launch
+            q.rpw = stride < window ? (int)std::min<long>(64, std::max<long>(1, R / (8L * c->n_cu))) : 1;
+            q.ent = ent_k + (size_t)k * R;
+            q.weights = k == 0 ? d_weights : nullptr; q.samples = k == 0 ? d_samples : nullptr; q.status = k == 0 ? d_status : nullptr;
+            const long grid = (R + q.rpw - 1) / q.rpw;
+            hipLaunchKernelGGL(vet::k_window_entropy_c, dim3((unsigned)grid), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
+        } else {
+            vet::WindowWParams q{};
+            q.hist = (const double*)(ws + off[k]); q.present = d_frame_present; q.n = L.n; q.hmax = L.hmax;
+            q.window = window; q.stride = stride; q.R = R;
+            q.ent = ent_k + (size_t)k * R;
+            q.weights = k == 0 ? d_weights : nullptr; q.samples = k == 0 ? d_samples : nullptr; q.status = k == 0 ? d_status : nullptr;
+            int nw = 4;
+            while (nw > 1 && (size_t)nw * L.n * 8 > 32 * 1024) nw /= 2;
+            const size_t lds = (size_t)nw * L.n * 8;
+            if (lds > c->lds_max) return fail(VET_ERR_UNSUPPORTED, "windowed: lattice of %d tiles does not fit the LDS", L.n);
+            hipLaunchKernelGGL(vet::k_window_entropy_w, dim3((unsigned)((R + nw - 1) / nw)), dim3(nw * vet::WAVE), lds, s, q);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (K > 1) {
+        ProfScope ps(c, s, KID_FINALIZE);
+        hipLaunchKernelGGL(vet::k_finalize, dim3(grid_for(R, 256, c->n_cu)), dim3(256), 0, s, (const double*)ent_k, K, R, d_entropy);
+        HIP_TRY(hipGetLastError());
+    }
+    return VET_OK;
+}
+
+int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
+    int rc = check_run_args(pl, U, T, out);
+    if (rc) return rc;
+    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
+    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
+    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
+    return VET_OK;
+}
+
+}  // namespace
+
+int window_set_attrs(vet_ctx* c) {
+    HIP_TRY(hipFuncSetAttribute((const void*)vet::k_window_entropy_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_max));
+    HIP_TRY(hipFuncSetAttribute((const void*)vet::k_window_entropy_c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_max));
+    return VET_OK;
+}
+
+}  // namespace vh
+
+using namespace vh;
+
+extern "C" {
+
+int64_t vet_window_rows(int n_frames, int window, int stride) {
+    if (n_frames < 1 || window < 1 || stride < 1 || window > n_frames) return VET_ERR_INVALID;
+    return ((int64_t)n_frames - window) / stride + 1;
+}
+
+int vet_spatial_entropy_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
+                                 double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
+    int rc = check_window_args(pl, U, T, window, stride, d_entropy);
+    if (rc) return rc;
+    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_spatial_entropy_windowed_ids");
+    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
+    return launch_windowed<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
+                                  stream ? (hipStream_t)stream : pl->ctx->stream);
+}
+
+int vet_spatial_entropy_windowed_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride,
+                                     double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
+    int rc = check_window_args(pl, U, T, window, stride, d_entropy);
+    if (rc) return rc;
+    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
+    return launch_windowed<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
+                                 stream ? (hipStream_t)stream : pl->ctx->stream);
+}
+
+}  // extern "C"

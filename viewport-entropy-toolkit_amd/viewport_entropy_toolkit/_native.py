@@ -98,6 +98,10 @@ SIGNATURES = {
     "vet_plan_read_nearest": (_I, [_P, _I, _P]),
     "vet_spatial_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_window_rows": (_I64, [_I, _I, _I]),
+    "vet_spatial_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_spatial_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_spatial_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -492,6 +496,26 @@ class Plan:
             _check(self.lib, rc)
         return dict(entropy=ent, assign=assign, weights=weights, present=present, code=rc)
 
+    def spatial_windowed(self, mu=None, mv=None, ids=None, window=None, stride=1, want_weights=False, check=True):
+        """Pooled entropy of sliding frame windows (include/vet.h: vet_spatial_entropy_windowed): row r pools every present
+        sample of frames [r * stride, r * stride + window) into one histogram per lattice.  ``window`` and ``stride`` count
+        frames.  Returns dict(entropy[R], weights[R,n0]|None, samples[R], code), R = (T - window) // stride + 1."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        if window is None:
+            raise ValueError("window (a number of frames) is required")
+        window, stride = int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        ent = np.empty(R, dtype=np.float64)
+        weights = np.empty((R, self.n_tiles[0]), dtype=np.float64) if want_weights else None
+        samples = np.empty(R, dtype=np.int32)
+        rc = self.lib.vet_spatial_entropy_windowed_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                                        _ptr(ent), _ptr(weights), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_EMPTY, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(entropy=ent, weights=weights, samples=samples, code=rc)
+
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -604,6 +628,12 @@ class Plan:
         _check(self.lib, self.lib.vet_spatial_entropy(self.handle, d_mu, d_mv, n_users, n_frames, d_entropy,
                                                       d_assign or None, d_weights or None, d_present or None,
                                                       d_status or None, _stream(stream)))
+
+    def spatial_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                d_entropy: int, d_weights: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
+        _check(self.lib, self.lib.vet_spatial_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
+                                                               int(stride), d_entropy, d_weights or None, d_samples or None,
+                                                               d_status or None, _stream(stream)))
 
     def transition_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, d_entropy: int, d_pairs: int = 0,
                           d_srccount: int = 0, d_common: int = 0, d_status: int = 0, stream=None):

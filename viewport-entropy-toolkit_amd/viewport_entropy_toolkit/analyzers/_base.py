@@ -209,5 +209,18 @@ class _EntropyAnalyzerBase:
         self._logger.info("entropy of %d frames x %d samples in %.3f ms (%.3g samples/s)", n_rows, n_samples,
                           seconds * 1e3, n_samples / max(seconds, 1e-12))
 
+    @staticmethod
+    def _window_args(window, stride, n_frames: int):
+        """(window, stride) as ints; ``ValueError`` unless 1 <= window <= n_frames and stride >= 1."""
+        for name, v in (("window", window), ("stride", stride)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer number of frames (got {v!r})")
+        window, stride = int(window), int(stride)
+        if window < 1 or stride < 1:
+            raise ValueError(f"window and stride must be at least 1 frame (got window={window}, stride={stride})")
+        if window > n_frames:
+            raise ValueError(f"window of {window} frames is longer than the data's {n_frames} frames")
+        return window, stride
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

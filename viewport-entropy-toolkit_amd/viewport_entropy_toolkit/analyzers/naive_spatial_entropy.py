@@ -97,6 +97,35 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         self._heatmap_source = (plan, mu, mv, self.config.tile_width, self.config.tile_height)
         return self._entropy_results
 
+    def compute_windowed_entropy(self, window: int, stride: int = 1) -> pd.DataFrame:
+        """Entropy of the users pooled over sliding windows of frames: row r counts every present sample of frames
+        [r * stride, r * stride + window) in ONE lat/lon cell histogram and takes ``compute_naive_spatial_entropy``'s
+        normalised entropy of it (the normaliser compares the window's samples, not users, with the tile count).
+        ``window`` and ``stride`` count frames, i.e. rows of ``vectors_df``.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with ``time`` / ``time_end`` (of the window's
+        first / last frame), ``entropy`` and ``samples`` (present samples of the window).  Raises ``ValidationError`` before
+        data is loaded, ``ValueError`` for an illegal ``window`` / ``stride``."""
+        if not self._data_cache or self._dense is None:
+            raise ValidationError("No data available. Call process_directory first.")
+        times, mu, mv, _ = self._dense
+        window, stride = self._window_args(window, stride, len(times))
+        try:
+            res = self._naive_plan().spatial_windowed(mu=mu, mv=mv, window=window, stride=stride)
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            if e.code == _native.VET_ERR_EMPTY:
+                raise ValidationError("Empty radial points dictionary")
+            raise
+        first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
+        return pd.DataFrame({
+            "time": np.asarray(times)[first],
+            "time_end": np.asarray(times)[first + window - 1],
+            "entropy": res["entropy"],
+            "samples": res["samples"],
+        })
+
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
     def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
         plan, _, _, tw, th = self._heatmap_source

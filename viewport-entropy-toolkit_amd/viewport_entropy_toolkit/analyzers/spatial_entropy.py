@@ -8,6 +8,7 @@ import logging
 import time
 from typing import Optional
 
+import numpy as np
 import pandas as pd
 
 from .. import _native
@@ -67,6 +68,44 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             "tile_assignments": FrameDictArray(DeviceRows(res["result"], 0, T), lambda row: TileAssignments(names, row)),
         })
         return self._entropy_results
+
+    def compute_windowed_entropy(self, window: int, stride: int = 1) -> pd.DataFrame:
+        """Entropy of the attention pooled over sliding windows of frames: row r puts every present sample of frames
+        [r * stride, r * stride + window) into ONE histogram per lattice and takes the reference's normalised entropy of it
+        (``compute_spatial_entropy`` on a dict holding all those samples), averaged over the lattices — not the mean of the
+        per-frame entropies.  ``window`` and ``stride`` count frames, i.e. rows of ``vectors_df`` (0.1 s each at the
+        reference's sampling): ``window=20, stride=1`` is a 2-second window every frame.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone)
+        with ``time`` / ``time_end`` (of the window's first / last frame), ``entropy``, ``samples`` (present samples of the
+        window) and ``tile_weights`` (lattice 0's pooled weights, the reference's dict-of-``Vector`` shape).
+        Raises ``ValidationError`` before data is loaded, ``ValueError`` for an illegal ``window`` / ``stride``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(window, stride, len(times))
+        try:
+            if kind == "grid":
+                res = self._get_plan().spatial_windowed(mu=a, mv=b, window=window, stride=stride, want_weights=True)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.spatial_windowed(ids=a, window=window, stride=stride, want_weights=True)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            if e.code == _native.VET_ERR_EMPTY:
+                raise ValidationError("Empty vector dictionary")
+            raise
+        tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
+        first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
+        return pd.DataFrame({
+            "time": np.asarray(times)[first],
+            "time_end": np.asarray(times)[first + window - 1],
+            "entropy": res["entropy"],
+            "samples": res["samples"],
+            "tile_weights": FrameDictArray(res["weights"], lambda row: TileWeights(tiles, row)),
+        })
 
     def _frame_present(self):
         return self._present
