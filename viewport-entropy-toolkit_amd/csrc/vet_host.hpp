@@ -8,7 +8,8 @@
 //   vet_window.hip      the sliding-window spatial-entropy kernels (pooled histograms of frame windows) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
-//   vet_hostapi.hip     host-buffer entry points, device-resident results, heatmaps and tilings (no kernels of their own)
+//   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
+//                       for heatmaps and tilings), device-resident results, the heatmap and tiling handles (no kernels)
 // Every kernel header is included by exactly one of them.  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
@@ -115,8 +116,8 @@ struct vet_ctx {
     size_t ws_bytes = 0;
     double* d_log2 = nullptr;      // log2(k), k = 0..4096
     bool attrs_set = false;        // dynamic-LDS limits of the run kernels raised (first plan)
-    // grow-only device staging buffers (no hipMalloc per call): 0-6 host-buffer entry points, (7 unused: batch descriptors live in the blob ring below),
-    // 8 transition scratch, 9 resolve list
+    // grow-only device staging buffers (no hipMalloc per call): 0-6 host-buffer entry points (the SLOT_* names of
+    // vet_hostapi.hip), (7 unused: batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list
     void* pool[12] = {};
     size_t pool_cap[12] = {};
     // descriptor blobs of the batch entry points: a ring of (pinned host, device) buffer pairs, each guarded by an event
