@@ -89,6 +89,10 @@ int vet_synchronize(vet_ctx *ctx);
 int vet_device_pci_bus_id(vet_ctx *ctx, char *buf, int len);
 /* Per-kernel timing with hipEvents on the launch stream (bench.py's roofline leg). */
 int vet_profile_enable(vet_ctx *ctx, int on);
+/* Test switch, not a tuning knob: on != 0 makes the tables that plans of this context build from now on keep every row whole
+ * (cap = stride, no overflow table; vet_plan_table_cap) — the layout of plans where no cap qualifies, so that a test can
+ * compare the two layouts in one process.  Results are bit-identical either way. */
+int vet_test_no_row_cap(vet_ctx *ctx, int on);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -208,11 +212,21 @@ int vet_plan_table_stride(const vet_plan *plan, int lattice);
 /* rows of a weight table = distinct directions up to the lattice's mirror symmetry (0 before the first table exists):
  * a table takes (rows + 1) * stride * 6 bytes */
 int64_t vet_plan_table_rows(const vet_plan *plan);
+/* Row cap of lattice k's own table (0 = no such table): integer tables of one-lattice plans keep `cap` entries per row — the
+ * smallest multiple of 64 that at most 1/32 of the rows exceed — and the tails of the longer rows in one 64-slot block each
+ * of an overflow table, numbered in row order (*overflow_rows of them, nullable; an all-zero row follows the last).
+ * cap == stride; a table whose rows are all whole has no overflow table (also forced by vet_test_no_row_cap). */
+int vet_plan_table_cap(const vet_plan *plan, int lattice, int64_t *overflow_rows);
 int vet_plan_last_formulation(const vet_plan *plan, int lattice);
 int vet_plan_error_bounds(vet_plan *plan, int lattice, double *table_bound, double *sweep_bound);
 /* Parity hooks: read back the device-built tables (synchronous). */
 int vet_plan_read_dirs(vet_plan *plan, double *h_xyz /* [n_dirs*3] rounded Vector xyz */);
 int vet_plan_read_nearest(vet_plan *plan, int lattice, int32_t *h_nearest /* [n_dirs] */);
+/* lattice k's own weight table (every output nullable): mantissas and tiles [(rows+1)*stride], meta words [rows+1]
+ * (entries of the main row in bits 0..11, bit 15 = the row continues in the overflow table, row shift from bit 16);
+ * capped tables only: the overflow table [(overflow_rows+1)*64] and every row's block in it [rows] (0xFFFFFFFF = none) */
+int vet_plan_read_table(vet_plan *plan, int lattice, uint32_t *h_w, uint16_t *h_tile, uint32_t *h_meta, uint32_t *h_ovf_w,
+                        uint16_t *h_ovf_tile, uint32_t *h_ovf_of_row);
 
 /* ---- hot path: SpatialEntropyAnalyzer.compute_entropy ---------------------
  * (analyzers/spatial_entropy.py:107-164 -> entropy_utils.py:147-211, 108-144, 89-106, 41-87)

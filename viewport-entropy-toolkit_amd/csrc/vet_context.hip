@@ -36,6 +36,9 @@ void Tuning::from_environment() {
     t_global = env_flag("VET_T_GLOBAL");
     if (const char* e = getenv("VET_LUT_TIMELINE")) lut_timeline = e;
     no_exact_rows = env_flag("VET_NO_EXACT_ROWS");
+    // (no_row_cap is the one switch that is not read here: the set of environment variables the library reads is pinned, so
+    // vet_test_no_row_cap sets it on a context.  A test switch, not a tuning knob: the uncapped row layout, cap = stride, next
+    // to the capped one in one process)
 }
 
 int collect_profile(vet_ctx* c) {
@@ -210,6 +213,11 @@ int vet_synchronize(vet_ctx* c) {
     return VET_OK;
 }
 
+int vet_test_no_row_cap(vet_ctx* c, int on) {
+    if (!c) return fail(VET_ERR_INVALID, "ctx is NULL");
+    c->tune.no_row_cap = on != 0;         // read by ensure_wtab when a plan of this context builds its table
+    return VET_OK;
+}
 int vet_profile_enable(vet_ctx* c, int on) {
     if (!c) return fail(VET_ERR_INVALID, "ctx is NULL");
     c->profiling = on != 0;

@@ -100,6 +100,8 @@ struct Tuning {
     int no_exact_rows = 0;      // VET_NO_EXACT_ROWS: the weights pass never builds the exact weight rows (as if they did not fit
                                 // the device): the precise sweep in weights-only mode serves — the fallback's test switch
                                 // (include/vet.h; test_fp64_formulation.py, test_hip_shapes.py)
+    int no_row_cap = 0;         // vet_test_no_row_cap (no environment variable): one-lattice tables keep cap = stride (every row whole, no side table) — the
+                                // layout of plans where no cap qualifies; so a test can compare the two layouts (test_row_cap.py)
     void from_environment();
 };
 
@@ -158,6 +160,12 @@ struct Lattice {
     int markers = 0;               // marker entries of the FP table (k_wtab): frames they decide go to the precise sweep
     int last_form = -1;            // formulation of the last weighted call (parity / bench introspection)
     int stride = 0;                // 0 = not built, -1 = not usable (too large)
+    // capped rows (vet_layout.hpp): stride == cap < the longest row; the longer rows' tails live in the side table
+    bool capped = false;
+    int n_ovf = 0;                 // rows with a block in the side table
+    uint32_t* d_ovf_w = nullptr;   // [n_ovf+1][ROW_BLOCK] (the last row all zero)
+    uint16_t* d_ovf_i = nullptr;   // [n_ovf+1][ROW_BLOCK]
+    uint32_t* d_ovf_of_row = nullptr;  // [n_rows] block of the row in the side table, NO_OVERFLOW = none
     int gs_log2 = 4;               // lanes per gather group (log2); fixed when the table is built
     bool interleaved = false;      // well-filled row blocks are dealt by LDS bank class (k_wtab)
     bool binned = false;           // caller-supplied direction -> bin table (naive lat/lon tiling)

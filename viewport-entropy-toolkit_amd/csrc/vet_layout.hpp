@@ -17,6 +17,23 @@ constexpr uint32_t ROW_MASK = (1u << ROW_BITS) - 1;
 constexpr unsigned DEDUP_MAX_DIRS = (1u << ROW_BITS) - 1;
 constexpr int DEDUP_MIN_USERS = 128;                     // frames of fewer users run the table kernel without the set (LutParams)
 
+// Capped rows (ensure_wtab; integer one-lattice tables with 16-lane rows).  Main rows are `cap` slots = cap / ROW_BLOCK whole
+// blocks, which the table kernel walks with a fixed, unrolled trip count; the few rows (at most 1 in 32) that are longer keep
+// their entries beyond `cap` in one ROW_BLOCK-slot block of a side table, found through ovf_of_row[row] by the rows whose meta
+// word has META_OVERFLOW set (the length of a capped row is at most cap <= 192: bit 15 of the length field is free, and the
+// record of k_dirrec carries it).  The fixed-trip kernels exist for 1..MAX_CAP_BLOCKS blocks.
+constexpr int ROW_BLOCK = 64;
+constexpr int MAX_CAP_BLOCKS = 3;
+constexpr uint32_t META_OVERFLOW = 1u << 15;
+constexpr uint32_t NO_OVERFLOW = 0xFFFFFFFFu;
+// entries of a frame's overflow list (LDS): with the set of distinct rows at most one per (overflow row, mirrored) — fewer than
+// DEDUP_MIN_USERS where a small video of a batch runs without the set —, otherwise one per user; never more than the chunk
+__host__ __device__ __forceinline__ int lut_ovf_slots(int UC, int n_ovf, bool dedup) {
+    if (n_ovf <= 0) return 0;
+    const int most = dedup ? (2 * n_ovf > DEDUP_MIN_USERS ? 2 * n_ovf : DEDUP_MIN_USERS) : UC;
+    return most < UC ? most : UC;
+}
+
 // ------------------------------------------------------------------------------------------
 // Fused histogram layout.  The plan's K lattices (analyzers/spatial_entropy.py:142-156 loops over
 // them per frame) share ONE histogram of N = Nr + 4K slots, Nr = 2 * (Hs + K), Hs = sum_k floor(n_k / 2):

@@ -179,9 +179,46 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(VET_ERR_DEVICE, "k_wtab<count> failed: %s", hipGetErrorString(e));
     // rows start on 128-byte lines (u16 tile rows) / 256 bytes (u32 weight rows); whole 64-entry blocks
-    const int stride = ((longest > 0 ? longest : 1) + 63) / 64 * 64;
+    int stride = ((longest > 0 ? longest : 1) + 63) / 64 * 64;
     const size_t rows = (size_t)R + 1;            // one extra, all-zero row (index n_rows) for the gather's idle lanes
-    const size_t bytes = rows * stride * 6 + rows * 4;
+    // Row cap (vet_layout.hpp): integer tables of one-lattice plans with 16-lane, class-dealt rows.  cap = the smallest
+    // multiple of the block such that at most 1/32 of the rows are longer, from the exact entry counts of a fill pass that
+    // stores nothing.  It is used where the fixed-trip walk has nothing to skip and the side table one block per row:
+    // every row reaches the last block below cap, no row exceeds cap by more than a block, cap <= MAX_CAP_BLOCKS blocks.
+    // Otherwise (and under vet_test_no_row_cap) cap = stride: the layout without a side table.
+    int cap = stride, n_ovf = 0;
+    std::vector<uint32_t> ovf_of_row;
+    if (!L.fp_table && pl->lat.size() == 1 && stride > vet::ROW_BLOCK && 4 * longest >= 3 * 64 && !c->tune.no_row_cap) {
+        DevBuf d_len;
+        HIP_TRY(d_len.alloc((size_t)R * sizeof(int)));
+        p.row_len = (int*)d_len.p; p.gs_log2 = -1;
+        {
+            ProfScope ps(c, s, KID_WTAB);
+            hipLaunchKernelGGL(vet::k_wtab<true>, dim3(blocks), dim3(256), 0, s, p);
+        }
+        std::vector<int> len((size_t)R);
+        HIP_TRY(hipMemcpyAsync(len.data(), d_len.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        p.row_len = nullptr;
+        int shortest = stride, most = 0;
+        for (int v : len) { shortest = std::min(shortest, v); most = std::max(most, v); }
+        for (int cnd = vet::ROW_BLOCK; cnd < stride && cnd <= vet::MAX_CAP_BLOCKS * vet::ROW_BLOCK; cnd += vet::ROW_BLOCK) {
+            long longer = 0;
+            for (int v : len) longer += v > cnd ? 1 : 0;
+            if (longer * 32 > R) continue;
+            if (shortest > cnd - vet::ROW_BLOCK && most <= cnd + vet::ROW_BLOCK) {
+                cap = cnd;
+                ovf_of_row.assign((size_t)R, vet::NO_OVERFLOW);
+                for (long r = 0; r < R; ++r)
+                    if (len[(size_t)r] > cap) ovf_of_row[(size_t)r] = (uint32_t)n_ovf++;      // densely numbered in row order
+            }
+            break;
+        }
+    }
+    const bool capped = cap < stride;
+    stride = cap;
+    const size_t ovf_rows = capped ? (size_t)n_ovf + 1 : 0;
+    const size_t bytes = rows * stride * 6 + rows * 4 + ovf_rows * vet::ROW_BLOCK * 6 + (capped ? (size_t)R * 4 : 0);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = kMaxTableBytes;
     // (the gather addresses entries with 32-bit offsets: fewer than 2^32 of them)
@@ -191,11 +228,17 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
         if (L.d_tab_w) { (void)hipFree(L.d_tab_w); L.d_tab_w = nullptr; }
         if (L.d_tab_i) { (void)hipFree(L.d_tab_i); L.d_tab_i = nullptr; }
         if (L.d_tab_meta) { (void)hipFree(L.d_tab_meta); L.d_tab_meta = nullptr; }
+        if (L.d_ovf_w) { (void)hipFree(L.d_ovf_w); L.d_ovf_w = nullptr; }
+        if (L.d_ovf_i) { (void)hipFree(L.d_ovf_i); L.d_ovf_i = nullptr; }
+        if (L.d_ovf_of_row) { (void)hipFree(L.d_ovf_of_row); L.d_ovf_of_row = nullptr; }
     };
     drop();
     if (hipMalloc((void**)&L.d_tab_w, rows * stride * 4) != hipSuccess ||
         hipMalloc((void**)&L.d_tab_i, rows * stride * 2) != hipSuccess ||
-        hipMalloc((void**)&L.d_tab_meta, rows * 4) != hipSuccess) {
+        hipMalloc((void**)&L.d_tab_meta, rows * 4) != hipSuccess ||
+        (capped && (hipMalloc((void**)&L.d_ovf_w, ovf_rows * vet::ROW_BLOCK * 4) != hipSuccess ||
+                    hipMalloc((void**)&L.d_ovf_i, ovf_rows * vet::ROW_BLOCK * 2) != hipSuccess ||
+                    hipMalloc((void**)&L.d_ovf_of_row, (size_t)R * 4) != hipSuccess))) {
         (void)hipGetLastError();                  // out of memory is not sticky: the sweep still works
         drop();
         L.stride = -1;
@@ -210,6 +253,10 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     while (L.gs_log2 < 4 && (4 << L.gs_log2) < longest) ++L.gs_log2;
     // 16-lane rows with at least one block that is 3/4 full get the class-dealt layout (k_wtab)
     L.interleaved = L.gs_log2 == 4 && stride % 64 == 0 && 4 * longest >= 3 * 64;
+    if (capped) {
+        HIP_TRY(hipMemcpyAsync(L.d_ovf_of_row, ovf_of_row.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+        p.cap = cap; p.ovf_of_row = L.d_ovf_of_row; p.ow = L.d_ovf_w; p.oi = L.d_ovf_i; p.n_ovf = n_ovf;
+    }
     p.stride = stride; p.w = L.d_tab_w; p.idx = L.d_tab_i; p.meta = L.d_tab_meta; p.maxcount = nullptr;
     p.markers = L.fp_table ? d_max + 1 : nullptr;
     p.gs_log2 = L.interleaved ? L.gs_log2 : -1;
@@ -231,6 +278,7 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     guard.armed = false;
     L.markers = markers;
+    L.capped = capped; L.n_ovf = capped ? n_ovf : 0;
     L.stride = stride;
     return VET_OK;
 }
@@ -592,6 +640,9 @@ int vet_plan_destroy(vet_plan* pl) {
         if (L.d_tab_w) (void)hipFree(L.d_tab_w);
         if (L.d_tab_i) (void)hipFree(L.d_tab_i);
         if (L.d_tab_meta) (void)hipFree(L.d_tab_meta);
+        if (L.d_ovf_w) (void)hipFree(L.d_ovf_w);
+        if (L.d_ovf_i) (void)hipFree(L.d_ovf_i);
+        if (L.d_ovf_of_row) (void)hipFree(L.d_ovf_of_row);
         if (L.d_row_s) (void)hipFree(L.d_row_s);
         if (L.d_row_e) (void)hipFree(L.d_row_e);
     }
@@ -634,6 +685,31 @@ int vet_plan_table_stride(const vet_plan* pl, int k) {
     // plans on the fused table (one row per direction over all lattices) never build the per-lattice ones
     if (pl->lat[k].stride == 0 && pl->fused.state == 1) return pl->fused.stride;
     return pl->lat[k].stride;
+}
+
+int vet_plan_table_cap(const vet_plan* pl, int k, int64_t* overflow_rows) {
+    if (overflow_rows) *overflow_rows = 0;
+    if (!pl || k < 0 || k >= (int)pl->lat.size() || pl->lat[k].stride <= 0) return 0;
+    if (overflow_rows) *overflow_rows = pl->lat[k].n_ovf;
+    return pl->lat[k].stride;            // capped rows: stride == cap; otherwise every row is whole
+}
+
+int vet_plan_read_table(vet_plan* pl, int k, uint32_t* h_w, uint16_t* h_tile, uint32_t* h_meta, uint32_t* h_ovf_w,
+                        uint16_t* h_ovf_tile, uint32_t* h_ovf_of_row) {
+    if (!pl) return fail(VET_ERR_INVALID, "plan is NULL");
+    if (k < 0 || k >= (int)pl->lat.size()) return fail(VET_ERR_INVALID, "lattice index %d out of range", k);
+    const vh::Lattice& L = pl->lat[k];
+    if (L.stride <= 0) return fail(VET_ERR_INVALID, "lattice %d has no table of its own", k);
+    HIP_TRY(hipSetDevice(pl->ctx->device));
+    const size_t rows = (size_t)pl->n_rows + 1, ovf = (size_t)L.n_ovf + 1;
+    if (h_w) HIP_TRY(hipMemcpy(h_w, L.d_tab_w, rows * L.stride * 4, hipMemcpyDeviceToHost));
+    if (h_tile) HIP_TRY(hipMemcpy(h_tile, L.d_tab_i, rows * L.stride * 2, hipMemcpyDeviceToHost));
+    if (h_meta) HIP_TRY(hipMemcpy(h_meta, L.d_tab_meta, rows * 4, hipMemcpyDeviceToHost));
+    if ((h_ovf_w || h_ovf_tile || h_ovf_of_row) && !L.capped) return fail(VET_ERR_INVALID, "lattice %d has no overflow table", k);
+    if (h_ovf_w) HIP_TRY(hipMemcpy(h_ovf_w, L.d_ovf_w, ovf * vet::ROW_BLOCK * 4, hipMemcpyDeviceToHost));
+    if (h_ovf_tile) HIP_TRY(hipMemcpy(h_ovf_tile, L.d_ovf_i, ovf * vet::ROW_BLOCK * 2, hipMemcpyDeviceToHost));
+    if (h_ovf_of_row) HIP_TRY(hipMemcpy(h_ovf_of_row, L.d_ovf_of_row, (size_t)pl->n_rows * 4, hipMemcpyDeviceToHost));
+    return VET_OK;
 }
 
 // vector_angle_distance / find_angular_distances (utilities/entropy_utils.py:41-87): synchronous, host buffers

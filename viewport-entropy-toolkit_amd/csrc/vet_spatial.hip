@@ -125,8 +125,17 @@ const void* lut_kernel_fused(bool il, bool occ8, bool dedup, bool narrow = false
     return nullptr;
 }
 
+// nb > 0: the fixed-trip kernels of capped rows of nb blocks (one class-dealt integer lattice, 8 workgroups per CU)
 template <bool FROM_IDS>
-const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false) {
+const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false, int nb = 0) {
+    if (nb) {
+        if (!il || !occ8 || fpt) return nullptr;
+#define VET_PICKC(N, D) if (nb == N && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, D, false, false, N>
+        VET_PICKC(1, false); VET_PICKC(1, true); VET_PICKC(2, false); VET_PICKC(2, true); VET_PICKC(3, false); VET_PICKC(3, true);
+#undef VET_PICKC
+        static_assert(vet::MAX_CAP_BLOCKS == 3, "one fixed-trip kernel per block count");
+        return nullptr;
+    }
     if (fpt) {      // FP table: 7 workgroups per CU (FP64 scale registers)
 #define VET_PICKF(I, D) if (il == I && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, I, false, D, true>
         VET_PICKF(false, false); VET_PICKF(true, false); VET_PICKF(false, true); VET_PICKF(true, true);
@@ -308,9 +317,14 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
         q.lat[k].gs_log2 = L.gs_log2; q.lat[k].interleaved = L.interleaved ? 1 : 0;
         q.lat[k].n = L.n; q.lat[k].hmax = L.hmax;
         q.lat[k].zrow = (uint32_t)pl->n_rows;
+        q.lat[k].ovf_w = L.d_ovf_w; q.lat[k].ovf_i = L.d_ovf_i; q.lat[k].ovf_of_row = L.d_ovf_of_row; q.lat[k].n_ovf = L.n_ovf;
         q.n_sum += L.n;
         il = il || L.interleaved;
     }
+    // capped rows (ensure_wtab: one-lattice plans only): the fixed-trip kernel of the row's block count
+    const Lattice& L0 = pl->lat[lat_idx[0]];
+    const int nb = L0.capped ? L0.stride / vet::ROW_BLOCK : 0;
+    if (nb && (K != 1 || lat_idx[0] != 0)) return fail(VET_ERR_UNSUPPORTED, "capped rows in a launch of several lattices");
     q.entropy = d_entropy; q.assign = d_assign; q.weights = d_weights; q.present = d_present;
     q.status = d_status;
     const bool dedup = dedup_lattices(pl, d_videos ? batch_max_users : U);
@@ -324,7 +338,8 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
         q.UC = U < 2048 ? U : 2048;
         int fpw = lut_frames_per_wg(U, T, c->n_cu, q.n_sum);
         for (;; fpw /= 2) {
-            lds = vet::lut_lds_bytes(U, q.UC, fpw, q.n_sum, dedup, d_resolve != nullptr, fpt ? threads / 64 : 1, q.sort_words);
+            lds = vet::lut_lds_bytes(U, q.UC, fpw, q.n_sum, dedup, d_resolve != nullptr, fpt ? threads / 64 : 1, q.sort_words,
+                                     nb ? vet::lut_ovf_slots(q.UC, L0.n_ovf, dedup) : 0);
             if (lds <= c->lds_max || fpw == 1) break;
         }
         if (lds > c->lds_max) return VET_OK;      // not launched: caller falls back to the sweep
@@ -337,7 +352,9 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     ProfScope ps(c, s, KID_SPATIAL);
     void* args[] = {(void*)&q};
     // 2 rows in flight per lane group measured best (4 and 8 were tried, profiles/r01/v3_*)
-    HIP_TRY(hipLaunchKernel(lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt), dim3((unsigned)blocks), dim3(threads), args, lds, s));
+    const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb);
+    if (!fn) return fail(VET_ERR_UNSUPPORTED, "no table kernel for this launch");
+    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(threads), args, lds, s));
     HIP_TRY(hipGetLastError());
     *launched = true;
     return VET_OK;
@@ -426,12 +443,12 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
 
 // LDS bytes and frames per workgroup of one video of a batch (0 = does not fit)
 size_t batch_video_geometry(const vet_ctx* c, int U, long total_frames, int n_sum, bool dedup, int* fpw_out, int* uc_out,
-                            int priv = 1, int sort_words = 0) {
+                            int priv = 1, int sort_words = 0, int n_ovf = 0) {
     const int UC = U < 2048 ? U : 2048;
     int fpw = lut_frames_per_wg(U, total_frames, c->n_cu, n_sum);
     size_t lds = 0;
     for (;; fpw /= 2) {
-        lds = vet::lut_lds_bytes(U, UC, fpw, n_sum, dedup, false, priv, sort_words);
+        lds = vet::lut_lds_bytes(U, UC, fpw, n_sum, dedup, false, priv, sort_words, vet::lut_ovf_slots(UC, n_ovf, dedup));
         if (lds <= c->lds_max || fpw == 1) break;
     }
     *fpw_out = fpw; *uc_out = UC;
@@ -823,6 +840,10 @@ int spatial_set_attrs(vet_ctx* c) {
         }
         ATTR_TRY(lut_kernel<false>(v & 1, v & 2, v & 4), c->lds_max);
         ATTR_TRY(lut_kernel<true>(v & 1, v & 2, v & 4), c->lds_max);
+        if (v < 2 * vet::MAX_CAP_BLOCKS) {      // the fixed-trip kernels of capped rows
+            ATTR_TRY(lut_kernel<false>(true, true, v & 1, false, 1 + v / 2), c->lds_max);
+            ATTR_TRY(lut_kernel<true>(true, true, v & 1, false, 1 + v / 2), c->lds_max);
+        }
         if (!(v & 2)) {
             ATTR_TRY(lut_kernel<false>(v & 1, false, v & 4, true), c->lds_max);
             ATTR_TRY(lut_kernel<true>(v & 1, false, v & 4, true), c->lds_max);
@@ -1076,7 +1097,8 @@ int vet_spatial_entropy_batch(vet_plan* pl, int n_videos, const vet_video* video
             d.mu = x.d_mu; d.mv = x.d_mv; d.U = x.n_users; d.T = x.n_frames;
             d.entropy = x.d_entropy; d.assign = x.d_assign; d.present = x.d_present;
             const size_t lds = batch_video_geometry(c, d.U, total_frames, n_sum, dedup, &d.FPW, &d.UC, form0 == F_FTABLE ? 4 : 1,
-                                                    (form0 == F_FTABLE && dedup && 2 * pl->n_rows <= 65536) ? (int)((2 * pl->n_rows + 31) / 32) : 0);
+                                                    (form0 == F_FTABLE && dedup && 2 * pl->n_rows <= 65536) ? (int)((2 * pl->n_rows + 31) / 32) : 0,
+                                                    pl->lat[0].capped ? pl->lat[0].n_ovf : 0);
             if (lds == 0) table = false;
             d.block0 = block; d.pad_ = 0;
             block += (d.T + d.FPW - 1) / d.FPW;

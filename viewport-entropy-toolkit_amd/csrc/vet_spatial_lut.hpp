@@ -70,7 +70,10 @@ __device__ __forceinline__ void lds_add_u64(uint32_t lds_byte_address, unsigned 
 // marked / bit0: FP tables with marker entries (vet_weight_table.hpp) — bitmap of the frame's tiles (bit0 = the lattice's
 // first bit) that were hit by a marker; null when the launch's tables hold none.
 // GSL_IL: lanes per row (log2) of the class-dealt layout this walk is compiled for (16-lane rows; 8-lane fused rows)
-template <int UN, bool INTERLEAVED, bool DEDUP, bool FPT, int GSL_IL = 4>
+// NB > 0: capped integer rows of exactly NB blocks of ROW_BLOCK slots (vet_layout.hpp), 16 lanes per row: every row is walked
+// over all NB blocks, unrolled — no length, no trip count to agree on, no redirect (ensure_wtab caps only where every row
+// reaches its last block); fmeta is read for the row shift alone.  The side table's rows are walked the same way with NB = 1.
+template <int UN, bool INTERLEAVED, bool DEDUP, bool FPT, int GSL_IL = 4, int NB = 0>
 __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t* fmeta, int nu,
                                           unsigned long long* hrow, int n,
                                           const uint32_t* __restrict__ tab_w, const uint16_t* __restrict__ tab_i,
@@ -81,6 +84,51 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
     // unconditional ds_add_u64 of entry * (multiplicity << row shift): padding slots and idle lanes
     // (which walk the all-zero row) add 0 to distinct tiles — no predicates around the adds.
     const int NW = blockDim.x >> 6, lane = lane_id(), wv = wave_id();
+    if constexpr (NB > 0) {
+        static_assert(!FPT && INTERLEAVED && GSL_IL == 4, "capped rows: integer tables with 16-lane rows");
+        constexpr int UPW = WAVE >> 4;
+        // (the lane's constants of the walk are formed here, behind an opaque copy of the lane: formed at kernel entry, as the
+        // compiler would, they are spilled across the prologue, whose sample batches need every register of the 64)
+        int lane_here = lane;
+        asm volatile("" : "+v"(lane_here));
+        const int sub = lane_here >> 4, sl = lane_here & 15, step = NW * UPW;
+        for (int j0 = wv * UPW; j0 < nu; j0 += UN * step) {
+            uint32_t row[UN], mult[UN], hb32[UN];
+            int sgn[UN];
+#pragma unroll
+            for (int k = 0; k < UN; ++k) {
+                const int j = j0 + k * step + sub;
+                const bool on = j < nu;
+                const uint32_t pk = on ? frows[j] : 0u, m = on ? fmeta[j] : 0u;
+                const uint32_t key = DEDUP ? pk >> 12 : pk;
+                const bool flip = ((DEDUP ? key >> ROW_BITS : key >> 31) & 1u) != 0u;
+                const uint32_t rid = DEDUP ? key & ROW_MASK : key & 0x7FFFFFFFu;
+                row[k] = (on ? rid * (uint32_t)(NB * ROW_BLOCK) : zero_row) + (uint32_t)(4 * sl);
+                const uint32_t cnt = DEDUP ? pk & 0xFFFu : (on ? 1u : 0u);
+                mult[k] = cnt << ((m >> 16) & 0x1Fu);
+                sgn[k] = flip ? -8 : 8;
+                hb32[k] = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)((char*)hrow + (flip ? (n - 1) * 8 : 0));
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                uint4 w[UN];
+                uint2 tp[UN];
+#pragma unroll
+                for (int k = 0; k < UN; ++k) {
+                    w[k] = *(const uint4*)(tab_w + row[k] + b * ROW_BLOCK);
+                    tp[k] = *(const uint2*)(tab_i + row[k] + b * ROW_BLOCK);
+                }
+#pragma unroll
+                for (int k = 0; k < UN; ++k) {
+                    lds_add_u64(lds_slot<false>(tp[k].x, sgn[k], hb32[k]), (unsigned long long)w[k].x * mult[k]);
+                    lds_add_u64(lds_slot<true>(tp[k].x, sgn[k], hb32[k]), (unsigned long long)w[k].y * mult[k]);
+                    lds_add_u64(lds_slot<false>(tp[k].y, sgn[k], hb32[k]), (unsigned long long)w[k].z * mult[k]);
+                    lds_add_u64(lds_slot<true>(tp[k].y, sgn[k], hb32[k]), (unsigned long long)w[k].w * mult[k]);
+                }
+            }
+        }
+        return;
+    }
     const int gs_log2 = INTERLEAVED ? GSL_IL : gs_log2_rt;  // class-dealt rows: the layout's own group size (ensure_wtab / ensure_fused)
     const int GS = 1 << gs_log2, UPW = WAVE >> gs_log2;
     const int sub = lane >> gs_log2, sl = lane & (GS - 1);
@@ -175,6 +223,8 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
 //       rows u32 [FPW][UC]     the frame's distinct rows (slot words), or one row per present user
 //       meta u32 [FPW][UC]     their meta words in the lattice being gathered
 //       cnt  i32 [FPW] rows in the chunk, [FPW] users present in the frame
+//       capped rows (NB > 0) with a side table:  i32 [FPW] entries of the frame's overflow list, u32 [FPW][OC] their slot
+//       words (the side table's row in place of the row), u32 [FPW][OC] their meta words;  OC = lut_ovf_slots
 // Prologue: sample -> direction id -> canonical row (alias: directions with the same Vector — the pole
 // row, the -180 / -90 remaps — share one row) -> set insert.  Users looking in exactly the same
 // direction cost one row walk with a multiplicity instead of one each: 1024 users are ~710 distinct
@@ -190,6 +240,11 @@ struct LutLattice {
     int stride, gs_log2, n, interleaved;
     double hmax;
     uint32_t zrow;                // index of the table's all-zero row (the number of its rows in use)
+    // capped rows (k_spatial_lut<NB > 0>; vet_layout.hpp): the side table, its rows in use (row n_ovf all zero), row -> its block
+    const uint32_t* ovf_w;
+    const uint16_t* ovf_i;
+    const uint32_t* ovf_of_row;
+    int n_ovf;
 };
 
 // One video of a batched launch (vet_spatial_entropy_batch): many short videos share one grid,
@@ -351,13 +406,13 @@ __host__ __device__ __forceinline__ int lut_marked_words(int n_sum) { return (n_
 // sort_words: FP tables put every frame's row list into a canonical order through a bitmap over (row, mirrored); the bitmap
 // (+ 256 scan words) lives in the histogram / set region too (the histograms are cleared after the sort)
 __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW, int n_sum, bool dedup, bool marked = false,
-                                                         int priv = 1, int sort_words = 0) {
+                                                         int priv = 1, int sort_words = 0, int ovf_slots = 0) {
     const size_t hist = (size_t)FPW * n_sum * 8 * priv, hash = dedup ? (size_t)FPW * lut_hash_slots(UC) * 4 : 0;
     const size_t srt = sort_words ? ((size_t)sort_words + 256) * 4 : 0;
     size_t a = (dedup && U <= UC) ? (hist > hash ? hist : hash) : hist + hash;
     if (dedup && U <= UC && srt > a) a = srt;
     return ((a + 15) & ~(size_t)15) + (size_t)FPW * UC * 8 + (size_t)2 * FPW * 4 + 64 +
-           (marked ? (size_t)FPW * lut_marked_words(n_sum) * 4 : 0);
+           (marked ? (size_t)FPW * lut_marked_words(n_sum) * 4 : 0) + (ovf_slots ? (size_t)FPW * (4 + (size_t)ovf_slots * 8) : 0);
 }
 
 // All K lattices of the plan in one launch: the samples are read once, every row is gathered into K
@@ -371,7 +426,9 @@ __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW,
 // FUSED: the table is the plan's fused one (FusedLayout above): one row per distinct direction over all lattices,
 // histogram slots instead of tiles, the exact total of every lattice in its total slots; the epilogue reads the
 // lattices back out of the fused histogram.
-template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false>
+// NB > 0: the launch's one lattice has capped rows of NB blocks (walk_rows): the main walk has a fixed trip count, and the rows
+// that continue in the side table are listed per frame while the row list is made and walked once more, against the side table.
+template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0>
 __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(const LutParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // the video this workgroup works on: the launch's only one, or one of a batch
@@ -410,6 +467,23 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     int* cnt_frame = cnt_chunk + FPW;                                            // [FPW]
     const int MW = lut_marked_words(p.n_sum);
     uint32_t* marked = (FPT && p.resolve) ? (uint32_t*)(cnt_frame + FPW) : nullptr;   // [FPW][MW]
+    // capped rows: the overflow list behind the counters — i32 [FPW] entries, u32 [FPW][OC] slot words, u32 [FPW][OC] meta
+    // words (formed where they are used: the kernel is short of scalar registers)
+    int* const ovf_cnt = cnt_frame + FPW;
+    auto ovf_slots = [&]() { return NB ? lut_ovf_slots(UC, p.lat[0].n_ovf, DEDUP) : 0; };
+    // a listed row whose meta word says so continues in the side table: its slot word with the side table's row in place of
+    // the row (multiplicity and mirror flag kept) and its meta word (the shift is the row's) join the frame's overflow list
+    auto note_overflow = [&](int fl, uint32_t word, uint32_t m) {
+        if (!(m & META_OVERFLOW)) return;
+        const int OC = ovf_slots();
+        uint32_t* ovf_rows = (uint32_t*)(ovf_cnt + FPW);
+        const uint32_t o = p.lat[0].ovf_of_row[DEDUP ? (word >> 12) & ROW_MASK : word & 0x7FFFFFFFu];
+        const int pos = atomicAdd(&ovf_cnt[fl], 1);
+        if (pos < OC) {
+            ovf_rows[(size_t)fl * OC + pos] = DEDUP ? (word & ~(ROW_MASK << 12)) | (o << 12) : (word & 0x80000000u) | o;
+            ovf_rows[(size_t)(FPW + fl) * OC + pos] = m;
+        }
+    };
     const int NW = blockDim.x >> 6;
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const long f0 = blk * FPW;
@@ -447,7 +521,10 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     for (int u0 = 0; u0 < U; u0 += UC) {
         const int uc = min(UC, U - u0);
         __syncthreads();
-        for (int i = tid; i < FPW; i += blockDim.x) cnt_chunk[i] = 0;
+        for (int i = tid; i < FPW; i += blockDim.x) {
+            cnt_chunk[i] = 0;
+            if (NB && p.lat[0].n_ovf) ovf_cnt[i] = 0;
+        }
         if (merge)
             for (int i = tid; i < FPW * HS; i += blockDim.x) hash[i] = EMPTY_KEY;
         __syncthreads();
@@ -574,7 +651,11 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             if (merge)
                 for (int i = tid; i < nf * UC; i += blockDim.x) {
                     const int fl = i / UC, j = i - fl * UC;
-                    if (j < cnt_chunk[fl]) rows[i] = hash[(size_t)fl * HS + rows[i]];
+                    if (j < cnt_chunk[fl]) {
+                        const uint32_t word = hash[(size_t)fl * HS + rows[i]];
+                        rows[i] = word;
+                        if (NB) note_overflow(fl, word, meta[i]);   // (the record's meta word: the launch's lattice is the plan's first)
+                    }
                 }
             if (overlay && !FPT) {
                 __syncthreads();
@@ -679,10 +760,25 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                     const int fl = i / UC, j = i - fl * UC;
                     if (j < cnt_chunk[fl]) meta[i] = L.tab_meta[DEDUP ? (rows[i] >> 12) & ROW_MASK : rows[i] & 0x7FFFFFFFu];
                 }
+            if (NB && !merge)                                       // one list entry per user: the overflow list is made here
+                for (int i = tid; i < nf * UC; i += blockDim.x) {
+                    const int fl = i / UC, j = i - fl * UC;
+                    if (j < cnt_chunk[fl]) note_overflow(fl, rows[i], meta[i]);
+                }
             __syncthreads();
             constexpr int GSL_IL = (FUSED && UN == 2) ? 3 : 4;      // the narrow fused kernel walks 8-lane rows
             for (int fl = 0; fl < nf; ++fl)
-                if (IL && L.interleaved)
+                if constexpr (NB > 0) {
+                    unsigned long long* hrow = hist + (size_t)fl * p.n_sum + hoff;
+                    walk_rows<UN, true, DEDUP, false, 4, NB>(rows + (size_t)fl * UC, meta + (size_t)fl * UC, cnt_chunk[fl], hrow, L.n,
+                                                             L.tab_w, L.tab_i, L.stride, 4, L.zrow * (uint32_t)(NB * ROW_BLOCK));
+                    if (const int OC = ovf_slots()) {
+                        const uint32_t* ovf_rows = (const uint32_t*)(ovf_cnt + FPW);
+                        walk_rows<UN, true, DEDUP, false, 4, 1>(ovf_rows + (size_t)fl * OC, ovf_rows + (size_t)(FPW + fl) * OC,
+                                                                min(ovf_cnt[fl], OC), hrow, L.n, L.ovf_w, L.ovf_i, ROW_BLOCK, 4,
+                                                                (uint32_t)L.n_ovf * (uint32_t)ROW_BLOCK);
+                    }
+                } else if (IL && L.interleaved)
                     walk_rows<UN, true, DEDUP, FPT, GSL_IL>(rows + (size_t)fl * UC, meta + (size_t)fl * UC, cnt_chunk[fl],
                                                hist + ((size_t)fl * PRIV + (FPT ? wv : 0)) * p.n_sum + hoff, L.n, L.tab_w, L.tab_i, L.stride, L.gs_log2,
                                                L.zrow * (uint32_t)L.stride, marked ? marked + (size_t)fl * MW : nullptr, hoff);

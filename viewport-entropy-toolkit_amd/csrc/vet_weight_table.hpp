@@ -27,7 +27,8 @@ namespace vet {
 // for a frame made of rows i with multiplicities c_i, hence  |dH| / H <= max_d 36.5 q_d k_d / (S_d H_d).
 // Plans where that bound exceeds 1e-7 (rows with a single tile in the FoV, weights spanning many
 // orders of magnitude) take the FP64 formulation (k_spatial_w<PRECISE>) instead.
-// k_wtab<false> finds the longest row (conservative cone test), k_wtab<true> fills the rows.
+// k_wtab<false> finds the longest row (conservative cone test), k_wtab<true> fills the rows (without tables: counts
+// every row's entries exactly as the fill stores them, for the row cap of ensure_wtab).
 // One wave per direction; lane = tile.
 // ------------------------------------------------------------------------------------------
 // (TAB_X, the histogram unit 2^-(32+TAB_X), and MARKER_BITS live in vet_layout.hpp)
@@ -164,6 +165,15 @@ struct WtabParams {
     int Hs, N;
     int* maxcount;
     int gs_log2;        // >= 0: well-filled blocks dealt over the 2^gs_log2 lanes of a gather group
+    // capped rows (vet_layout.hpp; cap > 0: stride == cap): row d keeps its entries beyond cap in block ovf_of_row[d] of the
+    // side table ow / oi (ROW_BLOCK slots per row, zero padded, row n_ovf all zero); the host numbered the overflow rows from
+    // row_len.  row_len != null (fill pass without tables, w == null): only the exact entries per row are written
+    int cap;
+    const uint32_t* ovf_of_row;
+    uint32_t* ow;
+    uint16_t* oi;
+    int n_ovf;
+    int* row_len;
 };
 
 // Row layout.  The gather gives every lane of a group of GS = 2^gs_log2 lanes one 16-byte chunk
@@ -201,6 +211,8 @@ __global__ void k_wtab(const WtabParams p) {
         const long si = p.shift_by_dir ? dd : d;
         const int row_shift = FILL ? (p.fp ? (int)(p.row_e[si] & 0x7FFFu) : (int)p.row_s[si]) : 0;
         const bool force_ok = FILL && p.fp && (p.row_e[si] & ROW_E_FORCE_OK) != 0;
+        // capped rows: entries [cap, cap + ROW_BLOCK) of a longer row live in its block of the side table
+        const uint32_t ovf = (FILL && p.cap && p.w) ? p.ovf_of_row[d] : NO_OVERFLOW;
         const double scale = p.fp ? ldexp(1.0, row_shift) : ldexp(1.0, 32 + TAB_X - row_shift);        // 2^E / 2^(32 - e)
         for (int l = 0; l < nl; ++l) {
         const double* tiles = fused ? p.tiles_v[l] : p.tiles;
@@ -234,7 +246,7 @@ __global__ void k_wtab(const WtabParams p) {
                 hit = w32 != 0u;
             }
             const unsigned long long mask = __ballot(hit);
-            if (FILL && hit) {
+            if (FILL && hit && p.w) {
                 const int pos = count + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
                                         __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
                 int slot = t;
@@ -242,21 +254,35 @@ __global__ void k_wtab(const WtabParams p) {
                     const int h = n >> 1;
                     slot = t < h ? p.off_v[l] + t : (t >= n - h ? p.N - 1 - (p.off_v[l] + (n - 1 - t)) : 2 * p.nl + p.Hs + l);
                 }
-                p.w[d * p.stride + pos] = w32;
-                p.idx[d * p.stride + pos] = (uint16_t)slot;
+                if (!p.cap || pos < p.cap) {
+                    p.w[d * p.stride + pos] = w32;
+                    p.idx[d * p.stride + pos] = (uint16_t)slot;
+                } else if (ovf != NO_OVERFLOW && pos - p.cap < ROW_BLOCK) {
+                    p.ow[(size_t)ovf * ROW_BLOCK + (pos - p.cap)] = w32;
+                    p.oi[(size_t)ovf * ROW_BLOCK + (pos - p.cap)] = (uint16_t)slot;
+                }
             }
             count += __popcll(mask);
         }
         }
-        if (FILL) {
+        if (FILL && !p.w) {
+            if (lane == 0 && p.row_len) p.row_len[d] = count;
+        } else if (FILL) {
             // padding: weight 0 on distinct tiles, so the gather can add every slot unconditionally
             // without piling zero adds onto one LDS address
             for (int pos = count + lane; pos < p.stride; pos += WAVE) {
                 p.w[d * p.stride + pos] = 0u;
                 p.idx[d * p.stride + pos] = (uint16_t)(pos % slots);
             }
+            if (ovf != NO_OVERFLOW)
+                for (int pos = count - p.cap + lane; pos < ROW_BLOCK; pos += WAVE) {
+                    p.ow[(size_t)ovf * ROW_BLOCK + pos] = 0u;
+                    p.oi[(size_t)ovf * ROW_BLOCK + pos] = (uint16_t)((p.cap + pos) % slots);
+                }
+            // entries of the main row (capped rows: at most cap, META_OVERFLOW = the rest is in the side table)
+            const int main_count = p.cap ? min(count, p.cap) : count;
             if (lane == 0) {
-                if (p.meta) p.meta[d] = (uint32_t)count | ((uint32_t)row_shift << 16);
+                if (p.meta) p.meta[d] = (uint32_t)main_count | (ovf != NO_OVERFLOW ? META_OVERFLOW : 0u) | ((uint32_t)row_shift << 16);
             }
             // well-filled blocks of 16- and 8-lane rows: deal the entries by class (one wave pass per block, lane =
             // sorted entry; the loads of all lanes have returned before the first store issues).
@@ -269,10 +295,11 @@ __global__ void k_wtab(const WtabParams p) {
             if (p.gs_log2 == 4 || p.gs_log2 == 3) {
                 const int GSL = p.gs_log2, GS = 1 << GSL, B = 4 * GS;
                 const bool active = lane < B;
-                for (int eb = 0; eb < count; eb += B) {
-                    if (!block_interleaved(count, eb, GSL)) continue;
+                // (a capped row's blocks below cap are as full as those of the uncapped row: the same blocks are dealt)
+                for (int eb = 0; eb < main_count; eb += B) {
+                    if (!block_interleaved(main_count, eb, GSL)) continue;
                     __threadfence_block();
-                    const bool real = active && eb + lane < count;
+                    const bool real = active && eb + lane < main_count;
                     uint32_t wv = 0; uint16_t iv = 0;
                     if (real) { wv = p.w[d * p.stride + eb + lane]; iv = p.idx[d * p.stride + eb + lane]; }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -329,7 +356,12 @@ __global__ void k_wtab(const WtabParams p) {
         nmark = wave_sum(nmark);
         if (lane == 0 && nmark) atomicAdd(p.markers, nmark);
     }
-    if (FILL && wave == 0) {            // row D: the all-zero row idle lanes of the gather point at
+    if (FILL && wave == 0 && p.ow)      // the side table's all-zero row
+        for (int pos = lane; pos < ROW_BLOCK; pos += WAVE) {
+            p.ow[(size_t)p.n_ovf * ROW_BLOCK + pos] = 0u;
+            p.oi[(size_t)p.n_ovf * ROW_BLOCK + pos] = (uint16_t)((pos >> 2) & 15);
+        }
+    if (FILL && wave == 0 && p.w) {     // row D: the all-zero row idle lanes of the gather point at
         for (int pos = lane; pos < p.stride; pos += WAVE) {
             p.w[p.D * p.stride + pos] = 0u;
             // lane l of a 16-lane group adds its zeros to tile l: 16 classes, no conflict

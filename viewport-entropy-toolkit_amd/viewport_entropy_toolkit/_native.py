@@ -77,6 +77,7 @@ SIGNATURES = {
     "vet_synchronize": (_I, [_P]),
     "vet_device_pci_bus_id": (_I, [_P, C.c_char_p, _I]),
     "vet_profile_enable": (_I, [_P, _I]),
+    "vet_test_no_row_cap": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -92,10 +93,12 @@ SIGNATURES = {
     "vet_plan_set_raw_weights": (_I, [_P, _I]),
     "vet_plan_table_stride": (_I, [_P, _I]),
     "vet_plan_table_rows": (_I64, [_P]),
+    "vet_plan_table_cap": (_I, [_P, _I, C.POINTER(_I64)]),
     "vet_plan_last_formulation": (_I, [_P, _I]),
     "vet_plan_error_bounds": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_D)]),
     "vet_plan_read_dirs": (_I, [_P, _P]),
     "vet_plan_read_nearest": (_I, [_P, _I, _P]),
+    "vet_plan_read_table": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_window_rows": (_I64, [_I, _I, _I]),
@@ -321,6 +324,10 @@ class Engine:
             _check(self.lib, self.lib.vet_angular_distances(self.handle, _ptr(vectors), len(vectors), _ptr(tiles), len(tiles), _ptr(out)))
         return out
 
+    def test_no_row_cap(self, on: bool = True):
+        """Test switch: plans of this engine build their tables with every row whole (include/vet.h: vet_test_no_row_cap)."""
+        _check(self.lib, self.lib.vet_test_no_row_cap(self.handle, int(on)))
+
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
 
@@ -450,6 +457,12 @@ class Plan:
         """Rows of the plan's weight tables: distinct directions up to the lattices' mirror symmetry (0 before a table exists)."""
         return int(self.lib.vet_plan_table_rows(self.handle))
 
+    def table_cap(self, lattice: int = 0):
+        """(cap, overflow rows) of the lattice's own table: entries per main row, rows that continue in the overflow table
+        (include/vet.h: vet_plan_table_cap); (0, 0) before the table exists."""
+        n = C.c_int64()
+        return int(self.lib.vet_plan_table_cap(self.handle, lattice, C.byref(n))), int(n.value)
+
     def last_formulation(self, lattice: int = 0) -> str:
         """'table' | 'sweep' | 'precise' | 'ftable' | 'dtable' of the last weighted call ('' before any)."""
         return FORMULATIONS.get(int(self.lib.vet_plan_last_formulation(self.handle, lattice)), "")
@@ -469,6 +482,24 @@ class Plan:
     def read_nearest(self, lattice: int = 0) -> np.ndarray:
         out = np.empty(self.n_dirs, dtype=np.int32)
         _check(self.lib, self.lib.vet_plan_read_nearest(self.handle, lattice, _ptr(out)))
+        return out
+
+    def read_table(self, lattice: int = 0) -> dict:
+        """The lattice's own weight table as built on the device: w / tile [rows+1, stride], meta [rows+1] and, for a capped
+        table, ovf_w / ovf_tile [overflow rows + 1, 64] and ovf_of_row [rows] (include/vet.h: vet_plan_read_table)."""
+        cap, n_ovf = self.table_cap(lattice)
+        if cap <= 0:
+            raise ValueError("the lattice has no table of its own (yet)")
+        rows = self.table_rows()
+        out = {"w": np.empty((rows + 1, cap), np.uint32), "tile": np.empty((rows + 1, cap), np.uint16),
+               "meta": np.empty(rows + 1, np.uint32)}
+        if n_ovf:
+            out.update(ovf_w=np.empty((n_ovf + 1, 64), np.uint32), ovf_tile=np.empty((n_ovf + 1, 64), np.uint16),
+                       ovf_of_row=np.empty(rows, np.uint32))
+        _check(self.lib, self.lib.vet_plan_read_table(self.handle, lattice, _ptr(out["w"]), _ptr(out["tile"]), _ptr(out["meta"]),
+                                                      _ptr(out["ovf_w"]) if "ovf_w" in out else None,
+                                                      _ptr(out["ovf_tile"]) if "ovf_tile" in out else None,
+                                                      _ptr(out["ovf_of_row"]) if "ovf_of_row" in out else None))
         return out
 
     # --- host-buffer runs (what the analyzers use) ---------------------------
