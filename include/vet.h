@@ -93,6 +93,10 @@ int vet_profile_enable(vet_ctx *ctx, int on);
  * (cap = stride, no overflow table; vet_plan_table_cap) — the layout of plans where no cap qualifies, so that a test can
  * compare the two layouts in one process.  Results are bit-identical either way. */
 int vet_test_no_row_cap(vet_ctx *ctx, int on);
+/* Test switch, not a tuning knob: on != 0 makes the table launches of this context's plans read the 8-byte direction record
+ * (row, nearest tile, row meta) where a capped plan also has the 4-byte one (vet_plan_record_bytes).  Read at every launch,
+ * so one plan runs both kernels in one process.  Results are bit-identical either way. */
+int vet_test_rec8(vet_ctx *ctx, int on);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -217,6 +221,13 @@ int64_t vet_plan_table_rows(const vet_plan *plan);
  * of an overflow table, numbered in row order (*overflow_rows of them, nullable; an all-zero row follows the last).
  * cap == stride; a table whose rows are all whole has no overflow table (also forced by vet_test_no_row_cap). */
 int vet_plan_table_cap(const vet_plan *plan, int lattice, int64_t *overflow_rows);
+/* Bytes of the per-direction record that the plan's table launches with the set of distinct rows (frames of >= 128 users)
+ * gather per sample: 4 = the compact record (row 15 bits | mirrored | nearest tile 10 bits | -shift 5 bits | row continues in
+ * the overflow table), built beside the 8-byte one for capped one-lattice tables of fewer than 2^15 rows and at most 2^10
+ * tiles; 8 otherwise (also under vet_test_rec8); 0 = lattice 0 has no table with records yet.  vet_plan_read_records copies
+ * the compact records [n_dirs] to the host (an error where the plan has none). */
+int vet_plan_record_bytes(const vet_plan *plan);
+int vet_plan_read_records(vet_plan *plan, uint32_t *h_rec32);
 int vet_plan_last_formulation(const vet_plan *plan, int lattice);
 int vet_plan_error_bounds(vet_plan *plan, int lattice, double *table_bound, double *sweep_bound);
 /* Parity hooks: read back the device-built tables (synchronous). */

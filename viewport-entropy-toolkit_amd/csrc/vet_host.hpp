@@ -102,6 +102,8 @@ struct Tuning {
                                 // (include/vet.h; test_fp64_formulation.py, test_hip_shapes.py)
     int no_row_cap = 0;         // vet_test_no_row_cap (no environment variable): one-lattice tables keep cap = stride (every row whole, no side table) — the
                                 // layout of plans where no cap qualifies; so a test can compare the two layouts (test_row_cap.py)
+    int rec8 = 0;               // vet_test_rec8 (no environment variable): capped plans that have the compact record table launch the
+                                // kernels of the 8-byte record all the same; read at every launch, so one plan runs both (test_rec32.py)
     void from_environment();
 };
 
@@ -194,6 +196,8 @@ struct vet_plan {
     uint32_t* d_alias = nullptr;   // [n_dirs] direction id -> table row (dense) | mirrored << 31 (ensure_alias)
     bool mirror = false;           // rows are shared between mirror-image directions
     uint2* d_dirrec = nullptr;     // [n_dirs] alias | nearest tile | lattice-0 row meta (k_dirrec), dedup-capable plans
+    uint32_t* d_dirrec32 = nullptr;// [n_dirs] the same in 4 bytes (k_dirrec32; vet_layout.hpp: REC32_*): capped tables whose rows
+                                   // and tiles fit the fields; null otherwise — the capped kernels then read d_dirrec
     int n_rows = 0;                // table rows in use = canonical directions, densely numbered (ensure_alias)
     int* d_canon = nullptr;        // [n_rows] table row -> its direction
     // fused table: one row per distinct direction over ALL lattices (vet_layout.hpp)
@@ -216,6 +220,11 @@ struct vet_plan {
 };
 
 namespace vh {
+
+// the capped kernels of this plan read the 4-byte record (launches with the set of distinct rows; vet_test_rec8 forces the other)
+inline bool use_rec32(const vet_plan* pl) {
+    return pl->d_dirrec32 && !pl->ctx->tune.rec8 && !pl->lat.empty() && pl->lat[0].capped;
+}
 
 // hipEvent pair around the launches of a scope, on the launch stream (vet_profile_*)
 struct ProfScope {

@@ -26,6 +26,31 @@ constexpr int ROW_BLOCK = 64;
 constexpr int MAX_CAP_BLOCKS = 3;
 constexpr uint32_t META_OVERFLOW = 1u << 15;
 constexpr uint32_t NO_OVERFLOW = 0xFFFFFFFFu;
+
+// Compact direction record of the capped kernels (k_dirrec32; k_spatial_lut<REC32>): a capped row has no length to carry, so
+// what a sample needs fits one word —  row | mirrored << 15 | nearest tile << 16 | -shift << 26 | continues in the side
+// table << 31  (shift = the row's block-floating-point exponent in [-TAB_X, 0]: the meta word holds TAB_X + shift).  Built
+// beside the 8-byte record where rows + 1 <= 2^REC32_ROW_BITS and the lattice has at most 2^REC32_TILE_BITS tiles.
+constexpr int REC32_ROW_BITS = 15;
+constexpr int REC32_TILE_BITS = 10;
+constexpr int REC32_SHIFT_BITS = 5;
+constexpr uint32_t REC32_ROW_MASK = (1u << REC32_ROW_BITS) - 1;
+constexpr uint32_t REC32_KEY_MASK = (1u << (REC32_ROW_BITS + 1)) - 1;       // row | mirrored: the set's key
+constexpr int REC32_TILE_POS = REC32_ROW_BITS + 1;
+constexpr int REC32_SHIFT_POS = REC32_TILE_POS + REC32_TILE_BITS;
+constexpr uint32_t REC32_OVERFLOW = 1u << 31;
+constexpr uint32_t REC32_AUX_MASK = ~((1u << REC32_SHIFT_POS) - 1);          // -shift and the overflow bit, as they sit
+static_assert(REC32_SHIFT_POS + REC32_SHIFT_BITS == 31, "row, mirror, tile, shift and the overflow bit fill 32 bits");
+static_assert(TAB_X < (1 << REC32_SHIFT_BITS), "-shift in [0, TAB_X] fits its field");
+static_assert(REC32_ROW_BITS <= ROW_BITS, "a compact row is a row of the set");
+// The row list of the REC32 kernels, one word per row and no meta word:  left shift (TAB_X + shift) in bits 0..4 |
+// multiplicity - 1 (chunks of at most 2048 users) << 5 | row << 16 | mirrored << 31.  Rows listed one per user (no set) have
+// multiplicity 1: bit 5 then marks "continues in the side table" until the overflow list is made.
+constexpr int WALK32_CNT_POS = 5, WALK32_CNT_BITS = 11, WALK32_ROW_POS = 16;
+constexpr int REC32_MAX_CHUNK = 1 << WALK32_CNT_BITS;
+constexpr uint32_t WALK32_OVF_TMP = 1u << WALK32_CNT_POS;
+static_assert(WALK32_CNT_POS + WALK32_CNT_BITS == WALK32_ROW_POS && WALK32_ROW_POS + REC32_ROW_BITS + 1 == 32, "walk word");
+static_assert(TAB_X < (1 << WALK32_CNT_POS), "the left shift fits below the multiplicity");
 // entries of a frame's overflow list (LDS): with the set of distinct rows at most one per (overflow row, mirrored) — fewer than
 // DEDUP_MIN_USERS where a small video of a batch runs without the set —, otherwise one per user; never more than the chunk
 __host__ __device__ __forceinline__ int lut_ovf_slots(int UC, int n_ovf, bool dedup) {

@@ -272,10 +272,24 @@ int ensure_wtab(vet_plan* pl, int k, hipStream_t s) {
                            L.d_nearest, L.d_tab_meta, (long)pl->n_dirs, pl->d_dirrec);
         HIP_TRY(hipGetLastError());
     }
+    // capped rows carry no length: where rows and tiles fit its fields, the 4-byte record beside the 8-byte one (REC32_*)
+    const bool rec32 = k == 0 && capped && pl->d_dirrec && (uint64_t)pl->n_rows + 1 <= ((uint64_t)1 << vet::REC32_ROW_BITS) &&
+                       L.n <= (1 << vet::REC32_TILE_BITS);
+    if (pl->d_dirrec32) { (void)hipFree(pl->d_dirrec32); pl->d_dirrec32 = nullptr; }
+    if (rec32) {
+        HIP_TRY(hipMalloc((void**)&pl->d_dirrec32, (size_t)pl->n_dirs * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int), s));      // [0] is free again: directions that do not fit the record
+        ProfScope ps(c, s, KID_WTAB);
+        hipLaunchKernelGGL(vet::k_dirrec32, dim3(grid_for(pl->n_dirs, 256, c->n_cu)), dim3(256), 0, s, pl->d_alias,
+                           L.d_nearest, L.d_tab_meta, (long)pl->n_dirs, pl->d_dirrec32, d_max);
+        HIP_TRY(hipGetLastError());
+    }
     // the table is complete before this returns: a later call may run on another stream (first use only)
-    int markers = 0;
-    HIP_TRY(hipMemcpyAsync(&markers, d_max + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    int counts[2] = {0, 0};                    // [0] unfit directions of the compact record, [1] markers
+    HIP_TRY(hipMemcpyAsync(counts, d_max, sizeof(counts), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    const int markers = counts[1];
+    if (rec32 && counts[0] != 0) { (void)hipFree(pl->d_dirrec32); pl->d_dirrec32 = nullptr; }   // (a shift outside [-TAB_X, 0])
     guard.armed = false;
     L.markers = markers;
     L.capped = capped; L.n_ovf = capped ? n_ovf : 0;
@@ -649,6 +663,7 @@ int vet_plan_destroy(vet_plan* pl) {
     if (pl->d_alias) (void)hipFree(pl->d_alias);
     if (pl->d_canon) (void)hipFree(pl->d_canon);
     if (pl->d_dirrec) (void)hipFree(pl->d_dirrec);
+    if (pl->d_dirrec32) (void)hipFree(pl->d_dirrec32);
     {
         auto& F = pl->fused;
         for (void* q : {(void*)F.d_row_s, (void*)F.d_w, (void*)F.d_i, (void*)F.d_meta, (void*)F.d_dirrec})
@@ -692,6 +707,20 @@ int vet_plan_table_cap(const vet_plan* pl, int k, int64_t* overflow_rows) {
     if (!pl || k < 0 || k >= (int)pl->lat.size() || pl->lat[k].stride <= 0) return 0;
     if (overflow_rows) *overflow_rows = pl->lat[k].n_ovf;
     return pl->lat[k].stride;            // capped rows: stride == cap; otherwise every row is whole
+}
+
+int vet_plan_record_bytes(const vet_plan* pl) {
+    if (!pl || pl->lat.empty()) return 0;
+    if (pl->lat[0].stride <= 0 || !pl->d_dirrec) return pl->fused.state == 1 && pl->fused.d_dirrec ? 8 : 0;
+    return vh::use_rec32(pl) ? 4 : 8;
+}
+
+int vet_plan_read_records(vet_plan* pl, uint32_t* h_rec32) {
+    if (!pl || !h_rec32) return fail(VET_ERR_INVALID, "plan or output is NULL");
+    if (!pl->d_dirrec32) return fail(VET_ERR_INVALID, "the plan has no compact record table");
+    HIP_TRY(hipSetDevice(pl->ctx->device));
+    HIP_TRY(hipMemcpy(h_rec32, pl->d_dirrec32, (size_t)pl->n_dirs * 4, hipMemcpyDeviceToHost));
+    return VET_OK;
 }
 
 int vet_plan_read_table(vet_plan* pl, int k, uint32_t* h_w, uint16_t* h_tile, uint32_t* h_meta, uint32_t* h_ovf_w,

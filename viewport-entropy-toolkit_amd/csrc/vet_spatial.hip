@@ -125,11 +125,15 @@ const void* lut_kernel_fused(bool il, bool occ8, bool dedup, bool narrow = false
     return nullptr;
 }
 
-// nb > 0: the fixed-trip kernels of capped rows of nb blocks (one class-dealt integer lattice, 8 workgroups per CU)
+// nb > 0: the fixed-trip kernels of capped rows of nb blocks (one class-dealt integer lattice, 8 workgroups per CU);
+// rec32: their instantiations over the 4-byte direction record (with the set of distinct rows only)
 template <bool FROM_IDS>
-const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false, int nb = 0) {
+const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false, int nb = 0, bool rec32 = false) {
     if (nb) {
-        if (!il || !occ8 || fpt) return nullptr;
+        if (!il || !occ8 || fpt || (rec32 && !dedup)) return nullptr;
+#define VET_PICKR(N) if (rec32 && nb == N) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, true, false, false, N, true>
+        VET_PICKR(1); VET_PICKR(2); VET_PICKR(3);
+#undef VET_PICKR
 #define VET_PICKC(N, D) if (nb == N && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, D, false, false, N>
         VET_PICKC(1, false); VET_PICKC(1, true); VET_PICKC(2, false); VET_PICKC(2, true); VET_PICKC(3, false); VET_PICKC(3, true);
 #undef VET_PICKC
@@ -306,6 +310,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     q.nearest = pl->lat[lat_idx[0]].d_nearest;
     q.alias = pl->d_alias;
     q.dirrec = pl->d_dirrec;
+    q.dirrec32 = pl->d_dirrec32;
     q.rec_meta = lat_idx[0] == 0 ? 1 : 0;
     q.K = K; q.n_sum = 0;
     bool il = false;
@@ -328,6 +333,9 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     q.entropy = d_entropy; q.assign = d_assign; q.weights = d_weights; q.present = d_present;
     q.status = d_status;
     const bool dedup = dedup_lattices(pl, d_videos ? batch_max_users : U);
+    // the 4-byte record where the plan has it (ensure_wtab): capped rows, the launch keeps the set of distinct rows
+    const bool rec32 = nb && dedup && use_rec32(pl);
+    static_assert(2048 <= vet::REC32_MAX_CHUNK, "a chunk's multiplicities fit the walk word");
     int blocks = blocks_batch;
     const int threads = 256;     // __launch_bounds__(256); the FP table's row sort counts on 256 threads
     size_t lds = lds_batch;
@@ -339,7 +347,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
         int fpw = lut_frames_per_wg(U, T, c->n_cu, q.n_sum);
         for (;; fpw /= 2) {
             lds = vet::lut_lds_bytes(U, q.UC, fpw, q.n_sum, dedup, d_resolve != nullptr, fpt ? threads / 64 : 1, q.sort_words,
-                                     nb ? vet::lut_ovf_slots(q.UC, L0.n_ovf, dedup) : 0);
+                                     nb ? vet::lut_ovf_slots(q.UC, L0.n_ovf, dedup) : 0, rec32);
             if (lds <= c->lds_max || fpw == 1) break;
         }
         if (lds > c->lds_max) return VET_OK;      // not launched: caller falls back to the sweep
@@ -352,7 +360,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     ProfScope ps(c, s, KID_SPATIAL);
     void* args[] = {(void*)&q};
     // 2 rows in flight per lane group measured best (4 and 8 were tried, profiles/r01/v3_*)
-    const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb);
+    const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb, rec32);
     if (!fn) return fail(VET_ERR_UNSUPPORTED, "no table kernel for this launch");
     HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(threads), args, lds, s));
     HIP_TRY(hipGetLastError());
@@ -443,12 +451,12 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
 
 // LDS bytes and frames per workgroup of one video of a batch (0 = does not fit)
 size_t batch_video_geometry(const vet_ctx* c, int U, long total_frames, int n_sum, bool dedup, int* fpw_out, int* uc_out,
-                            int priv = 1, int sort_words = 0, int n_ovf = 0) {
+                            int priv = 1, int sort_words = 0, int n_ovf = 0, bool rec32 = false) {
     const int UC = U < 2048 ? U : 2048;
     int fpw = lut_frames_per_wg(U, total_frames, c->n_cu, n_sum);
     size_t lds = 0;
     for (;; fpw /= 2) {
-        lds = vet::lut_lds_bytes(U, UC, fpw, n_sum, dedup, false, priv, sort_words, vet::lut_ovf_slots(UC, n_ovf, dedup));
+        lds = vet::lut_lds_bytes(U, UC, fpw, n_sum, dedup, false, priv, sort_words, vet::lut_ovf_slots(UC, n_ovf, dedup), rec32);
         if (lds <= c->lds_max || fpw == 1) break;
     }
     *fpw_out = fpw; *uc_out = UC;
@@ -1098,7 +1106,8 @@ int vet_spatial_entropy_batch(vet_plan* pl, int n_videos, const vet_video* video
             d.entropy = x.d_entropy; d.assign = x.d_assign; d.present = x.d_present;
             const size_t lds = batch_video_geometry(c, d.U, total_frames, n_sum, dedup, &d.FPW, &d.UC, form0 == F_FTABLE ? 4 : 1,
                                                     (form0 == F_FTABLE && dedup && 2 * pl->n_rows <= 65536) ? (int)((2 * pl->n_rows + 31) / 32) : 0,
-                                                    pl->lat[0].capped ? pl->lat[0].n_ovf : 0);
+                                                    pl->lat[0].capped ? pl->lat[0].n_ovf : 0,
+                                                    pl->lat[0].capped && dedup && use_rec32(pl));
             if (lds == 0) table = false;
             d.block0 = block; d.pad_ = 0;
             block += (d.T + d.FPW - 1) / d.FPW;

@@ -73,7 +73,8 @@ __device__ __forceinline__ void lds_add_u64(uint32_t lds_byte_address, unsigned 
 // NB > 0: capped integer rows of exactly NB blocks of ROW_BLOCK slots (vet_layout.hpp), 16 lanes per row: every row is walked
 // over all NB blocks, unrolled — no length, no trip count to agree on, no redirect (ensure_wtab caps only where every row
 // reaches its last block); fmeta is read for the row shift alone.  The side table's rows are walked the same way with NB = 1.
-template <int UN, bool INTERLEAVED, bool DEDUP, bool FPT, int GSL_IL = 4, int NB = 0>
+// REC32: frows holds the one-word row list of the compact record (vet_layout.hpp: WALK32_*), fmeta is not read.
+template <int UN, bool INTERLEAVED, bool DEDUP, bool FPT, int GSL_IL = 4, int NB = 0, bool REC32 = false>
 __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t* fmeta, int nu,
                                           unsigned long long* hrow, int n,
                                           const uint32_t* __restrict__ tab_w, const uint16_t* __restrict__ tab_i,
@@ -86,6 +87,7 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
     const int NW = blockDim.x >> 6, lane = lane_id(), wv = wave_id();
     if constexpr (NB > 0) {
         static_assert(!FPT && INTERLEAVED && GSL_IL == 4, "capped rows: integer tables with 16-lane rows");
+        static_assert(!REC32 || DEDUP, "the one-word row list belongs to the kernels with the set");
         constexpr int UPW = WAVE >> 4;
         // (the lane's constants of the walk are formed here, behind an opaque copy of the lane: formed at kernel entry, as the
         // compiler would, they are spilled across the prologue, whose sample batches need every register of the 64)
@@ -99,13 +101,24 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
             for (int k = 0; k < UN; ++k) {
                 const int j = j0 + k * step + sub;
                 const bool on = j < nu;
-                const uint32_t pk = on ? frows[j] : 0u, m = on ? fmeta[j] : 0u;
-                const uint32_t key = DEDUP ? pk >> 12 : pk;
-                const bool flip = ((DEDUP ? key >> ROW_BITS : key >> 31) & 1u) != 0u;
-                const uint32_t rid = DEDUP ? key & ROW_MASK : key & 0x7FFFFFFFu;
-                row[k] = (on ? rid * (uint32_t)(NB * ROW_BLOCK) : zero_row) + (uint32_t)(4 * sl);
-                const uint32_t cnt = DEDUP ? pk & 0xFFFu : (on ? 1u : 0u);
-                mult[k] = cnt << ((m >> 16) & 0x1Fu);
+                bool flip;
+                if constexpr (REC32) {
+                    // (the shift instruction takes its count from the word's low five bits as they are)
+                    const uint32_t pk = on ? frows[j] : 0u;
+                    flip = (int)pk < 0;
+                    const uint32_t rid = (pk >> WALK32_ROW_POS) & REC32_ROW_MASK;
+                    row[k] = (on ? rid * (uint32_t)(NB * ROW_BLOCK) : zero_row) + (uint32_t)(4 * sl);
+                    const uint32_t cnt = on ? ((pk >> WALK32_CNT_POS) & ((1u << WALK32_CNT_BITS) - 1)) + 1u : 0u;
+                    mult[k] = cnt << (pk & 0x1Fu);
+                } else {
+                    const uint32_t pk = on ? frows[j] : 0u, m = on ? fmeta[j] : 0u;
+                    const uint32_t key = DEDUP ? pk >> 12 : pk;
+                    flip = ((DEDUP ? key >> ROW_BITS : key >> 31) & 1u) != 0u;
+                    const uint32_t rid = DEDUP ? key & ROW_MASK : key & 0x7FFFFFFFu;
+                    row[k] = (on ? rid * (uint32_t)(NB * ROW_BLOCK) : zero_row) + (uint32_t)(4 * sl);
+                    const uint32_t cnt = DEDUP ? pk & 0xFFFu : (on ? 1u : 0u);
+                    mult[k] = cnt << ((m >> 16) & 0x1Fu);
+                }
                 sgn[k] = flip ? -8 : 8;
                 hb32[k] = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)((char*)hrow + (flip ? (n - 1) * 8 : 0));
             }
@@ -221,7 +234,8 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
 //                              shares the histogram's space (the set is compacted before the first add)
 //                              unless the users arrive in several chunks
 //       rows u32 [FPW][UC]     the frame's distinct rows (slot words), or one row per present user
-//       meta u32 [FPW][UC]     their meta words in the lattice being gathered
+//       meta u32 [FPW][UC]     their meta words in the lattice being gathered (REC32: no such array — the row list's word
+//                              carries the shift, vet_layout.hpp: WALK32_*; the overflow list has no meta words either)
 //       cnt  i32 [FPW] rows in the chunk, [FPW] users present in the frame
 //       capped rows (NB > 0) with a side table:  i32 [FPW] entries of the frame's overflow list, u32 [FPW][OC] their slot
 //       words (the side table's row in place of the row), u32 [FPW][OC] their meta words;  OC = lut_ovf_slots
@@ -285,6 +299,8 @@ struct LutParams {
     unsigned long long* dbg;      // development builds (-DVET_STAGE_CYCLES=1): [4] cycles of thread 0 per stage, summed over the workgroups
     uint32_t* resolve;            // FP tables with marker entries: [0] = number of frames handed to the precise sweep
                                   // (a marked tile whose histogram stayed 0.0), then the frames; null otherwise
+    const uint32_t* dirrec32;     // [n_dirs] REC32: dirrec in one word for capped rows (k_dirrec32; vet_layout.hpp).  (Last: the
+                                  // other kernels' argument offsets, and with them their scalar loads, stay what they were)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -393,6 +409,13 @@ __device__ __forceinline__ void lut_epilogue_fused(const unsigned long long* his
     }
 }
 
+// REC32, rows listed one per user (no set): the walk word of multiplicity 1 from the set key (row | mirrored << 15) and the
+// record's top bits; "continues in the side table" waits in bit WALK32_CNT_POS until the overflow list is made
+__device__ __forceinline__ uint32_t walk32_single(uint32_t key, uint32_t aux) {
+    return (key << WALK32_ROW_POS) | ((uint32_t)TAB_X - ((aux >> REC32_SHIFT_POS) & ((1u << REC32_SHIFT_BITS) - 1))) |
+           ((aux & REC32_OVERFLOW) ? WALK32_OVF_TMP : 0u);
+}
+
 // hash slots per frame: power of two >= 2 * UC, at least one wave's worth
 __host__ __device__ __forceinline__ int lut_hash_slots(int UC) {
     int hs = 64;
@@ -406,13 +429,14 @@ __host__ __device__ __forceinline__ int lut_marked_words(int n_sum) { return (n_
 // sort_words: FP tables put every frame's row list into a canonical order through a bitmap over (row, mirrored); the bitmap
 // (+ 256 scan words) lives in the histogram / set region too (the histograms are cleared after the sort)
 __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW, int n_sum, bool dedup, bool marked = false,
-                                                         int priv = 1, int sort_words = 0, int ovf_slots = 0) {
+                                                         int priv = 1, int sort_words = 0, int ovf_slots = 0, bool rec32 = false) {
     const size_t hist = (size_t)FPW * n_sum * 8 * priv, hash = dedup ? (size_t)FPW * lut_hash_slots(UC) * 4 : 0;
     const size_t srt = sort_words ? ((size_t)sort_words + 256) * 4 : 0;
     size_t a = (dedup && U <= UC) ? (hist > hash ? hist : hash) : hist + hash;
     if (dedup && U <= UC && srt > a) a = srt;
-    return ((a + 15) & ~(size_t)15) + (size_t)FPW * UC * 8 + (size_t)2 * FPW * 4 + 64 +
-           (marked ? (size_t)FPW * lut_marked_words(n_sum) * 4 : 0) + (ovf_slots ? (size_t)FPW * (4 + (size_t)ovf_slots * 8) : 0);
+    const size_t per_row = rec32 ? 4 : 8;       // row word + meta word, or the one word of the compact record's kernels
+    return ((a + 15) & ~(size_t)15) + (size_t)FPW * UC * per_row + (size_t)2 * FPW * 4 + 64 +
+           (marked ? (size_t)FPW * lut_marked_words(n_sum) * 4 : 0) + (ovf_slots ? (size_t)FPW * (4 + (size_t)ovf_slots * per_row) : 0);
 }
 
 // All K lattices of the plan in one launch: the samples are read once, every row is gathered into K
@@ -428,8 +452,13 @@ __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW,
 // lattices back out of the fused histogram.
 // NB > 0: the launch's one lattice has capped rows of NB blocks (walk_rows): the main walk has a fixed trip count, and the rows
 // that continue in the side table are listed per frame while the row list is made and walked once more, against the side table.
-template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0>
+// REC32: the prologue gathers the 4-byte record p.dirrec32 (capped rows need no length); the set's slot word stays
+// key << 12 | count with key = row | mirrored << 15; the record's shift and overflow bits ride in the spare top bits of the row
+// list's slot number until the slot numbers become walk words (WALK32_*: shift in the low bits, where the walk's shift
+// instruction reads it unmasked), so there is no meta array and the overflow test is on a bit of the word in hand.
+template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0, bool REC32 = false>
 __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(const LutParams p) {
+    static_assert(!REC32 || (NB > 0 && DEDUP && !FPT && !FUSED), "the compact record serves the capped kernels with the set");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // the video this workgroup works on: the launch's only one, or one of a batch
     SampleSrc src = p.src;
@@ -462,8 +491,8 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     unsigned long long* hist = (unsigned long long*)smem;                        // [FPW][n_sum]
     uint32_t* hash = (uint32_t*)(smem + (overlay ? 0 : hist_bytes));             // [FPW][HS]
     uint32_t* rows = (uint32_t*)(smem + ((a_bytes + 15) & ~(size_t)15));         // [FPW][UC]
-    uint32_t* meta = rows + (size_t)FPW * UC;                                    // [FPW][UC]
-    int* cnt_chunk = (int*)(meta + (size_t)FPW * UC);                            // [FPW]
+    uint32_t* meta = rows + (size_t)FPW * UC;                                    // [FPW][UC] (REC32: none)
+    int* cnt_chunk = (int*)(meta + (REC32 ? (size_t)0 : (size_t)FPW * UC));      // [FPW]
     int* cnt_frame = cnt_chunk + FPW;                                            // [FPW]
     const int MW = lut_marked_words(p.n_sum);
     uint32_t* marked = (FPT && p.resolve) ? (uint32_t*)(cnt_frame + FPW) : nullptr;   // [FPW][MW]
@@ -477,6 +506,12 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
         if (!(m & META_OVERFLOW)) return;
         const int OC = ovf_slots();
         uint32_t* ovf_rows = (uint32_t*)(ovf_cnt + FPW);
+        if constexpr (REC32) {      // word: a walk word; the list has no meta words
+            const uint32_t o = p.lat[0].ovf_of_row[(word >> WALK32_ROW_POS) & REC32_ROW_MASK];
+            const int pos = atomicAdd(&ovf_cnt[fl], 1);
+            if (pos < OC) ovf_rows[(size_t)fl * OC + pos] = (word & ~(REC32_ROW_MASK << WALK32_ROW_POS)) | (o << WALK32_ROW_POS);
+            return;
+        }
         const uint32_t o = p.lat[0].ovf_of_row[DEDUP ? (word >> 12) & ROW_MASK : word & 0x7FFFFFFFu];
         const int pos = atomicAdd(&ovf_cnt[fl], 1);
         if (pos < OC) {
@@ -571,7 +606,12 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             for (int k = 0; k < SPT; ++k) {
                 row[k] = 0u; near[k] = -1; m0[k] = 0u;
                 if (id[k] >= 0) {
-                    if (DEDUP) {
+                    if constexpr (REC32) {
+                        const uint32_t rec = p.dirrec32[id[k]];
+                        row[k] = rec & REC32_KEY_MASK;
+                        near[k] = (int)((rec >> REC32_TILE_POS) & ((1u << REC32_TILE_BITS) - 1));
+                        m0[k] = rec & REC32_AUX_MASK;           // -shift and the overflow bit, where they sit
+                    } else if (DEDUP) {
                         const uint2 rec = p.dirrec[id[k]];
                         row[k] = (rec.x & ROW_MASK) | ((rec.x >> 31) << ROW_BITS);
                         near[k] = (int)(((rec.x >> ROW_BITS) & 0xFFFu) | ((rec.y >> 28) << 12));
@@ -630,15 +670,23 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                     base = __builtin_amdgcn_readfirstlane(base);
                     if (won) {
                         const size_t pos = (size_t)fl0 * UC + base + below(mw);
-                        rows[pos] = merge ? h : (DEDUP ? (row[k] << 12) | 1u : row[k]);
-                        meta[pos] = m0[k];
+                        if constexpr (REC32) {
+                            rows[pos] = merge ? h | m0[k] : walk32_single(row[k], m0[k]);
+                        } else {
+                            rows[pos] = merge ? h : (DEDUP ? (row[k] << 12) | 1u : row[k]);
+                            meta[pos] = m0[k];
+                        }
                     }
                 } else {
                     if (valid) atomicAdd(&cnt_frame[fl], 1);
                     if (won) {
                         const size_t pos = (size_t)fl * UC + atomicAdd(&cnt_chunk[fl], 1);
-                        rows[pos] = merge ? h : (DEDUP ? (row[k] << 12) | 1u : row[k]);
-                        meta[pos] = m0[k];
+                        if constexpr (REC32) {
+                            rows[pos] = merge ? h | m0[k] : walk32_single(row[k], m0[k]);
+                        } else {
+                            rows[pos] = merge ? h : (DEDUP ? (row[k] << 12) | 1u : row[k]);
+                            meta[pos] = m0[k];
+                        }
                     }
                 }
             }
@@ -651,6 +699,16 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             if (merge)
                 for (int i = tid; i < nf * UC; i += blockDim.x) {
                     const int fl = i / UC, j = i - fl * UC;
+                    if constexpr (REC32) {
+                        // slot number | the record's top bits -> walk word: multiplicity - 1 (a chunk has at most 2^11 users)
+                        if (j < cnt_chunk[fl]) {
+                            const uint32_t r = rows[i], slot = hash[(size_t)fl * HS + (r & ~REC32_AUX_MASK)];
+                            const uint32_t word = ((slot >> 12) << WALK32_ROW_POS) | (((slot & 0xFFFu) - 1u) << WALK32_CNT_POS) |
+                                                  ((uint32_t)TAB_X - ((r >> REC32_SHIFT_POS) & ((1u << REC32_SHIFT_BITS) - 1)));
+                            rows[i] = word;
+                            if (r & REC32_OVERFLOW) note_overflow(fl, word, META_OVERFLOW);
+                        }
+                    } else
                     if (j < cnt_chunk[fl]) {
                         const uint32_t word = hash[(size_t)fl * HS + rows[i]];
                         rows[i] = word;
@@ -755,7 +813,7 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             // meta words (length, shift) of this lattice for every staged row: one parallel gather, so the
             // walk below has no dependent global load in front of its row loads
             if (k) __syncthreads();
-            if (!(k == 0 && p.rec_meta && (DEDUP || p.dirrec)))
+            if (!REC32 && !(k == 0 && p.rec_meta && (DEDUP || p.dirrec)))
                 for (int i = tid; i < nf * UC; i += blockDim.x) {
                     const int fl = i / UC, j = i - fl * UC;
                     if (j < cnt_chunk[fl]) meta[i] = L.tab_meta[DEDUP ? (rows[i] >> 12) & ROW_MASK : rows[i] & 0x7FFFFFFFu];
@@ -763,6 +821,13 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             if (NB && !merge)                                       // one list entry per user: the overflow list is made here
                 for (int i = tid; i < nf * UC; i += blockDim.x) {
                     const int fl = i / UC, j = i - fl * UC;
+                    if constexpr (REC32) {
+                        if (j < cnt_chunk[fl] && (rows[i] & WALK32_OVF_TMP)) {
+                            const uint32_t word = rows[i] & ~WALK32_OVF_TMP;
+                            rows[i] = word;
+                            note_overflow(fl, word, META_OVERFLOW);
+                        }
+                    } else
                     if (j < cnt_chunk[fl]) note_overflow(fl, rows[i], meta[i]);
                 }
             __syncthreads();
@@ -770,11 +835,11 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             for (int fl = 0; fl < nf; ++fl)
                 if constexpr (NB > 0) {
                     unsigned long long* hrow = hist + (size_t)fl * p.n_sum + hoff;
-                    walk_rows<UN, true, DEDUP, false, 4, NB>(rows + (size_t)fl * UC, meta + (size_t)fl * UC, cnt_chunk[fl], hrow, L.n,
+                    walk_rows<UN, true, DEDUP, false, 4, NB, REC32>(rows + (size_t)fl * UC, meta + (size_t)fl * UC, cnt_chunk[fl], hrow, L.n,
                                                              L.tab_w, L.tab_i, L.stride, 4, L.zrow * (uint32_t)(NB * ROW_BLOCK));
                     if (const int OC = ovf_slots()) {
                         const uint32_t* ovf_rows = (const uint32_t*)(ovf_cnt + FPW);
-                        walk_rows<UN, true, DEDUP, false, 4, 1>(ovf_rows + (size_t)fl * OC, ovf_rows + (size_t)(FPW + fl) * OC,
+                        walk_rows<UN, true, DEDUP, false, 4, 1, REC32>(ovf_rows + (size_t)fl * OC, ovf_rows + (size_t)(FPW + fl) * OC,
                                                                 min(ovf_cnt[fl], OC), hrow, L.n, L.ovf_w, L.ovf_i, ROW_BLOCK, 4,
                                                                 (uint32_t)L.n_ovf * (uint32_t)ROW_BLOCK);
                     }

@@ -443,4 +443,17 @@ __global__ void k_dirrec(const uint32_t* __restrict__ alias, const uint16_t* __r
     }
 }
 
+// The compact record of capped tables (vet_layout.hpp: REC32_*), one 4-byte gather per sample.  *unfit counts the directions
+// whose row, tile or shift does not fit its field: the host then drops the table.
+__global__ void k_dirrec32(const uint32_t* __restrict__ alias, const uint16_t* __restrict__ nearest,
+                           const uint32_t* __restrict__ meta0, long D, uint32_t* __restrict__ rec, int* __restrict__ unfit) {
+    for (long d = blockIdx.x * (long)blockDim.x + threadIdx.x; d < D; d += (long)gridDim.x * blockDim.x) {
+        const uint32_t a = alias[d], near = nearest[d], row = a & 0x7FFFFFFFu;
+        const uint32_t m = row <= REC32_ROW_MASK ? meta0[row] : 0u, left = m >> 16;
+        if (row > REC32_ROW_MASK || near >= (1u << REC32_TILE_BITS) || left > (uint32_t)TAB_X) { atomicAdd(unfit, 1); continue; }
+        rec[d] = row | ((a >> 31) << REC32_ROW_BITS) | (near << REC32_TILE_POS) | (((uint32_t)TAB_X - left) << REC32_SHIFT_POS) |
+                 ((m & META_OVERFLOW) ? REC32_OVERFLOW : 0u);
+    }
+}
+
 }  // namespace vet

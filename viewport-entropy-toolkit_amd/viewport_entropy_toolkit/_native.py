@@ -78,6 +78,7 @@ SIGNATURES = {
     "vet_device_pci_bus_id": (_I, [_P, C.c_char_p, _I]),
     "vet_profile_enable": (_I, [_P, _I]),
     "vet_test_no_row_cap": (_I, [_P, _I]),
+    "vet_test_rec8": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -94,6 +95,8 @@ SIGNATURES = {
     "vet_plan_table_stride": (_I, [_P, _I]),
     "vet_plan_table_rows": (_I64, [_P]),
     "vet_plan_table_cap": (_I, [_P, _I, C.POINTER(_I64)]),
+    "vet_plan_record_bytes": (_I, [_P]),
+    "vet_plan_read_records": (_I, [_P, _P]),
     "vet_plan_last_formulation": (_I, [_P, _I]),
     "vet_plan_error_bounds": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_D)]),
     "vet_plan_read_dirs": (_I, [_P, _P]),
@@ -328,6 +331,10 @@ class Engine:
         """Test switch: plans of this engine build their tables with every row whole (include/vet.h: vet_test_no_row_cap)."""
         _check(self.lib, self.lib.vet_test_no_row_cap(self.handle, int(on)))
 
+    def test_rec8(self, on: bool = True):
+        """Test switch: table launches of this engine's plans read the 8-byte direction record (include/vet.h: vet_test_rec8)."""
+        _check(self.lib, self.lib.vet_test_rec8(self.handle, int(on)))
+
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
 
@@ -462,6 +469,17 @@ class Plan:
         (include/vet.h: vet_plan_table_cap); (0, 0) before the table exists."""
         n = C.c_int64()
         return int(self.lib.vet_plan_table_cap(self.handle, lattice, C.byref(n))), int(n.value)
+
+    def record_bytes(self) -> int:
+        """4 where the plan's table launches gather the compact direction record, 8 otherwise, 0 before the table exists
+        (include/vet.h: vet_plan_record_bytes)."""
+        return int(self.lib.vet_plan_record_bytes(self.handle))
+
+    def read_records(self) -> np.ndarray:
+        """The compact direction records [n_dirs] (include/vet.h: vet_plan_read_records)."""
+        out = np.empty(self.n_dirs, dtype=np.uint32)
+        _check(self.lib, self.lib.vet_plan_read_records(self.handle, _ptr(out)))
+        return out
 
     def last_formulation(self, lattice: int = 0) -> str:
         """'table' | 'sweep' | 'precise' | 'ftable' | 'dtable' of the last weighted call ('' before any)."""
