@@ -51,7 +51,8 @@ extern "C" {
                            vet_heatmap_render_transition_result (heatmaps of transition results) and
                            vet_heatmap_create_latlon / vet_heatmap_render_binned(_host) (lat/lon cell
                            heatmaps of naive plans) added the same way; so were vet_window_rows and the
-                           vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows) */
+                           vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows), and
+                          then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -313,6 +314,52 @@ int vet_spatial_entropy_windowed_ids(vet_plan *plan, const int32_t *d_ids, int n
 int vet_spatial_entropy_windowed_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
                                       int n_users, int n_frames, int window, int stride, double *h_entropy,
                                       double *h_weights, int32_t *h_samples);
+
+/* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
+ * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1
+ * there are R = vet_window_rows(P, window, stride) rows; row r covers pairs [r*stride, r*stride + window).  Row r is, for
+ * every lattice of the plan, what compute_transition_entropy (utilities/entropy_utils.py:213-332) returns when BOTH dicts hold
+ * one entry per (pair, user) of the window — keys unique per (pair, user), inserted pair-major then in user order, the prior
+ * dict holding the direction at frame f and the current dict the direction at frame f + 1, and only the (pair, user)
+ * entries present in both frames inserted — then the mean over the lattices as TransitionEntropyAnalyzer.compute_entropy
+ * takes it.  In the reduced form the kernels evaluate (above) it is the per-pair algorithm with "user index" replaced by
+ * the sample's rank in the pooled order: per source tile m, K = 1 + #distinct destinations after the first sample, w = the
+ * count of the bucket whose first appearance is latest, cell = -(m/N) K (w/m) log2(w/m); the normaliser is log2(n) if
+ * N > n, else log2(N), N = pooled samples.  Quirks are reproduced: N = 1 gives the reference's NaN (0 / 0).
+ *   A window without a common sample: NaN in d_entropy, 0 in d_samples and d_status[1] += 1 — what vet_transition_entropy
+ *   does with such a pair; the _host entry then returns VET_ERR_EMPTY (outputs are still written).
+ * window = 1, stride = 1 is the per-pair series (d_samples = vet_transition_entropy's d_common).
+ *   d_entropy  [R]
+ *   d_srccount [R*n_0]  lattice 0's pooled samples per source tile (the reference's weight_per_tile)   (nullable)
+ *   d_samples  [R]      N of the row                                                                  (nullable)
+ *   d_status   [2]      {bad, #rows without a common sample}; the call ADDS, the caller zeroes        (nullable)
+ * The per-sample pairs are not returned; vet_transition_entropy has them.
+ * Two stages per lattice.  1: k_window_tiles over all T frames — every sample is quantised and looked up once, whatever the
+ * overlap — into [T][U] i32 of the context's grow-only workspace (one lattice's array, reused lattice after lattice; no
+ * allocation in steady state).  2: k_window_transition — a row's pooled samples are a contiguous slice of that array
+ * (sample q: source tiles[f0*U + q], destination tiles[f0*U + q + U], f0 = r*stride), walked by k_transition_big's row
+ * algorithm (shared device code).  Every row is computed from scratch: first-appearance order makes the statistic
+ * non-decomposable over frames, there is no running add / subtract.
+ * A row is a pure function of the plan and of the samples of its window + 1 frames: integer atomics only, the FP64 cell sum
+ * in a fixed order, the workgroup shape chosen by window * n_users alone — the same bits whatever stride selected the row,
+ * wherever its frames lie in the call, from run to run, and between the grid and the ids entry points.
+ * VET_ERR_INVALID: window < 1, stride < 1, window > n_frames - 1, n_frames < 2 (and what vet_transition_entropy refuses).
+ * VET_ERR_UNSUPPORTED (checked before anything is launched or allocated): window * n_users >= 2^19 (the kernel packs
+ * sample << 13 | hash slot), a lattice of more than 2800 tiles (TRANS_BIG_MAX_TILES).
+ * Profile ids: stage 1 is charged to k_spatial (k_window_tiles, as above), stage 2 to k_transition, the mean over the
+ * lattices to k_finalize.  Asynchronous on `stream` like vet_transition_entropy. */
+int vet_transition_entropy_windowed(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames,
+                                    int window, int stride, double *d_entropy, int32_t *d_srccount, int32_t *d_samples,
+                                    int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_transition_entropy_windowed_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window,
+                                        int stride, double *d_entropy, int32_t *d_srccount, int32_t *d_samples,
+                                        int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE / VET_ERR_EMPTY when the status words are non-zero (outputs are
+ * still written).  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_transition_entropy_windowed_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
+                                         int n_users, int n_frames, int window, int stride, double *h_entropy,
+                                         int32_t *h_srccount, int32_t *h_samples);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

@@ -5,7 +5,7 @@
 //                       error bounds; parity read-back hooks; angular distances; tile boundary geometry
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
-//   vet_window.hip      the sliding-window spatial-entropy kernels (pooled histograms of frame windows) and their launch logic
+//   vet_window.hip      the sliding-window spatial- and transition-entropy kernels (frame windows pooled) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline

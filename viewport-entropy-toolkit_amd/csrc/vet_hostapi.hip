@@ -476,6 +476,40 @@ int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const do
     return run.finish("%d window(s) without any sample (Empty vector dictionary)");
 }
 
+// Sliding-window transition entropy with host buffers (include/vet.h): R = vet_window_rows over the T - 1 frame pairs
+int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
+                                         int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {
+    int rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    if (rc) return rc;
+    const int64_t R = vet_window_rows(T - 1, window, stride);
+    if (R < 0)
+        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames - 1 and stride >= 1 (got window %d, stride %d, %d frames)",
+                    window, stride, T);
+    if ((int64_t)window * U >= ((int64_t)1 << 19))           // before the samples are staged; the device entry says the same
+        return fail(VET_ERR_UNSUPPORTED, "windowed transition: window * n_users = %lld pooled samples per row, the kernel packs "
+                    "fewer than 2^19", (long long)window * U);
+    const size_t c_bytes = (size_t)R * pl->lat[0].n * 4;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    hipStream_t s = run.s;
+    double* ent = nullptr;
+    int32_t *sc = nullptr, *cnt = nullptr;
+    POOL(SLOT_ENTROPY, (size_t)R * 8, ent);
+    if (h_srccount) POOL(SLOT_OUT1, c_bytes, sc);
+    POOL(SLOT_COUNT, (size_t)R * 4, cnt);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = run.ids ? vet_transition_entropy_windowed_ids(pl, run.ids, U, T, window, stride, ent, sc, cnt, run.status, s)
+                 : vet_transition_entropy_windowed(pl, run.mu, run.mv, U, T, window, stride, ent, sc, cnt, run.status, s);
+    if (rc) return run.drain(rc);
+    HIP_TRY(hipMemcpyAsync(h_entropy, ent, (size_t)R * 8, hipMemcpyDeviceToHost, s));
+    if (h_srccount) HIP_TRY(hipMemcpyAsync(h_srccount, sc, c_bytes, hipMemcpyDeviceToHost, s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    return run.finish("%d window(s) without a (pair, user) sample present in both frames");
+}
+
 // Both batch entries.  Concatenated host buffers: video v's samples start at element sum_{w<v} U_w*T_w of h_mu / h_mv, its
 // rows (T_v frames; transition: T_v - 1 frame pairs) at sum_{w<v} rows_w of h_entropy / h_count, and its output 0 (U_v*T_v
 // assignments; transition: U_v*(T_v-1) pairs of two) at the sum of the earlier videos' in h_out0.  Two H2D copies, one

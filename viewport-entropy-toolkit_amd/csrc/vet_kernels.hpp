@@ -32,6 +32,8 @@
 //                                                               histogram per row (weighted: the frames' exact FP64 sums added in
 //                                                               frame order; counts: add entering, subtract leaving frames) ->
 //                                                               the reference's entropy of the pooled histogram
+//                                              k_window_transition   sliding windows of frame pairs: the pooled (pair, user)
+//                                                               transitions of a row walked by k_transition_big's row algorithm
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

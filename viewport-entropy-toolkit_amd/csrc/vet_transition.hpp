@@ -243,191 +243,233 @@ __global__ void k_transition_any(const TransParams p) {
 // LDS: acc f64 [2][20] | first_u, m_cnt, k_cnt, last_fu u32 [n4] | pass u16 [n4] | hkey, hfu, hcnt u32 [8192]
 // ------------------------------------------------------------------------------------------
 constexpr int TRANS_BIG_HS = 8192, TRANS_BIG_MAX_TILES = 2800, TRANS_BIG_THREADS = 1024;
-__host__ __device__ __forceinline__ size_t trans_big_lds_bytes(int n) {
+__host__ __device__ __forceinline__ size_t trans_big_lds_bytes(int n, int hs = TRANS_BIG_HS) {
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-    return 2 * TRANS_ACC * 8 + 4 * n4 * 4 + ((n4 * 2 + 15) & ~(size_t)15) + (size_t)3 * TRANS_BIG_HS * 4 + 64;
+    return 2 * TRANS_ACC * 8 + 4 * n4 * 4 + ((n4 * 2 + 15) & ~(size_t)15) + (size_t)3 * hs * 4 + 64;
+}
+
+// The row's LDS words, carved in the order of the layout line above; HS = the hash's slots (k_transition_big: 8192)
+struct TransBigLds {
+    double* acc2;                                  // [2][TRANS_ACC]
+    unsigned *first_u, *m_cnt, *k_cnt, *last_fu;   // [n4]
+    unsigned short* pass_of;                       // [n4] range (pass) of every source tile
+    unsigned *hkey, *hfu, *hcnt;                   // [HS]
+    int* n_pass;
+    int n4;
+};
+__device__ __forceinline__ TransBigLds trans_big_carve(unsigned char* smem, int n, int HS) {
+    TransBigLds L;
+    L.acc2 = (double*)smem;
+    L.first_u = (unsigned*)(L.acc2 + 2 * TRANS_ACC);
+    L.n4 = (n + 3) & ~3;
+    L.m_cnt = L.first_u + L.n4;
+    L.k_cnt = L.m_cnt + L.n4;
+    L.last_fu = L.k_cnt + L.n4;
+    L.pass_of = (unsigned short*)(L.last_fu + L.n4);
+    L.hkey = (unsigned*)((unsigned char*)L.pass_of + ((L.n4 * 2 + 15) & ~15));
+    L.hfu = L.hkey + HS;
+    L.hcnt = L.hfu + HS;
+    L.n_pass = (int*)(L.hcnt + HS);
+    return L;
+}
+
+// per-tile words of a new row (the barrier at the end of the previous row precedes; the caller's barrier follows)
+template <int BD>
+__device__ __forceinline__ void trans_big_clear(const TransBigLds& L, double* acc) {
+    const int tid = threadIdx.x;
+    const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u), zeros = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = tid; i < L.n4 / 4; i += BD) {
+        ((uint4*)L.first_u)[i] = ones; ((uint4*)L.m_cnt)[i] = zeros; ((uint4*)L.k_cnt)[i] = zeros; ((uint4*)L.last_fu)[i] = zeros;
+    }
+    if (tid == 0) ((unsigned long long*)acc)[16] = 0ull;
+}
+
+// step (1) for sample u of the row (its rank in the row's order): source tile pa, destination tile cb, both >= 0 if and only
+// if the sample is present in both frames (entropy_utils.py:259-261).  Every lane of the wave calls it.  Returns the packed pair.
+__device__ __forceinline__ unsigned trans_big_count(const TransBigLds& L, double* acc, unsigned u, int pa, int cb) {
+    unsigned packed = EMPTY_KEY;
+    if (pa >= 0 && cb >= 0) {
+        packed = ((unsigned)pa << 16) | (unsigned)cb;
+        if (L.first_u[pa] > u) atomicMin(&L.first_u[pa], u);
+        atomicAdd(&L.m_cnt[pa], 1u);
+    }
+    const unsigned long long both = __ballot(packed != EMPTY_KEY);
+    if (lane_id() == 0 && both) atomicAdd((unsigned long long*)acc + 16, (unsigned long long)__popcll(both));
+    return packed;
+}
+
+// Everything after step (1), which left pc[u] = the packed pair of sample u (u < U; each thread wrote the words u = tid,
+// tid + BD, ... it reads back here) and first_u / m_cnt final behind a barrier: the source counts, the ranges of source
+// tiles, steps (2)-(5) once per range over the HS = 1 << LG slot hash, and the row's outputs.  cap = the bucket bound of a
+// range; the caller guarantees cap + n <= 0.6 HS, or that all of the row's samples fit the hash (then any cap >= U).
+// Samples u < 2^19 (user << 13 | slot), tiles < 4096 (the multi-pass packing).  All threads of the workgroup call it; the
+// barrier that ends it lets the caller start the next row.  A pure function of the row's (pa, cb) sequence, BD and n.
+template <int BD, int LG>
+__device__ __forceinline__ void trans_big_finish(const TransBigLds& L, unsigned* pc, int U, int n, int cap, bool tab,
+                                                 const double* log2_tab, double hmax_n, double* acc, long r, double* ent_k,
+                                                 int32_t* srccount, int32_t* common, int32_t* status) {
+    constexpr int HS = 1 << LG, NW = BD / WAVE;
+    constexpr unsigned hs_shift = 32 - LG;
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    unsigned *first_u = L.first_u, *m_cnt = L.m_cnt, *k_cnt = L.k_cnt, *last_fu = L.last_fu;
+    unsigned short* pass_of = L.pass_of;
+    unsigned *hkey = L.hkey, *hfu = L.hfu, *hcnt = L.hcnt;
+    // user count per source tile (m_cnt is final here).  Written for EVERY tile in a loop of its own: the passes below
+    // only visit tiles with pass_of[t] < n_pass, and empty tiles behind the last populated one get pass_of = n_pass
+    // when the row's bucket bound is an exact multiple of cap.
+    if (srccount)
+        for (int t = tid; t < n; t += BD) srccount[r * (long)n + t] = (int)m_cnt[t];
+    // ---- ranges of source tiles: tile t goes to pass floor(bound of the tiles before it / cap), bound = min(m, n)
+    if (wv == 0) {
+        unsigned carry = 0u;
+        for (int t0 = 0; t0 < n; t0 += WAVE) {
+            const int t = t0 + lane;
+            const unsigned b = t < n ? min(m_cnt[t], (unsigned)n) : 0u;
+            unsigned v = b;
+#pragma unroll
+            for (int o = 1; o < WAVE; o <<= 1) {
+                const unsigned up = __shfl_up(v, o, WAVE);
+                if (lane >= o) v += up;
+            }
+            if (t < n) pass_of[t] = (unsigned short)((carry + v - b) / (unsigned)cap);
+            carry += __shfl(v, WAVE - 1, WAVE);
+        }
+        if (lane == 0) *L.n_pass = carry ? (int)((carry - 1u) / (unsigned)cap) + 1 : 1;
+    }
+    __syncthreads();
+    const int passes = *L.n_pass;
+    const int N = (int)((const unsigned long long*)acc)[16];
+    const double inv_n = 1.0 / (double)N;
+    double h = 0.0;
+    // Several passes (an audience spread over many source tiles: the late rows of a long video): every pass scans all
+    // users, so the per-user test must be cheap.  The packed pairs are rewritten once as pass << 24 | source << 12 |
+    // destination (tiles < 4096: TRANS_BIG_MAX_TILES; 0xFF = not in any pass: absent, or the first user of its source
+    // tile) and the scans of steps (2) and (3) read one word per user and touch the LDS for the users of the pass only
+    // (before: a global word, the tile's pass and its first user, per user and scan).  Each thread rewrites and later
+    // reads its own users only: no barrier.
+    const bool multi = passes > 1 && passes < 255;
+    if (multi)
+        for (int u = tid; u < U; u += BD) {
+            const unsigned key = pc[u];
+            unsigned v = EMPTY_KEY;
+            if (key != EMPTY_KEY) {
+                const unsigned src = key >> 16;
+                if (first_u[src] != (unsigned)u) v = ((unsigned)pass_of[src] << 24) | (src << 12) | (key & 0xFFFu);
+            }
+            pc[u] = v;
+        }
+    for (int q = 0; q < passes; ++q) {
+        for (int i = tid; i < HS / 4; i += BD) {
+            ((uint4*)hkey)[i] = make_uint4(~0u, ~0u, ~0u, ~0u); ((uint4*)hfu)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+            ((uint4*)hcnt)[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();
+        // ---- (2) non-first users of the range: bucket insert; the creator counts the bucket into K
+        for (int u = tid; u < U; u += BD) {
+            unsigned key = pc[u], src;
+            if (multi) {
+                if ((key >> 24) != (unsigned)q) continue;
+                key &= 0xFFFFFFu; src = key >> 12;
+            } else {
+                if (key == EMPTY_KEY) continue;
+                src = key >> 16;
+                if (first_u[src] == (unsigned)u) continue;
+                // >= 255 passes (unreachable under the host's limits U < 2^19, n <= 2800: at most 248; kept so that the
+                // kernel is right by itself): the packed form has no room for the pass, test the tile's pass here
+                if (passes > 1 && (int)pass_of[src] != q) continue;
+            }
+            unsigned slot = (key * 2654435761u) >> hs_shift;
+            for (;;) {
+                const unsigned was = atomicCAS(&hkey[slot], EMPTY_KEY, key);
+                if (was == EMPTY_KEY) { atomicAdd(&k_cnt[src], 1u); break; }      // a new destination of this source tile
+                if (was == key) break;
+                slot = (slot + 1) & (unsigned)(HS - 1);
+            }
+            if (hfu[slot] > (unsigned)u) atomicMin(&hfu[slot], (unsigned)u);
+            atomicAdd(&hcnt[slot], 1u);
+        }
+        __syncthreads();
+        // ---- (3) the first user of every bucket: latest first appearance per source tile, user << 13 | slot
+        for (int u = tid; u < U; u += BD) {
+            unsigned key = pc[u], src;
+            if (multi) {
+                if ((key >> 24) != (unsigned)q) continue;
+                key &= 0xFFFFFFu; src = key >> 12;
+            } else {
+                if (key == EMPTY_KEY) continue;
+                src = key >> 16;
+                if (first_u[src] == (unsigned)u) continue;
+                if (passes > 1 && (int)pass_of[src] != q) continue;       // as in step (2)
+            }
+            unsigned slot = (key * 2654435761u) >> hs_shift;
+            while (hkey[slot] != key) slot = (slot + 1) & (unsigned)(HS - 1);
+            if (hfu[slot] == (unsigned)u) atomicMax(&last_fu[src], ((unsigned)u << 13) | slot);
+        }
+        __syncthreads();
+        // ---- (5) cells of the range's source tiles: -(m/N) K (w/m) log2(w/m), w = the latest bucket's count
+        for (int t = tid; t < n; t += BD) {
+            if ((int)pass_of[t] != q) continue;
+            const unsigned m = m_cnt[t];
+            if (!m) continue;
+            const unsigned K = 1u + k_cnt[t];
+            const unsigned w = m <= 1u ? 1u : hcnt[last_fu[t] & 0x1FFFu];
+            const double lq = tab ? log2_tab[w] - log2_tab[m] : log2((double)w / (double)m);
+            h -= ((double)((unsigned long long)K * w) * inv_n) * lq;
+        }
+        __syncthreads();
+    }
+    h = wave_sum(h);
+    if (lane == 0) acc[wv] = h;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int i = 0; i < NW; ++i) tot += acc[i];
+        double hmax = hmax_n;
+        if (!(N > n)) {
+            const double tp = 1.0 / (double)N;          // entropy_utils.py:322-327
+            hmax = (double)N * -tp * (tab ? -log2_tab[N] : log2(tp));
+        }
+        double e = tot / hmax;
+        if (N == 0) {
+            e = __builtin_nan("");
+            if (status) atomicAdd(&status[1], 1);
+        }
+        ent_k[r] = e;
+        if (common) common[r] = N;
+    }
 }
 
 template <bool FROM_IDS>
 __global__ __launch_bounds__(TRANS_BIG_THREADS) void k_transition_big(const TransParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int HS = TRANS_BIG_HS, BD = TRANS_BIG_THREADS, NW = BD / WAVE;
-    double* acc2 = (double*)smem;                              // [2][TRANS_ACC]
-    unsigned* first_u = (unsigned*)(acc2 + 2 * TRANS_ACC);     // [n4]
-    const int n4 = (p.n + 3) & ~3;
-    unsigned* m_cnt = first_u + n4;
-    unsigned* k_cnt = m_cnt + n4;
-    unsigned* last_fu = k_cnt + n4;
-    unsigned short* pass_of = (unsigned short*)(last_fu + n4); // [n4] range (pass) of every source tile
-    unsigned* hkey = (unsigned*)((unsigned char*)pass_of + ((n4 * 2 + 15) & ~15));
-    unsigned* hfu = hkey + HS;
-    unsigned* hcnt = hfu + HS;
-    int* n_pass = (int*)(hcnt + HS);
-    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    constexpr int HS = TRANS_BIG_HS, BD = TRANS_BIG_THREADS;
+    const TransBigLds L = trans_big_carve(smem, p.n, HS);
+    const int tid = threadIdx.x, lane = lane_id();
     const size_t U4 = ((size_t)p.U + 3) & ~(size_t)3;
     unsigned* pc = p.scratch + (size_t)blockIdx.x * U4;       // [U4] the row's packed pairs
     const long R = (long)p.T - 1;
     const int cap = HS * 6 / 10 - p.n;                         // bucket bound of a range (one more tile may join: + n at most)
-    const unsigned hs_shift = 32 - 13;
     bool bad = false;
     int parity = 0;
     for (long r = blockIdx.x; r < R; r += gridDim.x, parity ^= 1) {
-        double* acc = acc2 + TRANS_ACC * parity;
-        {   // per-tile words (the barrier at the end of the previous row precedes)
-            const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u), zeros = make_uint4(0u, 0u, 0u, 0u);
-            for (int i = tid; i < n4 / 4; i += BD) {
-                ((uint4*)first_u)[i] = ones; ((uint4*)m_cnt)[i] = zeros; ((uint4*)k_cnt)[i] = zeros; ((uint4*)last_fu)[i] = zeros;
-            }
-            if (tid == 0) ((unsigned long long*)acc)[16] = 0ull;
-        }
+        double* acc = L.acc2 + TRANS_ACC * parity;
+        trans_big_clear<BD>(L, acc);
         __syncthreads();
         // ---- (1) every user: tiles of both frames, first user and user count per source tile
         for (int u = tid; u < p.U; u += BD) {
             const int ia = sample_dir<FROM_IDS, false>(p.src, r * (long)p.U + u, bad);
             const int ib = sample_dir<FROM_IDS, false>(p.src, (r + 1) * (long)p.U + u, bad);
-            unsigned packed = EMPTY_KEY;
             int pa = -1, cb = -1;
-            if (ia >= 0 && ib >= 0) {           // user present in both frames (entropy_utils.py:259-261)
-                pa = p.nearest[ia]; cb = p.nearest[ib];
-                packed = ((unsigned)pa << 16) | (unsigned)cb;
-                if (first_u[pa] > (unsigned)u) atomicMin(&first_u[pa], (unsigned)u);
-                atomicAdd(&m_cnt[pa], 1u);
-            }
-            const unsigned long long both = __ballot(packed != EMPTY_KEY);
-            if (lane == 0 && both) atomicAdd((unsigned long long*)acc + 16, (unsigned long long)__popcll(both));
-            pc[u] = packed;
+            if (ia >= 0 && ib >= 0) { pa = p.nearest[ia]; cb = p.nearest[ib]; }       // user present in both frames
+            pc[u] = trans_big_count(L, acc, (unsigned)u, pa, cb);
             if (p.pairs) {      // written once: non-temporal
                 __builtin_nontemporal_store(pa, p.pairs + (r * (long)p.U + u) * 2);
                 __builtin_nontemporal_store(cb, p.pairs + (r * (long)p.U + u) * 2 + 1);
             }
         }
         __syncthreads();
-        // user count per source tile (m_cnt is final here).  Written for EVERY tile in a loop of its own: the passes below
-        // only visit tiles with pass_of[t] < n_pass, and empty tiles behind the last populated one get pass_of = n_pass
-        // when the row's bucket bound is an exact multiple of cap.
-        if (p.srccount)
-            for (int t = tid; t < p.n; t += BD) p.srccount[r * (long)p.n + t] = (int)m_cnt[t];
-        // ---- ranges of source tiles: tile t goes to pass floor(bound of the tiles before it / cap), bound = min(m, n)
-        if (wv == 0) {
-            unsigned carry = 0u;
-            for (int t0 = 0; t0 < p.n; t0 += WAVE) {
-                const int t = t0 + lane;
-                const unsigned b = t < p.n ? min(m_cnt[t], (unsigned)p.n) : 0u;
-                unsigned v = b;
-#pragma unroll
-                for (int o = 1; o < WAVE; o <<= 1) {
-                    const unsigned up = __shfl_up(v, o, WAVE);
-                    if (lane >= o) v += up;
-                }
-                if (t < p.n) pass_of[t] = (unsigned short)((carry + v - b) / (unsigned)cap);
-                carry += __shfl(v, WAVE - 1, WAVE);
-            }
-            if (lane == 0) *n_pass = carry ? (int)((carry - 1u) / (unsigned)cap) + 1 : 1;
-        }
-        __syncthreads();
-        const int passes = *n_pass;
-        const int N = (int)((const unsigned long long*)acc)[16];
-        const double inv_n = 1.0 / (double)N;
-        const bool tab = p.U <= 4096;
-        double h = 0.0;
-        // Several passes (an audience spread over many source tiles: the late rows of a long video): every pass scans all
-        // users, so the per-user test must be cheap.  The packed pairs are rewritten once as pass << 24 | source << 12 |
-        // destination (tiles < 4096: TRANS_BIG_MAX_TILES; 0xFF = not in any pass: absent, or the first user of its source
-        // tile) and the scans of steps (2) and (3) read one word per user and touch the LDS for the users of the pass only
-        // (before: a global word, the tile's pass and its first user, per user and scan).  Each thread rewrites and later
-        // reads its own users only: no barrier.
-        const bool multi = passes > 1 && passes < 255;
-        if (multi)
-            for (int u = tid; u < p.U; u += BD) {
-                const unsigned key = pc[u];
-                unsigned v = EMPTY_KEY;
-                if (key != EMPTY_KEY) {
-                    const unsigned src = key >> 16;
-                    if (first_u[src] != (unsigned)u) v = ((unsigned)pass_of[src] << 24) | (src << 12) | (key & 0xFFFu);
-                }
-                pc[u] = v;
-            }
-        for (int q = 0; q < passes; ++q) {
-            for (int i = tid; i < HS / 4; i += BD) {
-                ((uint4*)hkey)[i] = make_uint4(~0u, ~0u, ~0u, ~0u); ((uint4*)hfu)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-                ((uint4*)hcnt)[i] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            __syncthreads();
-            // ---- (2) non-first users of the range: bucket insert; the creator counts the bucket into K
-            for (int u = tid; u < p.U; u += BD) {
-                unsigned key = pc[u], src;
-                if (multi) {
-                    if ((key >> 24) != (unsigned)q) continue;
-                    key &= 0xFFFFFFu; src = key >> 12;
-                } else {
-                    if (key == EMPTY_KEY) continue;
-                    src = key >> 16;
-                    if (first_u[src] == (unsigned)u) continue;
-                    // >= 255 passes (unreachable under the host's limits U < 2^19, n <= 2800: at most 248; kept so that the
-                    // kernel is right by itself): the packed form has no room for the pass, test the tile's pass here
-                    if (passes > 1 && (int)pass_of[src] != q) continue;
-                }
-                unsigned slot = (key * 2654435761u) >> hs_shift;
-                for (;;) {
-                    const unsigned was = atomicCAS(&hkey[slot], EMPTY_KEY, key);
-                    if (was == EMPTY_KEY) { atomicAdd(&k_cnt[src], 1u); break; }      // a new destination of this source tile
-                    if (was == key) break;
-                    slot = (slot + 1) & (unsigned)(HS - 1);
-                }
-                if (hfu[slot] > (unsigned)u) atomicMin(&hfu[slot], (unsigned)u);
-                atomicAdd(&hcnt[slot], 1u);
-            }
-            __syncthreads();
-            // ---- (3) the first user of every bucket: latest first appearance per source tile, user << 13 | slot
-            for (int u = tid; u < p.U; u += BD) {
-                unsigned key = pc[u], src;
-                if (multi) {
-                    if ((key >> 24) != (unsigned)q) continue;
-                    key &= 0xFFFFFFu; src = key >> 12;
-                } else {
-                    if (key == EMPTY_KEY) continue;
-                    src = key >> 16;
-                    if (first_u[src] == (unsigned)u) continue;
-                    // >= 255 passes (unreachable under the host's limits U < 2^19, n <= 2800: at most 248; kept so that the
-                    // kernel is right by itself): the packed form has no room for the pass, test the tile's pass here
-                    if (passes > 1 && (int)pass_of[src] != q) continue;
-                }
-                unsigned slot = (key * 2654435761u) >> hs_shift;
-                while (hkey[slot] != key) slot = (slot + 1) & (unsigned)(HS - 1);
-                if (hfu[slot] == (unsigned)u) atomicMax(&last_fu[src], ((unsigned)u << 13) | slot);
-            }
-            __syncthreads();
-            // ---- (5) cells of the range's source tiles: -(m/N) K (w/m) log2(w/m), w = the latest bucket's count
-            for (int t = tid; t < p.n; t += BD) {
-                if ((int)pass_of[t] != q) continue;
-                const unsigned m = m_cnt[t];
-                if (!m) continue;
-                const unsigned K = 1u + k_cnt[t];
-                const unsigned w = m <= 1u ? 1u : hcnt[last_fu[t] & 0x1FFFu];
-                const double lq = tab ? p.log2_tab[w] - p.log2_tab[m] : log2((double)w / (double)m);
-                h -= ((double)((unsigned long long)K * w) * inv_n) * lq;
-            }
-            __syncthreads();
-        }
-        h = wave_sum(h);
-        if (lane == 0) acc[wv] = h;
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0;
-            for (int i = 0; i < NW; ++i) tot += acc[i];
-            double hmax = p.hmax;
-            if (!(N > p.n)) {
-                const double tp = 1.0 / (double)N;          // entropy_utils.py:322-327
-                hmax = (double)N * -tp * (tab ? -p.log2_tab[N] : log2(tp));
-            }
-            double e = tot / hmax;
-            if (N == 0) {
-                e = __builtin_nan("");
-                if (p.status) atomicAdd(&p.status[1], 1);
-            }
-            p.ent_k[r] = e;
-            if (p.common) p.common[r] = N;
-        }
+        trans_big_finish<BD, 13>(L, pc, p.U, p.n, cap, p.U <= 4096, p.log2_tab, p.hmax, acc, r, p.ent_k, p.srccount, p.common,
+                                 p.status);
     }
     if (p.status) {
         const unsigned long long anybad = __ballot(bad);

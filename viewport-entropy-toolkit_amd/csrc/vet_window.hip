@@ -12,10 +12,13 @@
 // A row is a pure function of the plan and of its frames' samples: the FP64 sums are re-added from the window's first frame
 // in ascending frame order for every row (never a running sum with subtractions), the integer counts are exact under add
 // and subtract, and every reduction runs in one wave in fixed lane order.
+// The same unit holds the sliding-window TRANSITION entropy behind vet_transition_entropy_windowed*: stage 1 is k_window_tiles
+// again (every sample quantised and looked up once), stage 2 is k_window_transition below.
 // No CPU compute path; nothing here reads the environment.
 #include "vet_host.hpp"
 #include "vet_common.hpp"
 #include "vet_finalize.hpp"
+#include "vet_transition.hpp"
 
 #include <algorithm>
 
@@ -203,6 +206,64 @@ __global__ __launch_bounds__(64) void k_window_entropy_c(const WindowCParams p) 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_window_transition — stage 2 of the windowed transition entropy: compute_transition_entropy (entropy_utils.py:213-332) on
+// the pooled (pair, user) samples of frame pairs [r * stride, r * stride + window), pair-major then user order, per row r.
+// tiles[T][U] is k_window_tiles' output for this lattice, so the pooled samples of a row are a CONTIGUOUS slice of it:
+// sample q in [0, window * U) has the source tile tiles[f0 * U + q] and the destination tile tiles[f0 * U + q + U],
+// f0 = r * stride, and is pooled when both are >= 0.  With "user index" = q the row algorithm is k_transition_big's,
+// device code shared (vet_transition.hpp: trans_big_clear / trans_big_count / trans_big_finish): per-tile words and the
+// bucket hash in LDS, source tiles cut into passes where sum min(m, n) exceeds the hash.
+// Every row is computed from scratch.  There is NO running add / subtract across overlapping rows: K and w of a source
+// tile depend on which sample of the window is the tile's first and on the order of first appearance of its destinations,
+// so a frame that leaves changes the roles of the samples that stay — the statistic is not decomposable over frames.
+// Persistent workgroups take rows blockIdx, blockIdx + gridDim, ...  Workgroup and hash are sized by the pooled samples
+// W = window * U alone (never by the stride, the row count or the device), so a row's bits are a pure function of the
+// plan and its window + 1 frames:
+//   W <= 256: 64 threads, 512 slots | W <= 1024: 256 threads, 2048 slots | W <= 2048: 256 threads, 4096 slots — the hash
+//   holds every sample (2 W <= slots: one pass) and the packed pairs stay in LDS behind the hash;
+//   else 1024 threads, 8192 slots, passes by k_transition_big's bound, packed pairs in a per-workgroup global slice.
+// Integer atomics only; the FP64 cell sum per thread in tile order, wave_sum's butterfly, the waves in order.
+// LDS: trans_big_lds_bytes(n, slots) | pc u32 [W4] (the three small shapes)
+// ------------------------------------------------------------------------------------------
+struct WindowTransParams {
+    const int32_t* tiles;        // [T][U]
+    int U, n;
+    double hmax;
+    int window, stride;
+    long R;
+    double* ent;                 // [R]
+    int32_t* srccount;           // [R][n] or null
+    int32_t* samples;            // [R] or null
+    int32_t* status;             // [2] or null
+    const double* log2_tab;      // [4097] log2(k)
+    uint32_t* scratch;           // 1024-thread shape: per-workgroup slices of W4 words
+};
+
+template <int BD, int LG>
+__global__ __launch_bounds__(BD) void k_window_transition(const WindowTransParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int HS = 1 << LG;
+    constexpr bool SMALL = LG < 13;
+    const TransBigLds L = trans_big_carve(smem, p.n, HS);
+    const int tid = threadIdx.x;
+    const int W = p.window * p.U;
+    const size_t W4 = ((size_t)W + 3) & ~(size_t)3;
+    unsigned* pc = SMALL ? (unsigned*)(smem + trans_big_lds_bytes(p.n, HS)) : p.scratch + (size_t)blockIdx.x * W4;
+    const int cap = SMALL ? 0x7FFFFFFF : HS * 6 / 10 - p.n;
+    const bool tab = W <= 4096;
+    int parity = 0;
+    for (long r = blockIdx.x; r < p.R; r += gridDim.x, parity ^= 1) {
+        double* acc = L.acc2 + TRANS_ACC * parity;
+        trans_big_clear<BD>(L, acc);
+        __syncthreads();
+        const int32_t* src = p.tiles + r * (long)p.stride * p.U;
+        for (int q = tid; q < W; q += BD) pc[q] = trans_big_count(L, acc, (unsigned)q, src[q], src[q + p.U]);
+        __syncthreads();
+        trans_big_finish<BD, LG>(L, pc, W, p.n, cap, tab, p.log2_tab, p.hmax, acc, r, p.ent, p.srccount, p.samples, p.status);
+    }
+}
+
 }  // namespace vet
 
 namespace vh {
@@ -317,11 +378,101 @@ int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, 
     return VET_OK;
 }
 
+// ---- windowed transition entropy
+// Shape of k_window_transition for W pooled samples per row (the kernel's header): a function of W alone
+struct WindowTransShape { int threads, lg; const void* fn; };
+WindowTransShape window_trans_shape(long W) {
+    if (W <= 256) return {64, 9, (const void*)vet::k_window_transition<64, 9>};
+    if (W <= 1024) return {256, 11, (const void*)vet::k_window_transition<256, 11>};
+    if (W <= 2048) return {256, 12, (const void*)vet::k_window_transition<256, 12>};
+    return {vet::TRANS_BIG_THREADS, 13, (const void*)vet::k_window_transition<vet::TRANS_BIG_THREADS, 13>};
+}
+size_t window_trans_lds(const WindowTransShape& g, int n, long W) {
+    return vet::trans_big_lds_bytes(n, 1 << g.lg) + (g.lg < 13 ? (size_t)((W + 3) & ~3L) * 4 : 0);
+}
+
+int check_window_trans_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
+    int rc = check_run_args(pl, U, T, out);
+    if (rc) return rc;
+    if (T < 2) return fail(VET_ERR_INVALID, "windowed transition entropy needs at least two frames (got %d)", T);
+    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame pair (got %d)", window);
+    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame pair (got %d)", stride);
+    if (window > T - 1)
+        return fail(VET_ERR_INVALID, "window of %d frame pairs is longer than the video's %d frame pairs", window, T - 1);
+    // the kernel's packing, before anything is allocated or launched
+    if ((long)window * U >= (1L << 19))
+        return fail(VET_ERR_UNSUPPORTED, "windowed transition: window * n_users = %ld pooled samples per row, the kernel packs "
+                    "fewer than 2^19", (long)window * U);
+    for (const auto& L : pl->lat)
+        if (L.n > vet::TRANS_BIG_MAX_TILES)
+            return fail(VET_ERR_UNSUPPORTED, "windowed transition: lattice of %d tiles (at most %d)", L.n, vet::TRANS_BIG_MAX_TILES);
+    return VET_OK;
+}
+
+template <bool FROM_IDS>
+int launch_window_transition(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
+                             int stride, double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status,
+                             hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const int K = (int)pl->lat.size();
+    const long R = (long)vet_window_rows(T - 1, window, stride), W = (long)window * U;
+    const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    const WindowTransShape g = window_trans_shape(W);
+    // persistent workgroups: as many as LDS and wave slots let run at once, at most one per row
+    size_t lds_most = 0;
+    for (const auto& L : pl->lat) lds_most = std::max(lds_most, window_trans_lds(g, L.n, W));
+    if (lds_most > kWholeLds) return fail(VET_ERR_UNSUPPORTED, "windowed transition: %zu B of LDS (max %zu)", lds_most, kWholeLds);
+    long per_cu = std::min<long>({(long)(kWholeLds / lds_most), 32 / (g.threads / vet::WAVE), 16});
+    const long grid = std::max<long>(1, std::min<long>(R, (long)c->n_cu * per_cu));
+    // workspace: per-lattice rows (K > 1) | one lattice's tiles [T][U], reused lattice after lattice on the stream | the
+    // packed pairs of the 1024-thread shape
+    const size_t ent_b = pad16(K > 1 ? (size_t)K * R * sizeof(double) : 0), tiles_b = pad16((size_t)T * U * sizeof(int32_t));
+    const size_t pc_b = g.lg < 13 ? 0 : (size_t)grid * ((W + 3) & ~3L) * 4;
+    int rc = ensure_ws(c, ent_b + tiles_b + pc_b);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    double* ent_k = K > 1 ? (double*)ws : d_entropy;
+    int32_t* tiles = (int32_t*)(ws + ent_b);
+    for (int k = 0; k < K; ++k) {
+        const Lattice& L = pl->lat[k];
+        {   // stage 1, charged to k_spatial as in the spatial windowed call
+            const int frames_per_wg = 4;
+            vet::WindowTilesParams q{};
+            q.src = src; q.U = U; q.T = T;
+            q.nearest = L.d_nearest; q.tiles = tiles;
+            q.status = k == 0 ? d_status : nullptr;
+            ProfScope ps(c, s, KID_SPATIAL);
+            hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, dim3((unsigned)((T + frames_per_wg - 1) / frames_per_wg)),
+                               dim3(frames_per_wg * vet::WAVE), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+        vet::WindowTransParams q{};
+        q.tiles = tiles; q.U = U; q.n = L.n; q.hmax = L.hmax;
+        q.window = window; q.stride = stride; q.R = R;
+        q.ent = ent_k + (size_t)k * R;
+        q.srccount = k == 0 ? d_srccount : nullptr; q.samples = k == 0 ? d_samples : nullptr; q.status = k == 0 ? d_status : nullptr;
+        q.log2_tab = c->d_log2;
+        q.scratch = (uint32_t*)(ws + ent_b + tiles_b);
+        ProfScope ps(c, s, KID_TRANSITION);
+        void* args[] = {(void*)&q};
+        HIP_TRY(hipLaunchKernel(g.fn, dim3((unsigned)grid), dim3(g.threads), args, window_trans_lds(g, L.n, W), s));
+        HIP_TRY(hipGetLastError());
+    }
+    if (K > 1) {
+        ProfScope ps(c, s, KID_FINALIZE);
+        hipLaunchKernelGGL(vet::k_finalize, dim3(grid_for(R, 256, c->n_cu)), dim3(256), 0, s, (const double*)ent_k, K, R, d_entropy);
+        HIP_TRY(hipGetLastError());
+    }
+    return VET_OK;
+}
+
 }  // namespace
 
 int window_set_attrs(vet_ctx* c) {
     HIP_TRY(hipFuncSetAttribute((const void*)vet::k_window_entropy_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_max));
     HIP_TRY(hipFuncSetAttribute((const void*)vet::k_window_entropy_c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_max));
+    for (long W : {1L, 257L, 1025L, 2049L})
+        HIP_TRY(hipFuncSetAttribute(window_trans_shape(W).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWholeLds));
     return VET_OK;
 }
 
@@ -353,6 +504,26 @@ int vet_spatial_entropy_windowed_ids(vet_plan* pl, const int32_t* d_ids, int U, 
     if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
     return launch_windowed<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
                                  stream ? (hipStream_t)stream : pl->ctx->stream);
+}
+
+int vet_transition_entropy_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
+                                    double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status, void* stream) {
+    int rc = check_window_trans_args(pl, U, T, window, stride, d_entropy);
+    if (rc) return rc;
+    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_transition_entropy_windowed_ids");
+    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
+    return launch_window_transition<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_srccount, d_samples,
+                                           d_status, stream ? (hipStream_t)stream : pl->ctx->stream);
+}
+
+int vet_transition_entropy_windowed_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride,
+                                        double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status,
+                                        void* stream) {
+    int rc = check_window_trans_args(pl, U, T, window, stride, d_entropy);
+    if (rc) return rc;
+    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
+    return launch_window_transition<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_srccount, d_samples,
+                                          d_status, stream ? (hipStream_t)stream : pl->ctx->stream);
 }
 
 }  // extern "C"

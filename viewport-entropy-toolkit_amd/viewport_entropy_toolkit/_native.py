@@ -108,6 +108,9 @@ SIGNATURES = {
     "vet_spatial_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_transition_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_transition_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_transition_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -579,6 +582,27 @@ class Plan:
             _check(self.lib, rc)
         return dict(entropy=ent, pairs=pairs, srccount=src, common=common, code=rc)
 
+    def transition_windowed(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
+        """Pooled transition entropy of sliding windows of frame pairs (include/vet.h: vet_transition_entropy_windowed): row r
+        pools the transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1).  ``window`` and
+        ``stride`` count frame pairs.  Returns dict(entropy[R], srccount[R,n0]|None, samples[R], code),
+        R = (T - 1 - window) // stride + 1."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        if window is None:
+            raise ValueError("window (a number of frame pairs) is required")
+        window, stride = int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T - 1, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames - 1 and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        ent = np.empty(R, dtype=np.float64)
+        src = np.empty((R, self.n_tiles[0]), dtype=np.int32) if want_srccount else None
+        samples = np.empty(R, dtype=np.int32)
+        rc = self.lib.vet_transition_entropy_windowed_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                                           _ptr(ent), _ptr(src), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_EMPTY, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(entropy=ent, srccount=src, samples=samples, code=rc)
+
     def spatial_resident(self, mu=None, mv=None, ids=None, check=True):
         """Like ``spatial`` but only entropy[T] and present[T] come back; the tile assignments and weights stay
         on the device in ``result`` (a ``DeviceResult``) and are fetched by row on demand."""
@@ -683,6 +707,12 @@ class Plan:
         _check(self.lib, self.lib.vet_spatial_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
                                                                int(stride), d_entropy, d_weights or None, d_samples or None,
                                                                d_status or None, _stream(stream)))
+
+    def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                   d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
+        _check(self.lib, self.lib.vet_transition_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
+                                                                  int(stride), d_entropy, d_srccount or None,
+                                                                  d_samples or None, d_status or None, _stream(stream)))
 
     def transition_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, d_entropy: int, d_pairs: int = 0,
                           d_srccount: int = 0, d_common: int = 0, d_status: int = 0, stream=None):

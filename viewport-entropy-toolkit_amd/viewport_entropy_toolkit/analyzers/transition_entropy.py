@@ -85,6 +85,62 @@ class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         })
         return self._entropy_results
 
+    @classmethod
+    def _empty_window_error(cls, kind, a, b, window: int, stride: int) -> Exception:
+        """The exception the reference raises on the pooled dicts of the FIRST window without a common sample: no sample at
+        all in the window's prior frames or in its current frames -> ValidationError("Empty vector dictionary")
+        (utilities/entropy_utils.py:239-240); otherwise the division by the zero total weight (:322-327)."""
+        present = cls._presence(kind, a, b)
+        common = (present[:-1] & present[1:]).any(axis=1)
+        for f0 in range(0, len(common) - window + 1, stride):
+            if not common[f0:f0 + window].any():
+                if not present[f0:f0 + window].any() or not present[f0 + 1:f0 + window + 1].any():
+                    return ValidationError("Empty vector dictionary")
+                break
+        return ZeroDivisionError("division by zero")
+
+    def compute_windowed_entropy(self, window: int, stride: int = 1) -> pd.DataFrame:
+        """Transition entropy of the transitions pooled over sliding windows of frame pairs: row r puts the (t -> t+1)
+        nearest-tile transition of every user present in both frames, for every pair of [r * stride, r * stride + window),
+        into ONE call of the reference's ``compute_transition_entropy`` (both dicts keyed per (pair, user), pair-major then
+        user order), averaged over the lattices — not the mean of the per-pair entropies.  ``window`` and ``stride`` count
+        frame pairs, i.e. rows of ``compute_entropy``'s result (0.1 s each at the reference's sampling): ``window=20,
+        stride=1`` is a 2-second window every frame.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone)
+        with ``time`` / ``time_end`` (the ``time`` ``compute_entropy`` gives the window's first / last pair), ``entropy``,
+        ``samples`` (pooled (pair, user) samples of the window) and ``tile_weights`` (lattice 0's pooled count per source
+        tile, in the shape of ``compute_entropy``'s column).  Raises ``ValidationError`` before data is loaded, ``ValueError``
+        for an illegal ``window`` / ``stride``, and for a window without a common sample what the reference raises on its
+        pooled dicts (``ValidationError("Empty vector dictionary")`` or ``ZeroDivisionError``)."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(window, stride, len(times) - 1)
+        try:
+            if kind == "grid":
+                res = self._get_plan().transition_windowed(mu=a, mv=b, window=window, stride=stride, want_srccount=True)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.transition_windowed(ids=a, window=window, stride=stride, want_srccount=True)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            if e.code == _native.VET_ERR_EMPTY:
+                raise self._empty_window_error(kind, a, b, window, stride)
+            raise
+        tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
+        first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
+        pair_time = np.asarray(times)[1:]
+        return pd.DataFrame({
+            "time": pair_time[first],
+            "time_end": pair_time[first + window - 1],
+            "entropy": res["entropy"],
+            "samples": res["samples"],
+            "tile_weights": FrameDictArray(res["srccount"], lambda row: TileWeights(tiles, row, as_int=True)),
+        })
+
     def _frame_present(self) -> np.ndarray:
         if self._present is None:
             self._present = self._prior_frame_present(*self._present_samples)
