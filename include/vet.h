@@ -52,7 +52,8 @@ extern "C" {
                            vet_heatmap_create_latlon / vet_heatmap_render_binned(_host) (lat/lon cell
                            heatmaps of naive plans) added the same way; so were vet_window_rows and the
                            vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows), and
-                          then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) */
+                          then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) and
+                          the vet_user_entropy* entry points (each viewer's own histogram over time) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -314,6 +315,56 @@ int vet_spatial_entropy_windowed_ids(vet_plan *plan, const int32_t *d_ids, int n
 int vet_spatial_entropy_windowed_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
                                       int n_users, int n_frames, int window, int stride, double *h_entropy,
                                       double *h_weights, int32_t *h_samples);
+
+/* ---- per-viewer spatial entropy: each user's own tile histogram over time ------------------------
+ * The transposed question of the windowed call: not "how spread out is the audience over these frames" but "how much of the
+ * sphere does this viewer visit".  For window = w, stride = s and n_frames = T there are R = vet_window_rows(T, w, s) rows per
+ * user; row (u, r) covers frames [r*s, r*s + w) of user u.  Its value is, for every lattice of the plan, what
+ * compute_spatial_entropy (utilities/entropy_utils.py:147-211; naive plans: compute_naive_spatial_entropy, :383-452) returns
+ * for ONE dict that holds user u's present samples of those frames in ascending frame order, then the mean over the lattices
+ * as compute_entropy takes it.  So, with `samples` = the user's present samples of the row:
+ *   weighted: the keys are the tiles with distance < fov/2 of some sample of the row, the normaliser is log2(n); a key whose
+ *     weights are all 0.0 makes the row NaN (0 * log2 0);
+ *   unweighted and binned (naive) lattices: every sample adds 1 to its tile / bin; the normaliser is log2(n) if
+ *     use_weight_distribution or samples > n, else log2(samples); one sample in the row gives the reference's NaN (0 / 0);
+ *   a row in which the user has no sample: NaN in d_entropy, 0 in d_samples and d_status[1] += 1.  Viewers join and leave, so
+ *     such rows are data, not errors: the _host entry does NOT turn them into VET_ERR_EMPTY.
+ * window = n_frames is the whole video (R = 1).  Outputs are user-major:
+ *   d_entropy [U][R]
+ *   d_weights [U][R][n_0]  lattice 0's histogram of the row, encoded and toleranced as vet_spatial_entropy's d_weights (-0.0 =
+ *                          key with the value 0.0, +0.0 = no key)                                                  (nullable)
+ *   d_samples [U][R]       the user's present samples of the row                                                   (nullable)
+ *   d_status  [2]          {bad, #rows without a sample}; the call ADDS, the caller zeroes                           (nullable)
+ * Two stages:
+ *   1 k_user_dirs: every sample is quantised once and its direction id written transposed, [U][T] i32 (-1 absent), through a
+ *     64 x 64 LDS tile (both the [T][U] read and the [U][T] write are coalesced).  d_status[0] is raised as k_window_tiles
+ *     raises it.  That array and, for plans of several lattices, K * U * R * 8 bytes of per-lattice rows are the context's
+ *     grow-only workspace: no allocation in steady state;
+ *   2 per (user, row) and lattice, over a contiguous slice of the user's ids.  Weighted Fibonacci lattices (k_user_entropy_w):
+ *     one workgroup per row; its NW waves take contiguous shares of the row's frames, each adds the exact FP64 weight rows
+ *     (`dtable`'s, built once per plan and lattice) of its frames IN ASCENDING FRAME ORDER into its own histogram, the waves'
+ *     histograms are added in wave order, then `dtable`'s epilogue in one wave.  Every row is summed from scratch (window
+ *     row-adds per row whatever the overlap); NW is 1 up to 64 frames per row, 2 up to 128, else 4 (fewer where NW * n * 8
+ *     bytes of histograms do not fit the LDS) — a function of the window and the plan alone.  There is no other formulation:
+ *     where a lattice's exact rows do not fit the device the call fails with VET_ERR_UNSUPPORTED.  Unweighted and binned
+ *     lattices (k_user_entropy_c): a wave owns a run of consecutive rows of one user, keeps the counts (u32 per tile) in LDS,
+ *     adds the frames that enter and subtracts those that leave (exact), then the windowed call's integer epilogue.
+ * A row is therefore a pure function of the plan and of its own samples: the same bits whatever stride selected it, wherever
+ * its frames lie in the call, whichever other users the call holds, from run to run, and between the ids and the grid entry
+ * points.
+ * Limits: as the windowed call's (n * 4 bytes of LDS for a counting lattice, n * 8 for a weighted one); U * R < 2^31.
+ * VET_ERR_INVALID: window < 1, stride < 1, window > n_frames (and what vet_spatial_entropy refuses).
+ * The kernels have no profile id of their own: stage 1 is charged to k_spatial, the weighted stage 2 to k_weights, the
+ * counting stage 2 and the mean over the lattices to k_finalize.  Asynchronous on `stream` like vet_spatial_entropy. */
+int vet_user_entropy(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                     double *d_entropy, double *d_weights, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_user_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                         double *d_entropy, double *d_weights, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_user_entropy_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                          int window, int stride, double *h_entropy, double *h_weights, int32_t *h_samples);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

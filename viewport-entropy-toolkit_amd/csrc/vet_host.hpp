@@ -6,11 +6,12 @@
 //   vet_spatial.hip     launch logic of the spatial-entropy kernels (single videos and batches)
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
 //   vet_window.hip      the sliding-window spatial- and transition-entropy kernels (frame windows pooled) and their launch logic
+//   vet_user.hip        the per-viewer spatial-entropy kernels (one histogram per user over time) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
 //                       for heatmaps and tilings), device-resident results, the heatmap and tiling handles (no kernels)
-// Every kernel header is included by exactly one of them.  There is no CPU compute path anywhere.
+// Every kernel header is included by exactly one of them (vet_user.hip shares the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp).  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
 #include "vet_layout.hpp"
@@ -349,5 +350,6 @@ int tiling_render(vet_ctx* c, const TilingGeom& g, const TilingCam* d_cam, int T
 int spatial_set_attrs(vet_ctx* c);
 int transition_set_attrs(vet_ctx* c);
 int window_set_attrs(vet_ctx* c);
+int user_set_attrs(vet_ctx* c);
 
 }  // namespace vh

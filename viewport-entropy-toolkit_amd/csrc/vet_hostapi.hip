@@ -476,6 +476,41 @@ int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const do
     return run.finish("%d window(s) without any sample (Empty vector dictionary)");
 }
 
+// Per-viewer spatial entropy with host buffers (include/vet.h): staged like the windowed entry, n_users * vet_window_rows output
+// rows, user-major.  Rows without a sample are data (NaN, samples 0): only VET_ERR_RANGE is decoded from the status words.
+int vet_user_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                          int stride, double* h_entropy, double* h_weights, int32_t* h_samples) {
+    int rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    if (rc) return rc;
+    const int64_t R = vet_window_rows(T, window, stride);
+    if (R < 0)
+        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
+                    stride, T);
+    const size_t rows = (size_t)R * U, w_bytes = rows * pl->lat[0].n * 8;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    hipStream_t s = run.s;
+    double *ent = nullptr, *wt = nullptr;
+    int32_t* cnt = nullptr;
+    POOL(SLOT_ENTROPY, rows * 8, ent);
+    if (h_weights) POOL(SLOT_OUT1, w_bytes, wt);
+    POOL(SLOT_COUNT, rows * 4, cnt);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = run.ids ? vet_user_entropy_ids(pl, run.ids, U, T, window, stride, ent, wt, cnt, run.status, s)
+                 : vet_user_entropy(pl, run.mu, run.mv, U, T, window, stride, ent, wt, cnt, run.status, s);
+    if (rc) return run.drain(rc);
+    HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
+    if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, wt, w_bytes, hipMemcpyDeviceToHost, s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
+    rc = run.sync(true);
+    if (rc) return rc;
+    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
+    return VET_OK;
+}
+
 // Sliding-window transition entropy with host buffers (include/vet.h): R = vet_window_rows over the T - 1 frame pairs
 int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
                                          int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {

@@ -623,6 +623,7 @@ int vet_plan_create(vet_ctx* c, const vet_plan_desc* d, vet_plan** out) {
         int rc = spatial_set_attrs(c);
         if (!rc) rc = transition_set_attrs(c);
         if (!rc) rc = window_set_attrs(c);
+        if (!rc) rc = user_set_attrs(c);
         if (rc) return cleanup(rc);
         c->attrs_set = true;
     }

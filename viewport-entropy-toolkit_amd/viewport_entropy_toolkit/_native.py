@@ -108,6 +108,9 @@ SIGNATURES = {
     "vet_spatial_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_user_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_user_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_user_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vet_transition_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -568,6 +571,26 @@ class Plan:
             _check(self.lib, rc)
         return dict(entropy=ent, weights=weights, samples=samples, code=rc)
 
+    def spatial_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_weights=False, check=True):
+        """Each user's own tile histogram over time (include/vet.h: vet_user_entropy): row (u, r) pools user u's present
+        samples of frames [r * stride, r * stride + window) into one histogram per lattice.  ``window=None`` is the whole
+        video (one row per user).  Returns dict(entropy[U,R], weights[U,R,n0]|None, samples[U,R], code),
+        R = (T - window) // stride + 1.  Rows in which the user has no sample are NaN with ``samples`` 0 — data, never an
+        error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        window, stride = T if window is None else int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        ent = np.empty((U, R), dtype=np.float64)
+        weights = np.empty((U, R, self.n_tiles[0]), dtype=np.float64) if want_weights else None
+        samples = np.empty((U, R), dtype=np.int32)
+        rc = self.lib.vet_user_entropy_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                            _ptr(ent), _ptr(weights), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(entropy=ent, weights=weights, samples=samples, code=rc)
+
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -707,6 +730,13 @@ class Plan:
         _check(self.lib, self.lib.vet_spatial_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
                                                                int(stride), d_entropy, d_weights or None, d_samples or None,
                                                                d_status or None, _stream(stream)))
+
+    def spatial_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                d_entropy: int, d_weights: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
+        """Outputs are user-major: d_entropy [U][R], d_weights [U][R][n0], d_samples [U][R] (include/vet.h: vet_user_entropy)."""
+        _check(self.lib, self.lib.vet_user_entropy(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
+                                                   d_entropy, d_weights or None, d_samples or None, d_status or None,
+                                                   _stream(stream)))
 
     def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

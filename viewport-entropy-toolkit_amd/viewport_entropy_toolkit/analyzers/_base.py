@@ -222,5 +222,22 @@ class _EntropyAnalyzerBase:
             raise ValueError(f"window of {window} frames is longer than the data's {n_frames} frames")
         return window, stride
 
+    @staticmethod
+    def _user_frame(names, times, window: int, stride: int, res: dict, tile_weights=None) -> pd.DataFrame:
+        """The per-viewer result as a DataFrame, user-major: one row per (user, r) in the order of ``res``'s [U][R] arrays."""
+        U, R = res["entropy"].shape
+        first = np.tile(np.arange(R, dtype=np.int64) * stride, U)
+        times = np.asarray(times)
+        cols = {
+            "user": np.repeat(np.asarray(list(names), dtype=object), R),
+            "time": times[first],
+            "time_end": times[first + window - 1],
+            "entropy": res["entropy"].reshape(-1),
+            "samples": res["samples"].reshape(-1),
+        }
+        if tile_weights is not None:
+            cols["tile_weights"] = tile_weights
+        return pd.DataFrame(cols)
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

@@ -126,6 +126,27 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             "samples": res["samples"],
         })
 
+    def compute_user_entropy(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """How many lat/lon cells each viewer visits: row (user, r) counts that user's present samples of frames
+        [r * stride, r * stride + window) in ONE cell histogram and takes ``compute_naive_spatial_entropy``'s normalised
+        entropy of it.  ``window=None`` is the whole video (one row per user); ``window`` and ``stride`` count frames.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, user-major, one row per (user, r): ``user``,
+        ``time`` / ``time_end`` (of the row's first / last frame), ``entropy`` and ``samples``.  A row in which the user has no
+        sample is NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is loaded and for
+        samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
+        if not self._data_cache or self._dense is None:
+            raise ValidationError("No data available. Call process_directory first.")
+        times, mu, mv, names = self._dense
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            res = self._naive_plan().spatial_per_user(mu=mu, mv=mv, window=window, stride=stride)
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._user_frame(names, times, window, stride, res)
+
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
     def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
         plan, _, _, tw, th = self._heatmap_source

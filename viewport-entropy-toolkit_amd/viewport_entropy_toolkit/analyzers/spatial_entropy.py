@@ -107,5 +107,38 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             "tile_weights": FrameDictArray(res["weights"], lambda row: TileWeights(tiles, row)),
         })
 
+    def compute_user_entropy(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """How much of the sphere each viewer visits: row (user, r) puts that user's present samples of frames
+        [r * stride, r * stride + window) into ONE histogram per lattice and takes the reference's normalised entropy of it
+        (``compute_spatial_entropy`` on a dict holding those samples in frame order), averaged over the lattices.
+        ``window=None`` is the whole video (one row per user); ``window`` and ``stride`` count frames, i.e. rows of
+        ``vectors_df``.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone),
+        user-major, one row per (user, r): ``user`` (the column name from ingest), ``time`` / ``time_end`` (of the row's first /
+        last frame), ``entropy``, ``samples`` (the user's present samples of the row) and ``tile_weights`` (lattice 0's
+        histogram, the reference's dict-of-``Vector`` shape).  A row in which the user has no sample is NaN with ``samples`` 0
+        — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1],
+        ``ValueError`` for an illegal ``window`` / ``stride``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            if kind == "grid":
+                res = self._get_plan().spatial_per_user(mu=a, mv=b, window=window, stride=stride, want_weights=True)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.spatial_per_user(ids=a, window=window, stride=stride, want_weights=True)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
+        weights = res["weights"].reshape(-1, res["weights"].shape[-1])
+        return self._user_frame(names, times, window, stride, res,
+                                FrameDictArray(weights, lambda row: TileWeights(tiles, row)))
+
     def _frame_present(self):
         return self._present
