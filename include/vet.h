@@ -99,6 +99,10 @@ int vet_test_no_row_cap(vet_ctx *ctx, int on);
  * (row, nearest tile, row meta) where a capped plan also has the 4-byte one (vet_plan_record_bytes).  Read at every launch,
  * so one plan runs both kernels in one process.  Results are bit-identical either way. */
 int vet_test_rec8(vet_ctx *ctx, int on);
+/* Test switch, not a tuning knob: on != 0 makes vet_user_transition_entropy* run rows of up to 64 frame pairs through the hash
+ * kernel of the longer rows (k_user_transition) instead of k_user_transition_wave.  Read at every launch, so one plan runs
+ * both kernels in one process.  The two sum a row's cells in different orders: results agree to rounding, not bit for bit. */
+int vet_test_user_transition_hash(vet_ctx *ctx, int on);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -411,6 +415,60 @@ int vet_transition_entropy_windowed_ids(vet_plan *plan, const int32_t *d_ids, in
 int vet_transition_entropy_windowed_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
                                          int n_users, int n_frames, int window, int stride, double *h_entropy,
                                          int32_t *h_srccount, int32_t *h_samples);
+
+/* ---- per-viewer transition entropy: each user's own tile moves over time --------------------------
+ * The transposed question of the windowed call: how predictably ONE viewer moves between tiles.  A video of T frames has
+ * P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1 every user has
+ * R = vet_window_rows(P, window, stride) rows; row (u, r) covers pairs [r*stride, r*stride + window) of user u and is, for
+ * every lattice of the plan, what compute_transition_entropy (utilities/entropy_utils.py:213-332) returns when BOTH dicts hold
+ * one entry per pair f of the row in which user u is present in frame f AND in frame f + 1 — keys unique per pair, inserted
+ * in ascending pair order, the prior dict holding the direction at frame f and the current dict the direction at frame f + 1
+ * — then the mean over the lattices as TransitionEntropyAnalyzer.compute_entropy takes it.  In the reduced form the kernels
+ * evaluate (the windowed section above) "user index" is the pair's rank in the row.  Quirks are reproduced: N = 1 gives the
+ * reference's NaN (0 / 0), so every window = 1 row is NaN or empty.
+ *   a row without a common sample: NaN in d_entropy, 0 in d_samples and d_status[1] += 1.  Viewers join and leave, so such
+ *     rows are data, not errors: the _host entry does NOT turn them into VET_ERR_EMPTY (vet_user_entropy's rule).
+ * window = n_frames - 1 is the whole video (R = 1).  Outputs are user-major:
+ *   d_entropy  [U][R]
+ *   d_srccount [U][R][n_0]  lattice 0's samples per source tile                                           (nullable)
+ *   d_samples  [U][R]       N of the row                                                                  (nullable)
+ *   d_status   [2]          {bad, #rows without a common sample}; the call ADDS, the caller zeroes        (nullable)
+ * Two stages:
+ *   1 k_user_dirs (vet_user_entropy's, unchanged): every sample quantised once, its direction id written transposed, [U][T]
+ *     i32, in the context's grow-only workspace (no allocation in steady state); the only place d_status[0] is raised.  One
+ *     transposition serves every lattice: stage 2 looks up nearest[id];
+ *   2 per (user, row) and lattice over the contiguous slice of the user's ids: pair q has the source nearest[dirs[u][f0 + q]]
+ *     and the destination nearest[dirs[u][f0 + q + 1]], f0 = r*stride.
+ *     window <= 64 (k_user_transition_wave): a row lives in one wave's registers, lane = pair, floor(64 / window) rows of one
+ *       user per wave as segments; three walks of `window` cross-lane reads give every lane whether it is its source tile's
+ *       first sample, m, whether it is its bucket's first sample and the bucket's count, then the tile's K and w, then the sum
+ *       of the segment's cells in ascending lane order.  No LDS, no per-tile words, no atomics: the cost does not depend on
+ *       the lattice size;
+ *     window > 64 (k_user_transition): k_window_transition's body — k_transition_big's row algorithm, device code shared —
+ *       with the destination at offset 1; 64 threads and 512 hash slots up to 256 pairs, 256 and 2048 up to 1024, 256 and
+ *       4096 up to 2048 (packed pairs in LDS), else 1024 threads, 8192 slots, passes by the bucket bound 0.6 * 8192 - n and
+ *       the packed pairs in per-workgroup global slices; persistent workgroups over the U * R rows.
+ *     vet_test_user_transition_hash sends the short windows through the second kernel; the two agree to rounding.
+ * A row is a pure function of the plan, `window` and its own window + 1 frames of its own user — which kernel runs and how
+ * the wave is segmented included: the same bits whatever stride selected it, wherever its frames lie in the call, whichever
+ * other users the call holds, from run to run, and between the ids and the grid entry points.
+ * VET_ERR_INVALID: window < 1, stride < 1, window > n_frames - 1, n_frames < 2 (and what vet_transition_entropy_windowed
+ * refuses about the plan).  VET_ERR_UNSUPPORTED (checked before anything is launched or allocated, for both stage-2 kernels
+ * alike): a lattice of more than 2800 tiles (TRANS_BIG_MAX_TILES), window >= 2^19, U * R >= 2^31.
+ * Profile ids: stage 1 is charged to k_spatial, stage 2 to k_transition, the mean over the lattices to k_finalize.
+ * Asynchronous on `stream` like vet_transition_entropy. */
+int vet_user_transition_entropy(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames,
+                                int window, int stride, double *d_entropy, int32_t *d_srccount, int32_t *d_samples,
+                                int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_user_transition_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                                    double *d_entropy, int32_t *d_srccount, int32_t *d_samples, int32_t *d_status,
+                                    void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_user_transition_entropy_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
+                                     int n_users, int n_frames, int window, int stride, double *h_entropy,
+                                     int32_t *h_srccount, int32_t *h_samples);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

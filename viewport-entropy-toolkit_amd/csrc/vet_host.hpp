@@ -105,6 +105,9 @@ struct Tuning {
                                 // layout of plans where no cap qualifies; so a test can compare the two layouts (test_row_cap.py)
     int rec8 = 0;               // vet_test_rec8 (no environment variable): capped plans that have the compact record table launch the
                                 // kernels of the 8-byte record all the same; read at every launch, so one plan runs both (test_rec32.py)
+    int user_transition_hash = 0;   // vet_test_user_transition_hash (no environment variable): per-viewer transition rows of up to 64
+                                // pairs run k_user_transition's hash shape instead of k_user_transition_wave; read at every
+                                // launch, so one plan runs both (test_user_transition_gpu.py)
     void from_environment();
 };
 
@@ -351,5 +354,10 @@ int spatial_set_attrs(vet_ctx* c);
 int transition_set_attrs(vet_ctx* c);
 int window_set_attrs(vet_ctx* c);
 int user_set_attrs(vet_ctx* c);
+int user_transition_set_attrs(vet_ctx* c);
+
+// vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched
+int check_user_transition_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out);
 
 }  // namespace vh

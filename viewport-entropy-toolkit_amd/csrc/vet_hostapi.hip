@@ -511,6 +511,39 @@ int vet_user_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, 
     return VET_OK;
 }
 
+// Per-viewer transition entropy with host buffers (include/vet.h): n_users * vet_window_rows(T - 1, ..) output rows, user-major.
+// Rows without a common sample are data (NaN, samples 0): only VET_ERR_RANGE is decoded from the status words.
+int vet_user_transition_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
+                                     int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {
+    int rc = check_user_transition_args(pl, U, T, window, stride, h_entropy);     // before the samples are looked at or staged
+    if (rc) return rc;
+    rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    if (rc) return rc;
+    const size_t rows = (size_t)vet_window_rows(T - 1, window, stride) * U, c_bytes = rows * pl->lat[0].n * 4;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    hipStream_t s = run.s;
+    double* ent = nullptr;
+    int32_t *sc = nullptr, *cnt = nullptr;
+    POOL(SLOT_ENTROPY, rows * 8, ent);
+    if (h_srccount) POOL(SLOT_OUT1, c_bytes, sc);
+    POOL(SLOT_COUNT, rows * 4, cnt);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = run.ids ? vet_user_transition_entropy_ids(pl, run.ids, U, T, window, stride, ent, sc, cnt, run.status, s)
+                 : vet_user_transition_entropy(pl, run.mu, run.mv, U, T, window, stride, ent, sc, cnt, run.status, s);
+    if (rc) return run.drain(rc);
+    HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
+    if (h_srccount) HIP_TRY(hipMemcpyAsync(h_srccount, sc, c_bytes, hipMemcpyDeviceToHost, s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
+    rc = run.sync(true);
+    if (rc) return rc;
+    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
+    return VET_OK;
+}
+
 // Sliding-window transition entropy with host buffers (include/vet.h): R = vet_window_rows over the T - 1 frame pairs
 int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
                                          int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {

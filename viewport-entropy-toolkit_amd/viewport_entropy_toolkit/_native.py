@@ -79,6 +79,7 @@ SIGNATURES = {
     "vet_profile_enable": (_I, [_P, _I]),
     "vet_test_no_row_cap": (_I, [_P, _I]),
     "vet_test_rec8": (_I, [_P, _I]),
+    "vet_test_user_transition_hash": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -114,6 +115,9 @@ SIGNATURES = {
     "vet_transition_entropy_windowed": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_windowed_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_windowed_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_user_transition_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_user_transition_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_user_transition_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -340,6 +344,11 @@ class Engine:
     def test_rec8(self, on: bool = True):
         """Test switch: table launches of this engine's plans read the 8-byte direction record (include/vet.h: vet_test_rec8)."""
         _check(self.lib, self.lib.vet_test_rec8(self.handle, int(on)))
+
+    def test_user_transition_hash(self, on: bool = True):
+        """Test switch: per-viewer transition rows of up to 64 pairs run the hash kernel of the longer rows
+        (include/vet.h: vet_test_user_transition_hash)."""
+        _check(self.lib, self.lib.vet_test_user_transition_hash(self.handle, int(on)))
 
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
@@ -626,6 +635,27 @@ class Plan:
             _check(self.lib, rc)
         return dict(entropy=ent, srccount=src, samples=samples, code=rc)
 
+    def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
+        """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
+        transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
+        reference's ``compute_transition_entropy``.  ``window`` and ``stride`` count frame pairs; ``window=None`` is all
+        T - 1 pairs (one row per user).  Returns dict(entropy[U,R], srccount[U,R,n0]|None, samples[U,R], code),
+        R = (T - 1 - window) // stride + 1.  Rows in which the user has no pair present in both frames are NaN with
+        ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        window, stride = T - 1 if window is None else int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T - 1, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames - 1 and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        ent = np.empty((U, R), dtype=np.float64)
+        src = np.empty((U, R, self.n_tiles[0]), dtype=np.int32) if want_srccount else None
+        samples = np.empty((U, R), dtype=np.int32)
+        rc = self.lib.vet_user_transition_entropy_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                                       _ptr(ent), _ptr(src), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(entropy=ent, srccount=src, samples=samples, code=rc)
+
     def spatial_resident(self, mu=None, mv=None, ids=None, check=True):
         """Like ``spatial`` but only entropy[T] and present[T] come back; the tile assignments and weights stay
         on the device in ``result`` (a ``DeviceResult``) and are fetched by row on demand."""
@@ -743,6 +773,14 @@ class Plan:
         _check(self.lib, self.lib.vet_transition_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
                                                                   int(stride), d_entropy, d_srccount or None,
                                                                   d_samples or None, d_status or None, _stream(stream)))
+
+    def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                   d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
+        """Outputs are user-major: d_entropy [U][R], d_srccount [U][R][n0], d_samples [U][R]
+        (include/vet.h: vet_user_transition_entropy)."""
+        _check(self.lib, self.lib.vet_user_transition_entropy(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
+                                                              int(stride), d_entropy, d_srccount or None, d_samples or None,
+                                                              d_status or None, _stream(stream)))
 
     def transition_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, d_entropy: int, d_pairs: int = 0,
                           d_srccount: int = 0, d_common: int = 0, d_status: int = 0, stream=None):

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import logging
 import time
+from typing import Optional
 
 import numpy as np
 import pandas as pd
@@ -140,6 +141,40 @@ class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             "samples": res["samples"],
             "tile_weights": FrameDictArray(res["srccount"], lambda row: TileWeights(tiles, row, as_int=True)),
         })
+
+    def compute_user_entropy(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """How predictably each viewer moves between tiles: row (user, r) puts that user's own (t -> t+1) nearest-tile
+        transitions of the pairs [r * stride, r * stride + window) in which the user is present in both frames into ONE call of
+        the reference's ``compute_transition_entropy`` (both dicts keyed per pair, in ascending pair order), averaged over the
+        lattices.  ``window=None`` is the whole video (one row per user); ``window`` and ``stride`` count frame pairs, i.e.
+        rows of ``compute_entropy``'s result.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone),
+        user-major, one row per (user, r): ``user`` (the column name from ingest), then ``compute_windowed_entropy``'s columns:
+        ``time`` / ``time_end`` (the ``time`` ``compute_entropy`` gives the row's first / last pair), ``entropy``, ``samples``
+        (the user's pairs of the row present in both frames) and ``tile_weights`` (lattice 0's count per source tile).  A row
+        without such a pair is NaN with ``samples`` 0 — returned, never raised; a row of one pair is the reference's NaN
+        (0 / 0).  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
+        ``window`` / ``stride``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(len(times) - 1 if window is None else window, stride, len(times) - 1)
+        try:
+            if kind == "grid":
+                res = self._get_plan().transition_per_user(mu=a, mv=b, window=window, stride=stride, want_srccount=True)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.transition_per_user(ids=a, window=window, stride=stride, want_srccount=True)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
+        src = res["srccount"].reshape(-1, res["srccount"].shape[-1])
+        return self._user_frame(names, np.asarray(times)[1:], window, stride, res,
+                                FrameDictArray(src, lambda row: TileWeights(tiles, row, as_int=True)))
 
     def _frame_present(self) -> np.ndarray:
         if self._present is None:
