@@ -53,7 +53,8 @@ extern "C" {
                            heatmaps of naive plans) added the same way; so were vet_window_rows and the
                            vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows), and
                           then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) and
-                          the vet_user_entropy* entry points (each viewer's own histogram over time) */
+                          the vet_user_entropy* entry points (each viewer's own histogram over time), and then the
+                          vet_user_divergence* entry points (a U x U Jensen-Shannon matrix between viewers per window) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -103,6 +104,10 @@ int vet_test_rec8(vet_ctx *ctx, int on);
  * kernel of the longer rows (k_user_transition) instead of k_user_transition_wave.  Read at every launch, so one plan runs
  * both kernels in one process.  The two sum a row's cells in different orders: results agree to rounding, not bit for bit. */
 int vet_test_user_transition_hash(vet_ctx *ctx, int on);
+/* Test switch, not a tuning knob: rows > 0 makes vet_user_divergence* build the viewers' histograms `rows` rows at a time
+ * instead of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at
+ * every launch.  Results are bit-identical whatever the value. */
+int vet_test_divergence_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -369,6 +374,59 @@ int vet_user_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int 
  * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
 int vet_user_entropy_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
                           int window, int stride, double *h_entropy, double *h_weights, int32_t *h_samples);
+
+/* ---- pairwise viewer divergence: a U x U Jensen-Shannon matrix per row --------------------------------
+ * The question that needs two histograms: do viewers look at the same places?  Rows are vet_user_entropy's: window = w,
+ * stride = s, R = vet_window_rows(T, w, s), row r covers frames [r*s, r*s + w).  For a lattice of n tiles let h_u be viewer u's
+ * histogram of the row — exactly what vet_user_entropy returns in d_weights for that lattice: the exact FP64 weight rows added
+ * in ascending frame order (weighted Fibonacci lattices), counts (unweighted and binned lattices) — W_u the sum over its keys and
+ *   S(h) = -sum_keys (h_t / W) log2(h_t / W)
+ * the reference's `entropy` of compute_spatial_entropy / compute_naive_spatial_entropy BEFORE it is divided by the normaliser
+ * (utilities/entropy_utils.py:194-198, :425-440; unnormalised bits on purpose: the unweighted normaliser depends on the sample
+ * count and differs between the three terms).  Then
+ *   D_k(u, v) = S(h_u + h_v) - (W_u S(h_u) + W_v S(h_v)) / (W_u + W_v)
+ *   D(u, v)   = mean over the plan's lattices of D_k(u, v)            bits, 0 <= D <= H2(W_u / (W_u + W_v)) <= 1
+ * S(h_u + h_v) is the reference's entropy of ONE dict holding both viewers' samples of the row: D is the Jensen-Shannon
+ * divergence with each viewer weighted by their mass.
+ *   D(u, v) is NaN when either viewer has no sample in the row (d_samples 0, d_status[1] += 1 per such (row, viewer)); such
+ *     rows are data, not errors, as in vet_user_entropy: the _host entry never returns VET_ERR_EMPTY;
+ *   D(u, v) is NaN exactly where one of the reference's three entropies is: a key whose sum is 0.0, or whose h_t / W underflows
+ *     to 0 (0 * log2 0);
+ *   D(u, u) is +0.0 for a present viewer (NaN where the viewer's own S is); the matrix is symmetric bit for bit.
+ *   d_div     [R][U][U]
+ *   d_samples [U][R]   the viewer's present samples of the row, as vet_user_entropy                             (nullable)
+ *   d_status  [2]      {bad, #(row, viewer) without a sample}; the call ADDS, the caller zeroes               (nullable)
+ * Three stages, the rows in chunks (as many rows as fit 256 MB of histograms, at least one), so the workspace is bounded
+ * whatever R is; everything lives in the context's grow-only workspace, no allocation in steady state:
+ *   1 k_user_dirs (vet_user_entropy's, unchanged): direction ids transposed once, [U][T] i32;
+ *   2 per lattice and chunk: every viewer's histogram [rows][U][n] f64 — k_user_hist_w runs k_user_entropy_w's walk (the same
+ *     add_exact_rows / waves_in_order sequence and wave split, so h_u has d_weights' bits), k_user_hist_c counts with
+ *     k_user_entropy_c's walk — with W_u and a flag: no sample, or the viewer's own S is NaN under the reference's q * log2 q;
+ *   3 k_user_divergence, the pair stage, in the overlap form.  With f(x) = x log2 x, W S(h) = f(W) - sum_t f(h_t), so
+ *       D_k = ( f(W_u + W_v) - (f(W_u) + f(W_v)) - sum_t [ f(a_t + b_t) - (f(a_t) + f(b_t)) ] ) / (W_u + W_v)
+ *     and the bracket is zero unless both viewers have weight on tile t: one FP64 log2 per tile of the OVERLAP of the two
+ *     supports per pair.  A workgroup owns a 32 x 32 block of pairs of one row, upper triangle only, stages the two groups of
+ *     histograms through LDS 32 tiles at a time and walks the tiles in ascending order with one accumulator per pair; the
+ *     lower triangle is a copy.  The pooled term's NaN: a tile with 0 < a_t + b_t < (W_u + W_v) * 2^-1000 takes a slow path
+ *     that performs the reference's division and marks the pair where the quotient is 0.
+ *   Several lattices: lattice 0's pair stage stores D_0 / K, lattice k's adds D_k / K, in lattice order, for every pair alike.
+ * D(u, v) is a pure function of the plan, the window and the two viewers' own samples of the row: the same bits whatever
+ * stride selected the row, wherever its frames lie in the call, whichever other viewers the call holds, however the rows are
+ * chunked, from run to run, and between the ids and the grid entry points.
+ * VET_ERR_INVALID: as vet_user_entropy.  VET_ERR_UNSUPPORTED (checked before anything is launched or allocated):
+ * vet_user_entropy's limits (n * 4 bytes of LDS for a counting lattice, n * 8 for a weighted one, whose exact rows must be on
+ * the device; U * R < 2^31; n_frames <= 65535 * 64) and fewer than 2^31 blocks of 32 x 32 pairs (U < 2 097 120).
+ * Profile ids: stage 1 is charged to k_spatial, the histograms as vet_user_entropy's (k_weights / k_finalize), the pair stage to
+ * k_finalize.  Asynchronous on `stream` like vet_spatial_entropy. */
+int vet_user_divergence(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                        double *d_div, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_user_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                            double *d_div, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_user_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                             int n_frames, int window, int stride, double *h_div, int32_t *h_samples);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

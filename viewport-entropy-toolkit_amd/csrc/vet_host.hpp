@@ -7,11 +7,13 @@
 //   vet_transition.hip  launch logic of the transition-entropy kernels (single videos and batches)
 //   vet_window.hip      the sliding-window spatial- and transition-entropy kernels (frame windows pooled) and their launch logic
 //   vet_user.hip        the per-viewer spatial-entropy kernels (one histogram per user over time) and their launch logic
+//   vet_user_divergence.hip
+//                       the pairwise viewer divergence kernels (a U x U Jensen-Shannon matrix per row) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
 //                       for heatmaps and tilings), device-resident results, the heatmap and tiling handles (no kernels)
-// Every kernel header is included by exactly one of them (vet_user.hip shares the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp).  There is no CPU compute path anywhere.
+// Every kernel header is included by exactly one of them (vet_user.hip and vet_user_divergence.hip share the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp).  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
 #include "vet_layout.hpp"
@@ -108,6 +110,9 @@ struct Tuning {
     int user_transition_hash = 0;   // vet_test_user_transition_hash (no environment variable): per-viewer transition rows of up to 64
                                 // pairs run k_user_transition's hash shape instead of k_user_transition_wave; read at every
                                 // launch, so one plan runs both (test_user_transition_gpu.py)
+    int divergence_chunk_rows = 0;  // vet_test_divergence_chunk_rows (no environment variable): rows per histogram chunk of
+                                // vet_user_divergence* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_user_divergence_gpu.py)
     void from_environment();
 };
 
@@ -355,6 +360,16 @@ int transition_set_attrs(vet_ctx* c);
 int window_set_attrs(vet_ctx* c);
 int user_set_attrs(vet_ctx* c);
 int user_transition_set_attrs(vet_ctx* c);
+int user_divergence_set_attrs(vet_ctx* c);
+
+// vet_user.hip, shared with vet_user_divergence.hip (which builds the same per-viewer histograms): lattice k counts integers
+// (unweighted / binned); waves per row of the weighted histogram kernel (a function of the window and the plan alone); what
+// the per-viewer spatial calls refuse about their arguments (VET_ERR_INVALID) and about the plan (VET_ERR_UNSUPPORTED; builds
+// the exact weight rows on first use)
+bool counts_lattice(const vet_plan* pl, int k);
+int user_nw(size_t lds_max, int n, int window);
+int check_user_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out);
+int check_user_plan(vet_plan* pl, const char* what, hipStream_t s);
 
 // vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched

@@ -133,17 +133,6 @@ struct UserCParams {
     int32_t* status;             // [2] or null
 };
 
-__device__ __forceinline__ void user_count(unsigned* cnt, int n, const int32_t* d, const uint16_t* nearest, long fa, long fb,
-                                           unsigned delta) {
-    for (long f = fa + lane_id(); f < fb; f += WAVE) {
-        const int id = d[f];
-        if (id >= 0) {
-            const int t = (int)nearest[id];
-            if (t < n) atomicAdd(&cnt[t], delta);
-        }
-    }
-}
-
 __global__ __launch_bounds__(64) void k_user_entropy_c(const UserCParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* cnt = (unsigned*)smem;
@@ -192,10 +181,7 @@ __global__ __launch_bounds__(64) void k_user_entropy_c(const UserCParams p) {
 
 namespace vh {
 
-namespace {
-
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
+// (declared in vet_host.hpp: vet_user_divergence.hip builds the same histograms)
 bool counts_lattice(const vet_plan* pl, int k) { return !pl->weighted || pl->lat[k].binned; }
 
 // waves per (user, row) workgroup of k_user_entropy_w: one per 64 frames of the window up to 4, fewer where the lattice's
@@ -205,6 +191,42 @@ int user_nw(size_t lds_max, int n, int window) {
     while (nw > 1 && vet::dtable_lds_bytes(nw, n) > lds_max) nw /= 2;
     return nw;
 }
+
+// whether this plan can run per user at all (before anything is launched); `what` names the call in the message
+int check_user_plan(vet_plan* pl, const char* what, hipStream_t s) {
+    const vet_ctx* c = pl->ctx;
+    for (int k = 0; k < (int)pl->lat.size(); ++k) {
+        const Lattice& L = pl->lat[k];
+        if (counts_lattice(pl, k)) {
+            if ((size_t)L.n * 4 > c->lds_max)
+                return fail(VET_ERR_UNSUPPORTED, "%s: %d bins do not fit the LDS histogram of a row (at most %zu)", what, L.n,
+                            c->lds_max / 4);
+        } else {
+            int rc = ensure_exact_rows(pl, k, s);
+            if (rc) return rc;
+            if (exact_rows(pl, k).state != 1)
+                return fail(VET_ERR_UNSUPPORTED, "%s: the exact FP64 weight rows of lattice %d are not on the device "
+                            "(too large for it); the call has no other formulation", what, k);
+            if (vet::dtable_lds_bytes(1, L.n) > c->lds_max)
+                return fail(VET_ERR_UNSUPPORTED, "%s: lattice of %d tiles does not fit the LDS", what, L.n);
+        }
+    }
+    return VET_OK;
+}
+
+// check_window_args of vet_window.hip, restated for the per-viewer units
+int check_user_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
+    int rc = check_run_args(pl, U, T, out);
+    if (rc) return rc;
+    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
+    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
+    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
+    return VET_OK;
+}
+
+namespace {
+
+size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 const void* user_w_kernel(int stride) {
     const int chunks = stride / vet::WAVE;
@@ -220,25 +242,11 @@ int launch_user(vet_plan* pl, const double* d_mu, const double* d_mv, const int3
     const long R = (long)vet_window_rows(T, window, stride), rows = R * (long)U;
     if (rows >= (1L << 31)) return fail(VET_ERR_UNSUPPORTED, "per-user entropy: %ld rows in one call (fewer than 2^31)", rows);
     // ---- whether this plan can run per user at all (before anything is launched)
-    for (int k = 0; k < K; ++k) {
-        const Lattice& L = pl->lat[k];
-        if (counts_lattice(pl, k)) {
-            if ((size_t)L.n * 4 > c->lds_max)
-                return fail(VET_ERR_UNSUPPORTED, "per-user entropy: %d bins do not fit the LDS histogram of a row (at most %zu)", L.n,
-                            c->lds_max / 4);
-        } else {
-            int rc = ensure_exact_rows(pl, k, s);
-            if (rc) return rc;
-            if (exact_rows(pl, k).state != 1)
-                return fail(VET_ERR_UNSUPPORTED, "per-user entropy: the exact FP64 weight rows of lattice %d are not on the device "
-                            "(too large for it); the call has no other formulation", k);
-            if (vet::dtable_lds_bytes(1, L.n) > c->lds_max)
-                return fail(VET_ERR_UNSUPPORTED, "per-user entropy: lattice of %d tiles does not fit the LDS", L.n);
-        }
-    }
+    int rc = check_user_plan(pl, "per-user entropy", s);
+    if (rc) return rc;
     // workspace: per-lattice rows (K > 1) | dirs [U][T]
     const size_t ent_b = pad16(K > 1 ? (size_t)K * rows * sizeof(double) : 0);
-    int rc = ensure_ws(c, ent_b + pad16((size_t)U * T * sizeof(int32_t)));
+    rc = ensure_ws(c, ent_b + pad16((size_t)U * T * sizeof(int32_t)));
     if (rc) return rc;
     char* ws = (char*)c->ws;
     double* ent_k = K > 1 ? (double*)ws : d_entropy;
@@ -291,16 +299,6 @@ int launch_user(vet_plan* pl, const double* d_mu, const double* d_mv, const int3
         hipLaunchKernelGGL(vet::k_finalize, dim3(grid_for(rows, 256, c->n_cu)), dim3(256), 0, s, (const double*)ent_k, K, rows, d_entropy);
         HIP_TRY(hipGetLastError());
     }
-    return VET_OK;
-}
-
-// check_window_args of vet_window.hip, restated for this unit
-int check_user_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
-    int rc = check_run_args(pl, U, T, out);
-    if (rc) return rc;
-    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
-    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
-    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
     return VET_OK;
 }
 

@@ -1,5 +1,6 @@
 // vet_user_dirs.hpp — k_user_dirs: stage 1 of the per-viewer entry points (vet_user.hip: vet_user_entropy*,
-// vet_user_transition.hip: vet_user_transition_entropy*): every sample quantised once, its direction id written transposed.
+// vet_user_transition.hip: vet_user_transition_entropy*, vet_user_divergence.hip: vet_user_divergence*): every sample quantised
+// once, its direction id written transposed.  Also user_count, the counting walk over one user's ids.
 // Part of the gfx950 device code of the viewport -> tile -> entropy path (see vet_kernels.hpp for the map).
 #pragma once
 #include "vet_common.hpp"
@@ -51,6 +52,19 @@ __global__ __launch_bounds__(256) void k_user_dirs(const UserDirsParams p) {
     if (p.status) {
         const unsigned long long anybad = __ballot(bad);
         if (anybad && lane == 0) atomicAdd(&p.status[0], (int)__popcll(anybad));
+    }
+}
+
+// Counts the nearest tiles / bins of frames [fa, fb) of one user's ids d into the wave's LDS histogram cnt (delta = 1, or
+// ~0u = -1 mod 2^32 for frames that leave a sliding row): k_user_entropy_c and k_user_hist_c.  Integers, exact in any order.
+__device__ __forceinline__ void user_count(unsigned* cnt, int n, const int32_t* d, const uint16_t* nearest, long fa, long fb,
+                                           unsigned delta) {
+    for (long f = fa + lane_id(); f < fb; f += WAVE) {
+        const int id = d[f];
+        if (id >= 0) {
+            const int t = (int)nearest[id];
+            if (t < n) atomicAdd(&cnt[t], delta);
+        }
     }
 }
 

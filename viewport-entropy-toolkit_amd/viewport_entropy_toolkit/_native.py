@@ -80,6 +80,7 @@ SIGNATURES = {
     "vet_test_no_row_cap": (_I, [_P, _I]),
     "vet_test_rec8": (_I, [_P, _I]),
     "vet_test_user_transition_hash": (_I, [_P, _I]),
+    "vet_test_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -118,6 +119,9 @@ SIGNATURES = {
     "vet_user_transition_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_user_transition_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_user_transition_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -349,6 +353,11 @@ class Engine:
         """Test switch: per-viewer transition rows of up to 64 pairs run the hash kernel of the longer rows
         (include/vet.h: vet_test_user_transition_hash)."""
         _check(self.lib, self.lib.vet_test_user_transition_hash(self.handle, int(on)))
+
+    def test_divergence_chunk_rows(self, rows: int = 0):
+        """Test switch: the viewer divergence builds its histograms ``rows`` rows at a time (0: the default budget); results do
+        not depend on it (include/vet.h: vet_test_divergence_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_divergence_chunk_rows(self.handle, int(rows)))
 
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
@@ -600,6 +609,26 @@ class Plan:
             _check(self.lib, rc)
         return dict(entropy=ent, weights=weights, samples=samples, code=rc)
 
+    def spatial_user_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, check=True):
+        """Do viewers look at the same places (include/vet.h: vet_user_divergence): for every row r — frames
+        [r * stride, r * stride + window), ``window=None`` the whole video — the U x U matrix of mass-weighted Jensen-Shannon
+        divergences, in bits, between the viewers' tile histograms of the row (``spatial_per_user``'s ``weights``), averaged
+        over the lattices.  Returns dict(divergence[R,U,U], samples[U,R], code), R = (T - window) // stride + 1.  The matrix
+        is symmetric with a +0.0 diagonal; the rows and columns of a viewer without a sample in the row are NaN with
+        ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        window, stride = T if window is None else int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        div = np.empty((R, U, U), dtype=np.float64)
+        samples = np.empty((U, R), dtype=np.int32)
+        rc = self.lib.vet_user_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                               _ptr(div), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(divergence=div, samples=samples, code=rc)
+
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -767,6 +796,12 @@ class Plan:
         _check(self.lib, self.lib.vet_user_entropy(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
                                                    d_entropy, d_weights or None, d_samples or None, d_status or None,
                                                    _stream(stream)))
+
+    def spatial_user_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                       d_div: int, d_samples: int = 0, d_status: int = 0, stream=None):
+        """d_div [R][U][U]; d_samples [U][R] (include/vet.h: vet_user_divergence)."""
+        _check(self.lib, self.lib.vet_user_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
+                                                      d_div, d_samples or None, d_status or None, _stream(stream)))
 
     def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

@@ -239,5 +239,22 @@ class _EntropyAnalyzerBase:
             cols["tile_weights"] = tile_weights
         return pd.DataFrame(cols)
 
+    @staticmethod
+    def _divergence_frame(names, times, window: int, stride: int, res: dict) -> pd.DataFrame:
+        """The pairwise viewer divergence as a DataFrame, one row per window: the ``divergence`` cell of row r is the [U, U] view
+        ``res["divergence"][r]`` (no copy), the ``samples`` cell the [U] samples of the row; ``attrs["users"]`` names the
+        viewers in matrix order."""
+        div = res["divergence"]
+        R = div.shape[0]
+        first = np.arange(R, dtype=np.int64) * stride
+        times = np.asarray(times)
+        per_row = np.ascontiguousarray(res["samples"].T)
+        d_col, s_col = np.empty(R, dtype=object), np.empty(R, dtype=object)
+        for r in range(R):
+            d_col[r], s_col[r] = div[r], per_row[r]
+        df = pd.DataFrame({"time": times[first], "time_end": times[first + window - 1], "divergence": d_col, "samples": s_col})
+        df.attrs["users"] = list(names)
+        return df
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

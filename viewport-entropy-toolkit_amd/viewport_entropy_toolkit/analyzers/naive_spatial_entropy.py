@@ -147,6 +147,29 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             raise
         return self._user_frame(names, times, window, stride, res)
 
+    def compute_user_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """Do viewers look at the same lat/lon cells: for every row r — frames [r * stride, r * stride + window),
+        ``window=None`` the whole video — the U x U matrix of Jensen-Shannon divergences, in bits, between the viewers' cell
+        counts of the row, each viewer weighted by their samples (``SpatialEntropyAnalyzer.compute_user_divergence`` on
+        ``compute_naive_spatial_entropy``'s histogram).
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end``,
+        ``divergence`` (a [U, U] view into the one result array) and ``samples`` ([U]); ``attrs["users"]`` holds the user names
+        in matrix order.  A viewer without a sample in the window has NaN rows and columns and ``samples`` 0 — returned, never
+        raised.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
+        ``window`` / ``stride``."""
+        if not self._data_cache or self._dense is None:
+            raise ValidationError("No data available. Call process_directory first.")
+        times, mu, mv, names = self._dense
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            res = self._naive_plan().spatial_user_divergence(mu=mu, mv=mv, window=window, stride=stride)
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._divergence_frame(names, times, window, stride, res)
+
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
     def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
         plan, _, _, tw, th = self._heatmap_source

@@ -140,5 +140,35 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         return self._user_frame(names, times, window, stride, res,
                                 FrameDictArray(weights, lambda row: TileWeights(tiles, row)))
 
+    def compute_user_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """Do viewers look at the same places: for every row r — frames [r * stride, r * stride + window), ``window=None`` the
+        whole video — the U x U matrix of Jensen-Shannon divergences, in bits, between the viewers' tile histograms of the row
+        (``compute_user_entropy``'s ``tile_weights``), each viewer weighted by their mass, averaged over the lattices:
+        ``D(u, v) = S(h_u + h_v) - (W_u S(h_u) + W_v S(h_v)) / (W_u + W_v)`` with ``S`` the reference's entropy of one dict
+        before the normaliser.  0 = the same places in the same proportions, 1 = equal masses on disjoint tiles.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end`` (of
+        the row's first / last frame), ``divergence`` (a [U, U] view into the one result array: symmetric, +0.0 diagonal) and
+        ``samples`` ([U]: each viewer's present samples of the row); ``attrs["users"]`` holds the user names in matrix order.
+        The rows and columns of a viewer without a sample in the window are NaN with ``samples`` 0 — returned, never raised.
+        Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
+        ``window`` / ``stride``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            if kind == "grid":
+                res = self._get_plan().spatial_user_divergence(mu=a, mv=b, window=window, stride=stride)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.spatial_user_divergence(ids=a, window=window, stride=stride)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._divergence_frame(names, times, window, stride, res)
+
     def _frame_present(self):
         return self._present
