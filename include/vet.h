@@ -54,7 +54,8 @@ extern "C" {
                            vet_spatial_entropy_windowed* entry points (pooled entropy of sliding frame windows), and
                           then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) and
                           the vet_user_entropy* entry points (each viewer's own histogram over time), and then the
-                          vet_user_divergence* entry points (a U x U Jensen-Shannon matrix between viewers per window) */
+                          vet_user_divergence* entry points (a U x U Jensen-Shannon matrix between viewers per window), and
+                          then the vet_window_divergence* entry points (a lag band of Jensen-Shannon distances between windows) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -108,6 +109,10 @@ int vet_test_user_transition_hash(vet_ctx *ctx, int on);
  * instead of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at
  * every launch.  Results are bit-identical whatever the value. */
 int vet_test_divergence_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes vet_window_divergence* take `rows` pair rows per histogram chunk (plus the halo
+ * of max_lag rows) instead of as many as its workspace budget holds, so that a small input runs several chunks and the halo
+ * crosses them; 0 restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
+int vet_test_window_divergence_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -427,6 +432,61 @@ int vet_user_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, i
  * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
 int vet_user_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                              int n_frames, int window, int stride, double *h_div, int32_t *h_samples);
+
+/* ---- window-to-window attention divergence: a lag band of Jensen-Shannon distances -------------------
+ * The question a windowed entropy series cannot answer: WHEN does the audience's attention move?  A crowd that jumps from one
+ * side of the sphere to the other keeps its entropy; the distance between the pooled histogram of one window and that of a
+ * later one shows the jump.  Rows are vet_spatial_entropy_windowed's: window = w, stride = s, R = vet_window_rows(T, w, s), row r
+ * covers frames [r*s, r*s + w).  For a lattice of n tiles let P_r be the pooled histogram of row r — exactly what
+ * vet_spatial_entropy_windowed returns in d_weights for that lattice: `dtable`'s FP64 frame sums added in ascending frame order
+ * (weighted Fibonacci lattices), counts (unweighted and binned lattices) — W_r the sum over its keys and
+ *   S(h) = -sum_keys (h_t / W) log2(h_t / W)
+ * the reference's `entropy` of compute_spatial_entropy / compute_naive_spatial_entropy BEFORE it is divided by the normaliser
+ * (utilities/entropy_utils.py:194-198, :425-440).  For the lags l = 1 .. L, L = max_lag (in rows):
+ *   D_k(r, l) = S(P_r + P_{r+l}) - (W_r S(P_r) + W_{r+l} S(P_{r+l})) / (W_r + W_{r+l})
+ *   D(r, l)   = mean over the plan's lattices of D_k(r, l)       bits, 0 <= D <= H2(W_r / (W_r + W_{r+l})) <= 1
+ * S(P_r + P_{r+l}) is the reference's entropy of ONE dict holding the samples of both windows (overlapping windows, s*l < w,
+ * hold the shared frames twice): D is the Jensen-Shannon divergence with each window weighted by its mass; 0 = the same tiles
+ * in the same proportions, H2 of the mass split (1 for equal masses) = disjoint tiles.  Lag 1 is the per-segment "attention
+ * shift" series, L = R - 1 the upper triangle of the video's recurrence matrix.
+ *   d_div     [R][L]   d_div[r][l - 1] = D(r, l); NaN where r + l >= R (there is no such row), where either window has no
+ *                      sample (such rows are data, not errors: the _host entry never returns VET_ERR_EMPTY), and exactly
+ *                      where one of the reference's three entropies is NaN: a key whose sum is 0.0, or whose h_t / W
+ *                      underflows to 0 (0 * log2 0)
+ *   d_samples [R]      present samples per row, as vet_spatial_entropy_windowed                                 (nullable)
+ *   d_status  [2]      {bad, #rows without a sample}; the call ADDS, the caller zeroes                          (nullable)
+ * Three stages; everything lives in the context's grow-only workspace, no allocation in steady state:
+ *   1 vet_spatial_entropy_windowed's stage 1, unchanged: every frame's histogram once (k_weights_gather / k_window_tiles);
+ *   2 per lattice and chunk of pair rows (as many as fit 256 MB of histograms together with the halo of L rows their lags
+ *     reach, at least one): the row histograms [rows][n] f64 — k_window_hist_w runs k_window_entropy_w's sum (the same
+ *     additions in ascending frame order, so P_r has d_weights' bits up to the sign of zero), k_window_hist_c counts — with W_r
+ *     and a flag: no sample, or the row's own S is NaN under the reference's q * log2 q;
+ *   3 k_window_divergence, the pair stage, in vet_user_divergence's overlap form: with f(x) = x log2 x,
+ *       D_k = ( f(W_a + W_b) - (f(W_a) + f(W_b)) - sum_t [ f(a_t + b_t) - (f(a_t) + f(b_t)) ] ) / (W_a + W_b)
+ *     one FP64 log2 per tile on which both windows have weight.  One thread owns one pair (r, l) and walks the tiles in
+ *     ascending order; a workgroup takes RB rows x LB lags — (256, 1) for max_lag = 1, (32, 8) up to 8, (8, 32) beyond, chosen
+ *     from max_lag alone — and stages the RB + (RB + LB - 1) histograms it needs through LDS.  The pooled term's NaN: a tile
+ *     with 0 < a_t + b_t < (W_a + W_b) * 2^-1000 takes a slow path that performs the reference's division and marks the pair
+ *     where the quotient is 0.
+ *   Several lattices: lattice 0's pair stage stores D_0 / K, lattice k's adds D_k / K, in lattice order, for every pair alike.
+ * D(r, l) is a pure function of the plan, the window and the frames of rows r and r + l: the same bits whatever n_frames,
+ * stride and max_lag selected the pair, wherever it falls in a launch or a row chunk, whichever block shape ran it, from run to
+ * run, and between the ids and the grid entry points.
+ * VET_ERR_INVALID (before anything is launched or allocated): vet_spatial_entropy_windowed's, R < 2, max_lag < 1 or
+ * max_lag > R - 1.  VET_ERR_UNSUPPORTED (likewise): vet_spatial_entropy_windowed's limits (n * 4 bytes of LDS for a counting
+ * lattice, n * 8 for a weighted one, whose exact rows must be on the device), max_lag > 65535 lag blocks, R >= 2^31 - 256.
+ * Profile ids: stage 1 as vet_spatial_entropy_windowed's (k_weights / k_spatial), stage 2 to k_finalize, the pair stage to
+ * k_transition — the one id the call does not use otherwise, so that the three stages can be told apart.  Asynchronous on
+ * `stream` like vet_spatial_entropy. */
+int vet_window_divergence(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                          int max_lag, double *d_div, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_window_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int max_lag,
+                              double *d_div, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_window_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                               int n_frames, int window, int stride, int max_lag, double *h_div, int32_t *h_samples);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

@@ -9,11 +9,13 @@
 //   vet_user.hip        the per-viewer spatial-entropy kernels (one histogram per user over time) and their launch logic
 //   vet_user_divergence.hip
 //                       the pairwise viewer divergence kernels (a U x U Jensen-Shannon matrix per row) and their launch logic
+//   vet_window_divergence.hip
+//                       the window-to-window divergence kernels (a lag band of Jensen-Shannon distances per row) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
 //                       for heatmaps and tilings), device-resident results, the heatmap and tiling handles (no kernels)
-// Every kernel header is included by exactly one of them (vet_user.hip and vet_user_divergence.hip share the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp).  There is no CPU compute path anywhere.
+// Every kernel header is included by exactly one of them (vet_user.hip and vet_user_divergence.hip share the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp, vet_window.hip and vet_window_divergence.hip those of vet_window_hist.hpp).  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
 #include "vet_layout.hpp"
@@ -113,6 +115,9 @@ struct Tuning {
     int divergence_chunk_rows = 0;  // vet_test_divergence_chunk_rows (no environment variable): rows per histogram chunk of
                                 // vet_user_divergence* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_user_divergence_gpu.py)
+    int window_divergence_chunk_rows = 0;   // vet_test_window_divergence_chunk_rows (no environment variable): pair rows per
+                                // histogram chunk of vet_window_divergence* (0 = sized by the workspace budget); read at every
+                                // launch; the results do not depend on it (test_window_divergence_gpu.py)
     void from_environment();
 };
 
@@ -361,6 +366,20 @@ int window_set_attrs(vet_ctx* c);
 int user_set_attrs(vet_ctx* c);
 int user_transition_set_attrs(vet_ctx* c);
 int user_divergence_set_attrs(vet_ctx* c);
+int window_divergence_set_attrs(vet_ctx* c);
+
+// vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
+// stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
+// (weighted: [T][n_k] f64 tile sums in the dense tile_weights encoding; counting: [T][U] i32 tiles) in the context's workspace,
+// refuses plans that cannot run windowed and builds the exact weight rows on first use; the caller calls ensure_ws(wf.bytes or
+// more) and then window_frames_run, which fills them (k_window_tiles, k_weights_gather) and raises d_status[0].
+struct WindowFrames {
+    size_t present_off = 0, off[64] = {}, bytes = 0;
+};
+int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out);
+int window_frames_layout(vet_plan* pl, int U, int T, size_t head_bytes, WindowFrames& wf, hipStream_t s);
+int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T,
+                      const WindowFrames& wf, int32_t* d_status, hipStream_t s);
 
 // vet_user.hip, shared with vet_user_divergence.hip (which builds the same per-viewer histograms): lattice k counts integers
 // (unweighted / binned); waves per row of the weighted histogram kernel (a function of the window and the plan alone); what

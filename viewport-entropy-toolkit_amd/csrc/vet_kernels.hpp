@@ -34,6 +34,10 @@
 //                                                               the reference's entropy of the pooled histogram
 //                                              k_window_transition   sliding windows of frame pairs: the pooled (pair, user)
 //                                                               transitions of a row walked by k_transition_big's row algorithm
+//   vet_window_divergence.hip  (in the unit)   k_window_hist_w, k_window_hist_c   the rows' pooled histograms (vet_window_hist.hpp:
+//                                                               k_window_entropy's sums), their totals and NaN flags, per row chunk
+//                                              k_window_divergence   one thread per (row, lag): Jensen-Shannon divergence of rows r
+//                                                               and r + l in the overlap form, histograms staged through LDS
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into
@@ -48,7 +52,8 @@
 //                                                               streamed RGB compose
 //   (several units)     vet_finalize.hpp       k_log2_table, k_finalize*   log2(k) table; mean over a plan's lattices
 // Shared, kernel-free headers: vet_layout.hpp (table / histogram layout constants), vet_common.hpp (wave helpers, the
-// sample -> direction-id quantiser), vet_weights.hpp (FoV weight, weighted frame entropy), vet_host.hpp (host state).
+// sample -> direction-id quantiser), vet_weights.hpp (FoV weight, weighted frame entropy), vet_window_hist.hpp (a window's pooled sums and counts),
+// vet_divergence.hpp (x log2 x, the reference's NaN test of a key), vet_host.hpp (host state).
 //
 // No MFMA: there is no dense contraction on this path.  Reference citations are relative to
 // /root/reference/src/viewport_entropy_toolkit/.  This header is documentation; the units include what they launch.

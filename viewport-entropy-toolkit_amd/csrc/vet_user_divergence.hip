@@ -33,6 +33,7 @@
 #include "vet_common.hpp"
 #include "vet_spatial_dtable.hpp"
 #include "vet_user_dirs.hpp"
+#include "vet_divergence.hpp"
 
 #include <algorithm>
 
@@ -44,12 +45,6 @@ struct DivStats {
     double* tot;                 // [CR][U]     W
     int32_t* flag;               // [CR][U]     1: no sample in the row, or the viewer's own S is NaN
 };
-
-// the reference's -q log2 q is NaN for this key (0 * -inf: the value is 0.0 or underflows against the total)
-__device__ __forceinline__ bool own_term_is_nan(double v, double tot) {
-    const double q = v / tot;
-    return isnan(q * log2(q));
-}
 
 // ------------------------------------------------------------------------------------------
 // k_user_hist_w — stage 2 of a weighted Fibonacci lattice for rows [r0, r0 + CR).  One workgroup per (row, user),
@@ -197,8 +192,6 @@ struct UserDivParams {
     double K;                    // lattices of the plan
     double* out;                 // [CR][U][U], the chunk's first row
 };
-
-__device__ __forceinline__ double xlog2x(double x) { return x * log2(x); }
 
 __global__ __launch_bounds__(256) void k_user_divergence(const UserDivParams p) {
     __shared__ double sa[2][DIV_B * DIV_LD], sf[2][DIV_B * DIV_LD];

@@ -19,13 +19,11 @@
 #include "vet_common.hpp"
 #include "vet_finalize.hpp"
 #include "vet_transition.hpp"
+#include "vet_window_hist.hpp"
 
 #include <algorithm>
 
 namespace vet {
-
-// -0.0 = "no key" in an FP64 histogram (vet_spatial_sweep.hpp: NO_KEY_BITS; this unit does not include the sweep kernels)
-constexpr unsigned long long WIN_NO_KEY_BITS = 0x8000000000000000ull;
 
 // ------------------------------------------------------------------------------------------
 // k_window_tiles — stage 1 of the integer-count lattices and the per-frame bookkeeping of every plan: one wave per frame;
@@ -87,8 +85,6 @@ struct WindowWParams {
     int32_t* status;             // [2] or null
 };
 
-__device__ __forceinline__ double window_term(double v) { return v == 0.0 ? -v : v; }   // dense encoding -> histogram value
-
 __global__ __launch_bounds__(256) void k_window_entropy_w(const WindowWParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int NW = blockDim.x >> 6, lane = lane_id(), wv = wave_id();
@@ -102,14 +98,7 @@ __global__ __launch_bounds__(256) void k_window_entropy_w(const WindowWParams p)
     double tot = 0.0;
     for (int t = lane; t < p.n; t += WAVE) {
         const double* col = p.hist + f0 * (long)p.n + t;
-        double acc = __longlong_as_double((long long)WIN_NO_KEY_BITS);
-        int j = 0;
-        for (; j + 4 <= p.window; j += 4) {
-            const double v0 = col[(long)j * p.n], v1 = col[(long)(j + 1) * p.n], v2 = col[(long)(j + 2) * p.n],
-                         v3 = col[(long)(j + 3) * p.n];
-            acc += window_term(v0); acc += window_term(v1); acc += window_term(v2); acc += window_term(v3);
-        }
-        for (; j < p.window; ++j) acc += window_term(col[(long)j * p.n]);
+        const double acc = window_tile_sum(col, p.n, p.window);
         h[t] = acc;
         const bool key = (unsigned long long)__double_as_longlong(acc) != WIN_NO_KEY_BITS;
         if (key) tot += acc;
@@ -154,15 +143,6 @@ struct WindowCParams {
     int32_t* samples;            // [R] or null
     int32_t* status;             // [2] or null
 };
-
-__device__ __forceinline__ void window_count(unsigned* cnt, int n, const int32_t* tiles, int U, long fa, long fb, unsigned delta) {
-    const int32_t* q = tiles + fa * (long)U;
-    const long m = (fb - fa) * (long)U;
-    for (long i = lane_id(); i < m; i += WAVE) {
-        const int t = q[i];
-        if ((unsigned)t < (unsigned)n) atomicAdd(&cnt[t], delta);      // -1 = absent
-    }
-}
 
 __global__ __launch_bounds__(64) void k_window_entropy_c(const WindowCParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -272,66 +252,55 @@ namespace {
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-bool counts_lattice(const vet_plan* pl, int k) { return !pl->weighted || pl->lat[k].binned; }
+template <bool FROM_IDS>
+int window_frames_launch(vet_plan* pl, const vet::SampleSrc& src, int U, int T, const WindowFrames& wf, int32_t* d_status,
+                         hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const int K = (int)pl->lat.size();
+    char* ws = (char*)c->ws;
+    const int frames_per_wg = 4;
+    const dim3 grid((unsigned)((T + frames_per_wg - 1) / frames_per_wg)), block(frames_per_wg * vet::WAVE);
+    bool booked = false;
+    for (int k = 0; k < K || !booked; ++k) {
+        if (k < K && !counts_lattice(pl, k)) continue;
+        vet::WindowTilesParams q{};
+        q.src = src; q.U = U; q.T = T;
+        q.nearest = k < K ? pl->lat[k].d_nearest : nullptr;
+        q.tiles = k < K ? (int32_t*)(ws + wf.off[k]) : nullptr;
+        q.present = booked ? nullptr : (int32_t*)(ws + wf.present_off);
+        q.status = booked ? nullptr : d_status;
+        booked = true;
+        ProfScope ps(c, s, KID_SPATIAL);
+        hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, grid, block, 0, s, q);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int k = 0; k < K; ++k) {
+        if (counts_lattice(pl, k)) continue;
+        int rc = exact_frame_rows(pl, k, src.mu, src.mv, src.ids, U, T, (double*)(ws + wf.off[k]), s);
+        if (rc) return rc;
+    }
+    return VET_OK;
+}
 
 template <bool FROM_IDS>
 int launch_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                     int stride, double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
     vet_ctx* c = pl->ctx;
     const int K = (int)pl->lat.size();
-    if (K > 64) return fail(VET_ERR_UNSUPPORTED, "more than 64 lattices in one plan");
     const long R = (long)vet_window_rows(T, window, stride);
-    const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
     // ---- what stage 1 leaves per lattice, and whether this plan can run windowed at all
-    size_t off[64], bytes = pad16(K > 1 ? (size_t)K * R * sizeof(double) : 0);
-    const size_t present_off = bytes;
-    bytes += pad16((size_t)T * sizeof(int32_t));
-    for (int k = 0; k < K; ++k) {
-        const Lattice& L = pl->lat[k];
-        off[k] = bytes;
-        if (counts_lattice(pl, k)) {
-            if ((size_t)L.n * 4 > c->lds_max)
-                return fail(VET_ERR_UNSUPPORTED, "windowed: %d bins do not fit the LDS histogram of a window (at most %zu)", L.n,
-                            c->lds_max / 4);
-            bytes += pad16((size_t)T * U * sizeof(int32_t));
-        } else {
-            int rc = ensure_exact_rows(pl, k, s);
-            if (rc) return rc;
-            if (exact_rows(pl, k).state != 1)
-                return fail(VET_ERR_UNSUPPORTED, "windowed: the exact FP64 weight rows of lattice %d are not on the device "
-                            "(too large for it); the windowed call has no other formulation", k);
-            bytes += pad16((size_t)T * L.n * sizeof(double));
-        }
-    }
-    int rc = ensure_ws(c, bytes);
+    WindowFrames wf;
+    int rc = window_frames_layout(pl, U, T, pad16(K > 1 ? (size_t)K * R * sizeof(double) : 0), wf, s);
+    if (rc) return rc;
+    rc = ensure_ws(c, wf.bytes);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    int32_t* d_frame_present = (int32_t*)(ws + present_off);
+    const size_t* off = wf.off;
+    int32_t* d_frame_present = (int32_t*)(ws + wf.present_off);
     double* ent_k = K > 1 ? (double*)ws : d_entropy;
     // ---- stage 1
-    {
-        const int frames_per_wg = 4;
-        const dim3 grid((unsigned)((T + frames_per_wg - 1) / frames_per_wg)), block(frames_per_wg * vet::WAVE);
-        bool booked = false;
-        for (int k = 0; k < K || !booked; ++k) {
-            if (k < K && !counts_lattice(pl, k)) continue;
-            vet::WindowTilesParams q{};
-            q.src = src; q.U = U; q.T = T;
-            q.nearest = k < K ? pl->lat[k].d_nearest : nullptr;
-            q.tiles = k < K ? (int32_t*)(ws + off[k]) : nullptr;
-            q.present = booked ? nullptr : d_frame_present;
-            q.status = booked ? nullptr : d_status;
-            booked = true;
-            ProfScope ps(c, s, KID_SPATIAL);
-            hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, grid, block, 0, s, q);
-            HIP_TRY(hipGetLastError());
-        }
-        for (int k = 0; k < K; ++k) {
-            if (counts_lattice(pl, k)) continue;
-            rc = exact_frame_rows(pl, k, d_mu, d_mv, d_ids, U, T, (double*)(ws + off[k]), s);
-            if (rc) return rc;
-        }
-    }
+    rc = window_frames_run(pl, d_mu, d_mv, d_ids, U, T, wf, d_status, s);
+    if (rc) return rc;
     // ---- stage 2, charged to the k_finalize scope (include/vet.h)
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
@@ -366,15 +335,6 @@ int launch_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, const 
         hipLaunchKernelGGL(vet::k_finalize, dim3(grid_for(R, 256, c->n_cu)), dim3(256), 0, s, (const double*)ent_k, K, R, d_entropy);
         HIP_TRY(hipGetLastError());
     }
-    return VET_OK;
-}
-
-int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
-    int rc = check_run_args(pl, U, T, out);
-    if (rc) return rc;
-    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
-    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
-    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
     return VET_OK;
 }
 
@@ -467,6 +427,51 @@ int launch_window_transition(vet_plan* pl, const double* d_mu, const double* d_m
 }
 
 }  // namespace
+
+// ---- stage 1 of the windowed spatial calls, shared with vet_window_divergence.hip (vet_host.hpp)
+int window_frames_layout(vet_plan* pl, int U, int T, size_t head_bytes, WindowFrames& wf, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const int K = (int)pl->lat.size();
+    if (K > 64) return fail(VET_ERR_UNSUPPORTED, "more than 64 lattices in one plan");
+    size_t bytes = head_bytes;
+    wf.present_off = bytes;
+    bytes += pad16((size_t)T * sizeof(int32_t));
+    for (int k = 0; k < K; ++k) {
+        const Lattice& L = pl->lat[k];
+        wf.off[k] = bytes;
+        if (counts_lattice(pl, k)) {
+            if ((size_t)L.n * 4 > c->lds_max)
+                return fail(VET_ERR_UNSUPPORTED, "windowed: %d bins do not fit the LDS histogram of a window (at most %zu)", L.n,
+                            c->lds_max / 4);
+            bytes += pad16((size_t)T * U * sizeof(int32_t));
+        } else {
+            int rc = ensure_exact_rows(pl, k, s);
+            if (rc) return rc;
+            if (exact_rows(pl, k).state != 1)
+                return fail(VET_ERR_UNSUPPORTED, "windowed: the exact FP64 weight rows of lattice %d are not on the device "
+                            "(too large for it); the windowed call has no other formulation", k);
+            bytes += pad16((size_t)T * L.n * sizeof(double));
+        }
+    }
+    wf.bytes = bytes;
+    return VET_OK;
+}
+
+int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T,
+                      const WindowFrames& wf, int32_t* d_status, hipStream_t s) {
+    const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    return d_ids ? window_frames_launch<true>(pl, src, U, T, wf, d_status, s)
+                 : window_frames_launch<false>(pl, src, U, T, wf, d_status, s);
+}
+
+int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
+    int rc = check_run_args(pl, U, T, out);
+    if (rc) return rc;
+    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
+    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
+    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
+    return VET_OK;
+}
 
 int window_set_attrs(vet_ctx* c) {
     HIP_TRY(hipFuncSetAttribute((const void*)vet::k_window_entropy_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_max));

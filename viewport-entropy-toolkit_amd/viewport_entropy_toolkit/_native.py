@@ -81,6 +81,7 @@ SIGNATURES = {
     "vet_test_rec8": (_I, [_P, _I]),
     "vet_test_user_transition_hash": (_I, [_P, _I]),
     "vet_test_divergence_chunk_rows": (_I, [_P, _I]),
+    "vet_test_window_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -122,6 +123,9 @@ SIGNATURES = {
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "vet_window_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vet_window_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "vet_window_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -358,6 +362,11 @@ class Engine:
         """Test switch: the viewer divergence builds its histograms ``rows`` rows at a time (0: the default budget); results do
         not depend on it (include/vet.h: vet_test_divergence_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_divergence_chunk_rows(self.handle, int(rows)))
+
+    def test_window_divergence_chunk_rows(self, rows: int = 0):
+        """Test switch: the window divergence takes ``rows`` pair rows per histogram chunk (0: the default budget); results do
+        not depend on it (include/vet.h: vet_test_window_divergence_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_window_divergence_chunk_rows(self.handle, int(rows)))
 
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
@@ -629,6 +638,35 @@ class Plan:
             _check(self.lib, rc)
         return dict(divergence=div, samples=samples, code=rc)
 
+    def _window_divergence_args(self, T, window, stride, max_lag):
+        if window is None:
+            raise ValueError("window (a number of frames) is required")
+        window, stride, max_lag = int(window), int(stride), int(max_lag)
+        R = int(self.lib.vet_window_rows(T, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        if not 1 <= max_lag <= R - 1:
+            raise ValueError(f"need 1 <= max_lag <= rows - 1 = {R - 1} (got max_lag={max_lag}; window={window}, stride={stride}, "
+                             f"{T} frames give {R} rows)")
+        return window, stride, max_lag, R
+
+    def spatial_window_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, max_lag=1, check=True):
+        """When does the audience's attention move (include/vet.h: vet_window_divergence): for every row r — frames
+        [r * stride, r * stride + window) — and every lag l = 1 .. max_lag the mass-weighted Jensen-Shannon divergence, in bits,
+        between the pooled tile histograms of rows r and r + l (``spatial_windowed``'s ``weights``), averaged over the lattices.
+        Returns dict(divergence[R,L], samples[R], code), R = (T - window) // stride + 1, ``divergence[r, l - 1] = D(r, l)``.
+        Entries with r + l >= R are NaN, and so is every pair with a window that has no sample (``samples`` 0) — data, never an
+        error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        window, stride, max_lag, R = self._window_divergence_args(T, window, stride, max_lag)
+        div = np.empty((R, max_lag), dtype=np.float64)
+        samples = np.empty(R, dtype=np.int32)
+        rc = self.lib.vet_window_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride, max_lag,
+                                                 _ptr(div), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(divergence=div, samples=samples, code=rc)
+
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -802,6 +840,19 @@ class Plan:
         """d_div [R][U][U]; d_samples [U][R] (include/vet.h: vet_user_divergence)."""
         _check(self.lib, self.lib.vet_user_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
                                                       d_div, d_samples or None, d_status or None, _stream(stream)))
+
+    def spatial_window_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                         max_lag: int, d_div: int, d_samples: int = 0, d_status: int = 0, stream=None,
+                                         d_ids: int = 0):
+        """d_div [R][max_lag]; d_samples [R] (include/vet.h: vet_window_divergence; ``d_ids``: vet_window_divergence_ids)."""
+        if d_ids:
+            _check(self.lib, self.lib.vet_window_divergence_ids(self.handle, d_ids, n_users, n_frames, int(window), int(stride),
+                                                                int(max_lag), d_div, d_samples or None, d_status or None,
+                                                                _stream(stream)))
+        else:
+            _check(self.lib, self.lib.vet_window_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
+                                                            int(max_lag), d_div, d_samples or None, d_status or None,
+                                                            _stream(stream)))
 
     def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

@@ -256,5 +256,34 @@ class _EntropyAnalyzerBase:
         df.attrs["users"] = list(names)
         return df
 
+    @staticmethod
+    def _lag_args(max_lag, window: int, stride: int, n_frames: int) -> int:
+        """max_lag as an int; ``ValueError`` unless 1 <= max_lag <= rows - 1."""
+        if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)):
+            raise ValueError(f"max_lag must be an integer number of rows (got {max_lag!r})")
+        rows = (n_frames - window) // stride + 1
+        if not 1 <= int(max_lag) <= rows - 1:
+            raise ValueError(f"max_lag must be between 1 and rows - 1 = {rows - 1} (got {max_lag}; window={window}, "
+                             f"stride={stride} give {rows} rows of {n_frames} frames)")
+        return int(max_lag)
+
+    @staticmethod
+    def _window_divergence_frame(times, window: int, stride: int, res: dict) -> pd.DataFrame:
+        """The window-to-window divergence as a DataFrame, one row per window: ``shift`` is the lag-1 value, the ``divergence``
+        cell of row r the [L] view ``res["divergence"][r]`` (no copy); ``attrs["lags"]`` / ``attrs["lag_frames"]`` give the lags
+        in rows and in frames."""
+        div = res["divergence"]
+        R, L = div.shape
+        first = np.arange(R, dtype=np.int64) * stride
+        times = np.asarray(times)
+        d_col = np.empty(R, dtype=object)
+        for r in range(R):
+            d_col[r] = div[r]
+        df = pd.DataFrame({"time": times[first], "time_end": times[first + window - 1], "samples": res["samples"],
+                           "shift": div[:, 0], "divergence": d_col})
+        df.attrs["lags"] = list(range(1, L + 1))
+        df.attrs["lag_frames"] = [stride * l for l in range(1, L + 1)]
+        return df
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

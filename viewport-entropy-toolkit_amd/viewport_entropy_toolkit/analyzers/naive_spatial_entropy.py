@@ -170,6 +170,31 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             raise
         return self._divergence_frame(names, times, window, stride, res)
 
+    def compute_window_divergence(self, window: int, stride: int = 1, max_lag: int = 1) -> pd.DataFrame:
+        """When does the audience's attention move between lat/lon cells: for every row r — frames
+        [r * stride, r * stride + window) — and every lag l = 1 .. ``max_lag`` (in rows) the Jensen-Shannon divergence, in bits,
+        between the pooled cell counts of rows r and r + l, each window weighted by its samples
+        (``SpatialEntropyAnalyzer.compute_window_divergence`` on ``compute_naive_spatial_entropy``'s histogram).
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end``,
+        ``samples``, ``shift`` (the lag-1 value) and ``divergence`` (an [L] view into the one result array);
+        ``attrs["lags"]`` = [1 .. L], ``attrs["lag_frames"]`` = [stride, 2 stride, ...].  Entries whose partner row does not
+        exist are NaN, and so are the pairs of a window without a sample — returned, never raised.  Raises ``ValidationError``
+        before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` /
+        ``max_lag``."""
+        if not self._data_cache or self._dense is None:
+            raise ValidationError("No data available. Call process_directory first.")
+        times, mu, mv, names = self._dense
+        window, stride = self._window_args(window, stride, len(times))
+        max_lag = self._lag_args(max_lag, window, stride, len(times))
+        try:
+            res = self._naive_plan().spatial_window_divergence(mu=mu, mv=mv, window=window, stride=stride, max_lag=max_lag)
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._window_divergence_frame(times, window, stride, res)
+
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
     def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
         plan, _, _, tw, th = self._heatmap_source

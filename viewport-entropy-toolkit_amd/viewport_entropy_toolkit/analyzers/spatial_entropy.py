@@ -170,5 +170,37 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             raise
         return self._divergence_frame(names, times, window, stride, res)
 
+    def compute_window_divergence(self, window: int, stride: int = 1, max_lag: int = 1) -> pd.DataFrame:
+        """When does the audience's attention move: for every row r — frames [r * stride, r * stride + window) — and every lag
+        l = 1 .. ``max_lag`` (in rows) the Jensen-Shannon divergence, in bits, between the pooled tile histograms of rows r and
+        r + l (``compute_windowed_entropy``'s ``tile_weights``), each window weighted by its mass, averaged over the lattices:
+        ``D(r, l) = S(P_r + P_{r+l}) - (W_r S(P_r) + W_{r+l} S(P_{r+l})) / (W_r + W_{r+l})`` with ``S`` the reference's entropy of
+        one dict before the normaliser.  0 = the same tiles in the same proportions, 1 = equal masses on disjoint tiles: a crowd
+        that jumps across the sphere keeps its entropy but shows here.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end`` (of
+        the row's first / last frame), ``samples``, ``shift`` (the lag-1 value: the attention-shift series) and ``divergence``
+        (an [L] view into the one result array; entry l - 1 is lag l); ``attrs["lags"]`` = [1 .. L] and
+        ``attrs["lag_frames"]`` = [stride, 2 stride, ...].  Entries whose partner row does not exist are NaN, and so are the
+        pairs of a window without a sample (``samples`` 0) — returned, never raised.  Raises ``ValidationError`` before data is
+        loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` / ``max_lag``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(window, stride, len(times))
+        max_lag = self._lag_args(max_lag, window, stride, len(times))
+        try:
+            if kind == "grid":
+                res = self._get_plan().spatial_window_divergence(mu=a, mv=b, window=window, stride=stride, max_lag=max_lag)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.spatial_window_divergence(ids=a, window=window, stride=stride, max_lag=max_lag)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._window_divergence_frame(times, window, stride, res)
+
     def _frame_present(self):
         return self._present
