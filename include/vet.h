@@ -55,7 +55,8 @@ extern "C" {
                           then the vet_transition_entropy_windowed* entry points (pooled transitions of windows of pairs) and
                           the vet_user_entropy* entry points (each viewer's own histogram over time), and then the
                           vet_user_divergence* entry points (a U x U Jensen-Shannon matrix between viewers per window), and
-                          then the vet_window_divergence* entry points (a lag band of Jensen-Shannon distances between windows) */
+                          then the vet_window_divergence* entry points (a lag band of Jensen-Shannon distances between windows) and the
+                          vet_crowd_divergence* entry points (each viewer's Kullback-Leibler divergence from the pooled crowd) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -113,6 +114,10 @@ int vet_test_divergence_chunk_rows(vet_ctx *ctx, int rows);
  * of max_lag rows) instead of as many as its workspace budget holds, so that a small input runs several chunks and the halo
  * crosses them; 0 restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
 int vet_test_window_divergence_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes vet_crowd_divergence* take `rows` rows per chunk instead of as many as its
+ * workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every launch.  Results are
+ * bit-identical whatever the value. */
+int vet_test_crowd_divergence_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -487,6 +492,62 @@ int vet_window_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users,
  * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
 int vet_window_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                                int n_frames, int window, int stride, int max_lag, double *h_div, int32_t *h_samples);
+
+/* ---- viewer-to-crowd divergence: each viewer's Kullback-Leibler divergence from the pooled crowd ------
+ * How typical is each viewer of the audience, window by window, and how much of a window's pooled entropy is disagreement between
+ * viewers rather than each viewer looking around?  Rows are vet_user_entropy's and vet_spatial_entropy_windowed's: window = w,
+ * stride = s, R = vet_window_rows(T, w, s), row r covers frames [r*s, r*s + w).  For a lattice of n tiles let h_u be viewer u's
+ * histogram of the row with total W_u — exactly what vet_user_entropy returns in d_weights — P_r the row's pooled histogram with
+ * total W_r — exactly what vet_spatial_entropy_windowed returns in d_weights — and
+ *   S(h) = -sum_keys (h_t / W) log2(h_t / W)
+ * the reference's `entropy` of compute_spatial_entropy / compute_naive_spatial_entropy BEFORE it is divided by the normaliser
+ * (utilities/entropy_utils.py:194-198, :425-440).  Then
+ *   D_k(u, r)  = sum_{t in keys of h_u} q_t log2(q_t / p_t),   q_t = h_ut / W_u,   p_t = P_rt / W_r
+ *   D(u, r)    = mean over the plan's lattices of D_k(u, r)     bits, 0 <= D <= log2(W_r / W_u)
+ * 0 = the viewer looks where the crowd looks, in the crowd's proportions; log2(W_r / W_u) = the viewer shares no tile with
+ * anybody.  Per row, summed over the viewers with a sample in it,
+ *   pooled[r]  = S(P_r)
+ *   within[r]  = sum_u (W_u / W_r) S(h_u)
+ *   between[r] = sum_u (W_u / W_r) D_k(u, r)        (taken directly, not as a difference)
+ * each the mean over the lattices; pooled = within + between up to rounding: between is the generalised Jensen-Shannon
+ * divergence of the whole audience.
+ *   d_div     [U][R]   user-major like vet_user_entropy.  NaN where the viewer has no sample in the row (such slots are data, not
+ *                      errors: the _host entry never returns VET_ERR_EMPTY), where the viewer's own S is NaN under the
+ *                      reference's q * log2 q (a key whose sum is 0.0, or whose h_t / W underflows to 0), and where the row's
+ *                      own S is
+ *   d_rows    [3][R]   pooled, within, between.  pooled is NaN exactly where the row has no sample or its own S is NaN; within
+ *                      and between are NaN there and where any present viewer's own S is NaN                     (nullable)
+ *   d_samples [U][R]   present samples per (viewer, row), as vet_user_entropy                                   (nullable)
+ *   d_status  [2]      {bad, #(row, viewer) slots without a sample}; the call ADDS, the caller zeroes             (nullable)
+ * Stages; everything lives in the context's grow-only workspace, no allocation in steady state:
+ *   1 k_user_dirs, unchanged: direction ids transposed once;
+ *   2 vet_spatial_entropy_windowed's stage 1, unchanged: every frame's histogram once;
+ *   3 per lattice and chunk of rows (as many as fit 256 MB of pooled histograms, their log2 tables and per-viewer statistics,
+ *     at least one): k_window_hist_w/_c leave P[rows][n], W_r and the row's flag, k_crowd_logp log2 p_t per row and tile;
+ *   4 k_crowd_w (weighted Fibonacci lattices) / k_crowd_c (unweighted and binned lattices): one workgroup per (row, viewer),
+ *     the viewer fastest.  The viewer's histogram is built in LDS by vet_user_entropy's walk (the same wave split, the same
+ *     order of additions) and never written to memory; one wave takes W_u, S(h_u) and D = sum q_t (log2 q_t - log2 p_t)
+ *     against the row's log2 p table read from global memory — the one FP64 log2 per key tile serves S and D — every
+ *     reduction in lane order followed by the wave butterfly;
+ *   5 k_crowd_rows: one wave per row, each lane sums its viewers in ascending order.
+ *   Several lattices: lattice 0 stores its value / K, lattice k adds its own, in lattice order.
+ * A value is a pure function of the plan, the window and the frames of its row: the same bits whatever n_frames and stride
+ * selected the row, wherever it falls in a launch or a row chunk, from run to run, and between the ids and the grid entry points.
+ * VET_ERR_INVALID (before anything is launched or allocated): vet_user_entropy's.  VET_ERR_UNSUPPORTED (likewise):
+ * R * n_users >= 2^31, n_frames > 65535 * 64, vet_user_entropy's and vet_spatial_entropy_windowed's limits on the plan.
+ * Profile ids: k_user_dirs to k_spatial, stage 2 as vet_spatial_entropy_windowed's (k_weights / k_spatial), k_window_hist_* and
+ * k_crowd_rows to k_finalize, k_crowd_w / k_crowd_c to k_transition — the one id the call does not use otherwise, so that the
+ * (row, viewer) stage can be told from stage 2's gather.  Asynchronous on `stream` like vet_spatial_entropy. */
+int vet_crowd_divergence(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                         double *d_div, double *d_rows, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_crowd_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                             double *d_div, double *d_rows, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa; h_rows and
+ * h_samples may be NULL. */
+int vet_crowd_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                              int n_frames, int window, int stride, double *h_div, double *h_rows, int32_t *h_samples);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

@@ -11,6 +11,7 @@
 //                       the pairwise viewer divergence kernels (a U x U Jensen-Shannon matrix per row) and their launch logic
 //   vet_window_divergence.hip
 //                       the window-to-window divergence kernels (a lag band of Jensen-Shannon distances per row) and their launch logic
+//   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
@@ -118,6 +119,9 @@ struct Tuning {
     int window_divergence_chunk_rows = 0;   // vet_test_window_divergence_chunk_rows (no environment variable): pair rows per
                                 // histogram chunk of vet_window_divergence* (0 = sized by the workspace budget); read at every
                                 // launch; the results do not depend on it (test_window_divergence_gpu.py)
+    int crowd_divergence_chunk_rows = 0;    // vet_test_crowd_divergence_chunk_rows (no environment variable): rows per chunk of
+                                // vet_crowd_divergence* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_crowd_divergence_gpu.py)
     void from_environment();
 };
 
@@ -367,6 +371,7 @@ int user_set_attrs(vet_ctx* c);
 int user_transition_set_attrs(vet_ctx* c);
 int user_divergence_set_attrs(vet_ctx* c);
 int window_divergence_set_attrs(vet_ctx* c);
+int crowd_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -381,7 +386,13 @@ int window_frames_layout(vet_plan* pl, int U, int T, size_t head_bytes, WindowFr
 int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T,
                       const WindowFrames& wf, int32_t* d_status, hipStream_t s);
 
-// vet_user.hip, shared with vet_user_divergence.hip (which builds the same per-viewer histograms): lattice k counts integers
+// vet_window_divergence.hip, shared with vet_crowd.hip: lattice k's pooled row histograms of rows [h0, h_end) from
+// window_frames_run's arrays (k_window_hist_w/_c) — hist [h_end - h0][n_k] f64 (+0.0 = no key), tot and flag per row (1: no sample,
+// or the row's own S is NaN); rows >= r_new also write samples[r] and add to status[1] where those are given.  Charged to k_finalize.
+int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int window, int stride, long h0, long h_end, long r_new,
+                    double* hist, double* tot, int32_t* flag, int32_t* samples, int32_t* status, hipStream_t s);
+
+// vet_user.hip, shared with vet_user_divergence.hip and vet_crowd.hip (which build the same per-viewer histograms): lattice k counts integers
 // (unweighted / binned); waves per row of the weighted histogram kernel (a function of the window and the plan alone); what
 // the per-viewer spatial calls refuse about their arguments (VET_ERR_INVALID) and about the plan (VET_ERR_UNSUPPORTED; builds
 // the exact weight rows on first use)

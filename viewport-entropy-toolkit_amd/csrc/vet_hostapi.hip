@@ -544,6 +544,41 @@ int vet_user_divergence_host(vet_plan* pl, const double* h_mu, const double* h_m
     return VET_OK;
 }
 
+// Viewer-to-crowd divergence with host buffers (include/vet.h): n_users * vet_window_rows values, user-major, and the three row
+// series.  (row, viewer) slots without a sample are data (NaN): only VET_ERR_RANGE is decoded from the status words.
+int vet_crowd_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                              int stride, double* h_div, double* h_rows, int32_t* h_samples) {
+    int rc = check_host_args(pl, U, T, h_div, h_mu, h_mv, h_ids);
+    if (rc) return rc;
+    const int64_t R = vet_window_rows(T, window, stride);
+    if (R < 0)
+        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
+                    stride, T);
+    const size_t slots = (size_t)R * U, r_bytes = (size_t)3 * R * 8;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    hipStream_t s = run.s;
+    double *div = nullptr, *rows = nullptr;
+    int32_t* cnt = nullptr;
+    POOL(SLOT_ENTROPY, slots * 8, div);
+    if (h_rows) POOL(SLOT_OUT1, r_bytes, rows);
+    POOL(SLOT_COUNT, slots * 4, cnt);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = run.ids ? vet_crowd_divergence_ids(pl, run.ids, U, T, window, stride, div, rows, cnt, run.status, s)
+                 : vet_crowd_divergence(pl, run.mu, run.mv, U, T, window, stride, div, rows, cnt, run.status, s);
+    if (rc) return run.drain(rc);
+    HIP_TRY(hipMemcpyAsync(h_div, div, slots * 8, hipMemcpyDeviceToHost, s));
+    if (h_rows) HIP_TRY(hipMemcpyAsync(h_rows, rows, r_bytes, hipMemcpyDeviceToHost, s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, slots * 4, hipMemcpyDeviceToHost, s));
+    rc = run.sync(true);
+    if (rc) return rc;
+    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
+    return VET_OK;
+}
+
 // Window-to-window divergence with host buffers (include/vet.h): vet_window_rows rows of max_lag lags.  Rows without a sample are
 // data (NaN across their band): only VET_ERR_RANGE is decoded from the status words.
 int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,

@@ -38,6 +38,10 @@
 //                                                               k_window_entropy's sums), their totals and NaN flags, per row chunk
 //                                              k_window_divergence   one thread per (row, lag): Jensen-Shannon divergence of rows r
 //                                                               and r + l in the overlap form, histograms staged through LDS
+//   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
+//                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
+//                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave
+//                                              k_crowd_rows     one wave per row: pooled, within and between
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

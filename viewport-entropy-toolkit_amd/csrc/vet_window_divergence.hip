@@ -226,6 +226,34 @@ __global__ __launch_bounds__(256) void k_window_divergence(const WindowDivParams
 
 namespace vh {
 
+// ---- stage 2, shared with vet_crowd.hip (vet_host.hpp): lattice k's pooled histograms of rows [h0, h_end) from stage 1's arrays
+int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int window, int stride, long h0, long h_end, long r_new,
+                    double* hist, double* tot, int32_t* flag, int32_t* samples, int32_t* status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const Lattice& Lk = pl->lat[k];
+    const char* ws = (const char*)c->ws;
+    const long hr = h_end - h0;
+    const vet::WinStats st{hist, tot, flag};
+    ProfScope ps(c, s, KID_FINALIZE);
+    if (counts_lattice(pl, k)) {
+        vet::WindowHistCParams q{};
+        q.tiles = (const int32_t*)(ws + wf.off[k]); q.U = U; q.n = Lk.n; q.window = window; q.stride = stride;
+        q.h0 = h0; q.r_new = r_new; q.out = st; q.samples = samples; q.status = status;
+        hipLaunchKernelGGL(vet::k_window_hist_c, dim3((unsigned)hr), dim3(vet::WAVE), (size_t)Lk.n * 4, s, q);
+    } else {
+        vet::WindowHistWParams q{};
+        q.frames = (const double*)(ws + wf.off[k]); q.present = (const int32_t*)(ws + wf.present_off);
+        q.n = Lk.n; q.window = window; q.stride = stride;
+        q.h0 = h0; q.h_end = h_end; q.r_new = r_new; q.out = st; q.samples = samples; q.status = status;
+        int nw = 4;                                    // k_window_entropy_w's launch shape
+        while (nw > 1 && (size_t)nw * Lk.n * 8 > 32 * 1024) nw /= 2;
+        hipLaunchKernelGGL(vet::k_window_hist_w, dim3((unsigned)((hr + nw - 1) / nw)), dim3(nw * vet::WAVE),
+                           (size_t)nw * Lk.n * 8, s, q);
+    }
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
+
 namespace {
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
@@ -286,30 +314,14 @@ int launch_window_divergence(vet_plan* pl, const double* d_mu, const double* d_m
     rc = window_frames_run(pl, d_mu, d_mv, d_ids, U, T, wf, d_status, s);
     if (rc) return rc;
     for (long r0 = 0; r0 < R; r0 += CR) {
-        const long r_end = std::min(R, r0 + CR), h_end = std::min(R, r_end + L), hr = h_end - r0;
+        const long r_end = std::min(R, r0 + CR), h_end = std::min(R, r_end + L);
         const long r_new = r0 == 0 ? 0 : std::min(R, r0 + L);      // rows below were written by the chunk before
         for (int k = 0; k < K; ++k) {
             const Lattice& Lk = pl->lat[k];
             int32_t *samples = k == 0 ? d_samples : nullptr, *status = k == 0 ? d_status : nullptr;
-            {   // ---- stage 2, charged to k_finalize
-                ProfScope ps(c, s, KID_FINALIZE);
-                if (counts_lattice(pl, k)) {
-                    vet::WindowHistCParams q{};
-                    q.tiles = (const int32_t*)(ws + wf.off[k]); q.U = U; q.n = Lk.n; q.window = window; q.stride = stride;
-                    q.h0 = r0; q.r_new = r_new; q.out = st; q.samples = samples; q.status = status;
-                    hipLaunchKernelGGL(vet::k_window_hist_c, dim3((unsigned)hr), dim3(vet::WAVE), (size_t)Lk.n * 4, s, q);
-                } else {
-                    vet::WindowHistWParams q{};
-                    q.frames = (const double*)(ws + wf.off[k]); q.present = (const int32_t*)(ws + wf.present_off);
-                    q.n = Lk.n; q.window = window; q.stride = stride;
-                    q.h0 = r0; q.h_end = h_end; q.r_new = r_new; q.out = st; q.samples = samples; q.status = status;
-                    int nw = 4;                                    // k_window_entropy_w's launch shape
-                    while (nw > 1 && (size_t)nw * Lk.n * 8 > 32 * 1024) nw /= 2;
-                    hipLaunchKernelGGL(vet::k_window_hist_w, dim3((unsigned)((hr + nw - 1) / nw)), dim3(nw * vet::WAVE),
-                                       (size_t)nw * Lk.n * 8, s, q);
-                }
-                HIP_TRY(hipGetLastError());
-            }
+            // ---- stage 2, charged to k_finalize
+            rc = window_hist_run(pl, k, U, wf, window, stride, r0, h_end, r_new, st.hist, st.tot, st.flag, samples, status, s);
+            if (rc) return rc;
             {   // ---- stage 3, charged to k_transition: the one profile id the call does not use otherwise
                 vet::WindowDivParams q{};
                 q.in = st; q.n = Lk.n; q.h0 = r0; q.h_end = h_end; q.r0 = r0; q.r_end = r_end; q.R = R; q.L = L;

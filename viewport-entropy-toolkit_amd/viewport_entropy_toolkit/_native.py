@@ -82,6 +82,7 @@ SIGNATURES = {
     "vet_test_user_transition_hash": (_I, [_P, _I]),
     "vet_test_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_window_divergence_chunk_rows": (_I, [_P, _I]),
+    "vet_test_crowd_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -126,6 +127,9 @@ SIGNATURES = {
     "vet_window_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_window_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_window_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vet_crowd_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_crowd_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_crowd_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -367,6 +371,11 @@ class Engine:
         """Test switch: the window divergence takes ``rows`` pair rows per histogram chunk (0: the default budget); results do
         not depend on it (include/vet.h: vet_test_window_divergence_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_window_divergence_chunk_rows(self.handle, int(rows)))
+
+    def test_crowd_divergence_chunk_rows(self, rows: int = 0):
+        """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
+        it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_crowd_divergence_chunk_rows(self.handle, int(rows)))
 
     def profile_enable(self, on: bool = True):
         _check(self.lib, self.lib.vet_profile_enable(self.handle, int(on)))
@@ -638,6 +647,29 @@ class Plan:
             _check(self.lib, rc)
         return dict(divergence=div, samples=samples, code=rc)
 
+    def spatial_crowd_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, check=True):
+        """How typical each viewer is of the audience (include/vet.h: vet_crowd_divergence): for every row r — frames
+        [r * stride, r * stride + window), ``window=None`` the whole video — and viewer u the Kullback-Leibler divergence, in
+        bits, of the viewer's tile histogram (``spatial_per_user``'s ``weights``) from the row's pooled histogram
+        (``spatial_windowed``'s ``weights``), averaged over the lattices: 0 = the crowd's places in the crowd's proportions,
+        log2(W_r / W_u) = no tile shared with anybody.  Returns dict(divergence[U,R], rows[3,R], samples[U,R], code),
+        R = (T - window) // stride + 1; ``rows`` holds pooled = S(P_r), within = sum_u (W_u / W_r) S(h_u) and
+        between = sum_u (W_u / W_r) D(u, r), pooled = within + between.  A viewer without a sample in the row is NaN with
+        ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        window, stride = T if window is None else int(window), int(stride)
+        R = int(self.lib.vet_window_rows(T, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        div = np.empty((U, R), dtype=np.float64)
+        rows = np.empty((3, R), dtype=np.float64)
+        samples = np.empty((U, R), dtype=np.int32)
+        rc = self.lib.vet_crowd_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
+                                                _ptr(div), _ptr(rows), _ptr(samples))
+        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(divergence=div, rows=rows, samples=samples, code=rc)
+
     def _window_divergence_args(self, T, window, stride, max_lag):
         if window is None:
             raise ValueError("window (a number of frames) is required")
@@ -840,6 +872,20 @@ class Plan:
         """d_div [R][U][U]; d_samples [U][R] (include/vet.h: vet_user_divergence)."""
         _check(self.lib, self.lib.vet_user_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
                                                       d_div, d_samples or None, d_status or None, _stream(stream)))
+
+    def spatial_crowd_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                        d_div: int, d_rows: int = 0, d_samples: int = 0, d_status: int = 0, stream=None,
+                                        d_ids: int = 0):
+        """d_div [U][R]; d_rows [3][R]; d_samples [U][R] (include/vet.h: vet_crowd_divergence; ``d_ids``:
+        vet_crowd_divergence_ids)."""
+        if d_ids:
+            _check(self.lib, self.lib.vet_crowd_divergence_ids(self.handle, d_ids, n_users, n_frames, int(window), int(stride),
+                                                               d_div, d_rows or None, d_samples or None, d_status or None,
+                                                               _stream(stream)))
+        else:
+            _check(self.lib, self.lib.vet_crowd_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
+                                                           d_div, d_rows or None, d_samples or None, d_status or None,
+                                                           _stream(stream)))
 
     def spatial_window_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                          max_lag: int, d_div: int, d_samples: int = 0, d_status: int = 0, stream=None,

@@ -257,6 +257,30 @@ class _EntropyAnalyzerBase:
         return df
 
     @staticmethod
+    def _crowd_frame(names, times, window: int, stride: int, res: dict) -> pd.DataFrame:
+        """The viewer-to-crowd divergence as a DataFrame, user-major: one row per (user, r) in the order of ``res``'s [U][R]
+        arrays; ``attrs["rows"]`` is the per-window DataFrame of the decomposition pooled = within + between,
+        ``attrs["users"]`` names the viewers."""
+        U, R = res["divergence"].shape
+        row_first = np.arange(R, dtype=np.int64) * stride
+        first = np.tile(row_first, U)
+        times = np.asarray(times)
+        df = pd.DataFrame({
+            "user": np.repeat(np.asarray(list(names), dtype=object), R),
+            "time": times[first],
+            "time_end": times[first + window - 1],
+            "divergence": res["divergence"].reshape(-1),
+            "samples": res["samples"].reshape(-1),
+        })
+        df.attrs["rows"] = pd.DataFrame({
+            "time": times[row_first], "time_end": times[row_first + window - 1],
+            "samples": res["samples"].sum(axis=0, dtype=np.int64),
+            "pooled": res["rows"][0], "within": res["rows"][1], "between": res["rows"][2],
+        })
+        df.attrs["users"] = list(names)
+        return df
+
+    @staticmethod
     def _lag_args(max_lag, window: int, stride: int, n_frames: int) -> int:
         """max_lag as an int; ``ValueError`` unless 1 <= max_lag <= rows - 1."""
         if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)):

@@ -195,6 +195,29 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             raise
         return self._window_divergence_frame(times, window, stride, res)
 
+    def compute_crowd_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """How typical each viewer is of the audience, on lat/lon cells: for every row r — frames
+        [r * stride, r * stride + window), ``window=None`` the whole video — and viewer u the Kullback-Leibler divergence, in
+        bits, of the viewer's cell counts from the window's pooled cell counts
+        (``SpatialEntropyAnalyzer.compute_crowd_divergence`` on ``compute_naive_spatial_entropy``'s histogram).
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, user-major, one row per (user, r): ``user``,
+        ``time`` / ``time_end``, ``divergence`` and ``samples``; ``attrs["rows"]`` is the per-window DataFrame (``time``,
+        ``time_end``, ``samples``, ``pooled``, ``within``, ``between``), ``attrs["users"]`` the user names.  A viewer without a
+        sample in the window is NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is
+        loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
+        if not self._data_cache or self._dense is None:
+            raise ValidationError("No data available. Call process_directory first.")
+        times, mu, mv, names = self._dense
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            res = self._naive_plan().spatial_crowd_divergence(mu=mu, mv=mv, window=window, stride=stride)
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._crowd_frame(names, times, window, stride, res)
+
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)
     def _heatmap(self, width: int, height: int, marker_radius: int) -> "_native.Heatmap":
         plan, _, _, tw, th = self._heatmap_source

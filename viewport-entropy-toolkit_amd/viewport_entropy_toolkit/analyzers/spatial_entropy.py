@@ -202,5 +202,38 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             raise
         return self._window_divergence_frame(times, window, stride, res)
 
+    def compute_crowd_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
+        """How typical each viewer is of the audience: for every row r — frames [r * stride, r * stride + window),
+        ``window=None`` the whole video — and viewer u the Kullback-Leibler divergence, in bits, of the viewer's tile histogram
+        (``compute_user_entropy``'s ``tile_weights``, total ``W_u``) from the window's pooled histogram
+        (``compute_windowed_entropy``'s ``tile_weights``, total ``W_r``), averaged over the lattices:
+        ``D(u, r) = sum_t q_t log2(q_t / p_t)``.  0 = the viewer looks where the crowd looks, in the crowd's proportions,
+        ``log2(W_r / W_u)`` = the viewer shares no tile with anybody.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, user-major, one row per (user, r): ``user``,
+        ``time`` / ``time_end`` (of the row's first / last frame), ``divergence`` and ``samples``.  ``attrs["rows"]`` is a
+        DataFrame with one row per window: ``time``, ``time_end``, ``samples``, ``pooled`` (the entropy of the pooled histogram
+        before the normaliser, bits), ``within`` (the mass-weighted mean of the viewers' own entropies) and ``between`` (the
+        mass-weighted mean of ``divergence``: the generalised Jensen-Shannon divergence of the audience);
+        ``pooled = within + between``.  ``attrs["users"]`` holds the user names.  A viewer without a sample in the window is NaN
+        with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside
+        [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
+        kind, times, a, b, names = self._samples()
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            if kind == "grid":
+                res = self._get_plan().spatial_crowd_divergence(mu=a, mv=b, window=window, stride=stride)
+            else:
+                plan = self._get_plan(dir_table=b)
+                try:
+                    res = plan.spatial_crowd_divergence(ids=a, window=window, stride=stride)
+                finally:
+                    plan.close()
+        except _native.NativeError as e:
+            if e.code == _native.VET_ERR_RANGE:
+                raise ValidationError(str(e))
+            raise
+        return self._crowd_frame(names, times, window, stride, res)
+
     def _frame_present(self):
         return self._present
