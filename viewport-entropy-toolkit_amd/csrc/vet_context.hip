@@ -136,6 +136,18 @@ int check_run_args(const vet_plan* pl, int U, int T, const void* out) {
     return VET_OK;
 }
 
+int entry_samples(const vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, const char* ids_entry,
+                  void* stream, hipStream_t* s) {
+    if (ids_entry) {
+        if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use %s", ids_entry);
+        if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
+    } else if (!d_ids) {
+        return fail(VET_ERR_INVALID, "d_ids is NULL");
+    }
+    *s = stream ? (hipStream_t)stream : pl->ctx->stream;
+    return VET_OK;
+}
+
 }  // namespace vh
 
 using namespace vh;

@@ -29,16 +29,14 @@
 #include "vet_common.hpp"
 #include "vet_spatial_dtable.hpp"
 #include "vet_user_dirs.hpp"
+#include "vet_row_hist.hpp"
 
 #include <algorithm>
 
 namespace vet {
 
-// what stage 3 leaves per row of the chunk (read-only here)
-struct CrowdRows {
-    const double* hist;          // [CR][n]  P_r (+0.0 where the row has no key)
-    const double* tot;           // [CR]     W_r
-    const int32_t* flag;         // [CR]     1: no sample in the row, or the row's own S is NaN
+// what stage 3 leaves per row of the chunk (read-only here): RowStats — P_r [CR][n], W_r [CR] and the row's flag [CR] — and
+struct CrowdRows : RowStats {
     const double* logp;          // [CR][n]  log2(P_rt / W_r) where P_rt > 0 (k_crowd_logp), +0.0 elsewhere
 };
 
@@ -63,20 +61,15 @@ struct CrowdOut {
 };
 
 // Wave 0's epilogue of k_crowd_w / k_crowd_c for slot = rc * U + u.  value(t, v): whether tile t is a key of the viewer's
-// histogram, and its value.  W_u in lane order over the keys, then S(h_u) and D in one pass in lane order: q = v / W_u,
-// S -= q log2 q (k_user_entropy_w's statement; the reference's term: NaN for q = 0), D += q (log2 q - log2 p_t) with log2 p_t
+// histogram, and its value (vet_row_hist.hpp).  W_u = row_total, then S(h_u) and D in one pass in lane order: q = v / W_u,
+// S -= q log2 q (row_entropy's statement; the reference's term: NaN for q = 0), D += q (log2 q - log2 p_t) with log2 p_t
 // read from the row's table: the one log2 of the tile serves both sums.
 template <class V>
 __device__ __forceinline__ void crowd_epilogue(const CrowdRows& in, const CrowdOut& o, long slot, int n, int n_present, V value) {
     const int lane = lane_id();
     const long rc = slot / o.U, u = slot - rc * o.U, r = o.r0 + rc;
     const double* LP = in.logp + rc * (long)n;
-    double tot = 0.0;
-    for (int t = lane; t < n; t += WAVE) {
-        double v;
-        if (value(t, v)) tot += v;
-    }
-    tot = wave_sum(tot);
+    const double tot = row_total(n, value);
     double hh = 0.0, dd = 0.0;
     for (int t = lane; t < n; t += WAVE) {
         double v;
@@ -104,8 +97,8 @@ __device__ __forceinline__ void crowd_epilogue(const CrowdRows& in, const CrowdO
 
 // ------------------------------------------------------------------------------------------
 // k_crowd_w — stage 4 of a weighted Fibonacci lattice for rows [r0, r0 + CR).  One workgroup per (row, viewer),
-// blockIdx = (r - r0) * U + u.  k_user_entropy_w up to its tile values in LDS (same loops, same NW from the host: add_exact_rows
-// in ascending frame order, waves_in_order); then wave 0 runs crowd_epilogue.  Nothing of the histogram is written to memory.
+// blockIdx = (r - r0) * U + u.  user_walk_w (vet_user_dirs.hpp: k_user_entropy_w's walk, same NW from the host) leaves the tile
+// values in LDS; then wave 0 runs crowd_epilogue.  Nothing of the histogram is written to memory.
 // LDS: dtable_lds_bytes(NW, n).
 // ------------------------------------------------------------------------------------------
 struct CrowdWParams {
@@ -122,42 +115,16 @@ template <int S>
 __global__ __launch_bounds__(256) void k_crowd_w(const CrowdWParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* hist = (double*)smem;                                  // [NW][n]
-    const int NW = blockDim.x >> 6, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
-    const int n = p.X.n;
-    int* cnt_w = (int*)(hist + (size_t)NW * n);                    // [NW] present samples per wave
     const long slot = blockIdx.x, rc = slot / p.o.U, u = slot - rc * p.o.U, r = p.o.r0 + rc;
-    const int32_t* d = p.dirs + u * (long)p.T + r * (long)p.stride;
-    double* h = hist + (size_t)wv * n;
-    for (int t = lane; t < n; t += WAVE) ((unsigned long long*)h)[t] = NO_KEY_BITS;
-    const int per = (p.window + NW - 1) / NW;
-    const int j_begin = min(p.window, wv * per), j_end = min(p.window, j_begin + per);
-    int np = 0;
-    for (int j0 = j_begin; j0 < j_end; j0 += WAVE) {
-        const int j = j0 + lane;
-        const int id = j < j_end ? d[j] : -1;
-        const uint32_t a = id >= 0 ? p.alias[id] : 0u;
-        add_exact_rows<S>(h, p.X, (int)(a & 0x7FFFFFFFu), (int)(a >> 31), id >= 0, min(WAVE, j_end - j0));
-        np += id >= 0 ? 1 : 0;
-    }
-    np = wave_sum(np);
-    if (lane == 0) cnt_w[wv] = np;
-    __syncthreads();
-    // tile values, wave order, into wave 0's share (every slot is read and written by one thread only)
-    for (int t = tid; t < n; t += blockDim.x) hist[t] = waves_in_order(hist, NW, n, t);
-    int n_present = 0;
-    for (int w2 = 0; w2 < NW; ++w2) n_present += cnt_w[w2];
-    __syncthreads();
-    if (wv != 0) return;
-    crowd_epilogue(p.in, p.o, slot, n, n_present, [&](int t, double& v) {
-        v = hist[t];
-        return (unsigned long long)__double_as_longlong(v) != NO_KEY_BITS;
-    });
+    const int n_present = user_walk_w<S>(hist, p.dirs + u * (long)p.T + r * (long)p.stride, p.alias, p.X, p.window, [](int, double) {});
+    if (wave_id() != 0) return;
+    crowd_epilogue(p.in, p.o, slot, p.X.n, n_present, KeyedHist{hist, NO_KEY_BITS});
 }
 
 // ------------------------------------------------------------------------------------------
 // k_crowd_c — stage 4 of an integer-count lattice (unweighted nearest tile, naive lat/lon bins) for rows [r0, r0 + CR).  One wave
-// per (row, viewer), blockIdx = (r - r0) * U + u: k_user_entropy_c's counting walk (user_count) over the row's frames, every row
-// counted afresh, then crowd_epilogue on the exact integers (a key is a tile with a count; W_u = the row's samples).
+// per (row, viewer), blockIdx = (r - r0) * U + u: user_row_count (vet_user_dirs.hpp) over the row's frames, every row counted
+// afresh, then crowd_epilogue on the exact integers (a key is a tile with a count; W_u = the row's samples).
 // LDS: u32 [n].
 // ------------------------------------------------------------------------------------------
 struct CrowdCParams {
@@ -173,16 +140,8 @@ struct CrowdCParams {
 __global__ __launch_bounds__(64) void k_crowd_c(const CrowdCParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* cnt = (unsigned*)smem;
-    const int lane = lane_id();
-    for (int t = lane; t < p.n; t += WAVE) cnt[t] = 0u;
-    __syncthreads();
     const long slot = blockIdx.x, rc = slot / p.o.U, u = slot - rc * p.o.U, r = p.o.r0 + rc;
-    const long f0 = r * (long)p.stride;
-    user_count(cnt, p.n, p.dirs + u * (long)p.T, p.nearest, f0, f0 + p.window, 1u);
-    __syncthreads();
-    int np = 0;
-    for (int t = lane; t < p.n; t += WAVE) np += (int)cnt[t];
-    np = wave_sum(np);
+    const int np = user_row_count(cnt, p.n, p.dirs + u * (long)p.T, p.nearest, r * (long)p.stride, p.window, [](int, unsigned) {});
     crowd_epilogue(p.in, p.o, slot, p.n, np, [&](int t, double& v) {
         const unsigned c = cnt[t];
         v = (double)c;
@@ -258,18 +217,11 @@ namespace vh {
 
 namespace {
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // bytes a chunk of rows may take in the workspace: the P rows and the per-(row, viewer) statistics
 constexpr size_t kCrowdBudget = (size_t)256 << 20;
 
-const void* crowd_w_kernel(int stride) {
-    const int chunks = stride / vet::WAVE;
-    return chunks <= 1 ? (const void*)vet::k_crowd_w<1> : chunks <= 2 ? (const void*)vet::k_crowd_w<2>
-         : chunks <= 4 ? (const void*)vet::k_crowd_w<4> : (const void*)vet::k_crowd_w<0>;
-}
+const void* crowd_w_kernel(int stride) { return VET_KERNEL_BY_S(vet::k_crowd_w, row_chunk_class(stride)); }
 
-template <bool FROM_IDS>
 int launch_crowd(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
                  double* d_div, double* d_rows, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
     vet_ctx* c = pl->ctx;
@@ -278,9 +230,9 @@ int launch_crowd(vet_plan* pl, const double* d_mu, const double* d_mv, const int
     // ---- what the call refuses, before anything is launched or allocated
     if (R * (long)U >= (1L << 31))
         return fail(VET_ERR_UNSUPPORTED, "crowd divergence: %ld rows x users in one call (fewer than 2^31)", R * (long)U);
-    const unsigned gy = (unsigned)((T + vet::UT - 1) / vet::UT);
-    if (gy > 65535u) return fail(VET_ERR_UNSUPPORTED, "crowd divergence: %d frames in one call (at most %d)", T, 65535 * vet::UT);
-    int rc = check_user_plan(pl, "crowd divergence", s);
+    int rc = check_user_dirs_frames(T, "crowd divergence");
+    if (rc) return rc;
+    rc = check_user_plan(pl, "crowd divergence", s);
     if (rc) return rc;
     WindowFrames wf;
     rc = window_frames_layout(pl, U, T, 0, wf, s);
@@ -295,32 +247,23 @@ int launch_crowd(vet_plan* pl, const double* d_mu, const double* d_mv, const int
     CR = std::max(1L, std::min({CR, R, ((1L << 31) - 1) / U}));
     // workspace: stage 2's arrays | dirs [U][T] | P [CR][n_max] | log2 p [CR][n_max] | W_r [CR] | row flag [CR] |
     //            D, W_u, S_u [CR][U] | flag [CR][U]
-    const size_t dirs_b = pad16((size_t)U * T * sizeof(int32_t)), hist_b = pad16((size_t)CR * n_max * sizeof(double)),
-                 tot_b = pad16((size_t)CR * sizeof(double)), rflag_b = pad16((size_t)CR * sizeof(int32_t)),
-                 su_b = pad16((size_t)CR * U * sizeof(double)), uflag_b = pad16((size_t)CR * U * sizeof(int32_t));
-    rc = ensure_ws(c, wf.bytes + dirs_b + 2 * hist_b + tot_b + rflag_b + 3 * su_b + uflag_b);
+    WsLayout lay{wf.bytes};
+    const size_t dirs_o = lay.take<int32_t>((size_t)U * T), P_o = lay.take<double>((size_t)CR * n_max),
+                 logp_o = lay.take<double>((size_t)CR * n_max), Wr_o = lay.take<double>((size_t)CR),
+                 rflag_o = lay.take<int32_t>((size_t)CR), div_o = lay.take<double>((size_t)CR * U),
+                 tot_o = lay.take<double>((size_t)CR * U), own_o = lay.take<double>((size_t)CR * U),
+                 uflag_o = lay.take<int32_t>((size_t)CR * U);
+    rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    char* at = ws + wf.bytes;
-    int32_t* dirs = (int32_t*)at;                    at += dirs_b;
-    double* P = (double*)at;                         at += hist_b;
-    double* logp = (double*)at;                      at += hist_b;
-    double* Wr = (double*)at;                        at += tot_b;
-    int32_t* rflag = (int32_t*)at;                   at += rflag_b;
-    vet::CrowdStats st{};
-    st.div = (double*)at;                            at += su_b;
-    st.tot = (double*)at;                            at += su_b;
-    st.own = (double*)at;                            at += su_b;
-    st.flag = (int32_t*)at;
-    const vet::CrowdRows in{P, Wr, rflag, logp};
-    {   // ---- stage 1, charged to k_spatial
-        vet::UserDirsParams q{};
-        q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
-        q.U = U; q.T = T; q.dirs = dirs; q.status = d_status;
-        ProfScope ps(c, s, KID_SPATIAL);
-        hipLaunchKernelGGL(vet::k_user_dirs<FROM_IDS>, dim3((unsigned)((U + vet::UT - 1) / vet::UT), gy), dim3(256), 0, s, q);
-        HIP_TRY(hipGetLastError());
-    }
+    int32_t* dirs = (int32_t*)(ws + dirs_o);
+    double *P = (double*)(ws + P_o), *logp = (double*)(ws + logp_o), *Wr = (double*)(ws + Wr_o);
+    int32_t* rflag = (int32_t*)(ws + rflag_o);
+    const vet::CrowdStats st{(double*)(ws + div_o), (double*)(ws + tot_o), (double*)(ws + own_o), (int32_t*)(ws + uflag_o)};
+    const vet::CrowdRows in{{P, Wr, rflag}, logp};
+    // ---- stage 1
+    rc = user_dirs_run(pl, d_mu, d_mv, d_ids, U, T, dirs, d_status, "crowd divergence", s);
+    if (rc) return rc;
     // ---- stage 2 (charged as vet_spatial_entropy_windowed's); a null status: stage 1 has counted the bad samples
     rc = window_frames_run(pl, d_mu, d_mv, d_ids, U, T, wf, nullptr, s);
     if (rc) return rc;
@@ -350,15 +293,12 @@ int launch_crowd(vet_plan* pl, const double* d_mu, const double* d_mv, const int
                     q.in = in; q.o = o;
                     hipLaunchKernelGGL(vet::k_crowd_c, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
                 } else {
-                    const WeightsCore::Exact& X = exact_rows(pl, k);
                     vet::CrowdWParams q{};
-                    q.dirs = dirs; q.T = T; q.alias = pl->d_alias;
-                    q.X = vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(),
-                                         X.stride, L.n};
+                    q.dirs = dirs; q.T = T; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
                     q.window = window; q.stride = stride; q.in = in; q.o = o;
                     const int nw = user_nw(c->lds_max, L.n, window);
                     void* args[] = {(void*)&q};
-                    HIP_TRY(hipLaunchKernel(crowd_w_kernel(X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
+                    HIP_TRY(hipLaunchKernel(crowd_w_kernel(q.X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
                                             vet::dtable_lds_bytes(nw, L.n), s));
                 }
                 HIP_TRY(hipGetLastError());
@@ -393,21 +333,18 @@ extern "C" {
 
 int vet_crowd_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, double* d_div,
                          double* d_rows, int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_div);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_crowd_divergence_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_crowd<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_div, d_rows, d_samples, d_status,
-                               stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_div);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_crowd_divergence_ids", stream, &s);
+    return rc ? rc : launch_crowd(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_div, d_rows, d_samples, d_status, s);
 }
 
 int vet_crowd_divergence_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double* d_div,
                              double* d_rows, int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_div);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_crowd<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_div, d_rows, d_samples, d_status,
-                              stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_div);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_crowd(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_div, d_rows, d_samples, d_status, s);
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
 //                       for heatmaps and tilings), device-resident results, the heatmap and tiling handles (no kernels)
-// Every kernel header is included by exactly one of them (vet_user.hip and vet_user_divergence.hip share the device helpers of vet_weights_pass.hpp / vet_spatial_dtable.hpp, vet_window.hip and vet_window_divergence.hip those of vet_window_hist.hpp).  There is no CPU compute path anywhere.
+// Every kernel header is included by exactly one of them (the per-viewer units share the device helpers of vet_user_dirs.hpp, the windowed units those of vet_window_hist.hpp, both those of vet_row_hist.hpp).  There is no CPU compute path anywhere.
 #pragma once
 #include "../../include/vet.h"
 #include "vet_layout.hpp"
@@ -285,9 +285,26 @@ struct BatchBlob {
 };
 
 int ensure_ws(vet_ctx* c, size_t bytes);                          // grow-only workspace (c->ws)
+// A workspace layout, described once: take<T>(count) places the next array — 16-byte padded, in the order of the calls — and
+// returns its byte offset; `at` ends as the bytes to ask ensure_ws for.  (An array that starts behind another unit's share,
+// WindowFrames::bytes, begins the layout there.)
+inline size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+struct WsLayout {
+    size_t at = 0;
+    template <class T> size_t take(size_t count) {
+        const size_t off = at;
+        at += pad16(count * sizeof(T));
+        return off;
+    }
+};
 int pooled(vet_ctx* c, int slot, size_t bytes, void** out);       // slot-indexed grow-only device buffer
 int grid_for(long work, int block, int n_cu);
 int check_run_args(const vet_plan* pl, int U, int T, const void* out);
+// What the extern "C" device entries of the row calls check after their own arguments, and the stream they launch on (the
+// caller's, or the context's).  ids_entry != null: the (d_mu, d_mv) entry — the plan needs a pixel grid ("...; use <ids_entry>")
+// and both arrays; null: the _ids entry — d_ids.
+int entry_samples(const vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, const char* ids_entry,
+                  void* stream, hipStream_t* s);
 
 constexpr size_t kMaxTableBytes = (size_t)24 << 30;   // per lattice; HBM is 288 GB
 constexpr double kContractMargin = 1e-7;              // bound on |dH|/H an integer formulation may have (contract: 1e-6)
@@ -308,6 +325,15 @@ int ensure_exact_weights(vet_plan* pl, hipStream_t s);
 // the same for lattice k (k = 0: ensure_exact_weights); exact_rows(pl, k) = its tables
 int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s);
 const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k);
+vet::ExactRows exact_rows_arg(const vet_plan* pl, int k);         // ... as the kernels take them (the rows must exist)
+// which instance of a kernel templated on S walks rows of this stride: S = 64-entry chunks of the longest row, 1, 2, 4, or 0 for
+// any number (add_exact_rows); VET_KERNEL_BY_S(k, S) names the instance
+inline int row_chunk_class(int stride) {
+    const int chunks = stride / vet::WAVE;
+    return chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 4 ? 4 : 0;
+}
+#define VET_KERNEL_BY_S(kernel, S)                                                                                       \
+    ((S) == 1 ? (const void*)kernel<1> : (S) == 2 ? (const void*)kernel<2> : (S) == 4 ? (const void*)kernel<4> : (const void*)kernel<0>)
 // vet_spatial.hip: per-frame tile sums of weighted lattice k from its exact rows (which must exist), [T][n_k] in the dense
 // tile_weights encoding, `dtable`'s bits — stage 1 of the windowed entry points (samples as d_mu / d_mv, or d_ids)
 int exact_frame_rows(vet_plan* pl, int k, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, double* out,
@@ -394,12 +420,17 @@ int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int wind
 
 // vet_user.hip, shared with vet_user_divergence.hip and vet_crowd.hip (which build the same per-viewer histograms): lattice k counts integers
 // (unweighted / binned); waves per row of the weighted histogram kernel (a function of the window and the plan alone); what
-// the per-viewer spatial calls refuse about their arguments (VET_ERR_INVALID) and about the plan (VET_ERR_UNSUPPORTED; builds
-// the exact weight rows on first use)
+// the per-viewer spatial calls refuse about the plan (VET_ERR_UNSUPPORTED; builds the exact weight rows on first use) — their
+// arguments are the windowed calls' (check_window_args)
 bool counts_lattice(const vet_plan* pl, int k);
 int user_nw(size_t lds_max, int n, int window);
-int check_user_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out);
 int check_user_plan(vet_plan* pl, const char* what, hipStream_t s);
+// stage 1 of every per-viewer call: k_user_dirs<d_ids given> over the samples -> dirs [U][T], raising d_status[0]; charged to
+// k_spatial.  One grid row per 64 frames: check_user_dirs_frames refuses (VET_ERR_UNSUPPORTED, "<what>: ...") what the grid
+// cannot hold — user_dirs_run calls it, and so does a call that must refuse before anything is staged or allocated
+int check_user_dirs_frames(int T, const char* what);
+int user_dirs_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int32_t* dirs,
+                  int32_t* d_status, const char* what, hipStream_t s);
 
 // vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched

@@ -73,6 +73,19 @@ static int check_host_args(const vet_plan* pl, int U, int T, const double* h_ent
     return VET_OK;
 }
 
+// The prologue of the row-call host entries, before anything is staged: check_host_args, then the rows of the call, *R =
+// vet_window_rows over the frames (pairs: over the n_frames - 1 frame pairs), refused where the window does not fit.
+static int check_row_args(const vet_plan* pl, int U, int T, int window, int stride, bool pairs, const double* h_out,
+                          const double* h_mu, const double* h_mv, const int32_t* h_ids, int64_t* R) {
+    int rc = check_host_args(pl, U, T, h_out, h_mu, h_mv, h_ids);
+    if (rc) return rc;
+    *R = vet_window_rows(pairs ? T - 1 : T, window, stride);
+    if (*R < 0)
+        return fail(VET_ERR_INVALID, "need 1 <= window <= %s and stride >= 1 (got window %d, stride %d, %d frames)",
+                    pairs ? "n_frames - 1" : "n_frames", window, stride, T);
+    return VET_OK;
+}
+
 // The message of VET_ERR_EMPTY for the per-frame entries (one %d: the rows without a sample).
 static const char* empty_rows_message(bool transition) {
     return transition ? "%d frame pair(s) without a user present in both frames"
@@ -124,6 +137,13 @@ struct StagedRun {
     int finish(const char* empty_msg) {
         int rc = sync(true);
         return rc ? rc : decode(empty_msg);
+    }
+    // the tail of the calls whose rows without a sample are data (NaN, samples 0): only VET_ERR_RANGE is decoded
+    int finish_rows_are_data() {
+        int rc = sync(true);
+        if (rc) return rc;
+        h_status[1] = 0;
+        return decode("");
     }
 };
 
@@ -448,12 +468,9 @@ int vet_transition_entropy_host(vet_plan* pl, const double* h_mu, const double* 
 // Sliding-window spatial entropy with host buffers (include/vet.h): staged like run_host, R = vet_window_rows output rows
 int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
                                       int window, int stride, double* h_entropy, double* h_weights, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
-                    stride, T);
     const size_t w_bytes = (size_t)R * pl->lat[0].n * 8;
     StagedRun run;
     rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
@@ -480,12 +497,9 @@ int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const do
 // rows, user-major.  Rows without a sample are data (NaN, samples 0): only VET_ERR_RANGE is decoded from the status words.
 int vet_user_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
                           int stride, double* h_entropy, double* h_weights, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
-                    stride, T);
     const size_t rows = (size_t)R * U, w_bytes = rows * pl->lat[0].n * 8;
     StagedRun run;
     rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
@@ -505,22 +519,16 @@ int vet_user_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, 
     HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
     if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, wt, w_bytes, hipMemcpyDeviceToHost, s));
     if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    rc = run.sync(true);
-    if (rc) return rc;
-    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
-    return VET_OK;
+    return run.finish_rows_are_data();
 }
 
 // Pairwise viewer divergence with host buffers (include/vet.h): vet_window_rows matrices of n_users x n_users, samples user-major.
 // (row, viewer) slots without a sample are data (NaN rows and columns): only VET_ERR_RANGE is decoded from the status words.
 int vet_user_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
                              int stride, double* h_div, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_div, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_div, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
-                    stride, T);
     const size_t rows = (size_t)R * U, d_bytes = rows * U * 8;
     StagedRun run;
     rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
@@ -538,22 +546,16 @@ int vet_user_divergence_host(vet_plan* pl, const double* h_mu, const double* h_m
     if (rc) return run.drain(rc);
     HIP_TRY(hipMemcpyAsync(h_div, div, d_bytes, hipMemcpyDeviceToHost, s));
     if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    rc = run.sync(true);
-    if (rc) return rc;
-    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
-    return VET_OK;
+    return run.finish_rows_are_data();
 }
 
 // Viewer-to-crowd divergence with host buffers (include/vet.h): n_users * vet_window_rows values, user-major, and the three row
 // series.  (row, viewer) slots without a sample are data (NaN): only VET_ERR_RANGE is decoded from the status words.
 int vet_crowd_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
                               int stride, double* h_div, double* h_rows, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_div, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_div, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
-                    stride, T);
     const size_t slots = (size_t)R * U, r_bytes = (size_t)3 * R * 8;
     StagedRun run;
     rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
@@ -573,22 +575,16 @@ int vet_crowd_divergence_host(vet_plan* pl, const double* h_mu, const double* h_
     HIP_TRY(hipMemcpyAsync(h_div, div, slots * 8, hipMemcpyDeviceToHost, s));
     if (h_rows) HIP_TRY(hipMemcpyAsync(h_rows, rows, r_bytes, hipMemcpyDeviceToHost, s));
     if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, slots * 4, hipMemcpyDeviceToHost, s));
-    rc = run.sync(true);
-    if (rc) return rc;
-    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
-    return VET_OK;
+    return run.finish_rows_are_data();
 }
 
 // Window-to-window divergence with host buffers (include/vet.h): vet_window_rows rows of max_lag lags.  Rows without a sample are
 // data (NaN across their band): only VET_ERR_RANGE is decoded from the status words.
 int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
                                int stride, int max_lag, double* h_div, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_div, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_div, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames and stride >= 1 (got window %d, stride %d, %d frames)", window,
-                    stride, T);
     if (max_lag < 1 || max_lag > R - 1)
         return fail(VET_ERR_INVALID, "max_lag must be between 1 and rows - 1 = %lld (got %d)", (long long)(R - 1), max_lag);
     const size_t d_bytes = (size_t)R * max_lag * 8;
@@ -608,10 +604,7 @@ int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h
     if (rc) return run.drain(rc);
     HIP_TRY(hipMemcpyAsync(h_div, div, d_bytes, hipMemcpyDeviceToHost, s));
     if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-    rc = run.sync(true);
-    if (rc) return rc;
-    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
-    return VET_OK;
+    return run.finish_rows_are_data();
 }
 
 // Per-viewer transition entropy with host buffers (include/vet.h): n_users * vet_window_rows(T - 1, ..) output rows, user-major.
@@ -620,9 +613,10 @@ int vet_user_transition_entropy_host(vet_plan* pl, const double* h_mu, const dou
                                      int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {
     int rc = check_user_transition_args(pl, U, T, window, stride, h_entropy);     // before the samples are looked at or staged
     if (rc) return rc;
-    rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    int64_t R;
+    rc = check_row_args(pl, U, T, window, stride, true, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t rows = (size_t)vet_window_rows(T - 1, window, stride) * U, c_bytes = rows * pl->lat[0].n * 4;
+    const size_t rows = (size_t)R * U, c_bytes = rows * pl->lat[0].n * 4;
     StagedRun run;
     rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
     if (rc) return rc;
@@ -641,21 +635,15 @@ int vet_user_transition_entropy_host(vet_plan* pl, const double* h_mu, const dou
     HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
     if (h_srccount) HIP_TRY(hipMemcpyAsync(h_srccount, sc, c_bytes, hipMemcpyDeviceToHost, s));
     if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    rc = run.sync(true);
-    if (rc) return rc;
-    if (run.h_status[0]) return fail(VET_ERR_RANGE, "Normalized coordinates must be between 0 and 1");
-    return VET_OK;
+    return run.finish_rows_are_data();
 }
 
 // Sliding-window transition entropy with host buffers (include/vet.h): R = vet_window_rows over the T - 1 frame pairs
 int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
                                          int window, int stride, double* h_entropy, int32_t* h_srccount, int32_t* h_samples) {
-    int rc = check_host_args(pl, U, T, h_entropy, h_mu, h_mv, h_ids);
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, true, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const int64_t R = vet_window_rows(T - 1, window, stride);
-    if (R < 0)
-        return fail(VET_ERR_INVALID, "need 1 <= window <= n_frames - 1 and stride >= 1 (got window %d, stride %d, %d frames)",
-                    window, stride, T);
     if ((int64_t)window * U >= ((int64_t)1 << 19))           // before the samples are staged; the device entry says the same
         return fail(VET_ERR_UNSUPPORTED, "windowed transition: window * n_users = %lld pooled samples per row, the kernel packs "
                     "fewer than 2^19", (long long)window * U);

@@ -57,7 +57,9 @@
 //   (several units)     vet_finalize.hpp       k_log2_table, k_finalize*   log2(k) table; mean over a plan's lattices
 // Shared, kernel-free headers: vet_layout.hpp (table / histogram layout constants), vet_common.hpp (wave helpers, the
 // sample -> direction-id quantiser), vet_weights.hpp (FoV weight, weighted frame entropy), vet_window_hist.hpp (a window's pooled sums and counts),
-// vet_divergence.hpp (x log2 x, the reference's NaN test of a key), vet_host.hpp (host state).
+// vet_divergence.hpp (x log2 x, the reference's NaN test of a key), vet_row_hist.hpp (a finished row histogram in one wave: total,
+// entropy, NaN flag, the epilogue over counts — one copy for the per-viewer and the windowed units), vet_host.hpp (host state).
+// vet_user_dirs.hpp holds k_user_dirs (stage 1 of the per-viewer units) and the two walks that build a viewer's row histogram.
 //
 // No MFMA: there is no dense contraction on this path.  Reference citations are relative to
 // /root/reference/src/viewport_entropy_toolkit/.  This header is documentation; the units include what they launch.

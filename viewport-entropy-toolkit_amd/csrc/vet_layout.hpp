@@ -87,4 +87,13 @@ __host__ __device__ __forceinline__ int fused_pos(const FusedLayout& L, int k, i
     return 2 * L.K + L.Hs + k;
 }
 
+// One lattice's exact weight rows as the gathers see them (k_wexact output; rows = the plan's canonical directions); the host
+// fills it with exact_rows_arg (vet_host.hpp)
+struct ExactRows {
+    const uint16_t* idx;        // [R][stride]
+    const double* w;            // [R][stride]
+    const uint32_t* len;        // [R]
+    int stride, n;
+};
+
 }  // namespace vet

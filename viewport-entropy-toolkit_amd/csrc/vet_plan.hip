@@ -367,6 +367,10 @@ int ensure_exact_rows(vet_plan* pl, int k, hipStream_t s) {
 int ensure_exact_weights(vet_plan* pl, hipStream_t s) { return ensure_exact_rows(pl, 0, s); }
 
 const WeightsCore::Exact& exact_rows(const vet_plan* pl, int k) { return k == 0 ? pl->wcore->ex : pl->lat[k].ex; }
+vet::ExactRows exact_rows_arg(const vet_plan* pl, int k) {
+    const WeightsCore::Exact& X = exact_rows(pl, k);
+    return vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(), X.stride, pl->lat[k].n};
+}
 
 bool any_binned(const vet_plan* pl) {
     for (const auto& L : pl->lat) if (L.binned) return true;

@@ -244,14 +244,12 @@ int launch_dtable(vet_plan* pl, const int* lat_idx, int K, int nw, const vet::Sa
     q.alias = pl->d_alias; q.nearest = pl->lat[0].d_nearest;
     q.K = K; q.n_sum = 0;
     int max_stride = 0;
-    auto chunk_class = [](int stride) { const int c = stride / vet::WAVE; return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 0; };
     for (int j = 0; j < K; ++j) {
         const Lattice& L = pl->lat[lat_idx[j]];
-        const WeightsCore::Exact& X = exact_rows(pl, lat_idx[j]);
-        q.off[j] = q.n_sum; q.hmax[j] = L.hmax; q.chunk[j] = chunk_class(X.stride);
-        q.lat[j] = vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(), X.stride, L.n};
+        q.lat[j] = exact_rows_arg(pl, lat_idx[j]);
+        q.off[j] = q.n_sum; q.hmax[j] = L.hmax; q.chunk[j] = row_chunk_class(q.lat[j].stride);
         q.n_sum += L.n;
-        max_stride = std::max(max_stride, X.stride);
+        max_stride = std::max(max_stride, q.lat[j].stride);
     }
     q.entropy = d_mean; q.ent_k = d_ent_k;
     const bool first = lat_idx[0] == 0;
@@ -260,7 +258,7 @@ int launch_dtable(vet_plan* pl, const int* lat_idx, int K, int nw, const vet::Sa
     const size_t lds = vet::dtable_lds_bytes(nw, q.n_sum);
     if (lds > c->lds_max) return fail(VET_ERR_UNSUPPORTED, "dtable: %zu B of LDS", lds);
     // the instance of the longest row of the launch; each lattice picks its own row walk inside it (q.chunk)
-    const int cls = chunk_class(max_stride);
+    const int cls = row_chunk_class(max_stride);
     const void* fn = cls == 1 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 1>
                    : cls == 2 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 2>
                    : cls == 4 ? (const void*)vet::k_spatial_dtable<FROM_IDS, 4> : (const void*)vet::k_spatial_dtable<FROM_IDS, 0>;

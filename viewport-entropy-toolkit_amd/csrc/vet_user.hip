@@ -9,9 +9,11 @@
 //      64 x 64 LDS tile — the samples lie [T][U], and a per-user walk over that layout would touch one value per cache line;
 //   2  per (user, row) and lattice, over the contiguous slice dirs[u][r * stride ..]:
 //        weighted Fibonacci lattices   k_user_entropy_w: the exact FP64 weight rows of the row's frames added in ascending
-//                                      frame order (add_exact_rows, waves_in_order), `dtable`'s epilogue in one wave
+//                                      frame order (user_walk_w, vet_user_dirs.hpp), `dtable`'s epilogue in one wave
 //        unweighted / binned lattices  k_user_entropy_c: u32 counts in LDS, a wave slides over a run of rows of one user,
 //                                      k_window_entropy_c's epilogue
+// The walks and the wave-level epilogues are shared with vet_user_divergence.hip and vet_crowd.hip (vet_user_dirs.hpp,
+// vet_row_hist.hpp): a viewer's histogram there is this unit's by construction.
 // A row is a pure function of the plan and of its own samples: the FP64 sums are taken from scratch for every row with a wave
 // split that depends on `window` alone, the integer counts are exact under add and subtract, and every reduction runs in one
 // wave in fixed lane order.
@@ -21,18 +23,17 @@
 #include "vet_finalize.hpp"
 #include "vet_spatial_dtable.hpp"
 #include "vet_user_dirs.hpp"
+#include "vet_row_hist.hpp"
 
 #include <algorithm>
 
 namespace vet {
 
 // ------------------------------------------------------------------------------------------
-// k_user_entropy_w — stage 2 of a weighted Fibonacci lattice.  One workgroup per (user, row), blockIdx = u * R + r.  Wave w
-// takes the w-th contiguous share of the row's frames in ascending order; a 64-frame chunk is one coalesced load of 64
-// consecutive ids of dirs[u], alias[id], and add_exact_rows into the wave's own LDS histogram (initialised to "no key"): the
-// frames of a chunk are added in lane = frame order, the waves' histograms in wave order (waves_in_order).  Every row is
-// summed from scratch.  The epilogue is k_spatial_dtable's for one lattice: total and -sum q log2 q over the keys in lane
-// order in wave 0, wave_sum's butterfly, / hmax; NaN (and status[1] += 1) for a row without a sample.
+// k_user_entropy_w — stage 2 of a weighted Fibonacci lattice.  One workgroup per (user, row), blockIdx = u * R + r.  The row's
+// histogram is user_walk_w's (vet_user_dirs.hpp: the exact rows of the row's frames added in ascending frame order, the waves
+// in order), the tile values leaving as weights on the way.  The epilogue is k_spatial_dtable's for one lattice, in wave 0:
+// row_total and row_entropy (vet_row_hist.hpp) over the keys, / hmax; NaN (and status[1] += 1) for a row without a sample.
 // blockDim (NW waves) is chosen by the host from `window` (and the lattice's LDS footprint) alone.
 // LDS: dtable_lds_bytes(NW, n): hist f64 [NW][n], present counts i32 [NW].
 // S: 64-entry chunks of the lattice's longest exact row (1, 2, 4; 0 = any number), as k_weights_gather.
@@ -55,52 +56,16 @@ template <int S>
 __global__ __launch_bounds__(256) void k_user_entropy_w(const UserWParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* hist = (double*)smem;                                  // [NW][n]
-    const int NW = blockDim.x >> 6, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const int n = p.X.n;
-    int* cnt_w = (int*)(hist + (size_t)NW * n);                    // [NW] present samples per wave
     const long row = blockIdx.x, u = row / p.R, r = row - u * p.R;
-    const int32_t* d = p.dirs + u * (long)p.T + r * (long)p.stride;
-    double* h = hist + (size_t)wv * n;
-    for (int t = lane; t < n; t += WAVE) ((unsigned long long*)h)[t] = NO_KEY_BITS;
-    const int per = (p.window + NW - 1) / NW;
-    const int j_begin = min(p.window, wv * per), j_end = min(p.window, j_begin + per);
-    int np = 0;
-    for (int j0 = j_begin; j0 < j_end; j0 += WAVE) {
-        const int j = j0 + lane;
-        const int id = j < j_end ? d[j] : -1;
-        const uint32_t a = id >= 0 ? p.alias[id] : 0u;
-        add_exact_rows<S>(h, p.X, (int)(a & 0x7FFFFFFFu), (int)(a >> 31), id >= 0, min(WAVE, j_end - j0));
-        np += id >= 0 ? 1 : 0;
-    }
-    np = wave_sum(np);
-    if (lane == 0) cnt_w[wv] = np;
-    __syncthreads();
-    // tile values, wave order, into wave 0's share (every slot is read and written by one thread only)
-    for (int t = tid; t < n; t += blockDim.x) {
-        const double v = waves_in_order(hist, NW, n, t);
-        hist[t] = v;
+    const int n_present = user_walk_w<S>(hist, p.dirs + u * (long)p.T + r * (long)p.stride, p.alias, p.X, p.window, [&](int t, double v) {
         if (p.weights) __builtin_nontemporal_store(weights_out(v), p.weights + row * (long)n + t);
-    }
-    int n_present = 0;
-    for (int w2 = 0; w2 < NW; ++w2) n_present += cnt_w[w2];
-    __syncthreads();
-    if (wv != 0) return;
-    double tot = 0.0;
-    for (int t = lane; t < n; t += WAVE) {
-        const double v = hist[t];
-        if ((unsigned long long)__double_as_longlong(v) != NO_KEY_BITS) tot += v;
-    }
-    tot = wave_sum(tot);
-    double hh = 0.0;
-    for (int t = lane; t < n; t += WAVE) {
-        const double v = hist[t];
-        if ((unsigned long long)__double_as_longlong(v) != NO_KEY_BITS) {
-            const double q = v / tot;
-            hh -= q * log2(q);
-        }
-    }
-    hh = wave_sum(hh);
-    if (lane == 0) {
+    });
+    if (wave_id() != 0) return;
+    const KeyedHist keys{hist, NO_KEY_BITS};
+    const double tot = row_total(n, keys);
+    const double hh = row_entropy(n, tot, keys);
+    if (lane_id() == 0) {
         p.ent[row] = n_present == 0 ? __builtin_nan("") : hh / p.hmax;
         if (p.samples) p.samples[row] = n_present;
         if (p.status && n_present == 0) atomicAdd(&p.status[1], 1);
@@ -112,10 +77,8 @@ __global__ __launch_bounds__(256) void k_user_entropy_w(const UserWParams p) {
 // workgroup owns rows [c * rpw, + rpw) of user u, blockIdx = u * chunks + c: the row's counts live in LDS; the first row adds
 // its `window` frames, every later row (stride < window; the host gives rpw = 1 otherwise) subtracts the `stride` frames
 // that leave and adds the `stride` frames that enter — k_window_entropy_c's scheme on a contiguous slice of dirs[u], the
-// tile taken from the lattice's nearest[id].  Integers, exact in any order.  The epilogue restates k_window_entropy_c's
-// operation for operation: samples = histogram total, h -= (v / N) * (log2 v - log2 N) in lane order, the normaliser log2(n)
-// if full_norm or N > norm_n, else log2(N) (entropy_utils.py:201-206; one sample gives the reference's 0 / 0), NaN and
-// status[1] += 1 for an empty row.
+// tile taken from the lattice's nearest[id].  Integers, exact in any order.  The epilogue is count_row_entropy
+// (vet_row_hist.hpp), the one k_window_entropy_c runs.
 // LDS: u32 [n].
 // ------------------------------------------------------------------------------------------
 struct UserCParams {
@@ -151,28 +114,7 @@ __global__ __launch_bounds__(64) void k_user_entropy_c(const UserCParams p) {
             user_count(cnt, p.n, d, p.nearest, f0 - p.stride + p.window, f0 + p.window, 1u);
         }
         __syncthreads();
-        int np = 0;
-        for (int t = lane; t < p.n; t += WAVE) np += (int)cnt[t];
-        np = wave_sum(np);
-        const double tw = (double)np, lgn = np ? log2(tw) : 0.0, inv_tw = 1.0 / tw;
-        double h = 0.0;
-        for (int t = lane; t < p.n; t += WAVE) {
-            const unsigned v = cnt[t];
-            if (v) h -= ((double)v * inv_tw) * (log2((double)v) - lgn);
-            if (p.weights) __builtin_nontemporal_store((double)v, p.weights + row * (long)p.n + t);
-        }
-        h = wave_sum(h);
-        if (lane == 0) {
-            double hmax = p.hmax;
-            if (!(tw > (double)p.norm_n) && !p.full_norm) hmax = -tw * (1.0 / tw) * -lgn;
-            double e = h / hmax;
-            if (np == 0) {
-                e = __builtin_nan("");
-                if (p.status) atomicAdd(&p.status[1], 1);
-            }
-            p.ent[row] = e;
-            if (p.samples) p.samples[row] = np;
-        }
+        count_row_entropy(cnt, p, row);
         __syncthreads();
     }
 }
@@ -214,27 +156,31 @@ int check_user_plan(vet_plan* pl, const char* what, hipStream_t s) {
     return VET_OK;
 }
 
-// check_window_args of vet_window.hip, restated for the per-viewer units
-int check_user_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
-    int rc = check_run_args(pl, U, T, out);
+int check_user_dirs_frames(int T, const char* what) {
+    if ((T + vet::UT - 1) / vet::UT > 65535)
+        return fail(VET_ERR_UNSUPPORTED, "%s: %d frames in one call (at most %d)", what, T, 65535 * vet::UT);
+    return VET_OK;
+}
+
+int user_dirs_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int32_t* dirs,
+                  int32_t* d_status, const char* what, hipStream_t s) {
+    int rc = check_user_dirs_frames(T, what);
     if (rc) return rc;
-    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
-    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
-    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
+    vet::UserDirsParams q{};
+    q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    q.U = U; q.T = T; q.dirs = dirs; q.status = d_status;
+    const dim3 grid((unsigned)((U + vet::UT - 1) / vet::UT), (unsigned)((T + vet::UT - 1) / vet::UT));
+    ProfScope ps(pl->ctx, s, KID_SPATIAL);
+    if (d_ids) hipLaunchKernelGGL(vet::k_user_dirs<true>, grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL(vet::k_user_dirs<false>, grid, dim3(256), 0, s, q);
+    HIP_TRY(hipGetLastError());
     return VET_OK;
 }
 
 namespace {
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+const void* user_w_kernel(int stride) { return VET_KERNEL_BY_S(vet::k_user_entropy_w, row_chunk_class(stride)); }
 
-const void* user_w_kernel(int stride) {
-    const int chunks = stride / vet::WAVE;
-    return chunks <= 1 ? (const void*)vet::k_user_entropy_w<1> : chunks <= 2 ? (const void*)vet::k_user_entropy_w<2>
-         : chunks <= 4 ? (const void*)vet::k_user_entropy_w<4> : (const void*)vet::k_user_entropy_w<0>;
-}
-
-template <bool FROM_IDS>
 int launch_user(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
                 double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
     vet_ctx* c = pl->ctx;
@@ -245,22 +191,16 @@ int launch_user(vet_plan* pl, const double* d_mu, const double* d_mv, const int3
     int rc = check_user_plan(pl, "per-user entropy", s);
     if (rc) return rc;
     // workspace: per-lattice rows (K > 1) | dirs [U][T]
-    const size_t ent_b = pad16(K > 1 ? (size_t)K * rows * sizeof(double) : 0);
-    rc = ensure_ws(c, ent_b + pad16((size_t)U * T * sizeof(int32_t)));
+    WsLayout lay;
+    const size_t ent_o = lay.take<double>(K > 1 ? (size_t)K * rows : 0), dirs_o = lay.take<int32_t>((size_t)U * T);
+    rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    double* ent_k = K > 1 ? (double*)ws : d_entropy;
-    int32_t* dirs = (int32_t*)(ws + ent_b);
-    {   // ---- stage 1, charged to k_spatial
-        vet::UserDirsParams q{};
-        q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
-        q.U = U; q.T = T; q.dirs = dirs; q.status = d_status;
-        const unsigned gy = (unsigned)((T + vet::UT - 1) / vet::UT);
-        if (gy > 65535u) return fail(VET_ERR_UNSUPPORTED, "per-user entropy: %d frames in one call (at most %d)", T, 65535 * vet::UT);
-        ProfScope ps(c, s, KID_SPATIAL);
-        hipLaunchKernelGGL(vet::k_user_dirs<FROM_IDS>, dim3((unsigned)((U + vet::UT - 1) / vet::UT), gy), dim3(256), 0, s, q);
-        HIP_TRY(hipGetLastError());
-    }
+    double* ent_k = K > 1 ? (double*)(ws + ent_o) : d_entropy;
+    int32_t* dirs = (int32_t*)(ws + dirs_o);
+    // ---- stage 1
+    rc = user_dirs_run(pl, d_mu, d_mv, d_ids, U, T, dirs, d_status, "per-user entropy", s);
+    if (rc) return rc;
     // ---- stage 2
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
@@ -280,16 +220,14 @@ int launch_user(vet_plan* pl, const double* d_mu, const double* d_mv, const int3
             ProfScope ps(c, s, KID_FINALIZE);
             hipLaunchKernelGGL(vet::k_user_entropy_c, dim3((unsigned)grid), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
         } else {
-            const WeightsCore::Exact& X = exact_rows(pl, k);
             vet::UserWParams q{};
-            q.dirs = dirs; q.T = T; q.alias = pl->d_alias;
-            q.X = vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(), X.stride, L.n};
+            q.dirs = dirs; q.T = T; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
             q.hmax = L.hmax; q.window = window; q.stride = stride; q.R = R;
             q.ent = ent_k + (size_t)k * rows; q.weights = weights; q.samples = samples; q.status = status;
             const int nw = user_nw(c->lds_max, L.n, window);
             void* args[] = {(void*)&q};
             ProfScope ps(c, s, KID_WEIGHTS);
-            HIP_TRY(hipLaunchKernel(user_w_kernel(X.stride), dim3((unsigned)rows), dim3(nw * vet::WAVE), args,
+            HIP_TRY(hipLaunchKernel(user_w_kernel(q.X.stride), dim3((unsigned)rows), dim3(nw * vet::WAVE), args,
                                     vet::dtable_lds_bytes(nw, L.n), s));
         }
         HIP_TRY(hipGetLastError());
@@ -319,21 +257,18 @@ extern "C" {
 
 int vet_user_entropy(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
                      double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_user_entropy_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_user<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
-                              stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_entropy);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_user_entropy_ids", stream, &s);
+    return rc ? rc : launch_user(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_weights, d_samples, d_status, s);
 }
 
 int vet_user_entropy_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double* d_entropy,
                          double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_user<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
-                             stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_entropy);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_user(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status, s);
 }
 
 }  // extern "C"

@@ -7,9 +7,8 @@
 // Three stages, rows in chunks so that the workspace stays bounded whatever R is:
 //   1  k_user_dirs (vet_user_dirs.hpp, unchanged): direction ids transposed once, dirs[U][T];
 //   2  per lattice and chunk of rows, every viewer's histogram [rows of the chunk][U][n] f64 with its total W and a flag:
-//        weighted Fibonacci lattices   k_user_hist_w: k_user_entropy_w's walk, statement for statement up to the tile values
-//                                      (add_exact_rows in ascending frame order, waves_in_order, the wave split user_nw()
-//                                      gives vet_user_entropy) and its total in wave 0;
+//        weighted Fibonacci lattices   k_user_hist_w: user_walk_w (vet_user_dirs.hpp), the walk k_user_entropy_w runs, at
+//                                      the wave split user_nw() gives vet_user_entropy, and row_total in wave 0;
 //        unweighted / binned lattices  k_user_hist_c: user_count over the row's frames, counts as f64;
 //      the flag is raised by a viewer without a sample in the row and by one whose own S is NaN under the reference's
 //      q * log2 q arithmetic (a key whose value is 0.0, or whose h_t / W underflows to 0);
@@ -33,23 +32,17 @@
 #include "vet_common.hpp"
 #include "vet_spatial_dtable.hpp"
 #include "vet_user_dirs.hpp"
+#include "vet_row_hist.hpp"
 #include "vet_divergence.hpp"
 
 #include <algorithm>
 
 namespace vet {
 
-// what stage 2 leaves per (row of the chunk, viewer), next to the histogram
-struct DivStats {
-    double* hist;                // [CR][U][n]  h_t (+0.0 where the viewer has no key)
-    double* tot;                 // [CR][U]     W
-    int32_t* flag;               // [CR][U]     1: no sample in the row, or the viewer's own S is NaN
-};
-
 // ------------------------------------------------------------------------------------------
 // k_user_hist_w — stage 2 of a weighted Fibonacci lattice for rows [r0, r0 + CR).  One workgroup per (row, user),
-// blockIdx = (r - r0) * U + u.  k_user_entropy_w up to its tile values and total (same loops, same NW from the host); instead
-// of the normalised entropy it leaves the histogram, W and the flag.  Lattice 0's launch also writes samples[u][r] and
+// blockIdx = (r - r0) * U + u.  user_walk_w and row_total as in k_user_entropy_w (same NW from the host); instead of the
+// normalised entropy it leaves the histogram, W and the flag (row_own_nan).  Lattice 0's launch also writes samples[u][r] and
 // status[1] as vet_user_entropy does.
 // LDS: dtable_lds_bytes(NW, n).
 // ------------------------------------------------------------------------------------------
@@ -60,7 +53,7 @@ struct UserHistWParams {
     ExactRows X;
     int window, stride;
     long R, r0;                  // rows per user, first row of the chunk
-    DivStats out;
+    RowStats out;
     int32_t* samples;            // [U][R] or null
     int32_t* status;             // [2] or null
 };
@@ -69,49 +62,17 @@ template <int S>
 __global__ __launch_bounds__(256) void k_user_hist_w(const UserHistWParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* hist = (double*)smem;                                  // [NW][n]
-    const int NW = blockDim.x >> 6, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const int n = p.X.n;
-    int* cnt_w = (int*)(hist + (size_t)NW * n);                    // [NW] present samples per wave
     const long slot = blockIdx.x, rc = slot / p.U, u = slot - rc * p.U, r = p.r0 + rc;
-    const int32_t* d = p.dirs + u * (long)p.T + r * (long)p.stride;
-    double* h = hist + (size_t)wv * n;
-    for (int t = lane; t < n; t += WAVE) ((unsigned long long*)h)[t] = NO_KEY_BITS;
-    const int per = (p.window + NW - 1) / NW;
-    const int j_begin = min(p.window, wv * per), j_end = min(p.window, j_begin + per);
-    int np = 0;
-    for (int j0 = j_begin; j0 < j_end; j0 += WAVE) {
-        const int j = j0 + lane;
-        const int id = j < j_end ? d[j] : -1;
-        const uint32_t a = id >= 0 ? p.alias[id] : 0u;
-        add_exact_rows<S>(h, p.X, (int)(a & 0x7FFFFFFFu), (int)(a >> 31), id >= 0, min(WAVE, j_end - j0));
-        np += id >= 0 ? 1 : 0;
-    }
-    np = wave_sum(np);
-    if (lane == 0) cnt_w[wv] = np;
-    __syncthreads();
-    for (int t = tid; t < n; t += blockDim.x) {
-        const double v = waves_in_order(hist, NW, n, t);
-        hist[t] = v;
+    const int n_present = user_walk_w<S>(hist, p.dirs + u * (long)p.T + r * (long)p.stride, p.alias, p.X, p.window, [&](int t, double v) {
         const bool key = (unsigned long long)__double_as_longlong(v) != NO_KEY_BITS;
         p.out.hist[slot * (long)n + t] = key ? v : 0.0;
-    }
-    int n_present = 0;
-    for (int w2 = 0; w2 < NW; ++w2) n_present += cnt_w[w2];
-    __syncthreads();
-    if (wv != 0) return;
-    double tot = 0.0;
-    for (int t = lane; t < n; t += WAVE) {
-        const double v = hist[t];
-        if ((unsigned long long)__double_as_longlong(v) != NO_KEY_BITS) tot += v;
-    }
-    tot = wave_sum(tot);
-    bool nan_key = false;
-    for (int t = lane; t < n; t += WAVE) {
-        const double v = hist[t];
-        if ((unsigned long long)__double_as_longlong(v) != NO_KEY_BITS) nan_key |= own_term_is_nan(v, tot);
-    }
-    const bool any_nan = __ballot(nan_key) != 0ull;
-    if (lane == 0) {
+    });
+    if (wave_id() != 0) return;
+    const KeyedHist keys{hist, NO_KEY_BITS};
+    const double tot = row_total(n, keys);
+    const bool any_nan = row_own_nan(n, tot, keys);
+    if (lane_id() == 0) {
         p.out.tot[slot] = tot;
         p.out.flag[slot] = (n_present == 0 || any_nan) ? 1 : 0;
         if (p.samples) p.samples[u * p.R + r] = n_present;
@@ -121,8 +82,8 @@ __global__ __launch_bounds__(256) void k_user_hist_w(const UserHistWParams p) {
 
 // ------------------------------------------------------------------------------------------
 // k_user_hist_c — stage 2 of an integer-count lattice (unweighted nearest tile, naive lat/lon bins) for rows [r0, r0 + CR).
-// One wave per (row, user), blockIdx = (r - r0) * U + u: k_user_entropy_c's counting walk (user_count) over the row's frames,
-// every row counted afresh; the counts leave as f64 (exact), W = the row's samples.  Counts of present viewers never make the
+// One wave per (row, user), blockIdx = (r - r0) * U + u: user_row_count (vet_user_dirs.hpp) over the row's frames, every row
+// counted afresh; the counts leave as f64 (exact), W = the row's samples.  Counts of present viewers never make the
 // reference's q * log2 q NaN (q >= 1 / N), so the flag is "no sample".
 // LDS: u32 [n].
 // ------------------------------------------------------------------------------------------
@@ -133,7 +94,7 @@ struct UserHistCParams {
     int n;
     int window, stride;
     long R, r0;
-    DivStats out;
+    RowStats out;
     int32_t* samples;            // [U][R] or null
     int32_t* status;             // [2] or null
 };
@@ -142,19 +103,10 @@ __global__ __launch_bounds__(64) void k_user_hist_c(const UserHistCParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* cnt = (unsigned*)smem;
     const int lane = lane_id();
-    for (int t = lane; t < p.n; t += WAVE) cnt[t] = 0u;
-    __syncthreads();
     const long slot = blockIdx.x, rc = slot / p.U, u = slot - rc * p.U, r = p.r0 + rc;
-    const long f0 = r * (long)p.stride;
-    user_count(cnt, p.n, p.dirs + u * (long)p.T, p.nearest, f0, f0 + p.window, 1u);
-    __syncthreads();
-    int np = 0;
-    for (int t = lane; t < p.n; t += WAVE) {
-        const unsigned v = cnt[t];
-        np += (int)v;
+    const int np = user_row_count(cnt, p.n, p.dirs + u * (long)p.T, p.nearest, r * (long)p.stride, p.window, [&](int t, unsigned v) {
         p.out.hist[slot * (long)p.n + t] = (double)v;
-    }
-    np = wave_sum(np);
+    });
     if (lane == 0) {
         p.out.tot[slot] = (double)np;
         p.out.flag[slot] = np == 0 ? 1 : 0;
@@ -186,7 +138,7 @@ constexpr int DIV_TC = 32;            // tiles per LDS stage
 constexpr int DIV_LD = DIV_TC + 1;    // leading dimension in doubles
 
 struct UserDivParams {
-    DivStats in;
+    RowStats in;
     int U, n, nblk;              // nblk = ceil(U / DIV_B)
     int first;                   // lattice 0: store; later lattices: add
     double K;                    // lattices of the plan
@@ -277,17 +229,10 @@ namespace vh {
 
 namespace {
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 constexpr size_t kDivHistBudget = (size_t)256 << 20;      // bytes of histograms a chunk of rows may take in the workspace
 
-const void* hist_w_kernel(int stride) {
-    const int chunks = stride / vet::WAVE;
-    return chunks <= 1 ? (const void*)vet::k_user_hist_w<1> : chunks <= 2 ? (const void*)vet::k_user_hist_w<2>
-         : chunks <= 4 ? (const void*)vet::k_user_hist_w<4> : (const void*)vet::k_user_hist_w<0>;
-}
+const void* hist_w_kernel(int stride) { return VET_KERNEL_BY_S(vet::k_user_hist_w, row_chunk_class(stride)); }
 
-template <bool FROM_IDS>
 int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                       int stride, double* d_div, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
     vet_ctx* c = pl->ctx;
@@ -300,9 +245,9 @@ int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, cons
     if (pair_blocks >= (1L << 31))
         return fail(VET_ERR_UNSUPPORTED, "viewer divergence: %d users give %ld pair blocks in one launch (fewer than 2^31)", U,
                     pair_blocks);
-    const unsigned gy = (unsigned)((T + vet::UT - 1) / vet::UT);
-    if (gy > 65535u) return fail(VET_ERR_UNSUPPORTED, "viewer divergence: %d frames in one call (at most %d)", T, 65535 * vet::UT);
-    int rc = check_user_plan(pl, "viewer divergence", s);
+    int rc = check_user_dirs_frames(T, "viewer divergence");
+    if (rc) return rc;
+    rc = check_user_plan(pl, "viewer divergence", s);
     if (rc) return rc;
     int n_max = 0;
     for (int k = 0; k < K; ++k) n_max = std::max(n_max, pl->lat[k].n);
@@ -311,21 +256,17 @@ int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, cons
                                                 : (long)(kDivHistBudget / ((size_t)U * n_max * sizeof(double)));
     CR = std::max(1L, std::min({CR, R, 65535L, ((1L << 31) - 1) / U}));
     // workspace: dirs [U][T] | hist [CR][U][n_max] | tot [CR][U] | flag [CR][U]
-    const size_t dirs_b = pad16((size_t)U * T * sizeof(int32_t)), hist_b = pad16((size_t)CR * U * n_max * sizeof(double)),
-                 tot_b = pad16((size_t)CR * U * sizeof(double)), flag_b = pad16((size_t)CR * U * sizeof(int32_t));
-    rc = ensure_ws(c, dirs_b + hist_b + tot_b + flag_b);
+    WsLayout lay;
+    const size_t dirs_o = lay.take<int32_t>((size_t)U * T), hist_o = lay.take<double>((size_t)CR * U * n_max),
+                 tot_o = lay.take<double>((size_t)CR * U), flag_o = lay.take<int32_t>((size_t)CR * U);
+    rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    int32_t* dirs = (int32_t*)ws;
-    const vet::DivStats st{(double*)(ws + dirs_b), (double*)(ws + dirs_b + hist_b), (int32_t*)(ws + dirs_b + hist_b + tot_b)};
-    {   // ---- stage 1, charged to k_spatial
-        vet::UserDirsParams q{};
-        q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
-        q.U = U; q.T = T; q.dirs = dirs; q.status = d_status;
-        ProfScope ps(c, s, KID_SPATIAL);
-        hipLaunchKernelGGL(vet::k_user_dirs<FROM_IDS>, dim3((unsigned)((U + vet::UT - 1) / vet::UT), gy), dim3(256), 0, s, q);
-        HIP_TRY(hipGetLastError());
-    }
+    int32_t* dirs = (int32_t*)(ws + dirs_o);
+    const vet::RowStats st{(double*)(ws + hist_o), (double*)(ws + tot_o), (int32_t*)(ws + flag_o)};
+    // ---- stage 1
+    rc = user_dirs_run(pl, d_mu, d_mv, d_ids, U, T, dirs, d_status, "viewer divergence", s);
+    if (rc) return rc;
     for (long r0 = 0; r0 < R; r0 += CR) {
         const long cr = std::min(CR, R - r0);
         for (int k = 0; k < K; ++k) {
@@ -339,15 +280,13 @@ int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, cons
                 ProfScope ps(c, s, KID_FINALIZE);
                 hipLaunchKernelGGL(vet::k_user_hist_c, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
             } else {
-                const WeightsCore::Exact& X = exact_rows(pl, k);
                 vet::UserHistWParams q{};
-                q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias;
-                q.X = vet::ExactRows{(const uint16_t*)X.idx.get(), (const double*)X.w.get(), (const uint32_t*)X.len.get(), X.stride, L.n};
+                q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
                 q.window = window; q.stride = stride; q.R = R; q.r0 = r0; q.out = st; q.samples = samples; q.status = status;
                 const int nw = user_nw(c->lds_max, L.n, window);
                 void* args[] = {(void*)&q};
                 ProfScope ps(c, s, KID_WEIGHTS);
-                HIP_TRY(hipLaunchKernel(hist_w_kernel(X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
+                HIP_TRY(hipLaunchKernel(hist_w_kernel(q.X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
                                         vet::dtable_lds_bytes(nw, L.n), s));
             }
             HIP_TRY(hipGetLastError());
@@ -381,21 +320,18 @@ extern "C" {
 
 int vet_user_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, double* d_div,
                         int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_div);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_user_divergence_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_divergence<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_div, d_samples, d_status,
-                                    stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_div);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_user_divergence_ids", stream, &s);
+    return rc ? rc : launch_divergence(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_div, d_samples, d_status, s);
 }
 
 int vet_user_divergence_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double* d_div,
                             int32_t* d_samples, int32_t* d_status, void* stream) {
-    int rc = check_user_args(pl, U, T, window, stride, d_div);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_divergence<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_div, d_samples, d_status,
-                                   stream ? (hipStream_t)stream : pl->ctx->stream);
+    hipStream_t s;
+    int rc = check_window_args(pl, U, T, window, stride, d_div);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_divergence(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_div, d_samples, d_status, s);
 }
 
 }  // extern "C"

@@ -179,8 +179,6 @@ namespace vh {
 
 namespace {
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // Shape of k_user_transition for rows of `window` pairs (the kernel's header): a function of the window alone
 struct UserTransShape { int threads, lg; const void* fn; };
 UserTransShape user_trans_shape(long window) {
@@ -201,7 +199,6 @@ size_t user_trans_lds_most(const vet_plan* pl, long window) {
     return most;
 }
 
-template <bool FROM_IDS>
 int launch_user_transition(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                            int stride, double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status,
                            hipStream_t s) {
@@ -211,7 +208,7 @@ int launch_user_transition(vet_plan* pl, const double* d_mu, const double* d_mv,
     const bool wave = window <= vet::WAVE && !c->tune.user_transition_hash;
     UserTransShape g{};
     long grid = 0;
-    size_t pc_b = 0;
+    size_t pc_words = 0;                                                  // a multiple of 4 per workgroup
     if (wave) {
         const long spw = vet::WAVE / window, groups = (R + spw - 1) / spw * U;
         grid = std::max<long>(1, std::min<long>(groups, (long)c->n_cu * 32));
@@ -221,24 +218,20 @@ int launch_user_transition(vet_plan* pl, const double* d_mu, const double* d_mv,
         const size_t lds_most = user_trans_lds_most(pl, window);          // <= kWholeLds: check_user_transition_args
         const long per_cu = std::min<long>({(long)(kWholeLds / lds_most), 32 / (g.threads / vet::WAVE), 16});
         grid = std::max<long>(1, std::min<long>(rows, (long)c->n_cu * per_cu));
-        pc_b = g.lg < 13 ? 0 : (size_t)grid * (((size_t)window + 3) & ~(size_t)3) * 4;
+        pc_words = g.lg < 13 ? 0 : (size_t)grid * (((size_t)window + 3) & ~(size_t)3);
     }
-    const unsigned gy = (unsigned)((T + vet::UT - 1) / vet::UT);          // <= 65535: check_user_transition_args
     // workspace: per-lattice rows (K > 1) | dirs [U][T] | the packed pairs of the 1024-thread shape
-    const size_t ent_b = pad16(K > 1 ? (size_t)K * rows * sizeof(double) : 0), dirs_b = pad16((size_t)U * T * sizeof(int32_t));
-    int rc = ensure_ws(c, ent_b + dirs_b + pc_b);
+    WsLayout lay;
+    const size_t ent_o = lay.take<double>(K > 1 ? (size_t)K * rows : 0), dirs_o = lay.take<int32_t>((size_t)U * T);
+    const size_t pc_o = lay.take<uint32_t>(pc_words);
+    int rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    double* ent_k = K > 1 ? (double*)ws : d_entropy;
-    int32_t* dirs = (int32_t*)(ws + ent_b);
-    {   // ---- stage 1, charged to k_spatial
-        vet::UserDirsParams q{};
-        q.src = vet::SampleSrc{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
-        q.U = U; q.T = T; q.dirs = dirs; q.status = d_status;
-        ProfScope ps(c, s, KID_SPATIAL);
-        hipLaunchKernelGGL(vet::k_user_dirs<FROM_IDS>, dim3((unsigned)((U + vet::UT - 1) / vet::UT), gy), dim3(256), 0, s, q);
-        HIP_TRY(hipGetLastError());
-    }
+    double* ent_k = K > 1 ? (double*)(ws + ent_o) : d_entropy;
+    int32_t* dirs = (int32_t*)(ws + dirs_o);
+    // ---- stage 1 (the frame count was refused by check_user_transition_args)
+    rc = user_dirs_run(pl, d_mu, d_mv, d_ids, U, T, dirs, d_status, "per-user transition", s);
+    if (rc) return rc;
     // ---- stage 2, charged to k_transition
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
@@ -248,7 +241,7 @@ int launch_user_transition(vet_plan* pl, const double* d_mu, const double* d_mv,
         q.ent = ent_k + (size_t)k * rows;
         q.srccount = k == 0 ? d_srccount : nullptr; q.samples = k == 0 ? d_samples : nullptr; q.status = k == 0 ? d_status : nullptr;
         q.log2_tab = c->d_log2;
-        q.scratch = (uint32_t*)(ws + ent_b + dirs_b);
+        q.scratch = (uint32_t*)(ws + pc_o);
         ProfScope ps(c, s, KID_TRANSITION);
         if (wave) {
             q.spw = vet::WAVE / window;
@@ -289,8 +282,8 @@ int check_user_transition_args(const vet_plan* pl, int U, int T, int window, int
             return fail(VET_ERR_UNSUPPORTED, "per-user transition: lattice of %d tiles (at most %d)", L.n, vet::TRANS_BIG_MAX_TILES);
     const long rows = (long)vet_window_rows(T - 1, window, stride) * U;
     if (rows >= (1L << 31)) return fail(VET_ERR_UNSUPPORTED, "per-user transition: %ld rows in one call (fewer than 2^31)", rows);
-    if ((T + vet::UT - 1) / vet::UT > 65535)           // k_user_dirs: one grid row per 64 frames
-        return fail(VET_ERR_UNSUPPORTED, "per-user transition: %d frames in one call (at most %d)", T, 65535 * vet::UT);
+    rc = check_user_dirs_frames(T, "per-user transition");
+    if (rc) return rc;
     // the hash kernel's LDS at this window (not reached with lattices of up to TRANS_BIG_MAX_TILES tiles; kept so that the
     // launch below has nothing left to refuse)
     const size_t lds_most = user_trans_lds_most(pl, window);
@@ -313,21 +306,18 @@ extern "C" {
 
 int vet_user_transition_entropy(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
                                 double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_user_transition_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_user_transition_entropy_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_user_transition<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_srccount, d_samples, d_status,
-                                         stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_user_transition_entropy_ids", stream, &s);
+    return rc ? rc : launch_user_transition(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_srccount, d_samples, d_status, s);
 }
 
 int vet_user_transition_entropy_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double* d_entropy,
                                     int32_t* d_srccount, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_user_transition_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_user_transition<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_srccount, d_samples,
-                                        d_status, stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_user_transition(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_srccount, d_samples, d_status, s);
 }
 
 }  // extern "C"

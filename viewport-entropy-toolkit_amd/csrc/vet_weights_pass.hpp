@@ -33,14 +33,6 @@ struct WeightsGatherParams {
     double* out;                // [T][n]
 };
 
-// One lattice's exact weight rows as the gathers see them (k_wexact output; rows = the plan's canonical directions)
-struct ExactRows {
-    const uint16_t* idx;        // [R][stride]
-    const double* w;            // [R][stride]
-    const uint32_t* len;        // [R]
-    int stride, n;
-};
-
 // Adds the rows of the cnt users of a 64-user chunk (lane j: user j's row / mirror flag, present = it has a direction) into
 // the wave's histogram h, users in lane order: each row's tiles are distinct, so every per-tile sum runs over the users in
 // order.  Shared by k_weights_gather and k_spatial_dtable — the same adds in the same order, hence the same bits.

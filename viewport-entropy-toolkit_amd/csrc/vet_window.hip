@@ -20,6 +20,7 @@
 #include "vet_finalize.hpp"
 #include "vet_transition.hpp"
 #include "vet_window_hist.hpp"
+#include "vet_row_hist.hpp"
 
 #include <algorithm>
 
@@ -68,8 +69,8 @@ __global__ __launch_bounds__(256) void k_window_tiles(const WindowTilesParams p)
 // a frame without the key adds -0.0 (no change), a zero-valued key adds +0.0 (-0.0 + +0.0 = +0.0: key with the value 0.0),
 // so one frame (window = 1) gives back k_spatial_dtable's own LDS value.  Lane l owns tiles l, l + 64, ...: the loads of a
 // frame row are coalesced, four frames are in flight per tile, and a frame row is read from L2 by the window / stride rows
-// that share it.  The epilogue is k_spatial_dtable's: total and -sum q log2 q over the keys in lane order, wave_sum's
-// butterfly, / hmax; NaN for a window without a sample (and status[1] += 1).
+// that share it (window_row_w, vet_window_hist.hpp, shared with k_window_hist_w).  The epilogue is k_spatial_dtable's:
+// row_entropy (vet_row_hist.hpp) over the keys, / hmax; NaN for a window without a sample (and status[1] += 1).
 // LDS: f64 [NW][n] (a wave reads back only what its own lanes wrote).
 // ------------------------------------------------------------------------------------------
 struct WindowWParams {
@@ -92,28 +93,11 @@ __global__ __launch_bounds__(256) void k_window_entropy_w(const WindowWParams p)
     if (r >= p.R) return;
     double* h = (double*)smem + (size_t)wv * p.n;
     const long f0 = r * (long)p.stride;
-    int np = 0;
-    for (int j = lane; j < p.window; j += WAVE) np += p.present[f0 + j];
-    np = wave_sum(np);
-    double tot = 0.0;
-    for (int t = lane; t < p.n; t += WAVE) {
-        const double* col = p.hist + f0 * (long)p.n + t;
-        const double acc = window_tile_sum(col, p.n, p.window);
-        h[t] = acc;
-        const bool key = (unsigned long long)__double_as_longlong(acc) != WIN_NO_KEY_BITS;
-        if (key) tot += acc;
+    double tot;
+    const int np = window_row_w(h, p.hist, p.present, p.n, p.window, f0, tot, [&](int t, double acc, bool key) {
         if (p.weights) __builtin_nontemporal_store(key ? (acc == 0.0 ? -0.0 : acc) : 0.0, p.weights + r * (long)p.n + t);
-    }
-    tot = wave_sum(tot);
-    double hh = 0.0;
-    for (int t = lane; t < p.n; t += WAVE) {
-        const double v = h[t];
-        if ((unsigned long long)__double_as_longlong(v) != WIN_NO_KEY_BITS) {
-            const double q = v / tot;
-            hh -= q * log2(q);
-        }
-    }
-    hh = wave_sum(hh);
+    });
+    const double hh = row_entropy(p.n, tot, KeyedHist{h, WIN_NO_KEY_BITS});
     if (lane == 0) {
         p.ent[r] = np == 0 ? __builtin_nan("") : hh / p.hmax;
         if (p.samples) p.samples[r] = np;
@@ -125,10 +109,8 @@ __global__ __launch_bounds__(256) void k_window_entropy_w(const WindowWParams p)
 // k_window_entropy_c — stage 2 of an integer-count lattice (unweighted nearest tile, naive lat/lon bins).  One wave per
 // workgroup owns rows [blockIdx * rpw, + rpw): the window's counts live in LDS; the first row adds its `window` frames, every
 // later row (stride < window; the host gives rpw = 1 otherwise) subtracts the `stride` frames that leave and adds the
-// `stride` frames that enter — integers, exact in any order.  The epilogue is k_spatial_u_lds's, operation for operation
-// (log2 taken directly where that kernel reads its log2 table: the same ocml values): samples = histogram total,
-// h -= (v / N) * (log2 v - log2 N) in lane order, the normaliser log2(n) if full_norm or N > norm_n, else log2(N)
-// (entropy_utils.py:201-206; one sample gives the reference's 0 / 0), NaN and status[1] += 1 for an empty window.
+// `stride` frames that enter — integers, exact in any order.  The epilogue is count_row_entropy (vet_row_hist.hpp), shared with
+// k_user_entropy_c: NaN and status[1] += 1 for an empty window.
 // LDS: u32 [n].
 // ------------------------------------------------------------------------------------------
 struct WindowCParams {
@@ -160,28 +142,7 @@ __global__ __launch_bounds__(64) void k_window_entropy_c(const WindowCParams p) 
             window_count(cnt, p.n, p.tiles, p.U, f0 - p.stride + p.window, f0 + p.window, 1u);
         }
         __syncthreads();
-        int np = 0;
-        for (int t = lane; t < p.n; t += WAVE) np += (int)cnt[t];
-        np = wave_sum(np);
-        const double tw = (double)np, lgn = np ? log2(tw) : 0.0, inv_tw = 1.0 / tw;
-        double h = 0.0;
-        for (int t = lane; t < p.n; t += WAVE) {
-            const unsigned v = cnt[t];
-            if (v) h -= ((double)v * inv_tw) * (log2((double)v) - lgn);
-            if (p.weights) __builtin_nontemporal_store((double)v, p.weights + r * (long)p.n + t);
-        }
-        h = wave_sum(h);
-        if (lane == 0) {
-            double hmax = p.hmax;
-            if (!(tw > (double)p.norm_n) && !p.full_norm) hmax = -tw * (1.0 / tw) * -lgn;
-            double e = h / hmax;
-            if (np == 0) {
-                e = __builtin_nan("");
-                if (p.status) atomicAdd(&p.status[1], 1);
-            }
-            p.ent[r] = e;
-            if (p.samples) p.samples[r] = np;
-        }
+        count_row_entropy(cnt, p, r);
         __syncthreads();
     }
 }
@@ -250,39 +211,22 @@ namespace vh {
 
 namespace {
 
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-template <bool FROM_IDS>
-int window_frames_launch(vet_plan* pl, const vet::SampleSrc& src, int U, int T, const WindowFrames& wf, int32_t* d_status,
-                         hipStream_t s) {
-    vet_ctx* c = pl->ctx;
-    const int K = (int)pl->lat.size();
-    char* ws = (char*)c->ws;
+// one launch of k_window_tiles<src.ids given> over frames [0, T), charged to k_spatial: tiles [T][U] through `nearest`, present [T]
+// and status[0], each where given
+int window_tiles_run(vet_ctx* c, const vet::SampleSrc& src, int U, int T, const uint16_t* nearest, int32_t* tiles, int32_t* present,
+                     int32_t* d_status, hipStream_t s) {
     const int frames_per_wg = 4;
     const dim3 grid((unsigned)((T + frames_per_wg - 1) / frames_per_wg)), block(frames_per_wg * vet::WAVE);
-    bool booked = false;
-    for (int k = 0; k < K || !booked; ++k) {
-        if (k < K && !counts_lattice(pl, k)) continue;
-        vet::WindowTilesParams q{};
-        q.src = src; q.U = U; q.T = T;
-        q.nearest = k < K ? pl->lat[k].d_nearest : nullptr;
-        q.tiles = k < K ? (int32_t*)(ws + wf.off[k]) : nullptr;
-        q.present = booked ? nullptr : (int32_t*)(ws + wf.present_off);
-        q.status = booked ? nullptr : d_status;
-        booked = true;
-        ProfScope ps(c, s, KID_SPATIAL);
-        hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, grid, block, 0, s, q);
-        HIP_TRY(hipGetLastError());
-    }
-    for (int k = 0; k < K; ++k) {
-        if (counts_lattice(pl, k)) continue;
-        int rc = exact_frame_rows(pl, k, src.mu, src.mv, src.ids, U, T, (double*)(ws + wf.off[k]), s);
-        if (rc) return rc;
-    }
+    vet::WindowTilesParams q{};
+    q.src = src; q.U = U; q.T = T;
+    q.nearest = nearest; q.tiles = tiles; q.present = present; q.status = d_status;
+    ProfScope ps(c, s, KID_SPATIAL);
+    if (src.ids) hipLaunchKernelGGL(vet::k_window_tiles<true>, grid, block, 0, s, q);
+    else hipLaunchKernelGGL(vet::k_window_tiles<false>, grid, block, 0, s, q);
+    HIP_TRY(hipGetLastError());
     return VET_OK;
 }
 
-template <bool FROM_IDS>
 int launch_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                     int stride, double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
     vet_ctx* c = pl->ctx;
@@ -369,7 +313,6 @@ int check_window_trans_args(const vet_plan* pl, int U, int T, int window, int st
     return VET_OK;
 }
 
-template <bool FROM_IDS>
 int launch_window_transition(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                              int stride, double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status,
                              hipStream_t s) {
@@ -386,33 +329,26 @@ int launch_window_transition(vet_plan* pl, const double* d_mu, const double* d_m
     const long grid = std::max<long>(1, std::min<long>(R, (long)c->n_cu * per_cu));
     // workspace: per-lattice rows (K > 1) | one lattice's tiles [T][U], reused lattice after lattice on the stream | the
     // packed pairs of the 1024-thread shape
-    const size_t ent_b = pad16(K > 1 ? (size_t)K * R * sizeof(double) : 0), tiles_b = pad16((size_t)T * U * sizeof(int32_t));
-    const size_t pc_b = g.lg < 13 ? 0 : (size_t)grid * ((W + 3) & ~3L) * 4;
-    int rc = ensure_ws(c, ent_b + tiles_b + pc_b);
+    WsLayout lay;
+    const size_t ent_o = lay.take<double>(K > 1 ? (size_t)K * R : 0), tiles_o = lay.take<int32_t>((size_t)T * U),
+                 pc_o = lay.take<uint32_t>(g.lg < 13 ? 0 : (size_t)grid * ((W + 3) & ~3L));
+    int rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    double* ent_k = K > 1 ? (double*)ws : d_entropy;
-    int32_t* tiles = (int32_t*)(ws + ent_b);
+    double* ent_k = K > 1 ? (double*)(ws + ent_o) : d_entropy;
+    int32_t* tiles = (int32_t*)(ws + tiles_o);
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
-        {   // stage 1, charged to k_spatial as in the spatial windowed call
-            const int frames_per_wg = 4;
-            vet::WindowTilesParams q{};
-            q.src = src; q.U = U; q.T = T;
-            q.nearest = L.d_nearest; q.tiles = tiles;
-            q.status = k == 0 ? d_status : nullptr;
-            ProfScope ps(c, s, KID_SPATIAL);
-            hipLaunchKernelGGL(vet::k_window_tiles<FROM_IDS>, dim3((unsigned)((T + frames_per_wg - 1) / frames_per_wg)),
-                               dim3(frames_per_wg * vet::WAVE), 0, s, q);
-            HIP_TRY(hipGetLastError());
-        }
+        // stage 1, as in the spatial windowed call
+        rc = window_tiles_run(c, src, U, T, L.d_nearest, tiles, nullptr, k == 0 ? d_status : nullptr, s);
+        if (rc) return rc;
         vet::WindowTransParams q{};
         q.tiles = tiles; q.U = U; q.n = L.n; q.hmax = L.hmax;
         q.window = window; q.stride = stride; q.R = R;
         q.ent = ent_k + (size_t)k * R;
         q.srccount = k == 0 ? d_srccount : nullptr; q.samples = k == 0 ? d_samples : nullptr; q.status = k == 0 ? d_status : nullptr;
         q.log2_tab = c->d_log2;
-        q.scratch = (uint32_t*)(ws + ent_b + tiles_b);
+        q.scratch = (uint32_t*)(ws + pc_o);
         ProfScope ps(c, s, KID_TRANSITION);
         void* args[] = {(void*)&q};
         HIP_TRY(hipLaunchKernel(g.fn, dim3((unsigned)grid), dim3(g.threads), args, window_trans_lds(g, L.n, W), s));
@@ -433,35 +369,49 @@ int window_frames_layout(vet_plan* pl, int U, int T, size_t head_bytes, WindowFr
     vet_ctx* c = pl->ctx;
     const int K = (int)pl->lat.size();
     if (K > 64) return fail(VET_ERR_UNSUPPORTED, "more than 64 lattices in one plan");
-    size_t bytes = head_bytes;
-    wf.present_off = bytes;
-    bytes += pad16((size_t)T * sizeof(int32_t));
+    WsLayout lay{head_bytes};
+    wf.present_off = lay.take<int32_t>((size_t)T);
     for (int k = 0; k < K; ++k) {
         const Lattice& L = pl->lat[k];
-        wf.off[k] = bytes;
         if (counts_lattice(pl, k)) {
             if ((size_t)L.n * 4 > c->lds_max)
                 return fail(VET_ERR_UNSUPPORTED, "windowed: %d bins do not fit the LDS histogram of a window (at most %zu)", L.n,
                             c->lds_max / 4);
-            bytes += pad16((size_t)T * U * sizeof(int32_t));
+            wf.off[k] = lay.take<int32_t>((size_t)T * U);
         } else {
             int rc = ensure_exact_rows(pl, k, s);
             if (rc) return rc;
             if (exact_rows(pl, k).state != 1)
                 return fail(VET_ERR_UNSUPPORTED, "windowed: the exact FP64 weight rows of lattice %d are not on the device "
                             "(too large for it); the windowed call has no other formulation", k);
-            bytes += pad16((size_t)T * L.n * sizeof(double));
+            wf.off[k] = lay.take<double>((size_t)T * L.n);
         }
     }
-    wf.bytes = bytes;
+    wf.bytes = lay.at;
     return VET_OK;
 }
 
 int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T,
                       const WindowFrames& wf, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
     const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
-    return d_ids ? window_frames_launch<true>(pl, src, U, T, wf, d_status, s)
-                 : window_frames_launch<false>(pl, src, U, T, wf, d_status, s);
+    const int K = (int)pl->lat.size();
+    char* ws = (char*)c->ws;
+    // the counting lattices' tiles; the first launch (one without tiles if there is no such lattice) books present and status
+    bool booked = false;
+    for (int k = 0; k < K || !booked; ++k) {
+        if (k < K && !counts_lattice(pl, k)) continue;
+        int rc = window_tiles_run(c, src, U, T, k < K ? pl->lat[k].d_nearest : nullptr, k < K ? (int32_t*)(ws + wf.off[k]) : nullptr,
+                                  booked ? nullptr : (int32_t*)(ws + wf.present_off), booked ? nullptr : d_status, s);
+        if (rc) return rc;
+        booked = true;
+    }
+    for (int k = 0; k < K; ++k) {
+        if (counts_lattice(pl, k)) continue;
+        int rc = exact_frame_rows(pl, k, d_mu, d_mv, d_ids, U, T, (double*)(ws + wf.off[k]), s);
+        if (rc) return rc;
+    }
+    return VET_OK;
 }
 
 int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
@@ -494,41 +444,35 @@ int64_t vet_window_rows(int n_frames, int window, int stride) {
 
 int vet_spatial_entropy_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
                                  double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_window_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_spatial_entropy_windowed_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_windowed<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
-                                  stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_spatial_entropy_windowed_ids", stream, &s);
+    return rc ? rc : launch_windowed(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_weights, d_samples, d_status, s);
 }
 
 int vet_spatial_entropy_windowed_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride,
                                      double* d_entropy, double* d_weights, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_window_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_windowed<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status,
-                                 stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_windowed(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_weights, d_samples, d_status, s);
 }
 
 int vet_transition_entropy_windowed(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
                                     double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_window_trans_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_transition_entropy_windowed_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_window_transition<false>(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_srccount, d_samples,
-                                           d_status, stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_transition_entropy_windowed_ids", stream, &s);
+    return rc ? rc : launch_window_transition(pl, d_mu, d_mv, nullptr, U, T, window, stride, d_entropy, d_srccount, d_samples, d_status, s);
 }
 
 int vet_transition_entropy_windowed_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride,
                                         double* d_entropy, int32_t* d_srccount, int32_t* d_samples, int32_t* d_status,
                                         void* stream) {
+    hipStream_t s;
     int rc = check_window_trans_args(pl, U, T, window, stride, d_entropy);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_window_transition<true>(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_srccount, d_samples,
-                                          d_status, stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_window_transition(pl, nullptr, nullptr, d_ids, U, T, window, stride, d_entropy, d_srccount, d_samples, d_status, s);
 }
 
 }  // extern "C"

@@ -9,8 +9,8 @@
 //   1  vet_spatial_entropy_windowed's stage 1, unchanged (vet_window.hip: window_frames_run): every frame's histogram once;
 //   2  per lattice and chunk of pair rows [r0, r0 + CR): the row histograms [r0, min(R, r0 + CR + L)) — the chunk's rows and
 //      the halo of L rows their lags reach — as [rows][n] f64 (+0.0 = no key) with the total W and a flag:
-//        weighted Fibonacci lattices   k_window_hist_w: k_window_entropy_w's sum (window_tile_sum: ascending frame order) and
-//                                      its total, operation for operation;
+//        weighted Fibonacci lattices   k_window_hist_w: window_row_w (vet_window_hist.hpp), the sums and total
+//                                      k_window_entropy_w takes (window_tile_sum: ascending frame order);
 //        unweighted / binned lattices  k_window_hist_c: window_count over the row's frames, every row afresh, counts as f64;
 //      the flag is raised by a row without a sample and by one whose own S is NaN under the reference's q * log2 q arithmetic;
 //   3  k_window_divergence: the pair stage in k_user_divergence's overlap form.  With f(x) = x log2 x,
@@ -24,23 +24,17 @@
 #include "vet_host.hpp"
 #include "vet_common.hpp"
 #include "vet_window_hist.hpp"
+#include "vet_row_hist.hpp"
 #include "vet_divergence.hpp"
 
 #include <algorithm>
 
 namespace vet {
 
-// what stage 2 leaves per histogram row of the chunk (index: row - h0)
-struct WinStats {
-    double* hist;                // [HR][n]  P_r (+0.0 where the row has no key)
-    double* tot;                 // [HR]     W_r
-    int32_t* flag;               // [HR]     1: no sample in the row, or the row's own S is NaN
-};
-
 // ------------------------------------------------------------------------------------------
 // k_window_hist_w — stage 2 of a weighted Fibonacci lattice for histogram rows [h0, h_end).  One wave per row, NW rows per
-// workgroup, no barriers: k_window_entropy_w up to its total (the same window_tile_sum per tile, the same lane-order sum and
-// wave_sum butterfly); instead of the entropy it leaves the histogram, W and the flag.  Lattice 0's launch writes samples[r] and
+// workgroup, no barriers: window_row_w as in k_window_entropy_w; instead of the entropy it leaves the histogram, W and the
+// flag (row_own_nan, vet_row_hist.hpp).  Lattice 0's launch writes samples[r] and
 // status[1] for rows >= r_new (the rows no earlier chunk has written: halo rows are rebuilt by the next chunk).
 // LDS: f64 [NW][n] (a wave reads back only what its own lanes wrote).
 // ------------------------------------------------------------------------------------------
@@ -49,7 +43,7 @@ struct WindowHistWParams {
     const int32_t* present;      // [T]
     int n, window, stride;
     long h0, h_end, r_new;
-    WinStats out;
+    RowStats out;
     int32_t* samples;            // [R] or null
     int32_t* status;             // [2] or null
 };
@@ -61,24 +55,11 @@ __global__ __launch_bounds__(256) void k_window_hist_w(const WindowHistWParams p
     if (r >= p.h_end) return;
     double* h = (double*)smem + (size_t)wv * p.n;
     const long f0 = r * (long)p.stride, slot = r - p.h0;
-    int np = 0;
-    for (int j = lane; j < p.window; j += WAVE) np += p.present[f0 + j];
-    np = wave_sum(np);
-    double tot = 0.0;
-    for (int t = lane; t < p.n; t += WAVE) {
-        const double acc = window_tile_sum(p.frames + f0 * (long)p.n + t, p.n, p.window);
-        h[t] = acc;
-        const bool key = (unsigned long long)__double_as_longlong(acc) != WIN_NO_KEY_BITS;
-        if (key) tot += acc;
+    double tot;
+    const int np = window_row_w(h, p.frames, p.present, p.n, p.window, f0, tot, [&](int t, double acc, bool key) {
         p.out.hist[slot * (long)p.n + t] = key ? acc : 0.0;
-    }
-    tot = wave_sum(tot);
-    bool nan_key = false;
-    for (int t = lane; t < p.n; t += WAVE) {
-        const double v = h[t];
-        if ((unsigned long long)__double_as_longlong(v) != WIN_NO_KEY_BITS) nan_key |= own_term_is_nan(v, tot);
-    }
-    const bool any_nan = __ballot(nan_key) != 0ull;
+    });
+    const bool any_nan = row_own_nan(p.n, tot, KeyedHist{h, WIN_NO_KEY_BITS});
     if (lane == 0) {
         p.out.tot[slot] = tot;
         p.out.flag[slot] = (np == 0 || any_nan) ? 1 : 0;
@@ -100,7 +81,7 @@ struct WindowHistCParams {
     const int32_t* tiles;        // [T][U]
     int U, n, window, stride;
     long h0, r_new;
-    WinStats out;
+    RowStats out;
     int32_t* samples;            // [R] or null
     int32_t* status;             // [2] or null
 };
@@ -152,7 +133,7 @@ __global__ __launch_bounds__(64) void k_window_hist_c(const WindowHistCParams p)
 //   <8, 32, 32>   24 816 bytes (6 workgroups per CU)    longer bands
 // ------------------------------------------------------------------------------------------
 struct WindowDivParams {
-    WinStats in;
+    RowStats in;
     int n;
     long h0, h_end;              // histogram rows of the chunk: [h0, h_end)
     long r0, r_end;              // pair rows of the chunk: [r0, r_end)
@@ -233,7 +214,7 @@ int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int wind
     const Lattice& Lk = pl->lat[k];
     const char* ws = (const char*)c->ws;
     const long hr = h_end - h0;
-    const vet::WinStats st{hist, tot, flag};
+    const vet::RowStats st{hist, tot, flag};
     ProfScope ps(c, s, KID_FINALIZE);
     if (counts_lattice(pl, k)) {
         vet::WindowHistCParams q{};
@@ -255,8 +236,6 @@ int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int wind
 }
 
 namespace {
-
-size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 constexpr size_t kWinDivHistBudget = (size_t)256 << 20;   // bytes of row histograms a chunk may take in the workspace
 
@@ -304,12 +283,12 @@ int launch_window_divergence(vet_plan* pl, const double* d_mu, const double* d_m
     CR = std::max(1L, std::min(CR, R));
     const long HR = std::min(R, CR + L);
     // workspace: stage 1's arrays | hist [HR][n_max] | tot [HR] | flag [HR]
-    const size_t hist_b = pad16((size_t)HR * n_max * sizeof(double)), tot_b = pad16((size_t)HR * sizeof(double)),
-                 flag_b = pad16((size_t)HR * sizeof(int32_t));
-    rc = ensure_ws(c, wf.bytes + hist_b + tot_b + flag_b);
+    WsLayout lay{wf.bytes};
+    const size_t hist_o = lay.take<double>((size_t)HR * n_max), tot_o = lay.take<double>((size_t)HR), flag_o = lay.take<int32_t>((size_t)HR);
+    rc = ensure_ws(c, lay.at);
     if (rc) return rc;
     char* ws = (char*)c->ws;
-    const vet::WinStats st{(double*)(ws + wf.bytes), (double*)(ws + wf.bytes + hist_b), (int32_t*)(ws + wf.bytes + hist_b + tot_b)};
+    const vet::RowStats st{(double*)(ws + hist_o), (double*)(ws + tot_o), (int32_t*)(ws + flag_o)};
     // ---- stage 1 (charged as vet_spatial_entropy_windowed's)
     rc = window_frames_run(pl, d_mu, d_mv, d_ids, U, T, wf, d_status, s);
     if (rc) return rc;
@@ -352,21 +331,18 @@ extern "C" {
 
 int vet_window_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, int max_lag,
                           double* d_div, int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_window_div_args(pl, U, T, window, stride, max_lag, d_div);
-    if (rc) return rc;
-    if (!pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; use vet_window_divergence_ids");
-    if (!d_mu || !d_mv) return fail(VET_ERR_INVALID, "d_mu / d_mv is NULL");
-    return launch_window_divergence(pl, d_mu, d_mv, nullptr, U, T, window, stride, max_lag, d_div, d_samples, d_status,
-                                    stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_window_divergence_ids", stream, &s);
+    return rc ? rc : launch_window_divergence(pl, d_mu, d_mv, nullptr, U, T, window, stride, max_lag, d_div, d_samples, d_status, s);
 }
 
 int vet_window_divergence_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, int max_lag, double* d_div,
                               int32_t* d_samples, int32_t* d_status, void* stream) {
+    hipStream_t s;
     int rc = check_window_div_args(pl, U, T, window, stride, max_lag, d_div);
-    if (rc) return rc;
-    if (!d_ids) return fail(VET_ERR_INVALID, "d_ids is NULL");
-    return launch_window_divergence(pl, nullptr, nullptr, d_ids, U, T, window, stride, max_lag, d_div, d_samples, d_status,
-                                    stream ? (hipStream_t)stream : pl->ctx->stream);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_window_divergence(pl, nullptr, nullptr, d_ids, U, T, window, stride, max_lag, d_div, d_samples, d_status, s);
 }
 
 }  // extern "C"

@@ -25,6 +25,29 @@ __device__ __forceinline__ double window_tile_sum(const double* col, int n, int 
     return acc;
 }
 
+// A weighted row in one wave (k_window_entropy_w, k_window_hist_w): the present samples of frames [f0, f0 + window), and per tile
+// (lane l owns tiles l, l + 64, ...) window_tile_sum over stage 1's frames[T][n], left in the wave's LDS histogram h[n] and
+// handed to each(t, acc, key) — key: the tile is a key of the row.  tot = the keys' values added in lane order, wave_sum's
+// butterfly.  Returns the row's samples.
+template <class Each>
+__device__ __forceinline__ int window_row_w(double* h, const double* frames, const int32_t* present, int n, int window, long f0,
+                                            double& tot, Each each) {
+    const int lane = lane_id();
+    int np = 0;
+    for (int j = lane; j < window; j += WAVE) np += present[f0 + j];
+    np = wave_sum(np);
+    double part = 0.0;
+    for (int t = lane; t < n; t += WAVE) {
+        const double acc = window_tile_sum(frames + f0 * (long)n + t, n, window);
+        h[t] = acc;
+        const bool key = (unsigned long long)__double_as_longlong(acc) != WIN_NO_KEY_BITS;
+        if (key) part += acc;
+        each(t, acc, key);
+    }
+    tot = wave_sum(part);
+    return np;
+}
+
 // Counts the tiles / bins of frames [fa, fb) of stage 1's tiles[T][U] into the wave's LDS histogram cnt (delta = 1, or
 // ~0u = -1 mod 2^32 for frames that leave a sliding run of rows).  Integers, exact in any order.
 __device__ __forceinline__ void window_count(unsigned* cnt, int n, const int32_t* tiles, int U, long fa, long fb, unsigned delta) {
