@@ -8,13 +8,24 @@ workgroup; strides 7 and 1.  Plans: weighted [50], [50, 100, 200] and [1000], un
 plan.  Calls: the host entries with (mu, mv) and with ids, the device entries with (mu, mv) and with ids; per-viewer and windowed
 spatial entropy with weights, viewer divergence, crowd divergence with its row series, window divergence at max_lag 1, 8 and
 R - 1, the two transition row calls; the divergence calls also at forced chunks of 1 and 7 rows.
-One line per case; exit status 1 on any difference.
-usage: python tools/ab_bits.py libA.so libB.so"""
+Then what the layers above the kernels must keep, on the weighted [50] plan.  The refusals of the seven host entries and of their
+device entries, called through ctypes: window 0, window one more than the frames (pairs), stride 0, max_lag 0 and R, a null
+primary output, neither ids nor (mu, mv), the windowed transition's 2^19 refusal (U = 2048, T = 258, window = 256) and the
+per-viewer transition's own refusal together with missing samples (which one wins); ids with a null h_mu is accepted and its
+outputs are compared.  The Plan wrappers: their ValueErrors, the optional output not wanted, the *_device wrappers (with d_ids
+where they take it).  The analyzers' twelve row methods on a 12 x 3 video: their frames, a sample of 1.5, a window without a
+sample.
+One line per case; exit status 1 on any difference.  A refusal's line holds the exception's type name or the code before the
+message, so the lines of profiles/refactor/row_calls_ab_bits.txt (message only) do not compare with today's.
+usage: python tools/ab_bits.py libA.so libB.so
+       python tools/ab_bits.py --dump LIB      the case lines of one library with the Python layer of this checkout, to diff
+                                               against the same from another checkout"""
 import hashlib
 import json
 import os
 import subprocess
 import sys
+import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'viewport-entropy-toolkit_amd'))
 
@@ -52,8 +63,8 @@ def child():
             try:
                 out = fn(**samples, **kw)
                 res = {k: (int(v) if k == "code" else digest(v)) for k, v in out.items()}
-            except _native.NativeError as e:
-                res = {"error": str(e)}
+            except (_native.NativeError, ValueError) as e:
+                res = {"error": f"{type(e).__name__}: {e}"}
             emit(f"{case} host {src}", res)
 
     def device(case, entry, window, stride, extra, shapes):
@@ -76,6 +87,149 @@ def child():
                 res = {name: digest(o.cpu().numpy()) for (name, _, _), o in zip(shapes, outs)}
                 res["status"] = digest(status.cpu().numpy())
             emit(f"{case} device {src}", res)
+
+
+    # the seven row calls: (name, C symbol stem, Plan method, windows of frame pairs, max_lag argument, outputs (key, dims, dtype)
+    # in the entries' order; dims: U users, R rows, n tiles, L max_lag)
+    ROW_CALLS = [
+        ("windowed", "vet_spatial_entropy_windowed", "spatial_windowed", False, False,
+         [("entropy", "R", "f8"), ("weights", "Rn", "f8"), ("samples", "R", "i4")]),
+        ("user_entropy", "vet_user_entropy", "spatial_per_user", False, False,
+         [("entropy", "UR", "f8"), ("weights", "URn", "f8"), ("samples", "UR", "i4")]),
+        ("user_divergence", "vet_user_divergence", "spatial_user_divergence", False, False,
+         [("divergence", "RUU", "f8"), ("samples", "UR", "i4")]),
+        ("crowd_divergence", "vet_crowd_divergence", "spatial_crowd_divergence", False, False,
+         [("divergence", "UR", "f8"), ("rows", "3R", "f8"), ("samples", "UR", "i4")]),
+        ("window_divergence", "vet_window_divergence", "spatial_window_divergence", False, True,
+         [("divergence", "RL", "f8"), ("samples", "R", "i4")]),
+        ("windowed_transition", "vet_transition_entropy_windowed", "transition_windowed", True, False,
+         [("entropy", "R", "f8"), ("srccount", "Rn", "i4"), ("samples", "R", "i4")]),
+        ("user_transition", "vet_user_transition_entropy", "transition_per_user", True, False,
+         [("entropy", "UR", "f8"), ("srccount", "URn", "i4"), ("samples", "UR", "i4")]),
+    ]
+
+    def layers(plan):
+        """The refusals of the C entries, the Plan wrappers and the analyzers (module docstring); plan: weighted [50]."""
+        n0 = plan.n_tiles[0]
+        big_u, big_t = 2048, 258                                 # window 256 of 257 pairs: window * U = 2^19
+        half = np.full((big_t, big_u), 0.5)
+        d_half = torch.from_numpy(half).to(dev)
+        d_big_ids = torch.zeros((big_t, big_u), dtype=torch.int32, device=dev)
+
+        def shape(dims, u, r, lag):                              # lag: the call's max_lag argument(s); a refused 0 still gets a buffer
+            return tuple({"U": u, "R": r, "n": n0, "L": max(lag[0], 1) if lag else 0, "3": 3}[d] for d in dims)
+
+        def raw_host(case, stem, outs, u, t, window, stride, lag, h_mu, h_mv, h_ids, r, no_primary=False):
+            bufs = [np.full(shape(dims, u, r, lag), -7, dtype=dt) for _, dims, dt in outs]
+            ptrs = [_native._ptr(b) for b in bufs]
+            if no_primary:
+                ptrs[0] = None
+            rc = getattr(lib, stem + "_host")(plan.handle, _native._ptr(h_mu), _native._ptr(h_mv), _native._ptr(h_ids), u, t,
+                                              window, stride, *lag, *ptrs)
+            if rc:
+                emit(case, {"error": f"{rc}: {(lib.vet_last_error() or b'').decode()}"})
+            else:
+                emit(case, {key: digest(b) for (key, _, _), b in zip(outs, bufs)})
+
+        def raw_device(case, stem, outs, u, t, window, stride, lag, samples, r, no_primary=False):
+            tdt = {"f8": torch.float64, "i4": torch.int32}
+            bufs = [torch.full(shape(dims, u, r, lag), -7, dtype=tdt[dt], device=dev) for _, dims, dt in outs]
+            ptrs = [b.data_ptr() for b in bufs]
+            if no_primary:
+                ptrs[0] = None
+            status.zero_()
+            torch.cuda.synchronize()
+            entry = getattr(lib, stem + ("_ids" if len(samples) == 1 else ""))
+            rc = entry(plan.handle, *samples, u, t, window, stride, *lag, *ptrs, status.data_ptr(), None)
+            eng.synchronize()
+            emit(case, {"error": f"{rc}: {(lib.vet_last_error() or b'').decode()}"} if rc else {"accepted": True})
+
+        for name, stem, method, pairs, has_lag, outs in ROW_CALLS:
+            n = T - 1 if pairs else T
+            r = (n - 20) // 7 + 1
+            lag = (2,) if has_lag else ()
+            refusals = [("window0", 0, 7, lag), ("window_long", n + 1, 7, lag), ("stride0", 20, 0, lag)]
+            if has_lag:
+                refusals += [("lag0", 20, 7, (0,)), ("lagR", 20, 7, (r,))]
+            for what, window, stride, lg in refusals:
+                raw_host(f"refusal {name} {what} host", stem, outs, U, T, window, stride, lg, mu, mv, None, r)
+                raw_device(f"refusal {name} {what} device", stem, outs, U, T, window, stride, lg, (d_mu.data_ptr(), d_mv.data_ptr()), r)
+                raw_device(f"refusal {name} {what} device ids", stem, outs, U, T, window, stride, lg, (d_ids.data_ptr(),), r)
+            raw_host(f"refusal {name} no_output host", stem, outs, U, T, 20, 7, lag, mu, mv, None, r, no_primary=True)
+            raw_device(f"refusal {name} no_output device", stem, outs, U, T, 20, 7, lag, (d_mu.data_ptr(), d_mv.data_ptr()), r,
+                       no_primary=True)
+            raw_host(f"refusal {name} no_samples host", stem, outs, U, T, 20, 7, lag, None, None, None, r)
+            raw_host(f"refusal {name} no_samples bad_window host", stem, outs, U, T, 0, 7, lag, None, None, None, r)
+            raw_device(f"refusal {name} no_samples device", stem, outs, U, T, 20, 7, lag, (None, None), r)
+            raw_device(f"refusal {name} no_samples device ids", stem, outs, U, T, 20, 7, lag, (None,), r)
+            raw_host(f"accepted {name} ids_null_mu host", stem, outs, U, T, 20, 7, lag, None, None, ids, r)
+            if name == "windowed_transition":
+                raw_host(f"refusal {name} 2^19 host", stem, outs, big_u, big_t, 256, 1, (), half, half, None, 2)
+                raw_device(f"refusal {name} 2^19 device", stem, outs, big_u, big_t, 256, 1, (), (d_half.data_ptr(), d_half.data_ptr()), 2)
+                raw_device(f"refusal {name} 2^19 device ids", stem, outs, big_u, big_t, 256, 1, (), (d_big_ids.data_ptr(),), 2)
+
+            # the Plan wrappers: ValueErrors, the optional output not wanted, the *_device wrapper
+            fn = getattr(plan, method)
+            kw = dict(max_lag=2) if has_lag else {}
+            for what, window, stride, extra in [("window_none", None, 7, kw), ("window0", 0, 7, kw), ("window_long", n + 1, 7, kw),
+                                                ("stride0", 20, 0, kw), ("plain", 20, 7, kw)] + \
+                                               ([("lag0", 20, 7, dict(max_lag=0)), ("lagR", 20, 7, dict(max_lag=r))] if has_lag else []):
+                host(f"plan {name} {what}", fn, window=window, stride=stride, **extra)
+            dev_fn = getattr(plan, method + "_device")
+            bufs = [torch.full(shape(dims, U, r, lag), -7, dtype={"f8": torch.float64, "i4": torch.int32}[dt], device=dev)
+                    for _, dims, dt in outs]
+            for src, samples in (("mu_mv", {}), ("ids", dict(d_ids=d_ids.data_ptr()))):
+                if src == "ids" and name not in ("crowd_divergence", "window_divergence"):
+                    continue
+                status.zero_()
+                torch.cuda.synchronize()
+                dev_fn(d_mu.data_ptr(), d_mv.data_ptr(), U, T, 20, 7, *lag, *(b.data_ptr() for b in bufs), d_status=status.data_ptr(),
+                       **samples)
+                eng.synchronize()
+                res = {key: digest(b.cpu().numpy()) for (key, _, _), b in zip(outs, bufs)}
+                res["status"] = digest(status.cpu().numpy())
+                emit(f"plan {name} device wrapper {src}", res)
+
+        # the analyzers on a 12 x 3 video with viewer 1 absent over frames 4..8; then a sample of 1.5; then frames 0..4 empty
+        from viewport_entropy_toolkit import SpatialEntropyAnalyzer, TransitionEntropyAnalyzer
+        from viewport_entropy_toolkit.config import AnalyzerConfig
+        a_mu, a_mv = _synthetic.random_walk_video(3, 12, base_seed=7, p_absent=0.1)
+        a_mu[4:9, 1] = np.nan; a_mv[4:9, 1] = np.nan
+        cfg = dict(video_width=VW, video_height=VH, entropy_config=EntropyConfig(use_weight_distribution=True),
+                   output_dir=os.path.join(tempfile.gettempdir(), "ab_bits"))
+        makers = [("spatial", lambda: SpatialEntropyAnalyzer(AnalyzerConfig(tile_counts=[50], **cfg))),
+                  ("naive", lambda: NaiveSpatialEntropyAnalyzer(NaiveAnalyzerConfig(tile_height=10, tile_width=20, **cfg))),
+                  ("transition", lambda: TransitionEntropyAnalyzer(AnalyzerConfig(tile_counts=[50], **cfg)))]
+        methods = [("compute_windowed_entropy", dict(window=5, stride=2)), ("compute_user_entropy", dict(window=5, stride=2)),
+                   ("compute_user_entropy", {}), ("compute_user_divergence", dict(window=5, stride=2)),
+                   ("compute_window_divergence", dict(window=5, stride=2, max_lag=2)),
+                   ("compute_crowd_divergence", dict(window=5, stride=2)), ("compute_windowed_entropy", dict(window=13))]
+
+        def frame(df):
+            out = {}
+            for col in df.columns:
+                if col != "tile_weights":
+                    v = df[col].to_numpy()
+                    out[col] = digest(np.stack(v)) if v.dtype == object and not isinstance(v[0], str) else \
+                        hashlib.sha256(repr(v.tolist()).encode()).hexdigest() if v.dtype == object else digest(v)
+            return out
+
+        for aname, make in makers:
+            for variant in ("plain", "out_of_range", "empty_window"):
+                x_mu, x_mv = a_mu.copy(), a_mv.copy()
+                if variant == "empty_window":
+                    x_mu[0:5] = np.nan; x_mv[0:5] = np.nan
+                an = make()
+                an.load_arrays(np.arange(12) * 0.1, x_mu, x_mv)
+                if variant == "out_of_range":                    # past load_arrays' own check: the engine's refusal
+                    an._dense[1][2, 0], an._dense[2][2, 0] = 1.5, 0.5
+                for method, kw in methods:
+                    if hasattr(an, method):
+                        try:
+                            res = frame(getattr(an, method)(**kw))
+                        except Exception as e:  # noqa: BLE001
+                            res = {"error": f"{type(e).__name__}: {e}"}
+                        emit(f"analyzer {aname} {variant} {method} {sorted(kw.items())}", res)
 
     f64, i32 = torch.float64, torch.int32
     lattice = lambda tcs: [_quantiser.lattice_xyz(tc) for tc in tcs]
@@ -128,6 +282,8 @@ def child():
                      check=False)
                 device(f"{ptag} windowed_transition", "vet_transition_entropy_windowed", pw, stride, (),
                        [("entropy", (Rp,), f64), ("srccount", (Rp, n0), i32), ("samples", (Rp,), i32)])
+        if pname == "w_50":
+            layers(plan)
         if pname != "naive_10x20":
             plan.close()
 
@@ -156,9 +312,19 @@ def main(lib_a, lib_b):
     return 1 if bad or rc_a or rc_b or not a else 0
 
 
+def dump(lib):
+    rc, cases = run_child(lib)
+    for case, outputs in cases.items():
+        print(f"{case}  {json.dumps(outputs, sort_keys=True)}")
+    print(f"{len(cases)} cases (exit {rc})")
+    return 1 if rc or not cases else 0
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["--child"]:
         child()
+    elif len(sys.argv) == 3 and sys.argv[1] == "--dump":
+        sys.exit(dump(sys.argv[2]))
     elif len(sys.argv) == 3:
         sys.exit(main(sys.argv[1], sys.argv[2]))
     else:

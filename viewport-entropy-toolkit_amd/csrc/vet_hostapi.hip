@@ -1,10 +1,10 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous) and BlockDownload (heatmaps and tilings: frames rendered in blocks, the download of one
-// block overlapping the render of the next).  Also here: device-resident results (vet_result), heatmaps (vet_heatmap: the
-// map, the palette and the uploads of a block; the kernels are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the
-// kernels are vet_tiling.hip's).  File-local types and templates come first, then the one extern "C" block.
-// No kernels of its own and no CPU compute path.
+// points in between, synchronous; staged_rows is the whole run of the seven row calls) and BlockDownload (heatmaps and
+// tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
+// device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
+// are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
+// templates come first, then the one extern "C" block.  No kernels of its own and no CPU compute path.
 #include "vet_host.hpp"
 
 #include <algorithm>
@@ -146,6 +146,40 @@ struct StagedRun {
         return decode("");
     }
 };
+
+// The seven row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, windowed /
+// per-viewer transition entropy) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
+// where the call has none) and the count per row; a null h = not wanted: no slot is taken, the launch gets nullptr and nothing
+// is downloaded — except the count, whose slot the device entries always write.  launch(run, d) enqueues the call on the
+// staged samples and the device outputs d[3]; empty_msg as StagedRun::decode, or kRowsAreData (finish_rows_are_data).
+struct RowOut { void* h; size_t bytes; int slot; };
+constexpr RowOut kNoOut = {nullptr, 0, SLOT_OUT1};
+constexpr const char* kRowsAreData = nullptr;
+
+// the _ids entry on the staged ids, else the (mu, mv) entry: both take the same arguments after the samples
+template <typename IdsEntry, typename GridEntry, typename... Args>
+static int launch_rows(const StagedRun& run, IdsEntry ids_entry, GridEntry grid_entry, vet_plan* pl, Args... args) {
+    return run.ids ? ids_entry(pl, run.ids, args...) : grid_entry(pl, run.mu, run.mv, args...);
+}
+
+template <typename Launch>
+static int staged_rows(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
+                       const RowOut (&outs)[3], const char* empty_msg, Launch launch) {
+    StagedRun run;
+    int rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    void* d[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; ++i)
+        if (outs[i].h || outs[i].slot == SLOT_COUNT) POOL(outs[i].slot, outs[i].bytes, d[i]);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = launch(run, d);
+    if (rc) return run.drain(rc);
+    for (int i = 0; i < 3; ++i)
+        if (outs[i].h) HIP_TRY(hipMemcpyAsync(outs[i].h, d[i], outs[i].bytes, hipMemcpyDeviceToHost, run.s));
+    return empty_msg ? run.finish(empty_msg) : run.finish_rows_are_data();
+}
 
 // Frames rendered on the device in blocks and brought to the caller's host array, the download of one block overlapping
 // the render of the next: two device blocks the render stream fills in turn, two pinned blocks a second, non-blocking
@@ -471,26 +505,13 @@ int vet_spatial_entropy_windowed_host(vet_plan* pl, const double* h_mu, const do
     int64_t R;
     int rc = check_row_args(pl, U, T, window, stride, false, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t w_bytes = (size_t)R * pl->lat[0].n * 8;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double *ent = nullptr, *wt = nullptr;
-    int32_t* cnt = nullptr;
-    POOL(SLOT_ENTROPY, (size_t)R * 8, ent);
-    if (h_weights) POOL(SLOT_OUT1, w_bytes, wt);
-    POOL(SLOT_COUNT, (size_t)R * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_spatial_entropy_windowed_ids(pl, run.ids, U, T, window, stride, ent, wt, cnt, run.status, s)
-                 : vet_spatial_entropy_windowed(pl, run.mu, run.mv, U, T, window, stride, ent, wt, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_entropy, ent, (size_t)R * 8, hipMemcpyDeviceToHost, s));
-    if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, wt, w_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-    return run.finish("%d window(s) without any sample (Empty vector dictionary)");
+    const RowOut outs[3] = {{h_entropy, (size_t)R * 8, SLOT_ENTROPY}, {h_weights, (size_t)R * pl->lat[0].n * 8, SLOT_OUT1},
+                            {h_samples, (size_t)R * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, "%d window(s) without any sample (Empty vector dictionary)",
+                       [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_spatial_entropy_windowed_ids, vet_spatial_entropy_windowed, pl, U, T, window, stride,
+                           (double*)d[0], (double*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Per-viewer spatial entropy with host buffers (include/vet.h): staged like the windowed entry, n_users * vet_window_rows output
@@ -500,26 +521,13 @@ int vet_user_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, 
     int64_t R;
     int rc = check_row_args(pl, U, T, window, stride, false, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t rows = (size_t)R * U, w_bytes = rows * pl->lat[0].n * 8;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double *ent = nullptr, *wt = nullptr;
-    int32_t* cnt = nullptr;
-    POOL(SLOT_ENTROPY, rows * 8, ent);
-    if (h_weights) POOL(SLOT_OUT1, w_bytes, wt);
-    POOL(SLOT_COUNT, rows * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_user_entropy_ids(pl, run.ids, U, T, window, stride, ent, wt, cnt, run.status, s)
-                 : vet_user_entropy(pl, run.mu, run.mv, U, T, window, stride, ent, wt, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
-    if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, wt, w_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    return run.finish_rows_are_data();
+    const size_t rows = (size_t)R * U;
+    const RowOut outs[3] = {{h_entropy, rows * 8, SLOT_ENTROPY}, {h_weights, rows * pl->lat[0].n * 8, SLOT_OUT1},
+                            {h_samples, rows * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_user_entropy_ids, vet_user_entropy, pl, U, T, window, stride, (double*)d[0], (double*)d[1],
+                           (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Pairwise viewer divergence with host buffers (include/vet.h): vet_window_rows matrices of n_users x n_users, samples user-major.
@@ -529,24 +537,12 @@ int vet_user_divergence_host(vet_plan* pl, const double* h_mu, const double* h_m
     int64_t R;
     int rc = check_row_args(pl, U, T, window, stride, false, h_div, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t rows = (size_t)R * U, d_bytes = rows * U * 8;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double* div = nullptr;
-    int32_t* cnt = nullptr;
-    POOL(SLOT_ENTROPY, d_bytes, div);
-    POOL(SLOT_COUNT, rows * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_user_divergence_ids(pl, run.ids, U, T, window, stride, div, cnt, run.status, s)
-                 : vet_user_divergence(pl, run.mu, run.mv, U, T, window, stride, div, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_div, div, d_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    return run.finish_rows_are_data();
+    const size_t rows = (size_t)R * U;
+    const RowOut outs[3] = {{h_div, rows * U * 8, SLOT_ENTROPY}, kNoOut, {h_samples, rows * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_user_divergence_ids, vet_user_divergence, pl, U, T, window, stride, (double*)d[0],
+                           (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Viewer-to-crowd divergence with host buffers (include/vet.h): n_users * vet_window_rows values, user-major, and the three row
@@ -556,26 +552,12 @@ int vet_crowd_divergence_host(vet_plan* pl, const double* h_mu, const double* h_
     int64_t R;
     int rc = check_row_args(pl, U, T, window, stride, false, h_div, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t slots = (size_t)R * U, r_bytes = (size_t)3 * R * 8;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double *div = nullptr, *rows = nullptr;
-    int32_t* cnt = nullptr;
-    POOL(SLOT_ENTROPY, slots * 8, div);
-    if (h_rows) POOL(SLOT_OUT1, r_bytes, rows);
-    POOL(SLOT_COUNT, slots * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_crowd_divergence_ids(pl, run.ids, U, T, window, stride, div, rows, cnt, run.status, s)
-                 : vet_crowd_divergence(pl, run.mu, run.mv, U, T, window, stride, div, rows, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_div, div, slots * 8, hipMemcpyDeviceToHost, s));
-    if (h_rows) HIP_TRY(hipMemcpyAsync(h_rows, rows, r_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, slots * 4, hipMemcpyDeviceToHost, s));
-    return run.finish_rows_are_data();
+    const size_t slots = (size_t)R * U;
+    const RowOut outs[3] = {{h_div, slots * 8, SLOT_ENTROPY}, {h_rows, (size_t)3 * R * 8, SLOT_OUT1}, {h_samples, slots * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_crowd_divergence_ids, vet_crowd_divergence, pl, U, T, window, stride, (double*)d[0],
+                           (double*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Window-to-window divergence with host buffers (include/vet.h): vet_window_rows rows of max_lag lags.  Rows without a sample are
@@ -587,24 +569,11 @@ int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h
     if (rc) return rc;
     if (max_lag < 1 || max_lag > R - 1)
         return fail(VET_ERR_INVALID, "max_lag must be between 1 and rows - 1 = %lld (got %d)", (long long)(R - 1), max_lag);
-    const size_t d_bytes = (size_t)R * max_lag * 8;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double* div = nullptr;
-    int32_t* cnt = nullptr;
-    POOL(SLOT_ENTROPY, d_bytes, div);
-    POOL(SLOT_COUNT, (size_t)R * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_window_divergence_ids(pl, run.ids, U, T, window, stride, max_lag, div, cnt, run.status, s)
-                 : vet_window_divergence(pl, run.mu, run.mv, U, T, window, stride, max_lag, div, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_div, div, d_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-    return run.finish_rows_are_data();
+    const RowOut outs[3] = {{h_div, (size_t)R * max_lag * 8, SLOT_ENTROPY}, kNoOut, {h_samples, (size_t)R * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_window_divergence_ids, vet_window_divergence, pl, U, T, window, stride, max_lag, (double*)d[0],
+                           (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Per-viewer transition entropy with host buffers (include/vet.h): n_users * vet_window_rows(T - 1, ..) output rows, user-major.
@@ -616,26 +585,13 @@ int vet_user_transition_entropy_host(vet_plan* pl, const double* h_mu, const dou
     int64_t R;
     rc = check_row_args(pl, U, T, window, stride, true, h_entropy, h_mu, h_mv, h_ids, &R);
     if (rc) return rc;
-    const size_t rows = (size_t)R * U, c_bytes = rows * pl->lat[0].n * 4;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double* ent = nullptr;
-    int32_t *sc = nullptr, *cnt = nullptr;
-    POOL(SLOT_ENTROPY, rows * 8, ent);
-    if (h_srccount) POOL(SLOT_OUT1, c_bytes, sc);
-    POOL(SLOT_COUNT, rows * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_user_transition_entropy_ids(pl, run.ids, U, T, window, stride, ent, sc, cnt, run.status, s)
-                 : vet_user_transition_entropy(pl, run.mu, run.mv, U, T, window, stride, ent, sc, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_entropy, ent, rows * 8, hipMemcpyDeviceToHost, s));
-    if (h_srccount) HIP_TRY(hipMemcpyAsync(h_srccount, sc, c_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, rows * 4, hipMemcpyDeviceToHost, s));
-    return run.finish_rows_are_data();
+    const size_t rows = (size_t)R * U;
+    const RowOut outs[3] = {{h_entropy, rows * 8, SLOT_ENTROPY}, {h_srccount, rows * pl->lat[0].n * 4, SLOT_OUT1},
+                            {h_samples, rows * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_user_transition_entropy_ids, vet_user_transition_entropy, pl, U, T, window, stride,
+                           (double*)d[0], (int32_t*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Sliding-window transition entropy with host buffers (include/vet.h): R = vet_window_rows over the T - 1 frame pairs
@@ -647,26 +603,13 @@ int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const
     if ((int64_t)window * U >= ((int64_t)1 << 19))           // before the samples are staged; the device entry says the same
         return fail(VET_ERR_UNSUPPORTED, "windowed transition: window * n_users = %lld pooled samples per row, the kernel packs "
                     "fewer than 2^19", (long long)window * U);
-    const size_t c_bytes = (size_t)R * pl->lat[0].n * 4;
-    StagedRun run;
-    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
-    if (rc) return rc;
-    vet_ctx* c = run.c;
-    hipStream_t s = run.s;
-    double* ent = nullptr;
-    int32_t *sc = nullptr, *cnt = nullptr;
-    POOL(SLOT_ENTROPY, (size_t)R * 8, ent);
-    if (h_srccount) POOL(SLOT_OUT1, c_bytes, sc);
-    POOL(SLOT_COUNT, (size_t)R * 4, cnt);
-    rc = run.clear_status();
-    if (rc) return rc;
-    rc = run.ids ? vet_transition_entropy_windowed_ids(pl, run.ids, U, T, window, stride, ent, sc, cnt, run.status, s)
-                 : vet_transition_entropy_windowed(pl, run.mu, run.mv, U, T, window, stride, ent, sc, cnt, run.status, s);
-    if (rc) return run.drain(rc);
-    HIP_TRY(hipMemcpyAsync(h_entropy, ent, (size_t)R * 8, hipMemcpyDeviceToHost, s));
-    if (h_srccount) HIP_TRY(hipMemcpyAsync(h_srccount, sc, c_bytes, hipMemcpyDeviceToHost, s));
-    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-    return run.finish("%d window(s) without a (pair, user) sample present in both frames");
+    const RowOut outs[3] = {{h_entropy, (size_t)R * 8, SLOT_ENTROPY}, {h_srccount, (size_t)R * pl->lat[0].n * 4, SLOT_OUT1},
+                            {h_samples, (size_t)R * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, "%d window(s) without a (pair, user) sample present in both frames",
+                       [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_transition_entropy_windowed_ids, vet_transition_entropy_windowed, pl, U, T, window, stride,
+                           (double*)d[0], (int32_t*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
 }
 
 // Both batch entries.  Concatenated host buffers: video v's samples start at element sum_{w<v} U_w*T_w of h_mu / h_mv, its

@@ -417,6 +417,28 @@ class DeviceResult:
             pass
 
 
+_F64, _I32 = np.float64, np.int32
+# The seven row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
+# frame pairs, not frames; window=None is all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
+# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, 3.
+_ROW_CALLS = {
+    "spatial_windowed": ("vet_spatial_entropy_windowed", False, False, True,
+                         (("entropy", "R", _F64, False), ("weights", "Rn", _F64, True), ("samples", "R", _I32, False))),
+    "spatial_per_user": ("vet_user_entropy", False, True, False,
+                         (("entropy", "UR", _F64, False), ("weights", "URn", _F64, True), ("samples", "UR", _I32, False))),
+    "spatial_user_divergence": ("vet_user_divergence", False, True, False,
+                                (("divergence", "RUU", _F64, False), ("samples", "UR", _I32, False))),
+    "spatial_crowd_divergence": ("vet_crowd_divergence", False, True, False,
+                                 (("divergence", "UR", _F64, False), ("rows", "3R", _F64, False), ("samples", "UR", _I32, False))),
+    "spatial_window_divergence": ("vet_window_divergence", False, False, False,
+                                  (("divergence", "RL", _F64, False), ("samples", "R", _I32, False))),
+    "transition_windowed": ("vet_transition_entropy_windowed", True, False, True,
+                            (("entropy", "R", _F64, False), ("srccount", "Rn", _I32, True), ("samples", "R", _I32, False))),
+    "transition_per_user": ("vet_user_transition_entropy", True, True, False,
+                            (("entropy", "UR", _F64, False), ("srccount", "URn", _I32, True), ("samples", "UR", _I32, False))),
+}
+
+
 class Plan:
     """Device tables of one analyzer configuration (quantiser, lattices, nearest LUTs)."""
 
@@ -574,6 +596,37 @@ class Plan:
             raise ValueError("mu and mv must be [n_frames, n_users] arrays of equal shape")
         return mu, mv, None, mu.shape
 
+    def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None):
+        """The host wrapper of row call ``call`` (_ROW_CALLS): arguments, outputs, the ``_host`` entry, the result dict."""
+        stem, pairs, whole, empty_ok, outputs = _ROW_CALLS[call]
+        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
+        n, unit, bound = (T - 1, "frame pairs", "n_frames - 1") if pairs else (T, "frames", "n_frames")
+        if window is None and not whole:
+            raise ValueError(f"window (a number of {unit}) is required")
+        window, stride = n if window is None else int(window), int(stride)
+        lag = (int(max_lag),) if "L" in outputs[0][1] else ()     # a primary output with a lag axis: the call takes max_lag
+        R = int(self.lib.vet_window_rows(n, window, stride))
+        if R < 0:
+            raise ValueError(f"need 1 <= window <= {bound} and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
+        if lag and not 1 <= lag[0] <= R - 1:
+            raise ValueError(f"need 1 <= max_lag <= rows - 1 = {R - 1} (got max_lag={lag[0]}; window={window}, stride={stride}, "
+                             f"{T} frames give {R} rows)")
+        dims = {"U": U, "R": R, "n": self.n_tiles[0], "L": lag[0] if lag else 0, "3": 3}
+        out = {key: None if optional and not want_optional else np.empty(tuple(dims[d] for d in shape), dtype=dtype)
+               for key, shape, dtype, optional in outputs}
+        rc = getattr(self.lib, stem + "_host")(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride, *lag,
+                                               *(_ptr(a) for a in out.values()))
+        if rc not in (VET_OK, VET_ERR_RANGE) + ((VET_ERR_EMPTY,) if empty_ok else ()) or (check and rc != VET_OK):
+            _check(self.lib, rc)
+        return dict(out, code=rc)
+
+    def _row_device(self, call, d_mu, d_mv, d_ids, n_users, n_frames, scalars, d_out, d_optional, stream):
+        """The device wrapper of row call ``call``: the ``_ids`` entry when ``d_ids`` is given, else the (mu, mv) entry."""
+        stem = _ROW_CALLS[call][0]
+        entry, samples = (getattr(self.lib, stem + "_ids"), (d_ids,)) if d_ids else (getattr(self.lib, stem), (d_mu, d_mv))
+        _check(self.lib, entry(self.handle, *samples, n_users, n_frames, *(int(v) for v in scalars), d_out,
+                               *(p or None for p in d_optional), _stream(stream)))
+
     def spatial(self, mu=None, mv=None, ids=None, want_assign=True, want_weights=False, check=True):
         """Returns dict(entropy[T], assign[T,U]|None, weights[T,n0]|None, present[T], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -591,21 +644,7 @@ class Plan:
         """Pooled entropy of sliding frame windows (include/vet.h: vet_spatial_entropy_windowed): row r pools every present
         sample of frames [r * stride, r * stride + window) into one histogram per lattice.  ``window`` and ``stride`` count
         frames.  Returns dict(entropy[R], weights[R,n0]|None, samples[R], code), R = (T - window) // stride + 1."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        if window is None:
-            raise ValueError("window (a number of frames) is required")
-        window, stride = int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        ent = np.empty(R, dtype=np.float64)
-        weights = np.empty((R, self.n_tiles[0]), dtype=np.float64) if want_weights else None
-        samples = np.empty(R, dtype=np.int32)
-        rc = self.lib.vet_spatial_entropy_windowed_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                                        _ptr(ent), _ptr(weights), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_EMPTY, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(entropy=ent, weights=weights, samples=samples, code=rc)
+        return self._row_host("spatial_windowed", mu, mv, ids, window, stride, want_weights, check)
 
     def spatial_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_weights=False, check=True):
         """Each user's own tile histogram over time (include/vet.h: vet_user_entropy): row (u, r) pools user u's present
@@ -613,19 +652,7 @@ class Plan:
         video (one row per user).  Returns dict(entropy[U,R], weights[U,R,n0]|None, samples[U,R], code),
         R = (T - window) // stride + 1.  Rows in which the user has no sample are NaN with ``samples`` 0 — data, never an
         error; ``code`` is VET_OK or VET_ERR_RANGE."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        window, stride = T if window is None else int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        ent = np.empty((U, R), dtype=np.float64)
-        weights = np.empty((U, R, self.n_tiles[0]), dtype=np.float64) if want_weights else None
-        samples = np.empty((U, R), dtype=np.int32)
-        rc = self.lib.vet_user_entropy_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                            _ptr(ent), _ptr(weights), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(entropy=ent, weights=weights, samples=samples, code=rc)
+        return self._row_host("spatial_per_user", mu, mv, ids, window, stride, want_weights, check)
 
     def spatial_user_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, check=True):
         """Do viewers look at the same places (include/vet.h: vet_user_divergence): for every row r — frames
@@ -634,18 +661,7 @@ class Plan:
         over the lattices.  Returns dict(divergence[R,U,U], samples[U,R], code), R = (T - window) // stride + 1.  The matrix
         is symmetric with a +0.0 diagonal; the rows and columns of a viewer without a sample in the row are NaN with
         ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        window, stride = T if window is None else int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        div = np.empty((R, U, U), dtype=np.float64)
-        samples = np.empty((U, R), dtype=np.int32)
-        rc = self.lib.vet_user_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                               _ptr(div), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(divergence=div, samples=samples, code=rc)
+        return self._row_host("spatial_user_divergence", mu, mv, ids, window, stride, False, check)
 
     def spatial_crowd_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, check=True):
         """How typical each viewer is of the audience (include/vet.h: vet_crowd_divergence): for every row r — frames
@@ -656,31 +672,7 @@ class Plan:
         R = (T - window) // stride + 1; ``rows`` holds pooled = S(P_r), within = sum_u (W_u / W_r) S(h_u) and
         between = sum_u (W_u / W_r) D(u, r), pooled = within + between.  A viewer without a sample in the row is NaN with
         ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        window, stride = T if window is None else int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        div = np.empty((U, R), dtype=np.float64)
-        rows = np.empty((3, R), dtype=np.float64)
-        samples = np.empty((U, R), dtype=np.int32)
-        rc = self.lib.vet_crowd_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                                _ptr(div), _ptr(rows), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(divergence=div, rows=rows, samples=samples, code=rc)
-
-    def _window_divergence_args(self, T, window, stride, max_lag):
-        if window is None:
-            raise ValueError("window (a number of frames) is required")
-        window, stride, max_lag = int(window), int(stride), int(max_lag)
-        R = int(self.lib.vet_window_rows(T, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        if not 1 <= max_lag <= R - 1:
-            raise ValueError(f"need 1 <= max_lag <= rows - 1 = {R - 1} (got max_lag={max_lag}; window={window}, stride={stride}, "
-                             f"{T} frames give {R} rows)")
-        return window, stride, max_lag, R
+        return self._row_host("spatial_crowd_divergence", mu, mv, ids, window, stride, False, check)
 
     def spatial_window_divergence(self, mu=None, mv=None, ids=None, window=None, stride=1, max_lag=1, check=True):
         """When does the audience's attention move (include/vet.h: vet_window_divergence): for every row r — frames
@@ -689,15 +681,7 @@ class Plan:
         Returns dict(divergence[R,L], samples[R], code), R = (T - window) // stride + 1, ``divergence[r, l - 1] = D(r, l)``.
         Entries with r + l >= R are NaN, and so is every pair with a window that has no sample (``samples`` 0) — data, never an
         error; ``code`` is VET_OK or VET_ERR_RANGE."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        window, stride, max_lag, R = self._window_divergence_args(T, window, stride, max_lag)
-        div = np.empty((R, max_lag), dtype=np.float64)
-        samples = np.empty(R, dtype=np.int32)
-        rc = self.lib.vet_window_divergence_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride, max_lag,
-                                                 _ptr(div), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(divergence=div, samples=samples, code=rc)
+        return self._row_host("spatial_window_divergence", mu, mv, ids, window, stride, False, check, max_lag)
 
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
@@ -718,21 +702,7 @@ class Plan:
         pools the transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1).  ``window`` and
         ``stride`` count frame pairs.  Returns dict(entropy[R], srccount[R,n0]|None, samples[R], code),
         R = (T - 1 - window) // stride + 1."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        if window is None:
-            raise ValueError("window (a number of frame pairs) is required")
-        window, stride = int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T - 1, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames - 1 and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        ent = np.empty(R, dtype=np.float64)
-        src = np.empty((R, self.n_tiles[0]), dtype=np.int32) if want_srccount else None
-        samples = np.empty(R, dtype=np.int32)
-        rc = self.lib.vet_transition_entropy_windowed_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                                           _ptr(ent), _ptr(src), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_EMPTY, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(entropy=ent, srccount=src, samples=samples, code=rc)
+        return self._row_host("transition_windowed", mu, mv, ids, window, stride, want_srccount, check)
 
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
@@ -741,19 +711,7 @@ class Plan:
         T - 1 pairs (one row per user).  Returns dict(entropy[U,R], srccount[U,R,n0]|None, samples[U,R], code),
         R = (T - 1 - window) // stride + 1.  Rows in which the user has no pair present in both frames are NaN with
         ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
-        mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        window, stride = T - 1 if window is None else int(window), int(stride)
-        R = int(self.lib.vet_window_rows(T - 1, window, stride))
-        if R < 0:
-            raise ValueError(f"need 1 <= window <= n_frames - 1 and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        ent = np.empty((U, R), dtype=np.float64)
-        src = np.empty((U, R, self.n_tiles[0]), dtype=np.int32) if want_srccount else None
-        samples = np.empty((U, R), dtype=np.int32)
-        rc = self.lib.vet_user_transition_entropy_host(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride,
-                                                       _ptr(ent), _ptr(src), _ptr(samples))
-        if rc not in (VET_OK, VET_ERR_RANGE) or (check and rc != VET_OK):
-            _check(self.lib, rc)
-        return dict(entropy=ent, srccount=src, samples=samples, code=rc)
+        return self._row_host("transition_per_user", mu, mv, ids, window, stride, want_srccount, check)
 
     def spatial_resident(self, mu=None, mv=None, ids=None, check=True):
         """Like ``spatial`` but only entropy[T] and present[T] come back; the tile assignments and weights stay
@@ -856,63 +814,47 @@ class Plan:
 
     def spatial_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                 d_entropy: int, d_weights: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
-        _check(self.lib, self.lib.vet_spatial_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
-                                                               int(stride), d_entropy, d_weights or None, d_samples or None,
-                                                               d_status or None, _stream(stream)))
+        self._row_device("spatial_windowed", d_mu, d_mv, 0, n_users, n_frames,
+                         (window, stride), d_entropy, (d_weights, d_samples, d_status), stream)
 
     def spatial_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                 d_entropy: int, d_weights: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
         """Outputs are user-major: d_entropy [U][R], d_weights [U][R][n0], d_samples [U][R] (include/vet.h: vet_user_entropy)."""
-        _check(self.lib, self.lib.vet_user_entropy(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
-                                                   d_entropy, d_weights or None, d_samples or None, d_status or None,
-                                                   _stream(stream)))
+        self._row_device("spatial_per_user", d_mu, d_mv, 0, n_users, n_frames,
+                         (window, stride), d_entropy, (d_weights, d_samples, d_status), stream)
 
     def spatial_user_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                        d_div: int, d_samples: int = 0, d_status: int = 0, stream=None):
         """d_div [R][U][U]; d_samples [U][R] (include/vet.h: vet_user_divergence)."""
-        _check(self.lib, self.lib.vet_user_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
-                                                      d_div, d_samples or None, d_status or None, _stream(stream)))
+        self._row_device("spatial_user_divergence", d_mu, d_mv, 0, n_users, n_frames,
+                         (window, stride), d_div, (d_samples, d_status), stream)
 
     def spatial_crowd_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                         d_div: int, d_rows: int = 0, d_samples: int = 0, d_status: int = 0, stream=None,
                                         d_ids: int = 0):
         """d_div [U][R]; d_rows [3][R]; d_samples [U][R] (include/vet.h: vet_crowd_divergence; ``d_ids``:
         vet_crowd_divergence_ids)."""
-        if d_ids:
-            _check(self.lib, self.lib.vet_crowd_divergence_ids(self.handle, d_ids, n_users, n_frames, int(window), int(stride),
-                                                               d_div, d_rows or None, d_samples or None, d_status or None,
-                                                               _stream(stream)))
-        else:
-            _check(self.lib, self.lib.vet_crowd_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
-                                                           d_div, d_rows or None, d_samples or None, d_status or None,
-                                                           _stream(stream)))
+        self._row_device("spatial_crowd_divergence", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride), d_div, (d_rows, d_samples, d_status), stream)
 
     def spatial_window_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                          max_lag: int, d_div: int, d_samples: int = 0, d_status: int = 0, stream=None,
                                          d_ids: int = 0):
         """d_div [R][max_lag]; d_samples [R] (include/vet.h: vet_window_divergence; ``d_ids``: vet_window_divergence_ids)."""
-        if d_ids:
-            _check(self.lib, self.lib.vet_window_divergence_ids(self.handle, d_ids, n_users, n_frames, int(window), int(stride),
-                                                                int(max_lag), d_div, d_samples or None, d_status or None,
-                                                                _stream(stream)))
-        else:
-            _check(self.lib, self.lib.vet_window_divergence(self.handle, d_mu, d_mv, n_users, n_frames, int(window), int(stride),
-                                                            int(max_lag), d_div, d_samples or None, d_status or None,
-                                                            _stream(stream)))
+        self._row_device("spatial_window_divergence", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, max_lag), d_div, (d_samples, d_status), stream)
 
     def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
-        _check(self.lib, self.lib.vet_transition_entropy_windowed(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
-                                                                  int(stride), d_entropy, d_srccount or None,
-                                                                  d_samples or None, d_status or None, _stream(stream)))
+        self._row_device("transition_windowed", d_mu, d_mv, 0, n_users, n_frames,
+                         (window, stride), d_entropy, (d_srccount, d_samples, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
         """Outputs are user-major: d_entropy [U][R], d_srccount [U][R][n0], d_samples [U][R]
         (include/vet.h: vet_user_transition_entropy)."""
-        _check(self.lib, self.lib.vet_user_transition_entropy(self.handle, d_mu, d_mv, n_users, n_frames, int(window),
-                                                              int(stride), d_entropy, d_srccount or None, d_samples or None,
-                                                              d_status or None, _stream(stream)))
+        self._row_device("transition_per_user", d_mu, d_mv, 0, n_users, n_frames,
+                         (window, stride), d_entropy, (d_srccount, d_samples, d_status), stream)
 
     def transition_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, d_entropy: int, d_pairs: int = 0,
                           d_srccount: int = 0, d_common: int = 0, d_status: int = 0, stream=None):

@@ -168,6 +168,35 @@ class _EntropyAnalyzerBase:
         xyz = np.array([[v.x, v.y, v.z] for v in table], dtype=np.float64).reshape(-1, 3)
         return "ids", vectors_df["time"].to_numpy(dtype=np.float64), ids, xyz, names
 
+    def _grid_plan(self) -> "_native.Plan":
+        """The cached plan of this analyzer's own (mu, mv) samples."""
+        return self._get_plan()
+
+    def _row_call(self, method: str, on_empty=None):
+        """One row call of the engine on the cached data.  Returns ``(times, names, call)``: ``call(**kwargs)`` runs
+        ``Plan.<method>`` on the samples — through the cached plan, or for hand-assigned vectors a temporary ``dir_table`` plan
+        — and returns its result dict.  Samples outside [0, 1] raise ``ValidationError``; rows without a sample (windowed calls
+        only) raise ``on_empty(kind, a, b, kwargs)``, the samples as ``_samples`` names them and the arguments of the call."""
+        kind, times, a, b, names = self._samples()
+
+        def call(**kwargs):
+            try:
+                if kind == "grid":
+                    return getattr(self._grid_plan(), method)(mu=a, mv=b, **kwargs)
+                plan = self._get_plan(dir_table=b)
+                try:
+                    return getattr(plan, method)(ids=a, **kwargs)
+                finally:
+                    plan.close()
+            except _native.NativeError as e:
+                if e.code == _native.VET_ERR_RANGE:
+                    raise ValidationError(str(e))
+                if e.code == _native.VET_ERR_EMPTY and on_empty is not None:
+                    raise on_empty(kind, a, b, kwargs)
+                raise
+
+        return times, names, call
+
     # ------------------------------------------------------------------ outputs
     def create_visualization(self, base_name: str) -> None:
         """Writes ``{base_name}_graph.png`` and ``{base_name}.csv`` (columns time, entropy).

@@ -73,10 +73,18 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
             self._plan_key = key
         return self._plan
 
-    def compute_entropy(self) -> pd.DataFrame:
+    def _samples(self):
+        """The engine's dense samples: this analyzer bins its own ingest only (no hand-assigned vectors)."""
         if not self._data_cache or self._dense is None:
             raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, _ = self._dense
+        times, mu, mv, names = self._dense
+        return "grid", times, mu, mv, names
+
+    def _grid_plan(self) -> "_native.Plan":
+        return self._naive_plan()
+
+    def compute_entropy(self) -> pd.DataFrame:
+        _, times, mu, mv, _ = self._samples()
         t_start = time.perf_counter()
         try:
             plan = self._naive_plan()
@@ -106,18 +114,9 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         Uses the data ``process_directory`` cached.  Returns a new DataFrame with ``time`` / ``time_end`` (of the window's
         first / last frame), ``entropy`` and ``samples`` (present samples of the window).  Raises ``ValidationError`` before
         data is loaded, ``ValueError`` for an illegal ``window`` / ``stride``."""
-        if not self._data_cache or self._dense is None:
-            raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, _ = self._dense
+        times, names, call = self._row_call("spatial_windowed", lambda *_: ValidationError("Empty radial points dictionary"))
         window, stride = self._window_args(window, stride, len(times))
-        try:
-            res = self._naive_plan().spatial_windowed(mu=mu, mv=mv, window=window, stride=stride)
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            if e.code == _native.VET_ERR_EMPTY:
-                raise ValidationError("Empty radial points dictionary")
-            raise
+        res = call(window=window, stride=stride)
         first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
         return pd.DataFrame({
             "time": np.asarray(times)[first],
@@ -135,16 +134,9 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         ``time`` / ``time_end`` (of the row's first / last frame), ``entropy`` and ``samples``.  A row in which the user has no
         sample is NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is loaded and for
         samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
-        if not self._data_cache or self._dense is None:
-            raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, names = self._dense
+        times, names, call = self._row_call("spatial_per_user")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            res = self._naive_plan().spatial_per_user(mu=mu, mv=mv, window=window, stride=stride)
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride)
         return self._user_frame(names, times, window, stride, res)
 
     def compute_user_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
@@ -158,16 +150,9 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         in matrix order.  A viewer without a sample in the window has NaN rows and columns and ``samples`` 0 — returned, never
         raised.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
         ``window`` / ``stride``."""
-        if not self._data_cache or self._dense is None:
-            raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, names = self._dense
+        times, names, call = self._row_call("spatial_user_divergence")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            res = self._naive_plan().spatial_user_divergence(mu=mu, mv=mv, window=window, stride=stride)
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride)
         return self._divergence_frame(names, times, window, stride, res)
 
     def compute_window_divergence(self, window: int, stride: int = 1, max_lag: int = 1) -> pd.DataFrame:
@@ -182,17 +167,10 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         exist are NaN, and so are the pairs of a window without a sample — returned, never raised.  Raises ``ValidationError``
         before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` /
         ``max_lag``."""
-        if not self._data_cache or self._dense is None:
-            raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, names = self._dense
+        times, names, call = self._row_call("spatial_window_divergence")
         window, stride = self._window_args(window, stride, len(times))
         max_lag = self._lag_args(max_lag, window, stride, len(times))
-        try:
-            res = self._naive_plan().spatial_window_divergence(mu=mu, mv=mv, window=window, stride=stride, max_lag=max_lag)
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride, max_lag=max_lag)
         return self._window_divergence_frame(times, window, stride, res)
 
     def compute_crowd_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
@@ -206,16 +184,9 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         ``time_end``, ``samples``, ``pooled``, ``within``, ``between``), ``attrs["users"]`` the user names.  A viewer without a
         sample in the window is NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is
         loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
-        if not self._data_cache or self._dense is None:
-            raise ValidationError("No data available. Call process_directory first.")
-        times, mu, mv, names = self._dense
+        times, names, call = self._row_call("spatial_crowd_divergence")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            res = self._naive_plan().spatial_crowd_divergence(mu=mu, mv=mv, window=window, stride=stride)
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride)
         return self._crowd_frame(names, times, window, stride, res)
 
     # ------------------------------------------------------------------ heatmaps (_HeatmapMixin)

@@ -80,23 +80,9 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         with ``time`` / ``time_end`` (of the window's first / last frame), ``entropy``, ``samples`` (present samples of the
         window) and ``tile_weights`` (lattice 0's pooled weights, the reference's dict-of-``Vector`` shape).
         Raises ``ValidationError`` before data is loaded, ``ValueError`` for an illegal ``window`` / ``stride``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("spatial_windowed", lambda *_: ValidationError("Empty vector dictionary"))
         window, stride = self._window_args(window, stride, len(times))
-        try:
-            if kind == "grid":
-                res = self._get_plan().spatial_windowed(mu=a, mv=b, window=window, stride=stride, want_weights=True)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.spatial_windowed(ids=a, window=window, stride=stride, want_weights=True)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            if e.code == _native.VET_ERR_EMPTY:
-                raise ValidationError("Empty vector dictionary")
-            raise
+        res = call(window=window, stride=stride, want_weights=True)
         tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
         first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
         return pd.DataFrame({
@@ -120,21 +106,9 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         histogram, the reference's dict-of-``Vector`` shape).  A row in which the user has no sample is NaN with ``samples`` 0
         — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1],
         ``ValueError`` for an illegal ``window`` / ``stride``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("spatial_per_user")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            if kind == "grid":
-                res = self._get_plan().spatial_per_user(mu=a, mv=b, window=window, stride=stride, want_weights=True)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.spatial_per_user(ids=a, window=window, stride=stride, want_weights=True)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride, want_weights=True)
         tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
         weights = res["weights"].reshape(-1, res["weights"].shape[-1])
         return self._user_frame(names, times, window, stride, res,
@@ -153,21 +127,9 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         The rows and columns of a viewer without a sample in the window are NaN with ``samples`` 0 — returned, never raised.
         Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
         ``window`` / ``stride``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("spatial_user_divergence")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            if kind == "grid":
-                res = self._get_plan().spatial_user_divergence(mu=a, mv=b, window=window, stride=stride)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.spatial_user_divergence(ids=a, window=window, stride=stride)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride)
         return self._divergence_frame(names, times, window, stride, res)
 
     def compute_window_divergence(self, window: int, stride: int = 1, max_lag: int = 1) -> pd.DataFrame:
@@ -184,22 +146,10 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         ``attrs["lag_frames"]`` = [stride, 2 stride, ...].  Entries whose partner row does not exist are NaN, and so are the
         pairs of a window without a sample (``samples`` 0) — returned, never raised.  Raises ``ValidationError`` before data is
         loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` / ``max_lag``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("spatial_window_divergence")
         window, stride = self._window_args(window, stride, len(times))
         max_lag = self._lag_args(max_lag, window, stride, len(times))
-        try:
-            if kind == "grid":
-                res = self._get_plan().spatial_window_divergence(mu=a, mv=b, window=window, stride=stride, max_lag=max_lag)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.spatial_window_divergence(ids=a, window=window, stride=stride, max_lag=max_lag)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride, max_lag=max_lag)
         return self._window_divergence_frame(times, window, stride, res)
 
     def compute_crowd_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
@@ -218,21 +168,9 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         ``pooled = within + between``.  ``attrs["users"]`` holds the user names.  A viewer without a sample in the window is NaN
         with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside
         [0, 1], ``ValueError`` for an illegal ``window`` / ``stride``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("spatial_crowd_divergence")
         window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
-        try:
-            if kind == "grid":
-                res = self._get_plan().spatial_crowd_divergence(mu=a, mv=b, window=window, stride=stride)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.spatial_crowd_divergence(ids=a, window=window, stride=stride)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride)
         return self._crowd_frame(names, times, window, stride, res)
 
     def _frame_present(self):

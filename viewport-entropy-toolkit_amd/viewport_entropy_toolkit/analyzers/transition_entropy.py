@@ -114,23 +114,10 @@ class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         tile, in the shape of ``compute_entropy``'s column).  Raises ``ValidationError`` before data is loaded, ``ValueError``
         for an illegal ``window`` / ``stride``, and for a window without a common sample what the reference raises on its
         pooled dicts (``ValidationError("Empty vector dictionary")`` or ``ZeroDivisionError``)."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call(
+            "transition_windowed", lambda kind, a, b, kw: self._empty_window_error(kind, a, b, kw["window"], kw["stride"]))
         window, stride = self._window_args(window, stride, len(times) - 1)
-        try:
-            if kind == "grid":
-                res = self._get_plan().transition_windowed(mu=a, mv=b, window=window, stride=stride, want_srccount=True)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.transition_windowed(ids=a, window=window, stride=stride, want_srccount=True)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            if e.code == _native.VET_ERR_EMPTY:
-                raise self._empty_window_error(kind, a, b, window, stride)
-            raise
+        res = call(window=window, stride=stride, want_srccount=True)
         tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
         first = np.arange(len(res["entropy"]), dtype=np.int64) * stride
         pair_time = np.asarray(times)[1:]
@@ -156,21 +143,9 @@ class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         without such a pair is NaN with ``samples`` 0 — returned, never raised; a row of one pair is the reference's NaN
         (0 / 0).  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal
         ``window`` / ``stride``."""
-        kind, times, a, b, names = self._samples()
+        times, names, call = self._row_call("transition_per_user")
         window, stride = self._window_args(len(times) - 1 if window is None else window, stride, len(times) - 1)
-        try:
-            if kind == "grid":
-                res = self._get_plan().transition_per_user(mu=a, mv=b, window=window, stride=stride, want_srccount=True)
-            else:
-                plan = self._get_plan(dir_table=b)
-                try:
-                    res = plan.transition_per_user(ids=a, window=window, stride=stride, want_srccount=True)
-                finally:
-                    plan.close()
-        except _native.NativeError as e:
-            if e.code == _native.VET_ERR_RANGE:
-                raise ValidationError(str(e))
-            raise
+        res = call(window=window, stride=stride, want_srccount=True)
         tiles = self._fibonacci_vectors[self.config.tile_counts[0]]
         src = res["srccount"].reshape(-1, res["srccount"].shape[-1])
         return self._user_frame(names, np.asarray(times)[1:], window, stride, res,
