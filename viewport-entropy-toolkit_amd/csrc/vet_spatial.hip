@@ -292,6 +292,50 @@ bool dedup_lattices(const vet_plan* pl, int users) {
     return (uint64_t)pl->n_rows <= vet::DEDUP_MAX_DIRS && pl->d_dirrec && dedup_fused(users);
 }
 
+#if VET_STAGE_CYCLES
+// Development builds: what k_spatial_lut's workgroups spend per stage — cycles of thread 0, summed over the workgroups and
+// printed per workgroup — or, with VET_LUT_TIMELINE=path, their wall-clock timeline written to that file instead of the
+// (intrusive: they wait on vmcnt) counters of the parts of the first stage.  The call synchronises.
+struct LutProbe {
+    DevBuf dbg, tl;
+    const char* tl_path = nullptr;
+    long blocks = 0;
+    int arm(vet_ctx* c, hipStream_t s, int blocks_, vet::LutParams* q) {
+        blocks = blocks_;
+        tl_path = c->tune.lut_timeline.empty() ? nullptr : c->tune.lut_timeline.c_str();
+        if (tl_path) {
+            HIP_TRY(tl.alloc((size_t)blocks * 48));
+            HIP_TRY(hipMemsetAsync(tl.p, 0, (size_t)blocks * 48, s));
+            q->timeline = (unsigned long long*)tl.p;
+        } else {
+            HIP_TRY(dbg.alloc(72));
+            HIP_TRY(hipMemsetAsync(dbg.p, 0, 72, s));
+            q->dbg = (unsigned long long*)dbg.p;
+        }
+        return VET_OK;
+    }
+    int report(hipStream_t s, const char* kernel, int fpw, size_t lds) {
+        if (tl_path) {
+            std::vector<unsigned long long> h((size_t)blocks * 6);
+            HIP_TRY(hipMemcpyAsync(h.data(), tl.p, h.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (FILE* f = fopen(tl_path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+            return VET_OK;
+        }
+        unsigned long long t[9] = {};
+        HIP_TRY(hipMemcpyAsync(t, dbg.p, 72, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const double b = (double)blocks, all = (double)(t[0] + t[1] + t[2] + t[3]);
+        fprintf(stderr, "[k_spatial_lut %s] blocks %ld FPW %d lds %zu | cycles per workgroup (thread 0): samples->set %.0f  lists %.0f  walk %.0f"
+                        " (main %.0f + overflow %.0f)  entropy %.0f | samples->set = init %.0f + sample loads %.0f + record gathers %.0f"
+                        " + inserts %.0f (+ barrier) | before the walk %.1f %% of the residency\n",
+                kernel, blocks, fpw, lds, t[0] / b, t[1] / b, t[2] / b, (t[2] - t[8]) / b, t[8] / b, t[3] / b, t[4] / b, t[5] / b, t[6] / b,
+                t[7] / b, all > 0 ? 100.0 * (double)(t[0] + t[1]) / all : 0.0);
+        return VET_OK;
+    }
+};
+#endif
+
 // one launch of the table kernel over lattices lat_idx[0..K) of the plan (single video or a batch)
 template <bool FROM_IDS>
 int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& src, int U, int T,
@@ -355,13 +399,22 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     } else {
         q.FPW = 1; q.UC = 1;
     }
-    ProfScope ps(c, s, KID_SPATIAL);
-    void* args[] = {(void*)&q};
     // 2 rows in flight per lane group measured best (4 and 8 were tried, profiles/r01/v3_*)
     const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb, rec32);
     if (!fn) return fail(VET_ERR_UNSUPPORTED, "no table kernel for this launch");
-    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(threads), args, lds, s));
-    HIP_TRY(hipGetLastError());
+#if VET_STAGE_CYCLES
+    LutProbe probe;
+    if (int rc = probe.arm(c, s, blocks, &q)) return rc;
+#endif
+    {
+        ProfScope ps(c, s, KID_SPATIAL);
+        void* args[] = {(void*)&q};
+        HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(threads), args, lds, s));
+        HIP_TRY(hipGetLastError());
+    }
+#if VET_STAGE_CYCLES
+    if (int rc = probe.report(s, rec32 ? "rec32" : nb ? "capped" : fpt ? "fp table" : "lattices", q.FPW, lds)) return rc;
+#endif
     *launched = true;
     return VET_OK;
 }
@@ -406,19 +459,8 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
     // batches (+1 %) or for frames without the set (config 2 +2 %)
     const bool occ8 = F.gs_log2 == 3 && !d_videos && dedup;
 #if VET_STAGE_CYCLES
-    DevBuf dbg, tl;                           // development builds: cycles per stage (thread 0 of every workgroup), synchronous
-    HIP_TRY(dbg.alloc(64));
-    HIP_TRY(hipMemsetAsync(dbg.p, 0, 64, s));
-    // VET_LUT_TIMELINE=path: per-workgroup wall-clock timeline instead of the (intrusive: waits on vmcnt) sub-stage counters
-    const char* tl_path = c->tune.lut_timeline.empty() ? nullptr : c->tune.lut_timeline.c_str();
-    const long n_items_tl = blocks;
-    if (tl_path) {
-        HIP_TRY(tl.alloc((size_t)n_items_tl * 48));
-        HIP_TRY(hipMemsetAsync(tl.p, 0, (size_t)n_items_tl * 48, s));
-        q.timeline = (unsigned long long*)tl.p;
-    } else {
-        q.dbg = (unsigned long long*)dbg.p;
-    }
+    LutProbe probe;
+    if (int rc = probe.arm(c, s, blocks, &q)) return rc;
 #endif
     {
         ProfScope ps(c, s, KID_SPATIAL);
@@ -427,21 +469,7 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
         HIP_TRY(hipGetLastError());
     }
 #if VET_STAGE_CYCLES
-    if (tl_path) {
-        std::vector<unsigned long long> h((size_t)n_items_tl * 6);
-        HIP_TRY(hipMemcpyAsync(h.data(), tl.p, h.size() * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (FILE* f = fopen(tl_path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    } else
-    {
-        unsigned long long t[8] = {};
-        HIP_TRY(hipMemcpyAsync(t, dbg.p, 64, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        fprintf(stderr, "[k_spatial_lut fused] blocks %d FPW %d lds %zu | cycles per workgroup (thread 0): samples->set %.0f  lists %.0f  walk %.0f  entropy %.0f"
-                        " | samples->set = init %.0f + sample loads %.0f + record gathers %.0f + inserts %.0f (+ barrier)\n",
-                blocks, q.FPW, lds, (double)t[0] / blocks, (double)t[1] / blocks, (double)t[2] / blocks, (double)t[3] / blocks,
-                (double)t[4] / blocks, (double)t[5] / blocks, (double)t[6] / blocks, (double)t[7] / blocks);
-    }
+    if (int rc = probe.report(s, "fused", q.FPW, lds)) return rc;
 #endif
     *launched = true;
     return VET_OK;

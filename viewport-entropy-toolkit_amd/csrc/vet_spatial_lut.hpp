@@ -296,7 +296,7 @@ struct LutParams {
                                   // an FP table's sums then do not depend on which videos share a batch)
     FusedLayout lay;              // FUSED: the launch's one "lattice" is the plan's fused table (n = lay.N slots)
     unsigned long long* timeline; // development builds: [workgroup][6] wall clock (100 MHz) at entry / after the set / lists / walk / entropy, HW id
-    unsigned long long* dbg;      // development builds (-DVET_STAGE_CYCLES=1): [4] cycles of thread 0 per stage, summed over the workgroups
+    unsigned long long* dbg;      // development builds (-DVET_STAGE_CYCLES=1): [9] cycles of thread 0 per stage and part of a stage, summed over the workgroups
     uint32_t* resolve;            // FP tables with marker entries: [0] = number of frames handed to the precise sweep
                                   // (a marked tile whose histogram stayed 0.0), then the frames; null otherwise
     const uint32_t* dirrec32;     // [n_dirs] REC32: dirrec in one word for capped rows (k_dirrec32; vet_layout.hpp).  (Last: the
@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     const long f0 = blk * FPW;
     const int nf = (int)min((long)FPW, (long)T - f0);
 #if VET_STAGE_CYCLES
-    unsigned long long tdbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = p.dbg ? __builtin_readcyclecounter() : 0ull, tsub = tlast;
+    unsigned long long tdbg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = p.dbg ? __builtin_readcyclecounter() : 0ull, tsub = tlast;
     if (p.timeline && tid == 0) {
         p.timeline[(long)blockIdx.x * 6 + 0] = wall_clock64();
         p.timeline[(long)blockIdx.x * 6 + 5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) /* HW_ID */ |
@@ -542,10 +542,20 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
             const unsigned long long now = __builtin_readcyclecounter(); tdbg[4 + i] += now - tsub; tsub = now;
         }
     };
+    // 8: the part of stage 2 (walk) spent on the overflow lists (capped rows)
+    auto ovf_walk = [&](bool done) {
+        if (p.dbg) { const unsigned long long now = __builtin_readcyclecounter(); if (done) tdbg[8] += now - tsub; else tsub = now; }
+    };
 #else
     auto stage = [](int) {};
     auto sub = [](int, bool) {};
+    auto ovf_walk = [](bool) {};
 #endif
+    // REC32: a new workgroup holds the CU's four youngest waves, and issue goes by priority, then age: at priority 0 its few
+    // instructions up to the walk wait behind seven older workgroups' walks (a third of its residency; profiles/early_walk/).
+    // Raised from here to the barrier in front of the walk, it starts its row loads sooner; the walk itself runs at 0.
+    constexpr int YOUNG_PRIO = 3;
+    if constexpr (REC32) __builtin_amdgcn_s_setprio(YOUNG_PRIO);
     if (!overlay)
         for (int i = tid; i < FPW * p.n_sum * PRIV; i += blockDim.x) hist[i] = 0ull;
     for (int i = tid; i < 2 * FPW; i += blockDim.x) cnt_chunk[i] = 0;
@@ -555,6 +565,7 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     const int hs_shift = 32 - (31 - __clz(HS | 1));
     for (int u0 = 0; u0 < U; u0 += UC) {
         const int uc = min(UC, U - u0);
+        if constexpr (REC32) { if (u0) __builtin_amdgcn_s_setprio(YOUNG_PRIO); }
         __syncthreads();
         for (int i = tid; i < FPW; i += blockDim.x) {
             cnt_chunk[i] = 0;
@@ -831,6 +842,8 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                     if (j < cnt_chunk[fl]) note_overflow(fl, rows[i], meta[i]);
                 }
             __syncthreads();
+            // (inside the loop over the lattices, the raise outside it: a REC32 launch has one lattice — capped rows, launch_lut)
+            if constexpr (REC32) __builtin_amdgcn_s_setprio(0);
             constexpr int GSL_IL = (FUSED && UN == 2) ? 3 : 4;      // the narrow fused kernel walks 8-lane rows
             for (int fl = 0; fl < nf; ++fl)
                 if constexpr (NB > 0) {
@@ -839,9 +852,11 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                                                              L.tab_w, L.tab_i, L.stride, 4, L.zrow * (uint32_t)(NB * ROW_BLOCK));
                     if (const int OC = ovf_slots()) {
                         const uint32_t* ovf_rows = (const uint32_t*)(ovf_cnt + FPW);
+                        ovf_walk(false);
                         walk_rows<UN, true, DEDUP, false, 4, 1, REC32>(ovf_rows + (size_t)fl * OC, ovf_rows + (size_t)(FPW + fl) * OC,
                                                                 min(ovf_cnt[fl], OC), hrow, L.n, L.ovf_w, L.ovf_i, ROW_BLOCK, 4,
                                                                 (uint32_t)L.n_ovf * (uint32_t)ROW_BLOCK);
+                        ovf_walk(true);
                     }
                 } else if (IL && L.interleaved)
                     walk_rows<UN, true, DEDUP, FPT, GSL_IL>(rows + (size_t)fl * UC, meta + (size_t)fl * UC, cnt_chunk[fl],
@@ -918,7 +933,7 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     if (p.dbg) {
         stage(3);
         if (tid == 0)
-            for (int i = 0; i < 8; ++i) atomicAdd(&p.dbg[i], tdbg[i]);
+            for (int i = 0; i < 9; ++i) atomicAdd(&p.dbg[i], tdbg[i]);
     }
 #endif
     if (p.status) {
