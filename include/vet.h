@@ -56,7 +56,9 @@ extern "C" {
                           the vet_user_entropy* entry points (each viewer's own histogram over time), and then the
                           vet_user_divergence* entry points (a U x U Jensen-Shannon matrix between viewers per window), and
                           then the vet_window_divergence* entry points (a lag band of Jensen-Shannon distances between windows) and the
-                          vet_crowd_divergence* entry points (each viewer's Kullback-Leibler divergence from the pooled crowd) */
+                          vet_crowd_divergence* entry points (each viewer's Kullback-Leibler divergence from the pooled crowd), and
+                          then the vet_bootstrap_entropy* entry points (confidence bands from viewers resampled with replacement)
+                          and vet_bootstrap_counts_host */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -118,6 +120,10 @@ int vet_test_window_divergence_chunk_rows(vet_ctx *ctx, int rows);
  * workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every launch.  Results are
  * bit-identical whatever the value. */
 int vet_test_crowd_divergence_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes vet_bootstrap_entropy* build the viewers' histograms `rows` rows at a time instead
+ * of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every
+ * launch.  Results are bit-identical whatever the value. */
+int vet_test_bootstrap_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -548,6 +554,76 @@ int vet_crowd_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, 
  * h_samples may be NULL. */
 int vet_crowd_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                               int n_frames, int window, int stride, double *h_div, double *h_rows, int32_t *h_samples);
+
+/* ---- bootstrap confidence bands over viewers for per-frame and windowed entropy ----------------------
+ * Every entropy the engine reports is a point estimate from one sample of viewers; an entropy from 30 viewers and one from 300
+ * are not comparable without an interval.  Viewers are the independent unit, so the audience is resampled with replacement (the
+ * cluster bootstrap) and the series recomputed, B times in one call.
+ * - Rows.  Rows are vet_spatial_entropy_windowed's.  Row r covers frames [r*stride, r*stride + window).  window = 1, stride = 1 is
+ *   the per-frame series.
+ * - Draw.  For replicate b (0-based) and draw j = 0 ... U-1, all in unsigned 64-bit arithmetic mod 2^64:
+ *     z = seed + (b*U + j + 1) * 0x9E3779B97F4A7C15
+ *     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *     viewer = ((z >> 32) * U) >> 32
+ *   c[b][u] = the number of draws of replicate b that picked u, and sum_u c[b][u] = U.  Replicate b does not depend on B.  The same
+ *   resample applies to every row and every lattice of a call.  This is the cluster bootstrap: a viewer's whole trajectory stays
+ *   together.
+ * - Value.  rep[r][b] is the reference's compute_spatial_entropy on ONE dict (naive plans use compute_naive_spatial_entropy).  The
+ *   dict holds every present sample of the row's frames for every drawn viewer, frame-major, then in draw order.  A viewer drawn c
+ *   times is entered c times.  The value is per lattice, then the mean over the lattices, as compute_entropy takes it.  The
+ *   normaliser follows the replicate's own total.  A replicate whose drawn viewers have no sample in the row is NaN.  That is
+ *   data, not an error.  Whatever the reference's 0 * log2 0 makes NaN is NaN: a key tile whose replicate sum is 0.0, or whose q
+ *   underflows to 0.
+ * - Summary per row.  Taken over the m finite replicates, sorted ascending: mean; sd: two-pass, ddof = 1, NaN for m < 2; lo and hi:
+ *   the quantiles (1 - confidence)/2 and 1 - (1 - confidence)/2, by linear interpolation between order statistics at position
+ *   q*(m - 1): x[i] + (x[i+1] - x[i])*g; valid = m.  m = 0 gives NaN for all four.
+ * - Bits.  A replicate's bits depend on the plan, the window, the row's frames, U, seed and b only.  They do not depend on stride,
+ *   B, the number of rows, the row chunk or the entry point.
+ *   d_summary    [4][R]      mean, sd, lo, hi
+ *   d_replicates [R][B]      rep[r][b]                                                                          (nullable)
+ *   d_weights    [R][B][n0]  lattice 0's replicate histograms sum_u c[b][u] h_u: PLAIN VALUES, +0.0 = no weight.  Not the dense
+ *                            tile_weights encoding: a key whose value is 0.0 reads +0.0 like a tile that is no key (whether such
+ *                            a key exists decides a NaN above, but is not recorded per tile)                       (nullable)
+ *   d_valid      [R]         m, the finite replicates of the row                                                 (nullable)
+ *   d_status     [2]         {bad, unused}; the call ADDS to [0], the caller zeroes                               (nullable)
+ * For one row, replicate b's histogram is sum_u c[b][u] h_u with h_u viewer u's own row histogram (vet_user_entropy's d_weights):
+ * a row's B replicate histograms are a [B x U] . [U x n] FP64 matrix product.  Stages; everything lives in the context's grow-only
+ * workspace, no allocation in steady state:
+ *   1 k_user_dirs, unchanged: direction ids transposed once;
+ *   2 k_bootstrap_counts: c[B][U] u16 from the draw, integer atomics (exact in any order);
+ *   3 per lattice and chunk of rows (as many as fit 256 MB of histograms, at least one): vet_user_divergence's k_user_hist_w/_c,
+ *     unchanged, leave hist[rows][U][n] f64; k_bootstrap_zero_keys marks, for the flagged (row, viewer) slots of weighted lattices
+ *     only, the tiles that are keys of the viewer with the value 0.0 (underflowing power_factor);
+ *   4 k_bootstrap_gemm: one workgroup per (row, 16 replicates); each of its 4 waves runs the whole K loop over the viewers in
+ *     ascending blocks of four into one accumulator per 16-tile column block with v_mfma_f64_16x16x4_f64 (no split-K, no atomics)
+ *     and leaves the 16 x n block in LDS; then one wave per replicate takes W, S and the normaliser as vet_user_entropy does
+ *     (counting lattices: log2(n) if W > n, else log2(W), as compute_spatial_entropy), every reduction in lane order followed by the
+ *     wave butterfly.  Lattice 0 stores value / K, lattice k adds its own, in lattice order;
+ *   5 k_bootstrap_summary: one workgroup per row sorts the finite replicates in LDS.
+ * The summation order inside one 16x16x4 MFMA is the hardware's and fixed: replicates reproduce bit for bit; against the reference
+ * they agree to rounding (the project's 1e-6 contract; integer plans exactly, their sums being integers).
+ * VET_ERR_INVALID (before anything is staged, launched or allocated): vet_user_entropy's; replicates outside [1, 4096]; confidence
+ * outside (0, 1).  VET_ERR_UNSUPPORTED (likewise): n_users > 65535 (16-bit counts); a lattice of more than 1276 tiles (the 16 x n
+ * FP64 block must fit the 160 KB LDS); R * n_users >= 2^31, n_frames > 65535 * 64, vet_user_entropy's limits on the plan.
+ * Profile ids: k_user_dirs to k_spatial, the histogram kernels as vet_user_entropy's (k_weights / k_finalize), k_bootstrap_gemm to
+ * k_transition — the one id the call does not use otherwise —, the rest to k_finalize.  Asynchronous on `stream` like
+ * vet_spatial_entropy. */
+int vet_bootstrap_entropy(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                          int replicates, uint64_t seed, double confidence, double *d_summary, double *d_replicates,
+                          double *d_weights, int32_t *d_valid, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_bootstrap_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                              int replicates, uint64_t seed, double confidence, double *d_summary, double *d_replicates,
+                              double *d_weights, int32_t *d_valid, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa;
+ * h_replicates, h_weights and h_valid may be NULL. */
+int vet_bootstrap_entropy_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                               int n_frames, int window, int stride, int replicates, uint64_t seed, double confidence,
+                               double *h_summary, double *h_replicates, double *h_weights, int32_t *h_valid);
+/* The draw alone: runs k_bootstrap_counts on the plan's context and downloads c[replicates][n_users], so that the draw can be
+ * pinned on its own.  Synchronous.  Errors as above (replicates, n_users). */
+int vet_bootstrap_counts_host(vet_plan *plan, int n_users, int replicates, uint64_t seed, uint16_t *h_counts);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

@@ -12,6 +12,8 @@
 //   vet_window_divergence.hip
 //                       the window-to-window divergence kernels (a lag band of Jensen-Shannon distances per row) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
+//   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
+//                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
@@ -122,6 +124,9 @@ struct Tuning {
     int crowd_divergence_chunk_rows = 0;    // vet_test_crowd_divergence_chunk_rows (no environment variable): rows per chunk of
                                 // vet_crowd_divergence* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_crowd_divergence_gpu.py)
+    int bootstrap_chunk_rows = 0;   // vet_test_bootstrap_chunk_rows (no environment variable): rows per histogram chunk of
+                                // vet_bootstrap_entropy* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_bootstrap_gpu.py)
     void from_environment();
 };
 
@@ -398,6 +403,7 @@ int user_transition_set_attrs(vet_ctx* c);
 int user_divergence_set_attrs(vet_ctx* c);
 int window_divergence_set_attrs(vet_ctx* c);
 int crowd_set_attrs(vet_ctx* c);
+int bootstrap_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -431,6 +437,16 @@ int check_user_plan(vet_plan* pl, const char* what, hipStream_t s);
 int check_user_dirs_frames(int T, const char* what);
 int user_dirs_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int32_t* dirs,
                   int32_t* d_status, const char* what, hipStream_t s);
+
+// vet_user_divergence.hip, shared with vet_bootstrap.hip: lattice k's per-viewer row histograms of rows [r0, r0 + cr) from dirs
+// (k_user_hist_w/_c) — hist [cr][U][n_k] f64 (+0.0 = no key, or a key whose value is 0.0), tot and flag per (row, viewer) (1: no
+// sample, or the viewer's own S is NaN); samples [U][R] and status[1] where those are given.  Charged as vet_user_entropy's stage 2.
+int user_hist_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int window, int stride, long R, long r0, long cr,
+                  double* hist, double* tot, int32_t* flag, int32_t* samples, int32_t* status, hipStream_t s);
+
+// vet_bootstrap.hip: what vet_bootstrap_entropy* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before
+// anything is staged, allocated or launched — after check_window_args
+int check_bootstrap_args(const vet_plan* pl, int U, int replicates, double confidence);
 
 // vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched

@@ -560,6 +560,36 @@ int vet_crowd_divergence_host(vet_plan* pl, const double* h_mu, const double* h_
     });
 }
 
+// Bootstrap confidence bands with host buffers (include/vet.h): the summary [4][R], and where wanted the replicates [R][B], lattice
+// 0's replicate histograms [R][B][n_0] and the finite replicates per row.  Four outputs, so its own staged run.  Replicates without
+// a sample are data (NaN): only VET_ERR_RANGE is decoded from the status words.
+int vet_bootstrap_entropy_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                               int stride, int replicates, uint64_t seed, double confidence, double* h_summary, double* h_replicates,
+                               double* h_weights, int32_t* h_valid) {
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_summary, h_mu, h_mv, h_ids, &R);
+    if (!rc) rc = check_bootstrap_args(pl, U, replicates, confidence);
+    if (rc) return rc;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    const size_t reps = (size_t)R * replicates;
+    struct { void* h; size_t bytes; int slot; void* d; } outs[4] = {
+        {h_summary, (size_t)4 * R * 8, SLOT_ENTROPY, nullptr}, {h_replicates, reps * 8, SLOT_OUT0, nullptr},
+        {h_weights, reps * pl->lat[0].n * 8, SLOT_OUT1, nullptr}, {h_valid, (size_t)R * 4, SLOT_COUNT, nullptr}};
+    for (auto& o : outs)
+        if (o.h) POOL(o.slot, o.bytes, o.d);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = launch_rows(run, vet_bootstrap_entropy_ids, vet_bootstrap_entropy, pl, U, T, window, stride, replicates, seed, confidence,
+                     (double*)outs[0].d, (double*)outs[1].d, (double*)outs[2].d, (int32_t*)outs[3].d, run.status, run.s);
+    if (rc) return run.drain(rc);
+    for (auto& o : outs)
+        if (o.h) HIP_TRY(hipMemcpyAsync(o.h, o.d, o.bytes, hipMemcpyDeviceToHost, run.s));
+    return run.finish_rows_are_data();
+}
+
 // Window-to-window divergence with host buffers (include/vet.h): vet_window_rows rows of max_lag lags.  Rows without a sample are
 // data (NaN across their band): only VET_ERR_RANGE is decoded from the status words.
 int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,

@@ -42,6 +42,13 @@
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave
 //                                              k_crowd_rows     one wave per row: pooled, within and between
+//   vet_bootstrap.hip   (in the unit)          k_bootstrap_counts   how often each replicate's draw picked each viewer, u16 [B][U]
+//                                              k_bootstrap_zero_keys   flagged (row, viewer) slots: the keys whose value is 0.0, as bits
+//                                              k_bootstrap_gemm one workgroup per (row, 16 replicates): counts x per-viewer histograms
+//                                                               (k_user_hist_w/_c's) on the FP64 matrix unit into LDS, then the
+//                                                               row calls' entropy epilogue per replicate
+//                                              k_bootstrap_summary   one workgroup per row: the finite replicates sorted in LDS ->
+//                                                               mean, sd and the two quantiles
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

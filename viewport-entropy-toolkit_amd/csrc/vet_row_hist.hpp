@@ -1,8 +1,8 @@
 // vet_row_hist.hpp — what one wave does with a finished row histogram, written once for the row calls: the per-viewer units
-// (vet_user.hip, vet_user_divergence.hip, vet_crowd.hip) and the windowed units (vet_window.hip, vet_window_divergence.hip).
+// (vet_user.hip, vet_user_divergence.hip, vet_crowd.hip, vet_bootstrap.hip) and the windowed units (vet_window.hip, vet_window_divergence.hip).
 // A row histogram is seen through a functor value(t, v): whether tile t is a key of the row, and its value v — KeyedHist for an
 // FP64 histogram in LDS with a "no key" bit pattern (the caller says which: NO_KEY_BITS and WIN_NO_KEY_BITS stay two names), a
-// lambda over u32 counts in vet_crowd.hip.  Every loop runs over the tiles in lane order and ends in wave_sum's butterfly (or
+// lambda over u32 counts in vet_crowd.hip, over a replicate's FP64 sums in vet_bootstrap.hip.  Every loop runs over the tiles in lane order and ends in wave_sum's butterfly (or
 // a ballot), so a value does not depend on which kernel asked for it.  Also RowStats, what the histogram kernels of the
 // divergence calls leave per row, and the reference's epilogue over integer counts.
 // Part of the gfx950 device code of the viewport -> tile -> entropy path (see vet_kernels.hpp for the map).

@@ -227,11 +227,38 @@ __global__ __launch_bounds__(256) void k_user_divergence(const UserDivParams p) 
 
 namespace vh {
 
+static const void* hist_w_kernel(int stride) { return VET_KERNEL_BY_S(vet::k_user_hist_w, row_chunk_class(stride)); }
+
+// stage 2 of lattice k for rows [r0, r0 + cr), charged as vet_user_entropy's (declared in vet_host.hpp: vet_bootstrap.hip builds the
+// same histograms)
+int user_hist_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int window, int stride, long R, long r0, long cr,
+                  double* hist, double* tot, int32_t* flag, int32_t* samples, int32_t* status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const Lattice& L = pl->lat[k];
+    const vet::RowStats st{hist, tot, flag};
+    if (counts_lattice(pl, k)) {
+        vet::UserHistCParams q{};
+        q.dirs = dirs; q.T = T; q.U = U; q.nearest = L.d_nearest; q.n = L.n; q.window = window; q.stride = stride;
+        q.R = R; q.r0 = r0; q.out = st; q.samples = samples; q.status = status;
+        ProfScope ps(c, s, KID_FINALIZE);
+        hipLaunchKernelGGL(vet::k_user_hist_c, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
+    } else {
+        vet::UserHistWParams q{};
+        q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
+        q.window = window; q.stride = stride; q.R = R; q.r0 = r0; q.out = st; q.samples = samples; q.status = status;
+        const int nw = user_nw(c->lds_max, L.n, window);
+        void* args[] = {(void*)&q};
+        ProfScope ps(c, s, KID_WEIGHTS);
+        HIP_TRY(hipLaunchKernel(hist_w_kernel(q.X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
+                                vet::dtable_lds_bytes(nw, L.n), s));
+    }
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
+
 namespace {
 
 constexpr size_t kDivHistBudget = (size_t)256 << 20;      // bytes of histograms a chunk of rows may take in the workspace
-
-const void* hist_w_kernel(int stride) { return VET_KERNEL_BY_S(vet::k_user_hist_w, row_chunk_class(stride)); }
 
 int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window,
                       int stride, double* d_div, int32_t* d_samples, int32_t* d_status, hipStream_t s) {
@@ -271,25 +298,9 @@ int launch_divergence(vet_plan* pl, const double* d_mu, const double* d_mv, cons
         const long cr = std::min(CR, R - r0);
         for (int k = 0; k < K; ++k) {
             const Lattice& L = pl->lat[k];
-            int32_t *samples = k == 0 ? d_samples : nullptr, *status = k == 0 ? d_status : nullptr;
-            // ---- stage 2, charged as vet_user_entropy's
-            if (counts_lattice(pl, k)) {
-                vet::UserHistCParams q{};
-                q.dirs = dirs; q.T = T; q.U = U; q.nearest = L.d_nearest; q.n = L.n; q.window = window; q.stride = stride;
-                q.R = R; q.r0 = r0; q.out = st; q.samples = samples; q.status = status;
-                ProfScope ps(c, s, KID_FINALIZE);
-                hipLaunchKernelGGL(vet::k_user_hist_c, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)L.n * 4, s, q);
-            } else {
-                vet::UserHistWParams q{};
-                q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
-                q.window = window; q.stride = stride; q.R = R; q.r0 = r0; q.out = st; q.samples = samples; q.status = status;
-                const int nw = user_nw(c->lds_max, L.n, window);
-                void* args[] = {(void*)&q};
-                ProfScope ps(c, s, KID_WEIGHTS);
-                HIP_TRY(hipLaunchKernel(hist_w_kernel(q.X.stride), dim3((unsigned)(cr * U)), dim3(nw * vet::WAVE), args,
-                                        vet::dtable_lds_bytes(nw, L.n), s));
-            }
-            HIP_TRY(hipGetLastError());
+            rc = user_hist_run(pl, k, dirs, U, T, window, stride, R, r0, cr, st.hist, st.tot, st.flag, k == 0 ? d_samples : nullptr,
+                               k == 0 ? d_status : nullptr, s);
+            if (rc) return rc;
             {   // ---- stage 3, charged to k_finalize
                 vet::UserDivParams q{};
                 q.in = st; q.U = U; q.n = L.n; q.nblk = (int)nblk; q.first = k == 0; q.K = (double)K;

@@ -67,7 +67,7 @@ class _PlanDesc(C.Structure):
 
 
 # name -> (restype, argtypes); also the list tests check against include/vet.h
-_P, _I, _I64, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t
+_P, _I, _I64, _D, _SZ, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_uint64
 SIGNATURES = {
     "vet_version": (_I, []),
     "vet_last_error": (C.c_char_p, []),
@@ -83,6 +83,7 @@ SIGNATURES = {
     "vet_test_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_window_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_crowd_divergence_chunk_rows": (_I, [_P, _I]),
+    "vet_test_bootstrap_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -130,6 +131,10 @@ SIGNATURES = {
     "vet_crowd_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_crowd_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_crowd_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_bootstrap_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _U64, _D, _P, _P, _P, _P, _P, _P]),
+    "vet_bootstrap_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _U64, _D, _P, _P, _P, _P, _P, _P]),
+    "vet_bootstrap_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _U64, _D, _P, _P, _P, _P]),
+    "vet_bootstrap_counts_host": (_I, [_P, _I, _I, _U64, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -372,6 +377,11 @@ class Engine:
         not depend on it (include/vet.h: vet_test_window_divergence_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_window_divergence_chunk_rows(self.handle, int(rows)))
 
+    def test_bootstrap_chunk_rows(self, rows: int = 0):
+        """Test switch: the bootstrap builds the viewers' histograms ``rows`` rows at a time (0: the default budget); results do
+        not depend on it (include/vet.h: vet_test_bootstrap_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_bootstrap_chunk_rows(self.handle, int(rows)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -418,9 +428,10 @@ class DeviceResult:
 
 
 _F64, _I32 = np.float64, np.int32
-# The seven row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
+# The eight row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
 # frame pairs, not frames; window=None is all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
-# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, 3.
+# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, B replicates, 3, 4.  A call's extra
+# scalars (max_lag; replicates, seed, confidence) follow stride in the C signatures; ``_row_host`` takes them as ``extra``.
 _ROW_CALLS = {
     "spatial_windowed": ("vet_spatial_entropy_windowed", False, False, True,
                          (("entropy", "R", _F64, False), ("weights", "Rn", _F64, True), ("samples", "R", _I32, False))),
@@ -432,6 +443,9 @@ _ROW_CALLS = {
                                  (("divergence", "UR", _F64, False), ("rows", "3R", _F64, False), ("samples", "UR", _I32, False))),
     "spatial_window_divergence": ("vet_window_divergence", False, False, False,
                                   (("divergence", "RL", _F64, False), ("samples", "R", _I32, False))),
+    "spatial_bootstrap": ("vet_bootstrap_entropy", False, True, False,
+                          (("summary", "4R", _F64, False), ("replicates", "RB", _F64, True), ("weights", "RBn", _F64, True),
+                           ("valid", "R", _I32, False))),
     "transition_windowed": ("vet_transition_entropy_windowed", True, False, True,
                             (("entropy", "R", _F64, False), ("srccount", "Rn", _I32, True), ("samples", "R", _I32, False))),
     "transition_per_user": ("vet_user_transition_entropy", True, True, False,
@@ -596,8 +610,10 @@ class Plan:
             raise ValueError("mu and mv must be [n_frames, n_users] arrays of equal shape")
         return mu, mv, None, mu.shape
 
-    def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None):
-        """The host wrapper of row call ``call`` (_ROW_CALLS): arguments, outputs, the ``_host`` entry, the result dict."""
+    def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None, extra=(), extra_dims=None):
+        """The host wrapper of row call ``call`` (_ROW_CALLS): arguments, outputs, the ``_host`` entry, the result dict.
+        ``want_optional``: one bool for every optional output, or the set of the wanted keys.  ``extra``: the call's scalars behind
+        stride (after max_lag, where the call has one), passed as they are; ``extra_dims``: the output dimensions they define."""
         stem, pairs, whole, empty_ok, outputs = _ROW_CALLS[call]
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
         n, unit, bound = (T - 1, "frame pairs", "n_frames - 1") if pairs else (T, "frames", "n_frames")
@@ -611,10 +627,11 @@ class Plan:
         if lag and not 1 <= lag[0] <= R - 1:
             raise ValueError(f"need 1 <= max_lag <= rows - 1 = {R - 1} (got max_lag={lag[0]}; window={window}, stride={stride}, "
                              f"{T} frames give {R} rows)")
-        dims = {"U": U, "R": R, "n": self.n_tiles[0], "L": lag[0] if lag else 0, "3": 3}
-        out = {key: None if optional and not want_optional else np.empty(tuple(dims[d] for d in shape), dtype=dtype)
+        dims = {"U": U, "R": R, "n": self.n_tiles[0], "L": lag[0] if lag else 0, "3": 3, "4": 4, **(extra_dims or {})}
+        wanted = (lambda key: key in want_optional) if isinstance(want_optional, (set, frozenset)) else (lambda key: want_optional)
+        out = {key: None if optional and not wanted(key) else np.empty(tuple(dims[d] for d in shape), dtype=dtype)
                for key, shape, dtype, optional in outputs}
-        rc = getattr(self.lib, stem + "_host")(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride, *lag,
+        rc = getattr(self.lib, stem + "_host")(self.handle, _ptr(mu), _ptr(mv), _ptr(ids), U, T, window, stride, *lag, *extra,
                                                *(_ptr(a) for a in out.values()))
         if rc not in (VET_OK, VET_ERR_RANGE) + ((VET_ERR_EMPTY,) if empty_ok else ()) or (check and rc != VET_OK):
             _check(self.lib, rc)
@@ -624,7 +641,7 @@ class Plan:
         """The device wrapper of row call ``call``: the ``_ids`` entry when ``d_ids`` is given, else the (mu, mv) entry."""
         stem = _ROW_CALLS[call][0]
         entry, samples = (getattr(self.lib, stem + "_ids"), (d_ids,)) if d_ids else (getattr(self.lib, stem), (d_mu, d_mv))
-        _check(self.lib, entry(self.handle, *samples, n_users, n_frames, *(int(v) for v in scalars), d_out,
+        _check(self.lib, entry(self.handle, *samples, n_users, n_frames, *(v if isinstance(v, float) else int(v) for v in scalars), d_out,
                                *(p or None for p in d_optional), _stream(stream)))
 
     def spatial(self, mu=None, mv=None, ids=None, want_assign=True, want_weights=False, check=True):
@@ -682,6 +699,40 @@ class Plan:
         Entries with r + l >= R are NaN, and so is every pair with a window that has no sample (``samples`` 0) — data, never an
         error; ``code`` is VET_OK or VET_ERR_RANGE."""
         return self._row_host("spatial_window_divergence", mu, mv, ids, window, stride, False, check, max_lag)
+
+    @staticmethod
+    def _bootstrap_scalars(replicates, seed, confidence):
+        """(replicates, seed, confidence) as the C entry takes them; ``ValueError`` outside [1, 4096], [0, 2^64) and (0, 1)."""
+        replicates, seed, confidence = int(replicates), int(seed), float(confidence)
+        if not 1 <= replicates <= 4096:
+            raise ValueError(f"replicates must be between 1 and 4096 (got {replicates})")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an unsigned 64-bit integer (got {seed})")
+        if not 0.0 < confidence < 1.0:
+            raise ValueError(f"confidence must be inside (0, 1) (got {confidence})")
+        return replicates, seed, confidence
+
+    def spatial_bootstrap(self, mu=None, mv=None, ids=None, window=None, stride=1, replicates=200, seed=0, confidence=0.95,
+                          want_replicates=False, want_weights=False, check=True):
+        """Bootstrap confidence bands over viewers (include/vet.h: vet_bootstrap_entropy): the audience is resampled with
+        replacement ``replicates`` times — the same resample for every row: a viewer's trajectory stays together — and every row
+        of ``spatial_windowed`` (frames [r * stride, r * stride + window), ``window=None`` the whole video) is recomputed for each
+        resample.  Returns dict(summary[4,R] (mean, sd, lo, hi over the finite replicates), replicates[R,B]|None,
+        weights[R,B,n0]|None (lattice 0's replicate histograms, plain values), valid[R], code), R = (T - window) // stride + 1.
+        A replicate whose drawn viewers have no sample in the row is NaN — data, never an error; ``code`` is VET_OK or
+        VET_ERR_RANGE."""
+        replicates, seed, confidence = self._bootstrap_scalars(replicates, seed, confidence)
+        want = {k for k, on in (("replicates", want_replicates), ("weights", want_weights)) if on}
+        return self._row_host("spatial_bootstrap", mu, mv, ids, window, stride, want, check,
+                              extra=(replicates, seed, confidence), extra_dims={"B": replicates})
+
+    def bootstrap_counts(self, n_users: int, replicates: int, seed: int = 0) -> np.ndarray:
+        """The bootstrap's draw alone, computed on the device: counts[replicates, n_users] uint16, how often replicate b picked
+        viewer u (include/vet.h: vet_bootstrap_counts_host)."""
+        replicates, seed, _ = self._bootstrap_scalars(replicates, seed, 0.5)
+        out = np.empty((replicates, int(n_users)), dtype=np.uint16)
+        _check(self.lib, self.lib.vet_bootstrap_counts_host(self.handle, int(n_users), replicates, seed, _ptr(out)))
+        return out
 
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
@@ -836,6 +887,15 @@ class Plan:
         vet_crowd_divergence_ids)."""
         self._row_device("spatial_crowd_divergence", d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride), d_div, (d_rows, d_samples, d_status), stream)
+
+    def spatial_bootstrap_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
+                                 replicates: int, seed: int, confidence: float, d_summary: int, d_replicates: int = 0,
+                                 d_weights: int = 0, d_valid: int = 0, d_status: int = 0, stream=None, d_ids: int = 0):
+        """d_summary [4][R]; d_replicates [R][B]; d_weights [R][B][n0]; d_valid [R] (include/vet.h: vet_bootstrap_entropy;
+        ``d_ids``: vet_bootstrap_entropy_ids)."""
+        self._row_device("spatial_bootstrap", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, replicates, seed, float(confidence)), d_summary,
+                         (d_replicates, d_weights, d_valid, d_status), stream)
 
     def spatial_window_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                          max_lag: int, d_div: int, d_samples: int = 0, d_status: int = 0, stream=None,

@@ -338,5 +338,56 @@ class _EntropyAnalyzerBase:
         df.attrs["lag_frames"] = [stride * l for l in range(1, L + 1)]
         return df
 
+    @staticmethod
+    def _bootstrap_args(replicates, confidence, seed):
+        """(replicates, confidence, seed) checked; ``ValueError`` unless 1 <= replicates <= 4096 (an integer), 0 < confidence < 1
+        and seed is an integer in [0, 2^64)."""
+        for name, v in (("replicates", replicates), ("seed", seed)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer (got {v!r})")
+        if not 1 <= int(replicates) <= 4096:
+            raise ValueError(f"replicates must be between 1 and 4096 (got {replicates})")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed must be an unsigned 64-bit integer (got {seed})")
+        if isinstance(confidence, bool) or not isinstance(confidence, (int, float, np.integer, np.floating)) \
+                or not 0.0 < float(confidence) < 1.0:
+            raise ValueError(f"confidence must be a number inside (0, 1) (got {confidence!r})")
+        return int(replicates), float(confidence), int(seed)
+
+    @staticmethod
+    def _bootstrap_frame(times, window: int, stride: int, point: dict, res: dict, replicates: int, seed: int,
+                         confidence: float) -> pd.DataFrame:
+        """The bootstrap as a DataFrame, one row per window: ``entropy`` / ``samples`` of the point estimate (``point``: the
+        ``spatial_windowed`` result) beside ``mean``, ``sd``, ``lo``, ``hi`` and ``valid`` of the replicates; where ``res`` holds
+        the replicates, the ``replicates`` cell of row r is the [B] view ``res["replicates"][r]`` (no copy)."""
+        R = len(point["entropy"])
+        first = np.arange(R, dtype=np.int64) * stride
+        times = np.asarray(times)
+        mean, sd, lo, hi = res["summary"]
+        cols = {"time": times[first], "time_end": times[first + window - 1], "entropy": point["entropy"],
+                "samples": point["samples"], "mean": mean, "sd": sd, "lo": lo, "hi": hi, "valid": res["valid"]}
+        if res.get("replicates") is not None:
+            r_col = np.empty(R, dtype=object)
+            for r in range(R):
+                r_col[r] = res["replicates"][r]
+            cols["replicates"] = r_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(replicates=replicates, seed=seed, confidence=confidence)
+        return df
+
+    def _entropy_bootstrap(self, window, stride, replicates, confidence, seed, keep_replicates) -> pd.DataFrame:
+        """``compute_entropy_bootstrap`` of the two spatial analyzers: the arguments are checked before the engine is touched;
+        the point estimate is the existing ``spatial_windowed`` call (rows without a sample are NaN here, not an error)."""
+        times, names, point_call = self._row_call("spatial_windowed")
+        _, _, boot_call = self._row_call("spatial_bootstrap")
+        window, stride = self._window_args(window, stride, len(times))
+        replicates, confidence, seed = self._bootstrap_args(replicates, confidence, seed)
+        point = point_call(window=window, stride=stride, check=False)
+        if point["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        res = boot_call(window=window, stride=stride, replicates=replicates, seed=seed, confidence=confidence,
+                        want_replicates=bool(keep_replicates))
+        return self._bootstrap_frame(times, window, stride, point, res, replicates, seed, confidence)
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

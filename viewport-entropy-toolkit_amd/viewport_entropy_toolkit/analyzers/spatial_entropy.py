@@ -173,5 +173,24 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         res = call(window=window, stride=stride)
         return self._crowd_frame(names, times, window, stride, res)
 
+    def compute_entropy_bootstrap(self, window: int = 1, stride: int = 1, replicates: int = 200, confidence: float = 0.95,
+                                  seed: int = 0, keep_replicates: bool = False) -> pd.DataFrame:
+        """Is a dip attention converging, or too few viewers: bootstrap confidence bands for the per-frame / windowed entropy.
+
+        Viewers are the independent unit, so the audience is resampled with replacement ``replicates`` times (the cluster
+        bootstrap: the same resample for every window, a viewer's whole trajectory stays together; the draw is a counter-based
+        generator on ``seed``, include/vet.h) and every window is recomputed for each resample on the GPU.  ``window=1,
+        stride=1`` is the per-frame series.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end`` (of
+        the window's first / last frame), ``entropy`` and ``samples`` (the point estimate: ``compute_windowed_entropy``'s values,
+        NaN with ``samples`` 0 for a window without a sample), ``mean`` and ``sd`` (ddof = 1) of the finite replicates, ``lo`` /
+        ``hi`` (their quantiles (1 - confidence) / 2 and 1 - (1 - confidence) / 2, linear interpolation) and ``valid`` (how many
+        replicates are finite: a resample whose viewers have no sample in the window is NaN).  ``keep_replicates`` adds
+        ``replicates``, a [B] view into the one result array per row.  ``attrs`` holds ``replicates``, ``seed`` and
+        ``confidence``.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an
+        illegal ``window`` / ``stride`` / ``replicates`` (1 .. 4096) / ``confidence`` (inside (0, 1)) / ``seed``."""
+        return self._entropy_bootstrap(window, stride, replicates, confidence, seed, keep_replicates)
+
     def _frame_present(self):
         return self._present
