@@ -58,7 +58,8 @@ extern "C" {
                           then the vet_window_divergence* entry points (a lag band of Jensen-Shannon distances between windows) and the
                           vet_crowd_divergence* entry points (each viewer's Kullback-Leibler divergence from the pooled crowd), and
                           then the vet_bootstrap_entropy* entry points (confidence bands from viewers resampled with replacement)
-                          and vet_bootstrap_counts_host */
+                          and vet_bootstrap_counts_host, and then the vet_group_divergence* entry points (a permutation test
+                          of the attention divergence between two audiences) and vet_group_labels_host */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -124,6 +125,10 @@ int vet_test_crowd_divergence_chunk_rows(vet_ctx *ctx, int rows);
  * of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every
  * launch.  Results are bit-identical whatever the value. */
 int vet_test_bootstrap_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes vet_group_divergence* build the viewers' histograms `rows` rows at a time instead
+ * of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every
+ * launch.  Results are bit-identical whatever the value. */
+int vet_test_group_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -624,6 +629,89 @@ int vet_bootstrap_entropy_host(vet_plan *plan, const double *h_mu, const double 
 /* The draw alone: runs k_bootstrap_counts on the plan's context and downloads c[replicates][n_users], so that the draw can be
  * pinned on its own.  Synchronous.  Errors as above (replicates, n_users). */
 int vet_bootstrap_counts_host(vet_plan *plan, int n_users, int replicates, uint64_t seed, uint16_t *h_counts);
+
+/* ---- two-audience permutation test of attention divergence -------------------------------------------
+ * Headset against desktop, sound against mute, first viewing against second: do two groups of viewers look at different places,
+ * in which segments, and by more than a random split of the same viewers would produce?  Viewers are the independent unit, so
+ * the null distribution comes from relabelling viewers, P times in one call.
+ * - Groups.  groups[U], int8, HOST memory in every entry, read and validated before the call returns: 0 = audience A, 1 = audience
+ *   B, -1 = excluded.  U_A, U_B >= 1.  The included viewers in ascending viewer order are v_0 ... v_{N-1}, N = U_A + U_B.
+ * - Rows.  Rows are vet_spatial_entropy_windowed's.  Row r covers frames [r*stride, r*stride + window).  window = n_frames is the
+ *   single whole-video row.
+ * - Statistic of one labelling, per lattice.  A = sum_{u in A} h_u and B = sum_{u in B} h_u, h_u viewer u's own row histogram
+ *   (vet_user_entropy's d_weights), the viewers added in ascending order, in blocks of four, into one accumulator, exactly as
+ *   k_bootstrap_gemm sums.  D_k = S(A + B) - (W_A*S(A) + W_B*S(B)) / (W_A + W_B), S(h) = -sum_keys (h_t / W) log2(h_t / W) and W as
+ *   in vet_window_divergence; D = the mean over the lattices, in bits.  In reference terms: three compute_spatial_entropy calls
+ *   (naive plans: compute_naive_spatial_entropy), on group A's present samples of the row, on group B's, and on a single dict
+ *   holding both, each group entered frame-major, then by ascending viewer, A before B in the pooled dict.  D is NaN where either
+ *   group has no sample in the row.  That is data, not an error.  D is NaN exactly where one of the reference's three entropies is:
+ *   a key whose sum is 0.0 (the bootstrap's zero-key rule, applied to the members of each group and to all included viewers for
+ *   the pooled term), or a proportion that underflows to 0.  B is never computed as pooled - A: the subtraction would leave
+ *   rounding residue on tiles that are exactly 0, and a tile is a key iff its sum is > 0.
+ * - Labellings.  Labelling 0 is the observed `groups`; labellings 1 ... P are permutations, P = permutations in [1, 4096].  For
+ *   permutation b (0-based) and included index i, all in unsigned 64-bit arithmetic mod 2^64:
+ *     z = seed + (b*N + i + 1) * 0x9E3779B97F4A7C15
+ *     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *     key = (z >> 16 << 16) | i
+ *   The U_A included viewers with the smallest keys are audience A, the rest B; excluded viewers stay excluded.  Permutation b does
+ *   not depend on P.  One permutation serves every row and every lattice: a viewer's trajectory stays together.  N <= 16384 (one
+ *   permutation's keys are ranked in LDS).
+ * - Summary per row, over the m finite values of the row's P permutation statistics: observed = D of labelling 0;
+ *   p_value = (1 + #{finite null >= observed}) / (1 + m); null_mean; null_crit = the quantile `confidence` by the bootstrap's rule
+ *   (linear interpolation between order statistics at position q*(m - 1)); valid = m; p_adjusted, the max-statistic family-wise
+ *   correction over the rows of the call: maxnull[b] = the largest finite null value of permutation b over all rows, M = the
+ *   permutations that have one, p_adjusted[r] = (1 + #{b: maxnull[b] >= observed[r]}) / (1 + M).  observed NaN: p_value and
+ *   p_adjusted NaN.  m = 0: null_mean and null_crit NaN.
+ * - Ties.  >= is taken on the stored doubles.  Labelling 0 goes through the same kernel and the same operand order as the
+ *   permutations: a permutation that reproduces the observed partition reproduces its bits, so ties are exact.
+ * - Bits.  A labelling's D depends on the plan, the window, the row's frames and the labelling's two viewer sets only.  It does
+ *   not depend on P, stride, the number of rows, the row chunk or the entry point.
+ *   d_summary [5][R]      observed, p_value, p_adjusted, null_mean, null_crit
+ *   d_null    [R][P]      the permutation statistics                                                              (nullable)
+ *   d_weights [R][2][n0]  lattice 0's histograms of the observed A and B: PLAIN VALUES, +0.0 = no weight        (nullable)
+ *   d_samples [2][R]      the present samples of the observed A and B in the row                                 (nullable)
+ *   d_valid   [R]         m                                                                                       (nullable)
+ *   d_status  [2]         {bad, unused}; the call ADDS to [0], the caller zeroes                                  (nullable)
+ * Stages; everything lives in the context's grow-only workspace, no allocation in steady state:
+ *   1 k_user_dirs, unchanged;
+ *   2 k_group_labels: one workgroup per permutation computes the keys, sorts them in LDS (bitonic) and writes labels[P+1][U] u8
+ *     (0, 1, 255 = excluded), row 0 the observed groups; no atomics;
+ *   3 per lattice and chunk of rows (as many as fit 256 MB of histograms, at least one): k_user_hist_w/_c, unchanged, with the
+ *     per-(viewer, row) samples; on weighted lattices k_bootstrap_zero_keys, unchanged;
+ *   4 k_group_gemm: one workgroup per (row, 8 labellings), 4 waves.  Rows 0-7 of the 16 x 16 x 4 FP64 MFMA tile hold the A sums of
+ *     the eight labellings, rows 8-15 their B sums: the A operand is labels == 0 for i < 8 and labels == 1 for i >= 8, the B
+ *     operand hist[u][t] is loaded once and serves both.  K loop as k_bootstrap_gemm: ascending blocks of four viewers, one
+ *     accumulator per column block, no split-K, no atomics.  The 16 x n block stays in LDS; then per labelling W and S over A,
+ *     over B and over a_t + b_t, the zero-key rule, D_k.  Lattice 0 stores D_0 / K, lattice k adds its own, in lattice order.
+ *     Speed only, no effect on a value: the edges are predicated through the mask operand (loads without branches), the kernel
+ *     asks for a two-waves-per-SIMD register budget (accumulators stay in VGPRs), and the one-dimensional launch is remapped so
+ *     that the workgroups of one row share an XCD's L2;
+ *   5 k_group_samples; k_group_maxnull: one thread per permutation walks the rows of null[R][P]; k_group_summary: one workgroup per
+ *     row takes the counts, the mean and sorts the finite values in LDS for the quantile.
+ * VET_ERR_INVALID (before anything is staged, launched or allocated): the windowed calls'; a group value outside {-1, 0, 1}; an
+ * empty group; permutations outside [1, 4096]; confidence outside (0, 1).  VET_ERR_UNSUPPORTED (likewise): N > 16384; a lattice of
+ * more than 1276 tiles (the 16 x n FP64 block must fit the 160 KB LDS); R * n_users >= 2^31, n_frames > 65535 * 64,
+ * vet_user_entropy's limits on the plan.  Profile ids: as the bootstrap's, k_group_gemm to k_transition, k_group_labels and stage
+ * 5 to k_finalize.  Asynchronous on `stream` like vet_spatial_entropy (`groups` is consumed before the call returns). */
+int vet_group_divergence(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                         const int8_t *groups, int permutations, uint64_t seed, double confidence, double *d_summary,
+                         double *d_null, double *d_weights, int32_t *d_samples, int32_t *d_valid, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_group_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                             const int8_t *groups, int permutations, uint64_t seed, double confidence, double *d_summary,
+                             double *d_null, double *d_weights, int32_t *d_samples, int32_t *d_valid, int32_t *d_status,
+                             void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa; h_null,
+ * h_weights, h_samples and h_valid may be NULL. */
+int vet_group_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                              int n_frames, int window, int stride, const int8_t *groups, int permutations, uint64_t seed,
+                              double confidence, double *h_summary, double *h_null, double *h_weights, int32_t *h_samples,
+                              int32_t *h_valid);
+/* The draw alone: runs k_group_labels on the plan's context and downloads labels[permutations + 1][n_users] (0 = A, 1 = B, 255 =
+ * excluded; row 0 the observed groups), so that the draw can be pinned on its own.  Synchronous.  Errors as above (groups,
+ * permutations, N). */
+int vet_group_labels_host(vet_plan *plan, int n_users, const int8_t *groups, int permutations, uint64_t seed, uint8_t *h_labels);
 
 /* ---- sliding-window transition entropy: the transitions of a window of frame pairs pooled ----------
  * A video of T frames has P = T - 1 frame pairs; pair f is (frame f, frame f + 1).  For 1 <= window <= P and stride >= 1

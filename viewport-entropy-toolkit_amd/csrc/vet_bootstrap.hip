@@ -24,6 +24,7 @@
 #include "vet_common.hpp"
 #include "vet_user_dirs.hpp"
 #include "vet_row_hist.hpp"
+#include "vet_rank.hpp"
 
 #include <algorithm>
 
@@ -249,7 +250,7 @@ __global__ __launch_bounds__(256) void k_bootstrap_gemm(const BootGemmParams p) 
 
 // ------------------------------------------------------------------------------------------
 // k_bootstrap_summary — stage 5.  One workgroup per row: rep[r][0 .. B) to LDS, everything that is not finite replaced by +inf
-// (so are the slots up to the next power of two), a bitonic sort, then wave 0 over the m finite values in ascending order:
+// (so are the slots up to the next power of two), a bitonic sort (vet_rank.hpp), then wave 0 over the m finite values in ascending order:
 // mean and the two-pass sd (ddof = 1) in lane order + wave_sum, and the quantiles q by linear interpolation between the order
 // statistics at position q (m - 1): x[i] + (x[i + 1] - x[i]) g.  m = 0: NaN for all four; m = 1: sd NaN.
 // LDS: f64 [4096] static.
@@ -262,13 +263,6 @@ struct BootSummaryParams {
     double* summary;             // [4][R] mean, sd, lo, hi
     int32_t* valid;              // [R] or null
 };
-
-__device__ __forceinline__ double boot_quantile(const double* x, int m, double q) {
-    const double pos = q * (double)(m - 1);
-    const int i = (int)floor(pos);
-    if (i >= m - 1) return x[m - 1];
-    return x[i] + (x[i + 1] - x[i]) * (pos - (double)i);
-}
 
 __global__ __launch_bounds__(256) void k_bootstrap_summary(const BootSummaryParams p) {
     __shared__ double x[BOOT_MAX_B];
@@ -289,18 +283,7 @@ __global__ __launch_bounds__(256) void k_bootstrap_summary(const BootSummaryPara
         x[i] = v;
     }
     if (mine) atomicAdd(&m_s, mine);
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int i = tid; i < P; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const double a = x[i], b = x[l];
-                    if ((a > b) == ((i & k) == 0)) { x[i] = b; x[l] = a; }
-                }
-            }
-        }
-    __syncthreads();
+    lds_bitonic_sort(x, P);
     if (wave_id() != 0) return;
     const int m = m_s;
     double s = 0.0;
@@ -317,8 +300,8 @@ __global__ __launch_bounds__(256) void k_bootstrap_summary(const BootSummaryPara
         const double nan = __builtin_nan("");
         p.summary[0 * p.R + r] = m ? mean : nan;
         p.summary[1 * p.R + r] = m >= 2 ? sqrt(ss / (double)(m - 1)) : nan;
-        p.summary[2 * p.R + r] = m ? boot_quantile(x, m, p.q_lo) : nan;
-        p.summary[3 * p.R + r] = m ? boot_quantile(x, m, p.q_hi) : nan;
+        p.summary[2 * p.R + r] = m ? lerp_quantile(x, m, p.q_lo) : nan;
+        p.summary[3 * p.R + r] = m ? lerp_quantile(x, m, p.q_hi) : nan;
         if (p.valid) p.valid[r] = m;
     }
 }
@@ -398,13 +381,8 @@ int launch_bootstrap(vet_plan* pl, const double* d_mu, const double* d_mv, const
             if (rc) return rc;
             const int zw = (L.n + 31) / 32;
             if (!counting) {
-                vet::BootZeroParams q{};
-                q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
-                q.window = window; q.stride = stride; q.r0 = r0; q.hist = hist; q.flag = flag; q.zmask = zmask; q.zflag = zflag;
-                q.zw = zw;
-                ProfScope ps(c, s, KID_FINALIZE);
-                hipLaunchKernelGGL(vet::k_bootstrap_zero_keys, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)zw * 4, s, q);
-                HIP_TRY(hipGetLastError());
+                rc = zero_keys_run(pl, k, dirs, U, T, window, stride, r0, cr, hist, flag, zmask, zflag, s);
+                if (rc) return rc;
             }
             {   // ---- stage 4, charged to k_transition: the one profile id the call does not use otherwise, so that the product
                 // can be told from the histogram walk
@@ -434,6 +412,18 @@ int launch_bootstrap(vet_plan* pl, const double* d_mu, const double* d_mv, const
 }
 
 }  // namespace
+
+int zero_keys_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int window, int stride, long r0, long cr, const double* hist,
+                  const int32_t* flag, uint32_t* zmask, int32_t* zflag, hipStream_t s) {
+    vet::BootZeroParams q{};
+    q.dirs = dirs; q.T = T; q.U = U; q.alias = pl->d_alias; q.X = exact_rows_arg(pl, k);
+    q.window = window; q.stride = stride; q.r0 = r0; q.hist = hist; q.flag = flag; q.zmask = zmask; q.zflag = zflag;
+    q.zw = (pl->lat[k].n + 31) / 32;
+    ProfScope ps(pl->ctx, s, KID_FINALIZE);
+    hipLaunchKernelGGL(vet::k_bootstrap_zero_keys, dim3((unsigned)(cr * U)), dim3(vet::WAVE), (size_t)q.zw * 4, s, q);
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
 
 int check_bootstrap_args(const vet_plan* pl, int U, int replicates, double confidence) {
     if (replicates < 1 || replicates > vet::BOOT_MAX_B)

@@ -14,6 +14,8 @@
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
+//   vet_group.hip       the two-audience permutation test (labellings ranked in LDS, an FP64 MFMA contraction of 0/1 group masks with
+//                       the per-viewer histograms, the Jensen-Shannon epilogue, the per-row summary) and its launch logic
 //   vet_heatmap.hip     the heatmap kernels (pixel -> tile / cell maps, palettes, fill, markers) and their launch logic
 //   vet_tiling.hip      the tiling kernels (arcs -> chords, splat, compose) and their launch logic
 //   vet_hostapi.hip     host-buffer entry points (one staged-run helper for the entropy entries, one block-download pipeline
@@ -127,6 +129,9 @@ struct Tuning {
     int bootstrap_chunk_rows = 0;   // vet_test_bootstrap_chunk_rows (no environment variable): rows per histogram chunk of
                                 // vet_bootstrap_entropy* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_bootstrap_gpu.py)
+    int group_chunk_rows = 0;       // vet_test_group_chunk_rows (no environment variable): rows per histogram chunk of
+                                // vet_group_divergence* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_group_divergence_gpu.py)
     void from_environment();
 };
 
@@ -404,6 +409,7 @@ int user_divergence_set_attrs(vet_ctx* c);
 int window_divergence_set_attrs(vet_ctx* c);
 int crowd_set_attrs(vet_ctx* c);
 int bootstrap_set_attrs(vet_ctx* c);
+int group_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -447,6 +453,16 @@ int user_hist_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int wi
 // vet_bootstrap.hip: what vet_bootstrap_entropy* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before
 // anything is staged, allocated or launched — after check_window_args
 int check_bootstrap_args(const vet_plan* pl, int U, int replicates, double confidence);
+
+// vet_bootstrap.hip, shared with vet_group.hip: k_bootstrap_zero_keys on the chunk of a weighted lattice k behind user_hist_run — for
+// the flagged (row, viewer) slots the tiles that are keys of the viewer with the value 0.0, zmask [cr][U][ceil(n_k / 32)] and
+// zflag [cr][U].  Charged to k_finalize.
+int zero_keys_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int window, int stride, long r0, long cr, const double* hist,
+                  const int32_t* flag, uint32_t* zmask, int32_t* zflag, hipStream_t s);
+
+// vet_group.hip: what vet_group_divergence* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before
+// anything is staged, allocated or launched — after check_window_args.  groups is host memory [U].
+int check_group_args(const vet_plan* pl, int U, const int8_t* groups, int permutations, double confidence);
 
 // vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched

@@ -590,6 +590,42 @@ int vet_bootstrap_entropy_host(vet_plan* pl, const double* h_mu, const double* h
     return run.finish_rows_are_data();
 }
 
+// The two-audience permutation test with host buffers (include/vet.h): the summary [5][R], and where wanted the null distribution
+// [R][P], labelling 0's two histograms of lattice 0 [R][2][n_0], the observed groups' samples [2][R] and the finite null values per
+// row.  Five outputs on four slots: samples and valid share the count slot.  Rows in which a group has no sample are data (NaN):
+// only VET_ERR_RANGE is decoded from the status words.
+int vet_group_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                              int stride, const int8_t* groups, int permutations, uint64_t seed, double confidence, double* h_summary,
+                              double* h_null, double* h_weights, int32_t* h_samples, int32_t* h_valid) {
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, h_summary, h_mu, h_mv, h_ids, &R);
+    if (!rc) rc = check_group_args(pl, U, groups, permutations, confidence);
+    if (rc) return rc;
+    StagedRun run;
+    rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
+    if (rc) return rc;
+    vet_ctx* c = run.c;
+    double *d_summary = nullptr, *d_null = nullptr, *d_weights = nullptr;
+    int32_t* d_counts = nullptr;                                   // samples [2][R] | valid [R]
+    const size_t null_bytes = (size_t)R * permutations * 8, w_bytes = (size_t)R * 2 * pl->lat[0].n * 8;
+    POOL(SLOT_ENTROPY, (size_t)5 * R * 8, d_summary);
+    if (h_null) POOL(SLOT_OUT0, null_bytes, d_null);
+    if (h_weights) POOL(SLOT_OUT1, w_bytes, d_weights);
+    POOL(SLOT_COUNT, (size_t)3 * R * 4, d_counts);
+    rc = run.clear_status();
+    if (rc) return rc;
+    rc = launch_rows(run, vet_group_divergence_ids, vet_group_divergence, pl, U, T, window, stride, groups, permutations, seed,
+                     confidence, d_summary, d_null, d_weights, h_samples ? d_counts : nullptr, h_valid ? d_counts + 2 * R : nullptr,
+                     run.status, run.s);
+    if (rc) return run.drain(rc);
+    HIP_TRY(hipMemcpyAsync(h_summary, d_summary, (size_t)5 * R * 8, hipMemcpyDeviceToHost, run.s));
+    if (h_null) HIP_TRY(hipMemcpyAsync(h_null, d_null, null_bytes, hipMemcpyDeviceToHost, run.s));
+    if (h_weights) HIP_TRY(hipMemcpyAsync(h_weights, d_weights, w_bytes, hipMemcpyDeviceToHost, run.s));
+    if (h_samples) HIP_TRY(hipMemcpyAsync(h_samples, d_counts, (size_t)2 * R * 4, hipMemcpyDeviceToHost, run.s));
+    if (h_valid) HIP_TRY(hipMemcpyAsync(h_valid, d_counts + 2 * R, (size_t)R * 4, hipMemcpyDeviceToHost, run.s));
+    return run.finish_rows_are_data();
+}
+
 // Window-to-window divergence with host buffers (include/vet.h): vet_window_rows rows of max_lag lags.  Rows without a sample are
 // data (NaN across their band): only VET_ERR_RANGE is decoded from the status words.
 int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,

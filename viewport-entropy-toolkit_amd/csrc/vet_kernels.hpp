@@ -49,6 +49,16 @@
 //                                                               row calls' entropy epilogue per replicate
 //                                              k_bootstrap_summary   one workgroup per row: the finite replicates sorted in LDS ->
 //                                                               mean, sd and the two quantiles
+//   vet_group.hip       (in the unit)          k_group_labels   one workgroup per permutation: the keys of the included viewers sorted in
+//                                                               LDS -> labels u8 [P + 1][U] (row 0 the observed groups)
+//                                              k_group_gemm     one workgroup per (row, 8 labellings): 0/1 group masks x per-viewer
+//                                                               histograms on the FP64 matrix unit, A sums in rows 0-7 and B sums
+//                                                               in rows 8-15 of the tile, into LDS; then W and S of A, B and A + B
+//                                                               and the Jensen-Shannon divergence per labelling
+//                                              k_group_samples  the observed audiences' present samples per row
+//                                              k_group_maxnull  one thread per permutation: its largest finite value over the rows
+//                                              k_group_summary  one workgroup per row: p-values, mean and the sorted quantile of the null
+//                       vet_rank.hpp           lds_bitonic_sort, lerp_quantile: shared by vet_bootstrap.hip and vet_group.hip
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

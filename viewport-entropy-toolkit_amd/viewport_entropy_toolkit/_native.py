@@ -84,6 +84,7 @@ SIGNATURES = {
     "vet_test_window_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_crowd_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_bootstrap_chunk_rows": (_I, [_P, _I]),
+    "vet_test_group_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -135,6 +136,10 @@ SIGNATURES = {
     "vet_bootstrap_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _U64, _D, _P, _P, _P, _P, _P, _P]),
     "vet_bootstrap_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _U64, _D, _P, _P, _P, _P]),
     "vet_bootstrap_counts_host": (_I, [_P, _I, _I, _U64, _P]),
+    "vet_group_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _U64, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_group_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _U64, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_group_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _U64, _D, _P, _P, _P, _P, _P]),
+    "vet_group_labels_host": (_I, [_P, _I, _P, _I, _U64, _P]),
     "vet_transition_entropy": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_transition_entropy_ids": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_spatial_entropy_batch": (_I, [_P, _I, _P, _P, _P]),
@@ -382,6 +387,11 @@ class Engine:
         not depend on it (include/vet.h: vet_test_bootstrap_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_bootstrap_chunk_rows(self.handle, int(rows)))
 
+    def test_group_chunk_rows(self, rows: int = 0):
+        """Test switch: the group divergence builds the viewers' histograms ``rows`` rows at a time (0: the default budget);
+        results do not depend on it (include/vet.h: vet_test_group_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_group_chunk_rows(self.handle, int(rows)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -428,10 +438,11 @@ class DeviceResult:
 
 
 _F64, _I32 = np.float64, np.int32
-# The eight row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
+# The nine row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
 # frame pairs, not frames; window=None is all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
-# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, B replicates, 3, 4.  A call's extra
-# scalars (max_lag; replicates, seed, confidence) follow stride in the C signatures; ``_row_host`` takes them as ``extra``.
+# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, B replicates, P permutations, 2, 3, 4,
+# 5.  A call's extra arguments (max_lag; replicates, seed, confidence; the host array groups, permutations, seed, confidence) follow
+# stride in the C signatures; ``_row_host`` takes them as ``extra``.
 _ROW_CALLS = {
     "spatial_windowed": ("vet_spatial_entropy_windowed", False, False, True,
                          (("entropy", "R", _F64, False), ("weights", "Rn", _F64, True), ("samples", "R", _I32, False))),
@@ -446,6 +457,9 @@ _ROW_CALLS = {
     "spatial_bootstrap": ("vet_bootstrap_entropy", False, True, False,
                           (("summary", "4R", _F64, False), ("replicates", "RB", _F64, True), ("weights", "RBn", _F64, True),
                            ("valid", "R", _I32, False))),
+    "spatial_group_divergence": ("vet_group_divergence", False, True, False,
+                                 (("summary", "5R", _F64, False), ("null", "RP", _F64, True), ("weights", "R2n", _F64, True),
+                                  ("samples", "2R", _I32, False), ("valid", "R", _I32, False))),
     "transition_windowed": ("vet_transition_entropy_windowed", True, False, True,
                             (("entropy", "R", _F64, False), ("srccount", "Rn", _I32, True), ("samples", "R", _I32, False))),
     "transition_per_user": ("vet_user_transition_entropy", True, True, False,
@@ -734,6 +748,59 @@ class Plan:
         _check(self.lib, self.lib.vet_bootstrap_counts_host(self.handle, int(n_users), replicates, seed, _ptr(out)))
         return out
 
+    @staticmethod
+    def _group_array(groups, n_users=None):
+        """``groups`` as the C entry takes it: int8 [U] of 0 (audience A), 1 (audience B), -1 (excluded), both audiences with a
+        viewer; ``ValueError`` otherwise."""
+        g = np.asarray(groups)
+        if g.ndim != 1 or g.size == 0 or g.dtype.kind not in "iu":
+            raise ValueError("groups must be a one-dimensional integer array: 0 = audience A, 1 = audience B, -1 = excluded")
+        if n_users is not None and g.size != n_users:
+            raise ValueError(f"groups has {g.size} entries for {n_users} users")
+        if not np.isin(g, (-1, 0, 1)).all():
+            raise ValueError("groups holds values outside {-1, 0, 1}")
+        if not (g == 0).any() or not (g == 1).any():
+            raise ValueError("both audiences need a viewer")
+        return np.ascontiguousarray(g, dtype=np.int8)
+
+    @staticmethod
+    def _group_scalars(permutations, seed, confidence):
+        """(permutations, seed, confidence) as the C entry takes them; ``ValueError`` outside [1, 4096], [0, 2^64) and (0, 1)."""
+        permutations, seed, confidence = int(permutations), int(seed), float(confidence)
+        if not 1 <= permutations <= 4096:
+            raise ValueError(f"permutations must be between 1 and 4096 (got {permutations})")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an unsigned 64-bit integer (got {seed})")
+        if not 0.0 < confidence < 1.0:
+            raise ValueError(f"confidence must be inside (0, 1) (got {confidence})")
+        return permutations, seed, confidence
+
+    def spatial_group_divergence(self, mu=None, mv=None, ids=None, groups=None, window=None, stride=1, permutations=999, seed=0,
+                                 confidence=0.95, want_null=False, want_weights=False, check=True):
+        """The two-audience permutation test (include/vet.h: vet_group_divergence): ``groups`` [U] is 0 (audience A), 1 (audience
+        B) or -1 (excluded); every row of ``spatial_windowed`` (frames [r * stride, r * stride + window), ``window=None`` the
+        whole video) gets the mass-weighted Jensen-Shannon divergence between the two audiences' pooled histograms, in bits, and
+        its place among ``permutations`` relabellings of the included viewers — the same relabelling for every row: a viewer's
+        trajectory stays together.  Returns dict(summary[5,R] (observed, p_value, p_adjusted, null_mean, null_crit),
+        null[R,P]|None, weights[R,2,n0]|None (lattice 0's histograms of A and B, plain values), samples[2,R], valid[R], code),
+        R = (T - window) // stride + 1.  A row in which an audience has no sample is NaN — data, never an error; ``code`` is
+        VET_OK or VET_ERR_RANGE."""
+        permutations, seed, confidence = self._group_scalars(permutations, seed, confidence)
+        first = ids if ids is not None else mu
+        g = self._group_array(groups, np.shape(first)[1] if np.ndim(first) == 2 else None)
+        want = {k for k, on in (("null", want_null), ("weights", want_weights)) if on}
+        return self._row_host("spatial_group_divergence", mu, mv, ids, window, stride, want, check,
+                              extra=(_ptr(g), permutations, seed, confidence), extra_dims={"P": permutations, "2": 2, "5": 5})
+
+    def group_labels(self, groups, permutations: int, seed: int = 0) -> np.ndarray:
+        """The permutation test's draw alone, computed on the device: labels[permutations + 1, U] uint8 (0 = A, 1 = B, 255 =
+        excluded); row 0 is ``groups`` itself, row b + 1 permutation b (include/vet.h: vet_group_labels_host)."""
+        permutations, seed, _ = self._group_scalars(permutations, seed, 0.5)
+        g = self._group_array(groups)
+        out = np.empty((permutations + 1, g.size), dtype=np.uint8)
+        _check(self.lib, self.lib.vet_group_labels_host(self.handle, int(g.size), _ptr(g), permutations, seed, _ptr(out)))
+        return out
+
     def transition(self, mu=None, mv=None, ids=None, want_pairs=True, want_srccount=False, check=True):
         """Returns dict(entropy[T-1], pairs[T-1,U,2]|None, srccount[T-1,n0]|None, common[T-1], code)."""
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
@@ -896,6 +963,17 @@ class Plan:
         self._row_device("spatial_bootstrap", d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, replicates, seed, float(confidence)), d_summary,
                          (d_replicates, d_weights, d_valid, d_status), stream)
+
+    def spatial_group_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, groups,
+                                        permutations: int, seed: int, confidence: float, d_summary: int, d_null: int = 0,
+                                        d_weights: int = 0, d_samples: int = 0, d_valid: int = 0, d_status: int = 0, stream=None,
+                                        d_ids: int = 0):
+        """``groups``: the host array [U]; d_summary [5][R]; d_null [R][P]; d_weights [R][2][n0]; d_samples [2][R]; d_valid [R]
+        (include/vet.h: vet_group_divergence; ``d_ids``: vet_group_divergence_ids)."""
+        g = self._group_array(groups, n_users)
+        self._row_device("spatial_group_divergence", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, g.ctypes.data, permutations, seed, float(confidence)), d_summary,
+                         (d_null, d_weights, d_samples, d_valid, d_status), stream)
 
     def spatial_window_divergence_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                          max_lag: int, d_div: int, d_samples: int = 0, d_status: int = 0, stream=None,

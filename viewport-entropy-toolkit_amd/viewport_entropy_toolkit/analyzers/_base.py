@@ -13,6 +13,7 @@ import os
 import time
 from datetime import datetime
 from pathlib import Path
+from collections.abc import Mapping
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -388,6 +389,75 @@ class _EntropyAnalyzerBase:
         res = boot_call(window=window, stride=stride, replicates=replicates, seed=seed, confidence=confidence,
                         want_replicates=bool(keep_replicates))
         return self._bootstrap_frame(times, window, stride, point, res, replicates, seed, confidence)
+
+    @staticmethod
+    def _group_labels(groups, names):
+        """(int8 [U] of 0 / 1 / -1 in the order of ``names``, (label A, label B)) from ``groups``: a sequence aligned with
+        ``names`` or a mapping from user name to label (a user it does not name is excluded).  ``None`` / NaN is excluded; there
+        must be exactly two distinct other labels, in sorted order the first is audience A.  ``ValueError`` otherwise."""
+        names = list(names)
+        if isinstance(groups, Mapping):
+            unknown = [k for k in groups if k not in set(names)]
+            if unknown:
+                raise ValueError(f"groups names users that are not loaded: {unknown[:5]}")
+            labels = [groups.get(name) for name in names]
+        else:
+            if groups is None or isinstance(groups, (str, bytes)) or not hasattr(groups, "__len__"):
+                raise ValueError("groups must be a sequence aligned with the users, or a mapping from user name to label")
+            labels = list(groups)
+            if len(labels) != len(names):
+                raise ValueError(f"groups has {len(labels)} entries for {len(names)} users")
+
+        def missing(v):
+            return v is None or (isinstance(v, (float, np.floating)) and np.isnan(v))
+
+        try:
+            distinct = sorted({v for v in labels if not missing(v)})
+        except TypeError:
+            raise ValueError("the group labels cannot be ordered (mixed types)")
+        if len(distinct) != 2:
+            raise ValueError(f"need exactly two distinct group labels (got {distinct[:5]})")
+        code = np.array([-1 if missing(v) else distinct.index(v) for v in labels], dtype=np.int8)
+        return code, (distinct[0], distinct[1])
+
+    @staticmethod
+    def _group_frame(times, names, window: int, stride: int, code, labels, res: dict, permutations: int, seed: int,
+                     confidence: float) -> pd.DataFrame:
+        """The permutation test as a DataFrame, one row per window; where ``res`` holds the null distribution, the ``null`` cell
+        of row r is the [P] view ``res["null"][r]`` (no copy)."""
+        observed, p_value, p_adjusted, null_mean, null_crit = res["summary"]
+        R = len(observed)
+        first = np.arange(R, dtype=np.int64) * stride
+        times = np.asarray(times)
+        cols = {"time": times[first], "time_end": times[first + window - 1], "samples_a": res["samples"][0],
+                "samples_b": res["samples"][1], "divergence": observed, "p_value": p_value, "p_adjusted": p_adjusted,
+                "null_mean": null_mean, "null_crit": null_crit, "valid": res["valid"]}
+        if res.get("null") is not None:
+            n_col = np.empty(R, dtype=object)
+            for r in range(R):
+                n_col[r] = res["null"][r]
+            cols["null"] = n_col
+        df = pd.DataFrame(cols)
+        names = list(names)
+        df.attrs.update(groups=labels, sizes=(int((code == 0).sum()), int((code == 1).sum())),
+                        users=([n for n, c in zip(names, code) if c == 0], [n for n, c in zip(names, code) if c == 1]),
+                        permutations=permutations, seed=seed, confidence=confidence)
+        return df
+
+    def _group_divergence(self, groups, window, stride, permutations, confidence, seed, keep_null) -> pd.DataFrame:
+        """``compute_group_divergence`` of the two spatial analyzers: the arguments are checked before the engine is touched."""
+        times, names, call = self._row_call("spatial_group_divergence")
+        code, labels = self._group_labels(groups, names)
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        try:
+            permutations, confidence, seed = self._bootstrap_args(permutations, confidence, seed)
+        except ValueError as e:
+            raise ValueError(str(e).replace("replicates", "permutations"))
+        res = call(groups=code, window=window, stride=stride, permutations=permutations, seed=seed, confidence=confidence,
+                   want_null=bool(keep_null), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._group_frame(times, names, window, stride, code, labels, res, permutations, seed, confidence)
 
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError

@@ -192,5 +192,27 @@ class SpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         illegal ``window`` / ``stride`` / ``replicates`` (1 .. 4096) / ``confidence`` (inside (0, 1)) / ``seed``."""
         return self._entropy_bootstrap(window, stride, replicates, confidence, seed, keep_replicates)
 
+    def compute_group_divergence(self, groups, window: Optional[int] = None, stride: int = 1, permutations: int = 999,
+                                 confidence: float = 0.95, seed: int = 0, keep_null: bool = False) -> pd.DataFrame:
+        """Do two audiences look at different places, in which segments, and by more than chance: a permutation test of the
+        attention divergence between two groups of viewers.
+
+        ``groups`` is a sequence aligned with the analyzer's user order, or a mapping from user name to label.  There must be
+        exactly two distinct labels; in sorted order the first is audience A.  ``None`` / NaN (or a user the mapping does not
+        name) is excluded.  Every window (``window=None``: the whole video as one row) gets the mass-weighted Jensen-Shannon
+        divergence, in bits, between the pooled histograms of the two audiences, and the same statistic for ``permutations``
+        relabellings of the included viewers that keep the group sizes (the same relabelling for every window: a viewer's
+        trajectory stays together; the draw is a counter-based generator on ``seed``, include/vet.h), all on the GPU.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end``,
+        ``samples_a`` / ``samples_b`` (present samples of each audience), ``divergence`` (NaN where an audience has no sample),
+        ``p_value`` ((1 + relabellings at least as divergent) / (1 + finite relabellings)), ``p_adjusted`` (the max-statistic
+        family-wise correction over the windows of the call), ``null_mean``, ``null_crit`` (the ``confidence`` quantile of the
+        null, linear interpolation) and ``valid`` (finite relabellings).  ``keep_null`` adds ``null``, a [P] view into the one
+        result array per row.  ``attrs`` holds ``groups`` (the two labels), ``sizes``, ``users``, ``permutations``, ``seed`` and
+        ``confidence``.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for
+        illegal ``groups`` / ``window`` / ``stride`` / ``permutations`` (1 .. 4096) / ``confidence`` (inside (0, 1)) / ``seed``."""
+        return self._group_divergence(groups, window, stride, permutations, confidence, seed, keep_null)
+
     def _frame_present(self):
         return self._present
