@@ -127,11 +127,20 @@ const void* lut_kernel_fused(bool il, bool occ8, bool dedup, bool narrow = false
 
 // nb > 0: the fixed-trip kernels of capped rows of nb blocks (one class-dealt integer lattice, 8 workgroups per CU);
 // rec32: their instantiations over the 4-byte direction record (with the set of distinct rows only)
+// Buckets (log2) of the bucket-ordered row lists of the compact record's kernels (k_spatial_lut<LB>): on config 3, 128, 256 and
+// 512 buckets measured within 0.6 % of each other and 1.2-1.7 % ahead of the arrival order, 64 and 1 024 half a percent ahead
+// (profiles/frame_group/components.txt).
+constexpr int kLutBucketLog2 = 8;
+
+// bucketed: the compact record's kernel with bucket-ordered row lists (one video, one frame per workgroup, one chunk of users)
 template <bool FROM_IDS>
-const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false, int nb = 0, bool rec32 = false) {
+const void* lut_kernel(bool il, bool occ8, bool dedup, bool fpt = false, int nb = 0, bool rec32 = false, bool bucketed = false) {
     if (nb) {
-        if (!il || !occ8 || fpt || (rec32 && !dedup)) return nullptr;
-#define VET_PICKR(N) if (rec32 && nb == N) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, true, false, false, N, true>
+        if (!il || !occ8 || fpt || (rec32 && !dedup) || (bucketed && !rec32)) return nullptr;
+#define VET_PICKR(N)                                                                                                              \
+    if (rec32 && nb == N)                                                                                                         \
+        return bucketed ? (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, true, false, false, N, true, kLutBucketLog2>   \
+                        : (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, true, false, false, N, true>
         VET_PICKR(1); VET_PICKR(2); VET_PICKR(3);
 #undef VET_PICKR
 #define VET_PICKC(N, D) if (nb == N && dedup == D) return (const void*)vet::k_spatial_lut<FROM_IDS, 2, true, true, D, false, false, N>
@@ -381,7 +390,7 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
     int blocks = blocks_batch;
     const int threads = 256;     // __launch_bounds__(256); the FP table's row sort counts on 256 threads
     size_t lds = lds_batch;
-    bool occ8 = true;
+    bool occ8 = true, bucketed = false;
     // FP table: canonical row order through a bitmap over (row, mirrored) where that is small (<= 8 KB of LDS)
     q.sort_words = (fpt && dedup && 2 * pl->n_rows <= 65536) ? (int)((2 * pl->n_rows + 31) / 32) : 0;
     if (!d_videos) {
@@ -396,11 +405,21 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
         q.FPW = fpw;
         blocks = (T + fpw - 1) / fpw;
         occ8 = K == 1;
+        // One video of one-frame workgroups over the compact record, the users in one chunk: the row lists in bucket order,
+        // the bucket counters behind the frame's LDS.  Everything else keeps its kernel and geometry.
+        if (rec32 && fpw == 1 && U <= q.UC) {
+            const size_t off = (lds + 15) & ~(size_t)15, with = off + ((size_t)1 << kLutBucketLog2) * 4;
+            if (with <= c->lds_max) {
+                bucketed = true;
+                q.bkt_off = (int)off;
+                lds = with;
+            }
+        }
     } else {
         q.FPW = 1; q.UC = 1;
     }
     // 2 rows in flight per lane group measured best (4 and 8 were tried, profiles/r01/v3_*)
-    const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb, rec32);
+    const void* fn = lut_kernel<FROM_IDS>(il, occ8 && !fpt, dedup, fpt, nb, rec32, bucketed);
     if (!fn) return fail(VET_ERR_UNSUPPORTED, "no table kernel for this launch");
 #if VET_STAGE_CYCLES
     LutProbe probe;

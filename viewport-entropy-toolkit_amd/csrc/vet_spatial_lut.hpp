@@ -239,6 +239,7 @@ __device__ __forceinline__ void walk_rows(const uint32_t* frows, const uint32_t*
 //       cnt  i32 [FPW] rows in the chunk, [FPW] users present in the frame
 //       capped rows (NB > 0) with a side table:  i32 [FPW] entries of the frame's overflow list, u32 [FPW][OC] their slot
 //       words (the side table's row in place of the row), u32 [FPW][OC] their meta words;  OC = lut_ovf_slots
+//       bucket order (LB > 0; FPW = 1):  u32 [2^LB] entries per bucket, then their first list positions, at p.bkt_off
 // Prologue: sample -> direction id -> canonical row (alias: directions with the same Vector — the pole
 // row, the -180 / -90 remaps — share one row) -> set insert.  Users looking in exactly the same
 // direction cost one row walk with a multiplicity instead of one each: 1024 users are ~710 distinct
@@ -284,6 +285,8 @@ struct LutParams {
     int rec_meta;                 // the record's meta word is that of this launch's first lattice
     int K;                        // lattices handled by this launch (<= MAX_LATTICES)
     int n_sum;                    // sum of n over the K lattices
+    int bkt_off;                  // k_spatial_lut<LB > 0>: byte offset of the frame's bucket counters in the workgroup's LDS (a
+                                  // multiple of 16; launch_lut).  (In the four bytes of padding in front of lat: no argument moves)
     LutLattice lat[MAX_LATTICES];
     double* entropy;              // [T] mean over the K lattices, summed in order
     int32_t* assign;
@@ -456,9 +459,17 @@ __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW,
 // key << 12 | count with key = row | mirrored << 15; the record's shift and overflow bits ride in the spare top bits of the row
 // list's slot number until the slot numbers become walk words (WALK32_*: shift in the low bits, where the walk's shift
 // instruction reads it unmasked), so there is no meta array and the overflow test is on a bit of the word in hand.
-template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0, bool REC32 = false>
+// LB > 0 (REC32; one video, one frame per workgroup, the users in one chunk): the lists pass places the walk words in bucket
+// order — bucket = row >> kshift, 2^LB buckets — instead of the order in which the users arrived.  Bucketed by the row, not by
+// the mirror bit: a direction and its mirror share a row, so the two entries meet in one bucket and the second request for the
+// row's lines finds them in the L1 or merges with the miss in flight; rows are also asked for in ascending address order.
+// Per-frame counters u32 [2^LB] at p.bkt_off: counted while the words are made (the rank in the bucket stays in a register
+// with the word), scanned by the first wave while the others clear the histogram, placed from the registers.  Integer adds
+// commute: every output bit is what the arrival order gives (profiles/frame_group/).
+template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0, bool REC32 = false, int LB = 0>
 __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(const LutParams p) {
     static_assert(!REC32 || (NB > 0 && DEDUP && !FPT && !FUSED), "the compact record serves the capped kernels with the set");
+    static_assert(LB == 0 || (REC32 && LB >= 6), "bucket order: the compact record's kernels; a lane of the scan takes 2^LB / 64 counters");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // the video this workgroup works on: the launch's only one, or one of a batch
     SampleSrc src = p.src;
@@ -523,6 +534,11 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const long f0 = blk * FPW;
     const int nf = (int)min((long)FPW, (long)T - f0);
+    // bucket order: the frame's counters, and the shift that leaves LB bits of a row (rows < zrow).  (Formed where they are
+    // used: the prologue needs every register)
+    constexpr int NBKT = LB ? 1 << LB : 0;
+    auto bkt_of = [&]() { return (uint32_t*)(smem + p.bkt_off); };
+    auto kshift_of = [&]() { return LB ? max(32 - __builtin_clz(p.lat[0].zrow | 1u) - LB, 0) : 0; };
 #if VET_STAGE_CYCLES
     unsigned long long tdbg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = p.dbg ? __builtin_readcyclecounter() : 0ull, tsub = tlast;
     if (p.timeline && tid == 0) {
@@ -559,6 +575,8 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
     if (!overlay)
         for (int i = tid; i < FPW * p.n_sum * PRIV; i += blockDim.x) hist[i] = 0ull;
     for (int i = tid; i < 2 * FPW; i += blockDim.x) cnt_chunk[i] = 0;
+    if constexpr (LB > 0)
+        for (int i = tid; i < NBKT; i += blockDim.x) bkt_of()[i] = 0u;
     if (FPT && marked)
         for (int i = tid; i < FPW * MW; i += blockDim.x) marked[i] = 0u;
     bool bad = false;
@@ -707,6 +725,52 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
         stage(0);
         if (DEDUP) {
             // slot numbers -> slot words (row << 12 | multiplicity)
+            if constexpr (LB > 0) {
+                // bucket order (one frame, one chunk): the walk words wait in registers with their rank in their bucket, the
+                // first wave turns the counts into list positions, then every word goes to its place.  (launch_lut picks this
+                // kernel only with the set, i.e. from DEDUP_MIN_USERS users on, so merge holds; were it false, the list would keep
+                // the order of arrival, already in walk words, and counters, barriers and scan would run over nothing)
+                constexpr int QB = REC32_MAX_CHUNK / 256;
+                uint32_t* const bkt = bkt_of();
+                const int kshift = kshift_of();
+                uint32_t bword[QB], brank[QB];
+#pragma unroll
+                for (int q = 0; q < QB; ++q) {
+                    const int i = tid + q * 256;
+                    bword[q] = 0u; brank[q] = 0xFFFFFFFFu;
+                    if (merge && i < cnt_chunk[0]) {
+                        const uint32_t r = rows[i], slot = hash[r & ~REC32_AUX_MASK];
+                        const uint32_t word = ((slot >> 12) << WALK32_ROW_POS) | (((slot & 0xFFFu) - 1u) << WALK32_CNT_POS) |
+                                              ((uint32_t)TAB_X - ((r >> REC32_SHIFT_POS) & ((1u << REC32_SHIFT_BITS) - 1)));
+                        bword[q] = word;
+                        brank[q] = atomicAdd(&bkt[((slot >> 12) & REC32_ROW_MASK) >> kshift], 1u);
+                        if (r & REC32_OVERFLOW) note_overflow(0, word, META_OVERFLOW);
+                    }
+                }
+                __syncthreads();
+                if (overlay)
+                    for (int i = tid; i < p.n_sum; i += blockDim.x) hist[i] = 0ull;
+                if (wv == 0) {                  // counts -> first list position of every bucket
+                    constexpr int PER = NBKT / WAVE;
+                    uint32_t c[PER], mine = 0u;
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) { c[e] = bkt[lane * PER + e]; mine += c[e]; }
+                    uint32_t incl = mine;
+#pragma unroll
+                    for (int o = 1; o < WAVE; o <<= 1) {
+                        const uint32_t up = (uint32_t)__shfl_up((int)incl, o, WAVE);
+                        if (lane >= o) incl += up;
+                    }
+                    uint32_t at = incl - mine;
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) { bkt[lane * PER + e] = at; at += c[e]; }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < QB; ++q)
+                    if (brank[q] != 0xFFFFFFFFu)
+                        rows[bkt[((bword[q] >> WALK32_ROW_POS) & REC32_ROW_MASK) >> kshift] + brank[q]] = bword[q];
+            } else
             if (merge)
                 for (int i = tid; i < nf * UC; i += blockDim.x) {
                     const int fl = i / UC, j = i - fl * UC;
@@ -726,7 +790,7 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                         if (NB) note_overflow(fl, word, meta[i]);   // (the record's meta word: the launch's lattice is the plan's first)
                     }
                 }
-            if (overlay && !FPT) {
+            if (LB == 0 && overlay && !FPT) {
                 __syncthreads();
                 for (int i = tid; i < FPW * p.n_sum; i += blockDim.x) hist[i] = 0ull;
             }
