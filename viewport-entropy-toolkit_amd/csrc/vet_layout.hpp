@@ -51,6 +51,21 @@ constexpr int REC32_MAX_CHUNK = 1 << WALK32_CNT_BITS;
 constexpr uint32_t WALK32_OVF_TMP = 1u << WALK32_CNT_POS;
 static_assert(WALK32_CNT_POS + WALK32_CNT_BITS == WALK32_ROW_POS && WALK32_ROW_POS + REC32_ROW_BITS + 1 == 32, "walk word");
 static_assert(TAB_X < (1 << WALK32_CNT_POS), "the left shift fits below the multiplicity");
+// Bucket-ordered row lists that start at bucket b0 and wrap around (k_spatial_lut<LB > 0>): the list position `pos` of the
+// ascending order moves to pos - p0, plus cnt where that is negative — p0 = the first position of bucket b0, cnt = the list's
+// entries, 0 <= pos, p0 <= cnt.  A bijection of 0 .. cnt - 1 that keeps the order on either side of the wrap.  p0 is the first
+// position of a bucket, so no bucket straddles it and rotated(first + rank) = rotated(first) + rank for every entry of a
+// bucket: the kernel rotates the buckets' first positions, once per bucket, and places the words as before.
+__host__ __device__ __forceinline__ uint32_t lut_rotated(uint32_t pos, uint32_t p0, uint32_t cnt) {
+    const int32_t d = (int32_t)pos - (int32_t)p0;
+    return (uint32_t)(d < 0 ? d + (int32_t)cnt : d);
+}
+// The sweep that tells a starting workgroup its b0: the 100 MHz wall clock passes all buckets once per 2^13 ticks = 82 us,
+// about the time a frame of ~700 distinct rows takes to walk its list (config 3: ~60 us).  Periods of 45 to 90 us measured
+// within 0.8 % of each other (profiles/phase_walk/components.txt): what counts is that walks that start together start at
+// the same bucket, so a power of two, which makes b0 one shift of the clock.
+constexpr int LUT_SWEEP_TICKS_LOG2 = 13;
+
 // entries of a frame's overflow list (LDS): with the set of distinct rows at most one per (overflow row, mirrored) — fewer than
 // DEDUP_MIN_USERS where a small video of a batch runs without the set —, otherwise one per user; never more than the chunk
 __host__ __device__ __forceinline__ int lut_ovf_slots(int UC, int n_ovf, bool dedup) {

@@ -466,6 +466,12 @@ __host__ __device__ __forceinline__ size_t lut_lds_bytes(int U, int UC, int FPW,
 // Per-frame counters u32 [2^LB] at p.bkt_off: counted while the words are made (the rank in the bucket stays in a register
 // with the word), scanned by the first wave while the others clear the histogram, placed from the registers.  Integer adds
 // commute: every output bit is what the arrival order gives (profiles/frame_group/).
+// The list begins at bucket b0 and wraps around, b0 read off the device's wall clock: one sweep of the 2^LB buckets per
+// 2^LUT_SWEEP_TICKS_LOG2 ticks, the same for every workgroup of the device.  The table (7.6 MB on config 3) does not fit an
+// XCD's L2 (4 MB), but the ~256 frames resident on an XCD want every row ~18 times: walks that all begin at bucket 0, each at
+// its own time, are spread over the whole table and fetch a row from beyond the L2 again and again; walks that begin where the
+// sweep is move through the table together, and a row is fetched by the first frame that asks (profiles/phase_walk/: 62 %
+// fewer bytes from beyond the L2, 7 % off the step).  Nothing is shared, stored or waited for, and no output depends on b0.
 template <bool FROM_IDS, int UN, bool IL, bool OCC8, bool DEDUP, bool FPT, bool FUSED = false, int NB = 0, bool REC32 = false, int LB = 0>
 __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(const LutParams p) {
     static_assert(!REC32 || (NB > 0 && DEDUP && !FPT && !FUSED), "the compact record serves the capped kernels with the set");
@@ -762,8 +768,19 @@ __global__ __launch_bounds__(256, OCC8 ? 8 : (FPT ? 6 : 7)) void k_spatial_lut(c
                         if (lane >= o) incl += up;
                     }
                     uint32_t at = incl - mine;
+                    // the list begins with bucket b0, where the device's sweep is now (header), and wraps around: every
+                    // bucket's first position rotated by p0, that of b0 (vet_layout.hpp: lut_rotated; the words are then
+                    // placed as before)
+                    static_assert(LB <= LUT_SWEEP_TICKS_LOG2, "a bucket of the sweep lasts at least one tick");
+                    const uint32_t b0 = (uint32_t)(wall_clock64() >> (LUT_SWEEP_TICKS_LOG2 - LB)) & (uint32_t)(NBKT - 1);
+                    uint32_t upto = at;
 #pragma unroll
-                    for (int e = 0; e < PER; ++e) { bkt[lane * PER + e] = at; at += c[e]; }
+                    for (int e = 0; e + 1 < PER; ++e)
+                        if ((uint32_t)e < b0 % PER) upto += c[e];
+                    const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)upto, (int)(b0 / PER));
+                    const uint32_t listed = (uint32_t)cnt_chunk[0];
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) { bkt[lane * PER + e] = lut_rotated(at, p0, listed); at += c[e]; }
                 }
                 __syncthreads();
 #pragma unroll
