@@ -59,7 +59,8 @@ extern "C" {
                           vet_crowd_divergence* entry points (each viewer's Kullback-Leibler divergence from the pooled crowd), and
                           then the vet_bootstrap_entropy* entry points (confidence bands from viewers resampled with replacement)
                           and vet_bootstrap_counts_host, and then the vet_group_divergence* entry points (a permutation test
-                          of the attention divergence between two audiences) and vet_group_labels_host */
+                          of the attention divergence between two audiences) and vet_group_labels_host, and then the
+                          vet_coverage* entry points (top-k tile sets per window and the share of later windows they hold) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -129,6 +130,10 @@ int vet_test_bootstrap_chunk_rows(vet_ctx *ctx, int rows);
  * of as many as its workspace budget holds, so that a small input runs several chunks; 0 restores the default.  Read at every
  * launch.  Results are bit-identical whatever the value. */
 int vet_test_group_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes vet_coverage* take `rows` rows per histogram chunk (plus the halo of max_lag
+ * rows) instead of as many as its workspace budget holds, so that a small input runs several chunks and the halo crosses them; 0
+ * restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
+int vet_test_coverage_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -503,6 +508,62 @@ int vet_window_divergence_ids(vet_plan *plan, const int32_t *d_ids, int n_users,
  * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
 int vet_window_divergence_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                                int n_frames, int window, int stride, int max_lag, double *h_div, int32_t *h_samples);
+
+/* ---- attention coverage: the top-k tile sets of a window and how well they forecast later windows ------
+ * How many tiles hold 80 % / 95 % of the audience's attention in a segment, which tiles are they, and what share of the attention
+ * of the NEXT segments do they still hold (tile-based delivery: fetch these tiles in high quality)?  Rows are
+ * vet_spatial_entropy_windowed's: window = w, stride = s, R = vet_window_rows(T, w, s), row r covers frames [r*s, r*s + w).
+ * Only LATTICE 0 takes part — the lattice whose tile_weights every row call returns; a plan of several lattices gives the bits
+ * of the plan of its first.  Let h_r[t] >= 0 be row r's histogram over lattice 0's n tiles: the windowed call's d_weights bit for
+ * bit, taken by absolute value (a key whose weight underflowed to 0.0 carries no mass).  Inputs: `fractions`, a HOST array of
+ * 1 <= Q <= 8 values, each in (0, 1], strictly increasing; max_lag = L in rows, 0 <= L <= R - 1.
+ *   rank order   order_r[j] = the tile at rank j: weight descending, equal weights by tile index ascending.  All n tiles are
+ *                listed, so the tiles of weight 0 come last in index order.  rank_r[t] = the rank of tile t.
+ *   mass         C_0 = 0, C_j = C_{j-1} + h_r[order_r[j-1]]: ONE accumulator, one FP64 addition per tile, in rank order (numpy's
+ *                cumsum of the sorted weights); W_r = C_n.  The summation order is part of the contract: with it `tiles` is an
+ *                exact integer statement.
+ *   d_tiles   i32 [R][Q]        tiles[r][i] = the smallest k with C_k >= fractions[i] * W_r (the product is one IEEE multiply);
+ *                               0 where W_r = 0: a row without a sample, or a weighted plan none of whose tiles is inside any
+ *                               viewport's FoV
+ *   d_hit     f64 [R][L+1][Q]   hit[r][l][i] = sum over {t : rank_r[t] < tiles[r][i]} of h_{r+l}[t], divided by W'_{r+l}, the
+ *                               windowed call's row total (the keys' values added in lane order, wave_sum's butterfly; counts:
+ *                               the row's samples).  l = 0: the coverage actually reached, >= fractions[i] up to rounding;
+ *                               l >= 1: the share of row r + l's attention that row r's tile set still holds.  NaN where
+ *                               r + l >= R, where W_r = 0 and where W'_{r+l} = 0 — data, not an error.  The sum runs in one
+ *                               wave: lane j adds its tiles j, j + 64, ... in ascending order, then wave_sum's butterfly — a
+ *                               function of n alone
+ *   d_order   i32 [R][n]        order_r                                                                             (nullable)
+ *   d_samples i32 [R]           present samples per row, as vet_spatial_entropy_windowed                            (nullable)
+ *   d_status  [2]               {bad, #rows without a sample}; the call ADDS, the caller zeroes                     (nullable)
+ * tiles[r], order_r and hit[r][0] are pure functions of the plan, the window, row r's frames and (per column i) fractions[i];
+ * hit[r][l][i] depends on row r + l's frames besides.  None depends on stride, max_lag, the other fractions, n_frames, the row
+ * chunk or the entry point: the same bits.
+ * Four stages, everything in the context's grow-only workspace: 1 vet_spatial_entropy_windowed's stage 1; 2 per chunk of rows
+ * (as many as fit 256 MB of histograms together with the halo of L rows, at least one) lattice 0's row histograms, as
+ * vet_window_divergence's stage 2; 3 k_coverage_rank, one workgroup per row: (weight bits, tile) records sorted in LDS (bitonic,
+ * padded to a power of two with records that sort last), the running sum by one lane, the Q thresholds, every tile's rank; 4
+ * k_coverage_hits, one wave per (row, lag).
+ * VET_ERR_INVALID (before anything is launched or allocated): vet_spatial_entropy_windowed's, fractions NULL, not strictly
+ * increasing or outside (0, 1], Q < 1 or Q > 8, max_lag < 0 or max_lag > R - 1.  VET_ERR_UNSUPPORTED (likewise): a lattice 0 of
+ * more than 2048 tiles (the LDS sort holds 2048 records of 16 bytes: every Fibonacci lattice the other calls accept and the naive
+ * 10 x 20 degree cells fit, 1 x 1 degree cells do not), max_lag >= 65535 * 16, R >= 2^31 - 256, and
+ * vet_spatial_entropy_windowed's limits.
+ * Profile ids: stage 1 as vet_spatial_entropy_windowed's (k_weights / k_spatial), stage 2 to k_finalize, k_coverage_rank to
+ * k_transition and k_coverage_hits to k_wtab — ids the call does not use otherwise, so that the stages can be told apart.
+ * Asynchronous on `stream` like vet_spatial_entropy. */
+int vet_coverage(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                 int max_lag, const double *fractions, int n_fractions, int32_t *d_tiles, double *d_hit, int32_t *d_order,
+                 int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_coverage_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int max_lag,
+                     const double *fractions, int n_fractions, int32_t *d_tiles, double *d_hit, int32_t *d_order,
+                     int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers ([n_frames][n_users] samples as everywhere): H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside
+ * [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa; h_order
+ * and h_samples may be NULL. */
+int vet_coverage_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                      int window, int stride, int max_lag, const double *fractions, int n_fractions, int32_t *h_tiles,
+                      double *h_hit, int32_t *h_order, int32_t *h_samples);
 
 /* ---- viewer-to-crowd divergence: each viewer's Kullback-Leibler divergence from the pooled crowd ------
  * How typical is each viewer of the audience, window by window, and how much of a window's pooled entropy is disagreement between

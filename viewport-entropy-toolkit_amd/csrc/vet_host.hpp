@@ -11,6 +11,8 @@
 //                       the pairwise viewer divergence kernels (a U x U Jensen-Shannon matrix per row) and their launch logic
 //   vet_window_divergence.hip
 //                       the window-to-window divergence kernels (a lag band of Jensen-Shannon distances per row) and their launch logic
+//   vet_coverage.hip    the attention coverage kernels (a window's tiles ranked in LDS, the top-k tile sets that hold given shares of
+//                       its mass, and the share of later windows' mass they still hold) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -132,6 +134,9 @@ struct Tuning {
     int group_chunk_rows = 0;       // vet_test_group_chunk_rows (no environment variable): rows per histogram chunk of
                                 // vet_group_divergence* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_group_divergence_gpu.py)
+    int coverage_chunk_rows = 0;    // vet_test_coverage_chunk_rows (no environment variable): rows per histogram chunk of
+                                // vet_coverage* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_coverage_gpu.py)
     void from_environment();
 };
 
@@ -424,7 +429,7 @@ int window_frames_layout(vet_plan* pl, int U, int T, size_t head_bytes, WindowFr
 int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T,
                       const WindowFrames& wf, int32_t* d_status, hipStream_t s);
 
-// vet_window_divergence.hip, shared with vet_crowd.hip: lattice k's pooled row histograms of rows [h0, h_end) from
+// vet_window_divergence.hip, shared with vet_crowd.hip and vet_coverage.hip: lattice k's pooled row histograms of rows [h0, h_end) from
 // window_frames_run's arrays (k_window_hist_w/_c) — hist [h_end - h0][n_k] f64 (+0.0 = no key), tot and flag per row (1: no sample,
 // or the row's own S is NaN); rows >= r_new also write samples[r] and add to status[1] where those are given.  Charged to k_finalize.
 int window_hist_run(vet_plan* pl, int k, int U, const WindowFrames& wf, int window, int stride, long h0, long h_end, long r_new,
@@ -463,6 +468,10 @@ int zero_keys_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int wi
 // vet_group.hip: what vet_group_divergence* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before
 // anything is staged, allocated or launched — after check_window_args.  groups is host memory [U].
 int check_group_args(const vet_plan* pl, int U, const int8_t* groups, int permutations, double confidence);
+
+// vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].
+int check_coverage_args(const vet_plan* pl, long R, int max_lag, const double* fractions, int Q, const void* hit);
 
 // vet_user_transition.hip: what vet_user_transition_entropy* refuse (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched

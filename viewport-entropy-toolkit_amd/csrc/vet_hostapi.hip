@@ -1,6 +1,6 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous; staged_rows is the whole run of the seven row calls) and BlockDownload (heatmaps and
+// points in between, synchronous; staged_rows is the whole run of the eight row calls) and BlockDownload (heatmaps and
 // tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
 // device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
 // are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
@@ -147,11 +147,12 @@ struct StagedRun {
     }
 };
 
-// The seven row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, windowed /
-// per-viewer transition entropy) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
+// The eight row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
+// / per-viewer transition entropy) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
 // where the call has none) and the count per row; a null h = not wanted: no slot is taken, the launch gets nullptr and nothing
-// is downloaded — except the count, whose slot the device entries always write.  launch(run, d) enqueues the call on the
-// staged samples and the device outputs d[3]; empty_msg as StagedRun::decode, or kRowsAreData (finish_rows_are_data).
+// is downloaded — except the count, whose slot the device entries always write.  (vet_coverage_host has two primary outputs:
+// four entries, each on a slot of its own.)  launch(run, d) enqueues the call on the staged samples and the device outputs
+// d[]; empty_msg as StagedRun::decode, or kRowsAreData (finish_rows_are_data).
 struct RowOut { void* h; size_t bytes; int slot; };
 constexpr RowOut kNoOut = {nullptr, 0, SLOT_OUT1};
 constexpr const char* kRowsAreData = nullptr;
@@ -162,21 +163,21 @@ static int launch_rows(const StagedRun& run, IdsEntry ids_entry, GridEntry grid_
     return run.ids ? ids_entry(pl, run.ids, args...) : grid_entry(pl, run.mu, run.mv, args...);
 }
 
-template <typename Launch>
+template <size_t N, typename Launch>
 static int staged_rows(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T,
-                       const RowOut (&outs)[3], const char* empty_msg, Launch launch) {
+                       const RowOut (&outs)[N], const char* empty_msg, Launch launch) {
     StagedRun run;
     int rc = run.begin(pl, h_mu, h_mv, h_ids, (size_t)U * T);
     if (rc) return rc;
     vet_ctx* c = run.c;
-    void* d[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3; ++i)
+    void* d[N] = {};
+    for (size_t i = 0; i < N; ++i)
         if (outs[i].h || outs[i].slot == SLOT_COUNT) POOL(outs[i].slot, outs[i].bytes, d[i]);
     rc = run.clear_status();
     if (rc) return rc;
     rc = launch(run, d);
     if (rc) return run.drain(rc);
-    for (int i = 0; i < 3; ++i)
+    for (size_t i = 0; i < N; ++i)
         if (outs[i].h) HIP_TRY(hipMemcpyAsync(outs[i].h, d[i], outs[i].bytes, hipMemcpyDeviceToHost, run.s));
     return empty_msg ? run.finish(empty_msg) : run.finish_rows_are_data();
 }
@@ -639,6 +640,23 @@ int vet_window_divergence_host(vet_plan* pl, const double* h_mu, const double* h
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_window_divergence_ids, vet_window_divergence, pl, U, T, window, stride, max_lag, (double*)d[0],
                            (int32_t*)d[2], run.status, run.s);
+    });
+}
+
+// Attention coverage with host buffers (include/vet.h): tiles [R][Q], hit [R][max_lag + 1][Q], and where wanted order [R][n_0] and
+// the samples per row.  Rows without a sample are data (tiles 0, hit NaN): only VET_ERR_RANGE is decoded from the status words.
+int vet_coverage_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                      int stride, int max_lag, const double* fractions, int Q, int32_t* h_tiles, double* h_hit, int32_t* h_order,
+                      int32_t* h_samples) {
+    int64_t R;
+    int rc = check_row_args(pl, U, T, window, stride, false, (const double*)h_tiles, h_mu, h_mv, h_ids, &R);
+    if (!rc) rc = check_coverage_args(pl, (long)R, max_lag, fractions, Q, h_hit);
+    if (rc) return rc;
+    const RowOut outs[4] = {{h_tiles, (size_t)R * Q * 4, SLOT_OUT0}, {h_hit, (size_t)R * (max_lag + 1) * Q * 8, SLOT_ENTROPY},
+                            {h_order, (size_t)R * pl->lat[0].n * 4, SLOT_OUT1}, {h_samples, (size_t)R * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_coverage_ids, vet_coverage, pl, U, T, window, stride, max_lag, fractions, Q, (int32_t*)d[0],
+                           (double*)d[1], (int32_t*)d[2], (int32_t*)d[3], run.status, run.s);
     });
 }
 

@@ -38,6 +38,10 @@
 //                                                               k_window_entropy's sums), their totals and NaN flags, per row chunk
 //                                              k_window_divergence   one thread per (row, lag): Jensen-Shannon divergence of rows r
 //                                                               and r + l in the overlap form, histograms staged through LDS
+//   vet_coverage.hip    (in the unit)          k_coverage_rank  one workgroup per row: lattice 0's pooled histogram sorted in LDS (vet_rank.hpp),
+//                                                               the sequential running sum in rank order, the top-k tile counts that hold
+//                                                               the asked shares of the mass, the rank of every tile
+//                                              k_coverage_hits  one wave per (row, lag): the share of row r + l's mass on row r's top-k tiles
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave
@@ -58,7 +62,7 @@
 //                                              k_group_samples  the observed audiences' present samples per row
 //                                              k_group_maxnull  one thread per permutation: its largest finite value over the rows
 //                                              k_group_summary  one workgroup per row: p-values, mean and the sorted quantile of the null
-//                       vet_rank.hpp           lds_bitonic_sort, lerp_quantile: shared by vet_bootstrap.hip and vet_group.hip
+//                       vet_rank.hpp           lds_bitonic_sort, lerp_quantile: shared by vet_bootstrap.hip, vet_group.hip and vet_coverage.hip
 //   vet_transition.hip  vet_transition.hpp     k_transition_run per frame pair: (prior tile, current tile) pairs -> bucket
 //                                                               statistics in LDS -> transition entropy; persistent workgroups
 //                                              k_transition_big more than 4096 users: the bucket hash in LDS, the row cut into

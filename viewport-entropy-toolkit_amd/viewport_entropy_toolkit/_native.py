@@ -85,6 +85,7 @@ SIGNATURES = {
     "vet_test_crowd_divergence_chunk_rows": (_I, [_P, _I]),
     "vet_test_bootstrap_chunk_rows": (_I, [_P, _I]),
     "vet_test_group_chunk_rows": (_I, [_P, _I]),
+    "vet_test_coverage_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -129,6 +130,9 @@ SIGNATURES = {
     "vet_window_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_window_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_window_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vet_coverage": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_coverage_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_coverage_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "vet_crowd_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_crowd_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_crowd_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -392,6 +396,11 @@ class Engine:
         results do not depend on it (include/vet.h: vet_test_group_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_group_chunk_rows(self.handle, int(rows)))
 
+    def test_coverage_chunk_rows(self, rows: int = 0):
+        """Test switch: the coverage call takes ``rows`` rows per histogram chunk (0: the default budget); results do not depend
+        on it (include/vet.h: vet_test_coverage_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_coverage_chunk_rows(self.handle, int(rows)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -438,10 +447,10 @@ class DeviceResult:
 
 
 _F64, _I32 = np.float64, np.int32
-# The nine row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
+# The ten row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
 # frame pairs, not frames; window=None is all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
-# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, B replicates, P permutations, 2, 3, 4,
-# 5.  A call's extra arguments (max_lag; replicates, seed, confidence; the host array groups, permutations, seed, confidence) follow
+# (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, M max_lag + 1 (a band that starts at
+# lag 0: max_lag may be 0), Q fractions, B replicates, P permutations, 2, 3, 4, 5.  A call's extra arguments (max_lag; replicates, seed, confidence; the host array groups, permutations, seed, confidence) follow
 # stride in the C signatures; ``_row_host`` takes them as ``extra``.
 _ROW_CALLS = {
     "spatial_windowed": ("vet_spatial_entropy_windowed", False, False, True,
@@ -454,6 +463,9 @@ _ROW_CALLS = {
                                  (("divergence", "UR", _F64, False), ("rows", "3R", _F64, False), ("samples", "UR", _I32, False))),
     "spatial_window_divergence": ("vet_window_divergence", False, False, False,
                                   (("divergence", "RL", _F64, False), ("samples", "R", _I32, False))),
+    "spatial_coverage": ("vet_coverage", False, False, False,
+                         (("tiles", "RQ", _I32, False), ("hit", "RMQ", _F64, False), ("order", "Rn", _I32, True),
+                          ("samples", "R", _I32, False))),
     "spatial_bootstrap": ("vet_bootstrap_entropy", False, True, False,
                           (("summary", "4R", _F64, False), ("replicates", "RB", _F64, True), ("weights", "RBn", _F64, True),
                            ("valid", "R", _I32, False))),
@@ -634,14 +646,17 @@ class Plan:
         if window is None and not whole:
             raise ValueError(f"window (a number of {unit}) is required")
         window, stride = n if window is None else int(window), int(stride)
-        lag = (int(max_lag),) if "L" in outputs[0][1] else ()     # a primary output with a lag axis: the call takes max_lag
+        axes = "".join(shape for _, shape, _, _ in outputs)
+        lag = (int(max_lag),) if "L" in axes or "M" in axes else ()     # an output with a lag axis: the call takes max_lag
+        lag_min = 0 if "M" in axes else 1                         # M: the band holds lag 0 too
         R = int(self.lib.vet_window_rows(n, window, stride))
         if R < 0:
             raise ValueError(f"need 1 <= window <= {bound} and stride >= 1 (got window={window}, stride={stride}, {T} frames)")
-        if lag and not 1 <= lag[0] <= R - 1:
-            raise ValueError(f"need 1 <= max_lag <= rows - 1 = {R - 1} (got max_lag={lag[0]}; window={window}, stride={stride}, "
+        if lag and not lag_min <= lag[0] <= R - 1:
+            raise ValueError(f"need {lag_min} <= max_lag <= rows - 1 = {R - 1} (got max_lag={lag[0]}; window={window}, stride={stride}, "
                              f"{T} frames give {R} rows)")
-        dims = {"U": U, "R": R, "n": self.n_tiles[0], "L": lag[0] if lag else 0, "3": 3, "4": 4, **(extra_dims or {})}
+        dims = {"U": U, "R": R, "n": self.n_tiles[0], "L": lag[0] if lag else 0, "M": lag[0] + 1 if lag else 1, "3": 3, "4": 4,
+                **(extra_dims or {})}
         wanted = (lambda key: key in want_optional) if isinstance(want_optional, (set, frozenset)) else (lambda key: want_optional)
         out = {key: None if optional and not wanted(key) else np.empty(tuple(dims[d] for d in shape), dtype=dtype)
                for key, shape, dtype, optional in outputs}
@@ -713,6 +728,36 @@ class Plan:
         Entries with r + l >= R are NaN, and so is every pair with a window that has no sample (``samples`` 0) — data, never an
         error; ``code`` is VET_OK or VET_ERR_RANGE."""
         return self._row_host("spatial_window_divergence", mu, mv, ids, window, stride, False, check, max_lag)
+
+    @staticmethod
+    def _fraction_array(fractions):
+        """``fractions`` as the C entry takes it: float64 [Q], 1 <= Q <= 8, each in (0, 1], strictly increasing; ``ValueError``
+        otherwise."""
+        try:
+            f = np.ascontiguousarray(fractions, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"fractions must be a sequence of numbers (got {fractions!r})")
+        if f.ndim != 1 or not 1 <= f.size <= 8:
+            raise ValueError(f"need 1 to 8 fractions in a one-dimensional sequence (got shape {f.shape})")
+        if not ((f > 0.0) & (f <= 1.0)).all():
+            raise ValueError(f"fractions must lie in (0, 1] (got {f.tolist()})")
+        if not (np.diff(f) > 0.0).all():
+            raise ValueError(f"fractions must be strictly increasing (got {f.tolist()})")
+        return f
+
+    def spatial_coverage(self, mu=None, mv=None, ids=None, window=None, stride=1, max_lag=0, fractions=(0.5, 0.8, 0.95),
+                         want_order=False, check=True):
+        """Which tiles hold the audience's attention, and for how long (include/vet.h: vet_coverage): for every row r — frames
+        [r * stride, r * stride + window) — lattice 0's tiles are ranked by the row's pooled weight (``spatial_windowed``'s
+        ``weights`` by absolute value; descending, equal weights by tile index) and ``tiles[r, i]`` is the smallest number of
+        top-ranked tiles whose running sum reaches ``fractions[i]`` of the row's mass; ``hit[r, l, i]`` is the share of row
+        r + l's mass that those tiles hold, l = 0 .. max_lag (lag 0: the coverage reached; later lags: the forecast).  Returns
+        dict(tiles[R,Q], hit[R,L+1,Q], order[R,n0]|None, samples[R], code), R = (T - window) // stride + 1.  A row without mass
+        has ``tiles`` 0 and NaN ``hit``; entries with r + l >= R and lags that reach a row without mass are NaN — data, never an
+        error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        f = self._fraction_array(fractions)
+        return self._row_host("spatial_coverage", mu, mv, ids, window, stride, bool(want_order), check, max_lag,
+                              extra=(_ptr(f), int(f.size)), extra_dims={"Q": int(f.size)})
 
     @staticmethod
     def _bootstrap_scalars(replicates, seed, confidence):
@@ -981,6 +1026,15 @@ class Plan:
         """d_div [R][max_lag]; d_samples [R] (include/vet.h: vet_window_divergence; ``d_ids``: vet_window_divergence_ids)."""
         self._row_device("spatial_window_divergence", d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, max_lag), d_div, (d_samples, d_status), stream)
+
+    def spatial_coverage_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, max_lag: int,
+                                fractions, d_tiles: int, d_hit: int, d_order: int = 0, d_samples: int = 0, d_status: int = 0,
+                                stream=None, d_ids: int = 0):
+        """``fractions``: the host sequence [Q]; d_tiles i32 [R][Q]; d_hit f64 [R][max_lag + 1][Q]; d_order i32 [R][n0];
+        d_samples [R] (include/vet.h: vet_coverage; ``d_ids``: vet_coverage_ids)."""
+        f = self._fraction_array(fractions)
+        self._row_device("spatial_coverage", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, max_lag, f.ctypes.data, f.size), d_tiles, (d_hit, d_order, d_samples, d_status), stream)
 
     def transition_windowed_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

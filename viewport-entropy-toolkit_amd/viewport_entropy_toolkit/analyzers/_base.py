@@ -340,6 +340,64 @@ class _EntropyAnalyzerBase:
         return df
 
     @staticmethod
+    def _coverage_args(fractions, max_lag, window: int, stride: int, n_frames: int):
+        """(fractions as a tuple of floats, max_lag as an int); ``ValueError`` unless there are 1 to 8 fractions, each a number in
+        (0, 1], strictly increasing, and 0 <= max_lag <= rows - 1."""
+        if isinstance(fractions, (str, bytes)) or not hasattr(fractions, "__len__"):
+            raise ValueError(f"fractions must be a sequence of numbers in (0, 1] (got {fractions!r})")
+        vals = list(fractions)
+        if not 1 <= len(vals) <= 8:
+            raise ValueError(f"need 1 to 8 fractions (got {len(vals)})")
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0:
+                raise ValueError(f"fractions must be numbers in (0, 1] (got {v!r})")
+        vals = [float(v) for v in vals]
+        if any(b <= a for a, b in zip(vals, vals[1:])):
+            raise ValueError(f"fractions must be strictly increasing (got {vals})")
+        if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)):
+            raise ValueError(f"max_lag must be an integer number of rows (got {max_lag!r})")
+        rows = (n_frames - window) // stride + 1
+        if not 0 <= int(max_lag) <= rows - 1:
+            raise ValueError(f"max_lag must be between 0 and rows - 1 = {rows - 1} (got {max_lag}; window={window}, "
+                             f"stride={stride} give {rows} rows of {n_frames} frames)")
+        return tuple(vals), int(max_lag)
+
+    @staticmethod
+    def _coverage_frame(times, window: int, stride: int, res: dict, fractions, n_tiles: int) -> pd.DataFrame:
+        """The coverage as a DataFrame, one row per window: ``tiles`` is the [Q] view ``res["tiles"][r]``, ``share`` =
+        ``tiles / n_tiles`` (a share of the tiles, not of the sphere's area), ``covered`` the [Q] view ``res["hit"][r, 0]``,
+        ``forecast`` the [L, Q] view ``res["hit"][r, 1:]`` and, where ``res`` holds it, ``order`` the [n] view
+        ``res["order"][r]`` (no copies); ``attrs`` hold ``fractions``, ``lags`` / ``lag_frames`` (lags 1 .. L in rows and in
+        frames) and ``n_tiles``."""
+        tiles, hit = res["tiles"], res["hit"]
+        R, L = hit.shape[0], hit.shape[1] - 1
+        first = np.arange(R, dtype=np.int64) * stride
+        times = np.asarray(times)
+        share = tiles / float(n_tiles)
+        names = ["tiles", "share", "covered", "forecast"] + (["order"] if res.get("order") is not None else [])
+        cells = {name: np.empty(R, dtype=object) for name in names}
+        for r in range(R):
+            cells["tiles"][r], cells["share"][r] = tiles[r], share[r]
+            cells["covered"][r], cells["forecast"][r] = hit[r, 0], hit[r, 1:]
+            if "order" in cells:
+                cells["order"][r] = res["order"][r]
+        df = pd.DataFrame({"time": times[first], "time_end": times[first + window - 1], "samples": res["samples"], **cells})
+        df.attrs.update(fractions=tuple(fractions), lags=list(range(1, L + 1)), lag_frames=[stride * l for l in range(1, L + 1)],
+                        n_tiles=int(n_tiles))
+        return df
+
+    def _coverage(self, window, stride, fractions, max_lag, keep_order, n_tiles) -> pd.DataFrame:
+        """``compute_coverage`` of the two spatial analyzers: the arguments are checked before the engine is touched.
+        ``n_tiles()``: the tiles of lattice 0 (asked after the call)."""
+        times, names, call = self._row_call("spatial_coverage")
+        window, stride = self._window_args(window, stride, len(times))
+        fractions, max_lag = self._coverage_args(fractions, max_lag, window, stride, len(times))
+        res = call(window=window, stride=stride, max_lag=max_lag, fractions=fractions, want_order=bool(keep_order), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._coverage_frame(times, window, stride, res, fractions, n_tiles())
+
+    @staticmethod
     def _bootstrap_args(replicates, confidence, seed):
         """(replicates, confidence, seed) checked; ``ValueError`` unless 1 <= replicates <= 4096 (an integer), 0 < confidence < 1
         and seed is an integer in [0, 2^64)."""

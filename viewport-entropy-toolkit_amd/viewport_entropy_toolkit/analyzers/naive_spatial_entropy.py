@@ -173,6 +173,26 @@ class NaiveSpatialEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         res = call(window=window, stride=stride, max_lag=max_lag)
         return self._window_divergence_frame(times, window, stride, res)
 
+    def compute_coverage(self, window: int = 1, stride: int = 1, fractions=(0.5, 0.8, 0.95), max_lag: int = 0,
+                         keep_order: bool = False) -> pd.DataFrame:
+        """Which lat/lon cells hold the audience's attention, and for how long: for every row r — frames
+        [r * stride, r * stride + window) — the cells are ranked by the window's pooled sample counts and the top-ranked cells
+        that hold 50 % / 80 % / 95 % (``fractions``) of the samples are counted; then the share of the NEXT windows' samples in
+        those same cells is taken (``SpatialEntropyAnalyzer.compute_coverage`` on ``compute_naive_spatial_entropy``'s histogram;
+        cells are numbered ``lon index * cells per column + lat index`` and differ in area).
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame with one row per window: ``time`` / ``time_end`` (of
+        the row's first / last frame), ``samples``, ``tiles`` ([Q]: the smallest number of top-ranked cells whose running sum
+        reaches each fraction of the window's mass), ``share`` (``tiles / n``: a share of the cells, not of the sphere's area),
+        ``covered`` ([Q]: the share actually reached, lag 0), ``forecast`` (an [L, Q] view: the share of the mass of the windows
+        1 .. ``max_lag`` rows later that the same cells hold) and, with ``keep_order``, ``order`` ([n]: the cells by weight
+        descending, equal weights by index).  ``attrs`` hold ``fractions``, ``lags`` = [1 .. L], ``lag_frames`` = [stride,
+        2 stride, ...] and ``n_tiles``.  A window without mass has ``tiles`` 0 and NaN shares, and so have the lags that reach
+        past the last window — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside
+        [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` / ``fractions`` (1 to 8 numbers in (0, 1], strictly
+        increasing) / ``max_lag`` (0 .. rows - 1)."""
+        return self._coverage(window, stride, fractions, max_lag, keep_order, lambda: self._naive_plan().n_tiles[0])
+
     def compute_crowd_divergence(self, window: Optional[int] = None, stride: int = 1) -> pd.DataFrame:
         """How typical each viewer is of the audience, on lat/lon cells: for every row r — frames
         [r * stride, r * stride + window), ``window=None`` the whole video — and viewer u the Kullback-Leibler divergence, in
