@@ -60,7 +60,9 @@ extern "C" {
                           then the vet_bootstrap_entropy* entry points (confidence bands from viewers resampled with replacement)
                           and vet_bootstrap_counts_host, and then the vet_group_divergence* entry points (a permutation test
                           of the attention divergence between two audiences) and vet_group_labels_host, and then the
-                          vet_coverage* entry points (top-k tile sets per window and the share of later windows they hold) */
+                          vet_coverage* entry points (top-k tile sets per window and the share of later windows they hold), and
+                          then the vet_transition_markov* entry points (tile-to-tile transition counts per window: entropy rate,
+                          stationary and destination entropy, mutual information at a lag, stay share) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -134,6 +136,10 @@ int vet_test_group_chunk_rows(vet_ctx *ctx, int rows);
  * rows) instead of as many as its workspace budget holds, so that a small input runs several chunks and the halo crosses them; 0
  * restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
 int vet_test_coverage_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: rows > 0 makes the chunked shape of vet_transition_markov* (window * n_users > 32768) build the
+ * dense matrices of `rows` rows per pass instead of as many as its workspace budget holds, so that a small input runs several passes;
+ * 0 restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
+int vet_test_markov_chunk_rows(vet_ctx *ctx, int rows);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -873,6 +879,63 @@ int vet_user_transition_entropy_ids(vet_plan *plan, const int32_t *d_ids, int n_
 int vet_user_transition_entropy_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids,
                                      int n_users, int n_frames, int window, int stride, double *h_entropy,
                                      int32_t *h_srccount, int32_t *h_samples);
+
+/* ---- windowed Markov transition statistics: entropy rate, mutual information, the transition matrix ------
+ * The three calls above evaluate the reference's compute_transition_entropy, whose value depends on first-appearance order (K, w).
+ * These entries give the textbook quantities of the same tile-to-tile moves instead; they are plain functions of integer pair
+ * counts and share nothing with that statistic but stage 1.
+ * Parameters: window, stride and lag >= 1.  A video of T frames has T - lag pairs; pair f is (frame f, frame f + lag).  Row r
+ * covers pairs [r*stride, r*stride + window), R = vet_window_rows(T - lag, window, stride) rows; window = T - lag is the whole
+ * video's matrix (one row).  A (pair, user) is pooled when the user has a sample in both frames of the pair; the frames in
+ * between do not matter.  Per lattice, with p / c the nearest tiles of the two samples (k_window_tiles' values):
+ *   N pooled samples, n_pc samples per (source, destination), n_p = sum_c n_pc, m_c = sum_p n_pc, f(k) = k log2 k on integers
+ *   (f(0) = f(1) = 0; log2 k from the context's table for k <= 4096, FP64 log2 beyond).  The five statistics, in bits but `stay`:
+ *   0 rate        H(c | p) = (A - B) / N, A = sum_p f(n_p) and B = sum_pc f(n_pc) taken over the sources with at least two distinct
+ *                 destinations ONLY: a source with one destination enters neither sum, so a row in which every source has one
+ *                 destination is +0.0 exactly; any other source contributes at least 2 / N, so the value is never negative
+ *   1 stationary  H(p) = log2 N - sum_p f(n_p) / N  (all sources)
+ *   2 dest        H(c) = log2 N - sum_c f(m_c) / N
+ *   3 mutual      dest - rate: the bits about the tile `lag` frames ahead that the tile now gives; not clamped, may sit within
+ *                 rounding of 0
+ *   4 stay        sum_p n_pp / N
+ * each the mean over the plan's lattices (k_finalize over [K][5 R]).
+ *   d_stats   [5][R]            statistic-major
+ *   d_matrix  [R][n_0][n_0]     lattice 0's dense count matrix, source-major, i32                            (nullable)
+ *   d_samples [R]               N of the row                                                                 (nullable)
+ *   d_status  [2]               {bad, #rows without a pooled sample}; the call ADDS, the caller zeroes       (nullable)
+ * A row with N = 0 has five NaN, samples 0 and a zero matrix: data, not an error (the _host entry returns VET_OK).  N = 1 is well
+ * defined: rate, stationary, dest and mutual are 0, stay is 0 or 1.
+ * Stage 1 is vet_transition_entropy_windowed's, unchanged: per lattice k_window_tiles leaves tiles[T][U], so a row's candidates are
+ * the contiguous slice q in [0, W), W = window * n_users, source tiles[f0*U + q], destination tiles[(f0 + lag)*U + q].  Stage 2 by
+ * W alone:
+ *   W <= 32768  k_markov_rows<P>, P the power of two >= W from 1024: one 256-thread workgroup per row (persistent over the rows),
+ *               the keys p*n + c (0xFFFFFFFF absent) sorted in LDS (mk_sort, the unit's own walk of vet_rank.hpp's bitonic network: the
+ *               P / 2 pairs of a stage, four in flight per thread — measured about twice as fast as lds_bitonic_sort,
+ *               profiles/markov/markov_timing.json); the thread at a run start finds the run's
+ *               end by a galloping / binary search and learns from the neighbouring keys whether the run is its source's only
+ *               destination; n_p and m_c are LDS integer histograms; the matrix is written by plain stores into the zeroed output;
+ *   W >  32768  k_markov_count: the same sort and run lengths per chunk of 32768 candidates, one global integer atomicAdd per run
+ *               into a dense u32 [n][n] matrix per row (the workspace, or d_matrix for lattice 0), rows in passes under a 256 MB
+ *               budget (vet_test_markov_chunk_rows); then k_markov_cells, one workgroup per row, walks the matrix in index order.
+ * Counts are integers and exact in any order; the FP64 sums are taken per thread over positions tid, tid + 256, ... in ascending
+ * order, then wave_sum's butterfly, then the four waves in order.  A value's bits depend on the plan, window, lag and the row's
+ * frames only — not on stride, the number of rows, the video's length, the rows per pass, the entry point, or whether the matrix
+ * was asked for.  No FP atomics.
+ * VET_ERR_INVALID (before anything is allocated or launched): lag < 1, lag > n_frames - 1, window < 1, stride < 1,
+ * window > n_frames - lag.  VET_ERR_UNSUPPORTED: a lattice of more than 2048 tiles or bins (the key must stay below 2^22), a
+ * matrix output of more than 2^31 - 1 cells per call, window * n_users above 2^31 - 1.
+ * Profile ids: stage 1 to k_spatial, k_markov_rows / k_markov_count (with the zeroing of the matrices) to k_transition,
+ * k_markov_cells to k_wtab, the mean over the lattices to k_finalize.  Asynchronous on `stream` like vet_transition_entropy. */
+int vet_transition_markov(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                          int lag, double *d_stats, int32_t *d_matrix, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_transition_markov_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int lag,
+                              double *d_stats, int32_t *d_matrix, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_transition_markov_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                               int n_frames, int window, int stride, int lag, double *h_stats, int32_t *h_matrix,
+                               int32_t *h_samples);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

@@ -13,6 +13,9 @@
 //                       the window-to-window divergence kernels (a lag band of Jensen-Shannon distances per row) and their launch logic
 //   vet_coverage.hip    the attention coverage kernels (a window's tiles ranked in LDS, the top-k tile sets that hold given shares of
 //                       its mass, and the share of later windows' mass they still hold) and their launch logic
+//   vet_markov.hip      the windowed Markov transition statistics (a row's (source, destination) tile pairs sorted in LDS into integer
+//                       pair counts; entropy rate, stationary and destination entropy, mutual information, stay share; the dense
+//                       transition matrix) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -137,6 +140,9 @@ struct Tuning {
     int coverage_chunk_rows = 0;    // vet_test_coverage_chunk_rows (no environment variable): rows per histogram chunk of
                                 // vet_coverage* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_coverage_gpu.py)
+    int markov_chunk_rows = 0;      // vet_test_markov_chunk_rows (no environment variable): rows per pass of the chunked shape of
+                                // vet_transition_markov* (0 = sized by the workspace budget); read at every launch; the results do
+                                // not depend on it (test_markov_gpu.py)
     void from_environment();
 };
 
@@ -415,6 +421,7 @@ int window_divergence_set_attrs(vet_ctx* c);
 int crowd_set_attrs(vet_ctx* c);
 int bootstrap_set_attrs(vet_ctx* c);
 int group_set_attrs(vet_ctx* c);
+int markov_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -468,6 +475,15 @@ int zero_keys_run(vet_plan* pl, int k, const int32_t* dirs, int U, int T, int wi
 // vet_group.hip: what vet_group_divergence* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before
 // anything is staged, allocated or launched — after check_window_args.  groups is host memory [U].
 int check_group_args(const vet_plan* pl, int U, const int8_t* groups, int permutations, double confidence);
+
+// vet_window.hip, for vet_markov.hip: stage 1 of the windowed transition call for lattice k alone — one launch of k_window_tiles over
+// frames [0, T): tiles [T][U] i32 (-1 absent), d_status[0] raised where given.  Charged to k_spatial.
+int window_tiles_lattice(vet_plan* pl, int k, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int32_t* tiles,
+                         int32_t* d_status, hipStream_t s);
+
+// vet_markov.hip: what vet_transition_markov* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched
+int check_markov_args(const vet_plan* pl, int U, int T, int window, int stride, int lag, const void* stats, const void* matrix);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

@@ -1,6 +1,6 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous; staged_rows is the whole run of the eight row calls) and BlockDownload (heatmaps and
+// points in between, synchronous; staged_rows is the whole run of the nine row calls) and BlockDownload (heatmaps and
 // tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
 // device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
 // are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
@@ -147,8 +147,8 @@ struct StagedRun {
     }
 };
 
-// The eight row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
-// / per-viewer transition entropy) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
+// The nine row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
+// / per-viewer transition entropy, the Markov transition statistics) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
 // where the call has none) and the count per row; a null h = not wanted: no slot is taken, the launch gets nullptr and nothing
 // is downloaded — except the count, whose slot the device entries always write.  (vet_coverage_host has two primary outputs:
 // four entries, each on a slot of its own.)  launch(run, d) enqueues the call on the staged samples and the device outputs
@@ -693,6 +693,22 @@ int vet_transition_entropy_windowed_host(vet_plan* pl, const double* h_mu, const
                        [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_transition_entropy_windowed_ids, vet_transition_entropy_windowed, pl, U, T, window, stride,
                            (double*)d[0], (int32_t*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
+}
+
+// Windowed Markov transition statistics with host buffers (include/vet.h): stats [5][R], and where wanted lattice 0's matrices
+// [R][n_0][n_0] and the samples per row, R = vet_window_rows over the T - lag pairs.  Rows without a pooled sample are data (NaN,
+// samples 0, a zero matrix): only VET_ERR_RANGE is decoded from the status words.
+int vet_transition_markov_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                               int stride, int lag, double* h_stats, int32_t* h_matrix, int32_t* h_samples) {
+    int rc = check_host_args(pl, U, T, h_stats, h_mu, h_mv, h_ids);
+    if (!rc) rc = check_markov_args(pl, U, T, window, stride, lag, h_stats, h_matrix);
+    if (rc) return rc;
+    const size_t R = (size_t)vet_window_rows(T - lag, window, stride), n0 = (size_t)pl->lat[0].n;
+    const RowOut outs[3] = {{h_stats, 5 * R * 8, SLOT_ENTROPY}, {h_matrix, R * n0 * n0 * 4, SLOT_OUT1}, {h_samples, R * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_transition_markov_ids, vet_transition_markov, pl, U, T, window, stride, lag, (double*)d[0],
+                           (int32_t*)d[1], (int32_t*)d[2], run.status, run.s);
     });
 }
 

@@ -42,6 +42,14 @@
 //                                                               the sequential running sum in rank order, the top-k tile counts that hold
 //                                                               the asked shares of the mass, the rank of every tile
 //                                              k_coverage_hits  one wave per (row, lag): the share of row r + l's mass on row r's top-k tiles
+//   vet_markov.hip      (in the unit)          k_markov_rows    one workgroup per row of up to 32768 candidate samples: the keys source * n +
+//                                                               destination sorted in LDS (the unit's own walk of a bitonic network), run lengths = pair counts ->
+//                                                               entropy rate, stationary / destination entropy, mutual information,
+//                                                               stay share; the dense transition matrix by plain stores
+//                                              k_markov_count   longer rows: the same sort and run lengths per chunk of 32768 samples,
+//                                                               one global integer atomicAdd per run into the row's dense matrix
+//                                              k_markov_cells   one workgroup per row: the dense matrix walked in index order -> the
+//                                                               same five statistics
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

@@ -414,6 +414,12 @@ int window_frames_run(vet_plan* pl, const double* d_mu, const double* d_mv, cons
     return VET_OK;
 }
 
+int window_tiles_lattice(vet_plan* pl, int k, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int32_t* tiles,
+                         int32_t* d_status, hipStream_t s) {
+    const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, (long)pl->n_dirs};
+    return window_tiles_run(pl->ctx, src, U, T, pl->lat[k].d_nearest, tiles, nullptr, d_status, s);
+}
+
 int check_window_args(const vet_plan* pl, int U, int T, int window, int stride, const void* out) {
     int rc = check_run_args(pl, U, T, out);
     if (rc) return rc;

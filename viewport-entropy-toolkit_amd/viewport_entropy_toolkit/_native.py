@@ -86,6 +86,7 @@ SIGNATURES = {
     "vet_test_bootstrap_chunk_rows": (_I, [_P, _I]),
     "vet_test_group_chunk_rows": (_I, [_P, _I]),
     "vet_test_coverage_chunk_rows": (_I, [_P, _I]),
+    "vet_test_markov_chunk_rows": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -124,6 +125,9 @@ SIGNATURES = {
     "vet_user_transition_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_user_transition_entropy_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_user_transition_entropy_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_transition_markov": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_transition_markov_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_transition_markov_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -401,6 +405,11 @@ class Engine:
         on it (include/vet.h: vet_test_coverage_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_coverage_chunk_rows(self.handle, int(rows)))
 
+    def test_markov_chunk_rows(self, rows: int = 0):
+        """Test switch: the chunked shape of the Markov transition call builds the matrices of ``rows`` rows per pass (0: the
+        default budget); results do not depend on it (include/vet.h: vet_test_markov_chunk_rows)."""
+        _check(self.lib, self.lib.vet_test_markov_chunk_rows(self.handle, int(rows)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -447,11 +456,12 @@ class DeviceResult:
 
 
 _F64, _I32 = np.float64, np.int32
-# The ten row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
-# frame pairs, not frames; window=None is all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
+# The eleven row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
+# frame pairs, not frames (T - 1 of them, or T - lag for the call that takes a lag between the two frames of a pair); window=None is
+# all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
 # (result key, dims, dtype, optional); dims: U users, R rows, n tiles of lattice 0, L max_lag, M max_lag + 1 (a band that starts at
 # lag 0: max_lag may be 0), Q fractions, B replicates, P permutations, 2, 3, 4, 5.  A call's extra arguments (max_lag; replicates, seed, confidence; the host array groups, permutations, seed, confidence) follow
-# stride in the C signatures; ``_row_host`` takes them as ``extra``.
+# stride in the C signatures; ``_row_host`` takes them as ``extra``.  (transition_markov's extra is ``lag``.)
 _ROW_CALLS = {
     "spatial_windowed": ("vet_spatial_entropy_windowed", False, False, True,
                          (("entropy", "R", _F64, False), ("weights", "Rn", _F64, True), ("samples", "R", _I32, False))),
@@ -476,6 +486,8 @@ _ROW_CALLS = {
                             (("entropy", "R", _F64, False), ("srccount", "Rn", _I32, True), ("samples", "R", _I32, False))),
     "transition_per_user": ("vet_user_transition_entropy", True, True, False,
                             (("entropy", "UR", _F64, False), ("srccount", "URn", _I32, True), ("samples", "UR", _I32, False))),
+    "transition_markov": ("vet_transition_markov", True, True, False,
+                          (("stats", "5R", _F64, False), ("matrix", "Rnn", _I32, True), ("samples", "R", _I32, False))),
 }
 
 
@@ -636,13 +648,15 @@ class Plan:
             raise ValueError("mu and mv must be [n_frames, n_users] arrays of equal shape")
         return mu, mv, None, mu.shape
 
-    def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None, extra=(), extra_dims=None):
+    def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None, extra=(), extra_dims=None,
+                  pair_lag=1):
         """The host wrapper of row call ``call`` (_ROW_CALLS): arguments, outputs, the ``_host`` entry, the result dict.
         ``want_optional``: one bool for every optional output, or the set of the wanted keys.  ``extra``: the call's scalars behind
-        stride (after max_lag, where the call has one), passed as they are; ``extra_dims``: the output dimensions they define."""
+        stride (after max_lag, where the call has one), passed as they are; ``extra_dims``: the output dimensions they define.
+        ``pair_lag``: the frames between the two frames of a pair (a call over pairs has T - pair_lag of them)."""
         stem, pairs, whole, empty_ok, outputs = _ROW_CALLS[call]
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
-        n, unit, bound = (T - 1, "frame pairs", "n_frames - 1") if pairs else (T, "frames", "n_frames")
+        n, unit, bound = (T - pair_lag, "frame pairs", f"n_frames - {pair_lag}") if pairs else (T, "frames", "n_frames")
         if window is None and not whole:
             raise ValueError(f"window (a number of {unit}) is required")
         window, stride = n if window is None else int(window), int(stride)
@@ -867,6 +881,28 @@ class Plan:
         R = (T - 1 - window) // stride + 1."""
         return self._row_host("transition_windowed", mu, mv, ids, window, stride, want_srccount, check)
 
+    @staticmethod
+    def _pair_lag(lag, n_frames=None):
+        """``lag`` as an int; ``ValueError`` unless it is an integer with 1 <= lag <= n_frames - 1."""
+        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)):
+            raise ValueError(f"lag must be an integer number of frames (got {lag!r})")
+        if lag < 1 or (n_frames is not None and lag > n_frames - 1):
+            raise ValueError(f"need 1 <= lag <= n_frames - 1 (got lag={lag}" + (f", {n_frames} frames)" if n_frames is not None else ")"))
+        return int(lag)
+
+    def transition_markov(self, mu=None, mv=None, ids=None, window=None, stride=1, lag=1, want_matrix=False, check=True):
+        """Tile-to-tile transition statistics of sliding windows of frame pairs (include/vet.h: vet_transition_markov): pair f is
+        (frame f, frame f + lag), row r pools the (pair, user) samples of pairs [r * stride, r * stride + window) present in both
+        frames into integer counts n_pc per (source tile, destination tile).  ``window`` and ``stride`` count pairs;
+        ``window=None`` is all T - lag pairs (one row: the whole video).  Returns dict(stats[5,R] (rate = H(next | current),
+        stationary = H(current), dest = H(next), mutual = dest - rate, stay; bits, mean over the lattices), matrix[R,n0,n0]|None
+        (lattice 0's counts, source-major), samples[R], code), R = (T - lag - window) // stride + 1.  A row without a pooled sample
+        is NaN with ``samples`` 0 and a zero matrix — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        first = ids if ids is not None else mu
+        lag = self._pair_lag(lag, np.shape(first)[0] if np.ndim(first) == 2 else None)
+        return self._row_host("transition_markov", mu, mv, ids, window, stride, bool(want_matrix), check, extra=(lag,),
+                              extra_dims={"5": 5}, pair_lag=lag)
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1040,6 +1076,13 @@ class Plan:
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):
         self._row_device("transition_windowed", d_mu, d_mv, 0, n_users, n_frames,
                          (window, stride), d_entropy, (d_srccount, d_samples, d_status), stream)
+
+    def transition_markov_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, lag: int,
+                                 d_stats: int, d_matrix: int = 0, d_samples: int = 0, d_status: int = 0, stream=None, d_ids: int = 0):
+        """d_stats f64 [5][R]; d_matrix i32 [R][n0][n0]; d_samples [R] (include/vet.h: vet_transition_markov; ``d_ids``:
+        vet_transition_markov_ids)."""
+        self._row_device("transition_markov", d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, lag), d_stats, (d_matrix, d_samples, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

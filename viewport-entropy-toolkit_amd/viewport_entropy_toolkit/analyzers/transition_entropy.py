@@ -151,6 +151,44 @@ class TransitionEntropyAnalyzer(_HeatmapMixin, _EntropyAnalyzerBase):
         return self._user_frame(names, np.asarray(times)[1:], window, stride, res,
                                 FrameDictArray(src, lambda row: TileWeights(tiles, row, as_int=True)))
 
+    def compute_markov_entropy(self, window: Optional[int] = None, stride: int = 1, lag: int = 1,
+                               keep_matrix: bool = False) -> pd.DataFrame:
+        """The textbook statistics of the tile-to-tile moves, from integer transition counts: pair f is (frame f, frame f + lag),
+        row r pools every (pair, user) of the pairs [r * stride, r * stride + window) with a sample in both frames (the frames in
+        between do not matter) into the counts n_pc per (source tile, destination tile).  ``window`` and ``stride`` count pairs;
+        ``window=None`` is the whole video (one row).  Not ``compute_entropy``'s statistic: that one is the reference's
+        ``compute_transition_entropy``, which depends on the order in which users and destinations first appear.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone), one row
+        per window: ``time`` / ``time_end`` (the time of the later frame of the row's first / last pair), ``samples`` (pooled
+        samples N), ``rate`` (the entropy rate H(next | current)), ``stationary`` (H(current)), ``dest`` (H(next)), ``mutual``
+        (dest - rate: the bits about the tile ``lag`` frames ahead that the current tile gives) and ``stay`` (the share of samples
+        that stay on their tile) — bits, averaged over the lattices — and with ``keep_matrix`` the column ``matrix``: lattice 0's
+        [n, n] count matrix, source-major, a view into one result array.  ``attrs`` hold ``lag``, ``lag_frames``, ``n_tiles``
+        and ``users``.  A window without a pooled sample is NaN with ``samples`` 0 — returned, never raised.  Raises
+        ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` /
+        ``stride`` / ``lag``."""
+        times, names, call = self._row_call("transition_markov")
+        lag = _native.Plan._pair_lag(lag, len(times))
+        n_pairs = len(times) - lag
+        window, stride = self._window_args(n_pairs if window is None else window, stride, n_pairs)
+        res = call(window=window, stride=stride, lag=lag, want_matrix=bool(keep_matrix), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        rate, stationary, dest, mutual, stay = res["stats"]
+        first = np.arange(len(rate), dtype=np.int64) * stride
+        pair_time = np.asarray(times)[lag:]
+        cols = {"time": pair_time[first], "time_end": pair_time[first + window - 1], "samples": res["samples"], "rate": rate,
+                "stationary": stationary, "dest": dest, "mutual": mutual, "stay": stay}
+        if keep_matrix:
+            m_col = np.empty(len(rate), dtype=object)
+            for r in range(len(rate)):
+                m_col[r] = res["matrix"][r]
+            cols["matrix"] = m_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(lag=lag, lag_frames=lag, n_tiles=len(self._fibonacci_vectors[self.config.tile_counts[0]]), users=list(names))
+        return df
+
     def _frame_present(self) -> np.ndarray:
         if self._present is None:
             self._present = self._prior_frame_present(*self._present_samples)
