@@ -62,7 +62,9 @@ extern "C" {
                           of the attention divergence between two audiences) and vet_group_labels_host, and then the
                           vet_coverage* entry points (top-k tile sets per window and the share of later windows they hold), and
                           then the vet_transition_markov* entry points (tile-to-tile transition counts per window: entropy rate,
-                          stationary and destination entropy, mutual information at a lag, stay share) */
+                          stationary and destination entropy, mutual information at a lag, stay share), and then the
+                          vet_head_motion* entry points (angular speed of the heads: moments, exact quantiles and a histogram of the
+                          angle between a viewer's directions `lag` frames apart, per window and per viewer) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -140,6 +142,10 @@ int vet_test_coverage_chunk_rows(vet_ctx *ctx, int rows);
  * dense matrices of `rows` rows per pass instead of as many as its workspace budget holds, so that a small input runs several passes;
  * 0 restores the default.  Read at every launch.  Results are bit-identical whatever the value. */
 int vet_test_markov_chunk_rows(vet_ctx *ctx, int rows);
+/* Test switch, not a tuning knob: n > 0 lowers the most values of a row that one workgroup of vet_head_motion* takes from 16384 to
+ * n (rounded down to a multiple of 1024, at least 1024, at most 16384), so that small inputs reach the chunked shape; 0 restores the
+ * default.  Read at every launch.  Results are bit-identical whatever the value. */
+int vet_test_motion_lds_values(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -936,6 +942,74 @@ int vet_transition_markov_ids(vet_plan *plan, const int32_t *d_ids, int n_users,
 int vet_transition_markov_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                                int n_frames, int window, int stride, int lag, double *h_stats, int32_t *h_matrix,
                                int32_t *h_samples);
+
+/* ---- head-motion statistics: the angular speed of the heads, per window and per viewer -------------------
+ * Not in the reference, and independent of the lattices: only the plan's direction table is read.  Every call above describes where
+ * attention sits on the tiling; this one reports how fast heads turn.
+ * Parameters: lag >= 1, window, stride, per_user.  A video of T frames has P = T - lag pairs; pair f is (frame f, frame f + lag).
+ * A (pair, viewer) is a SAMPLE when the viewer has a sample in both frames (the frames in between do not matter).  Its angle a, in
+ * radians, is the reference's vector_angle_distance (entropy_utils.py:41-63) of the two samples' Vectors with k_angular_distances'
+ * arithmetic: with A and B the rows of the plan's unit table (Vector / |Vector|: sqrt of the sum of squares, three divisions),
+ *   c = fma(A.z, B.z, fma(A.y, B.y, A.x * B.x)),   a = acos(min(max(c, -1), 1))   (ocml acos).
+ * One departure from the reference: two samples with the SAME Vector (x, y, z equal as numbers, -0.0 == 0.0, whatever their
+ * direction ids: the pixels of a pole row of a grid share one Vector) have a = +0.0 exactly and count as STILL.  The reference's
+ * arccos of a dot that rounded to 1 - 2^-53 gives 1.5e-8 rad for a head that did not move.  (`still` counts a == 0: the same-Vector
+ * samples and, on direction tables with distinct Vectors closer than about 2^-26 rad, those whose clipped dot is 1.  A sample whose
+ * angle is NaN — a zero-length Vector in an explicit table — is not a sample.)
+ * Layouts:
+ *   per_user = 0  pooled: row r pools the samples of pairs [r*stride, r*stride + window) over all viewers.  R = vet_window_rows(P,
+ *                 window, stride), Rows = R; window = P is the whole video.  The row's values in position order: pair-major,
+ *                 viewer-minor, W = window * n_users positions (absent ones included).
+ *   per_user = 1  row (u, r) holds viewer u's own samples of the same pairs: W = window positions in pair order.  Outputs are
+ *                 user-major, Rows = n_users * R, row index u * R + r.
+ * Outputs per row, N = its samples:
+ *   d_stats     [4][Rows] f64, statistic-major: 0 mean = total / N; 1 sd = sqrt(sum (a - mean)^2 / (N - 1)) (ddof = 1, two passes;
+ *               N = 1: NaN as numpy gives; an all-still row: +0.0 exactly); 2 max; 3 total = sum a (the path the head travelled)
+ *   d_quantiles [Rows][Q] f64: for fraction q, with x the row's angles ascending, pos = q (N - 1), i = floor(pos):
+ *               x[i] + (x[i+1] - x[i]) (pos - i), evaluated as fma(x[i+1] - x[i], pos - i, x[i]); x[N-1] where i >= N - 1 (q = 1
+ *               is `max` bit for bit).  x[i] and x[i+1] are EXACT order statistics of the row's own values: not a sketch   (nullable)
+ *   d_hist      [Rows][B] i32: bin b counts e_b <= a < e_(b+1) for the B + 1 edges e; values outside [e_0, e_B) are not counted;
+ *               e_0 = 0.0 takes the still samples                                                                     (nullable)
+ *   d_still     [Rows] i32  samples with a == 0                                                                        (nullable)
+ *   d_samples   [Rows] i32  N                                                                                          (nullable)
+ *   d_status    [2]   {bad, #rows with N = 0}; the call ADDS, the caller zeroes                                        (nullable)
+ * h_fractions [Q] (0 <= Q <= 8, each in [0, 1], strictly increasing) and h_edges [B + 1] (0 <= B <= 64, finite, strictly ascending,
+ * radians) are HOST arrays in every entry, consumed before the call returns.  Q = 0 / B = 0 (or a NULL output) skip that output.
+ * A row with N = 0 has NaN stats and quantiles, a zero histogram and still = samples = 0: data, not an error.
+ * FP sums follow one fixed order that depends on the row only: the row's W positions are cut into blocks of 1024 from its start; in a
+ * block, thread t of 256 adds its positions t, t + 256, t + 512, t + 768 in that order (an absent position adds nothing), the 64
+ * lanes of a wave combine by wave_sum's butterfly (offsets 32, 16, 8, 4, 2, 1), the four waves are added in order, and the blocks are
+ * added in ascending order.  `total` sums a; sd sums fma(d, d, acc) with d = a - mean per position by the same rule.  Counts, the
+ * maximum and the histogram are integers or order-free.  A value's bits depend on the plan, lag, window, the layout and the row's
+ * frames only — not on stride, the number of rows, the video's length, the entry point, which optional outputs were asked for, the
+ * other fractions, or vet_test_motion_lds_values.  No FP atomics.
+ * Stage 1, k_motion_angles: one angle per (pair, viewer), NaN = absent, [P][U] (pooled; the samples quantised by sample_dir) or
+ * [U][P] (per viewer; behind k_user_dirs' transposed ids), so a row is a contiguous slice of the array in both layouts.  Stage 2 by
+ * W alone: W <= 64: k_motion_wave, one wave per row (lane t holds position t; the block rule with one busy wave; the bit patterns
+ * sorted across the lanes by a bitonic network of shuffles).  W <= 16384: k_motion_rows, one 256-thread workgroup per row (persistent over the rows): two walks for the sums, the u64
+ * bit patterns (non-negative doubles order as their bits) sorted in LDS by lds_bitonic_sort, the quantiles read off.  W > 16384:
+ * chunks of 16384 positions, one workgroup each (k_motion_chunk), rows in passes under a 256 MB workspace budget; partial sums per
+ * block, combined in order by k_motion_select; the order statistics by a radix selection of the bit patterns, most significant digit
+ * first, eight passes of eight bits: a pass counts, for each distinct prefix the wanted ranks still share (at most 16), the next
+ * digit of the values under it (integer atomics), and k_motion_select narrows every rank to its digit; after the eighth pass the
+ * prefix is the value.  Exact whatever the ties.  Not built: several short rows per wave (a row of 20 values leaves 44 lanes idle); bucket
+ * histograms shared between overlapping stride-1 rows (each row is selected on its own).
+ * VET_ERR_INVALID (before anything is allocated or launched): lag < 1, lag > n_frames - 1, window < 1, window > n_frames - lag,
+ * stride < 1, Q outside [0, 8] or fractions not strictly increasing in [0, 1], B outside [0, 64] or edges not strictly ascending.
+ * VET_ERR_UNSUPPORTED: window * n_users above 2^31 - 1; per_user with more than 65535 * 64 frames.
+ * Profile ids: stage 1 (with k_user_dirs) to k_spatial, the row kernels to k_transition.  Asynchronous on `stream`. */
+int vet_head_motion(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride, int lag,
+                    int per_user, const double *h_fractions, int Q, const double *h_edges, int B, double *d_stats,
+                    double *d_quantiles, int32_t *d_hist, int32_t *d_still, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_head_motion_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int lag, int per_user,
+                        const double *h_fractions, int Q, const double *h_edges, int B, double *d_stats, double *d_quantiles,
+                        int32_t *d_hist, int32_t *d_still, int32_t *d_samples, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_head_motion_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                         int window, int stride, int lag, int per_user, const double *h_fractions, int Q, const double *h_edges, int B,
+                         double *h_stats, double *h_quantiles, int32_t *h_hist, int32_t *h_still, int32_t *h_samples);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

@@ -16,6 +16,9 @@
 //   vet_markov.hip      the windowed Markov transition statistics (a row's (source, destination) tile pairs sorted in LDS into integer
 //                       pair counts; entropy rate, stationary and destination entropy, mutual information, stay share; the dense
 //                       transition matrix) and their launch logic
+//   vet_motion.hip      the head-motion statistics (one angle per (frame pair, viewer) from the direction table; per row the moments,
+//                       exact order statistics — an LDS sort, or a radix selection over chunks — and an edge histogram of the
+//                       angles) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -143,6 +146,10 @@ struct Tuning {
     int markov_chunk_rows = 0;      // vet_test_markov_chunk_rows (no environment variable): rows per pass of the chunked shape of
                                 // vet_transition_markov* (0 = sized by the workspace budget); read at every launch; the results do
                                 // not depend on it (test_markov_gpu.py)
+    int motion_lds_values = 0;      // vet_test_motion_lds_values (no environment variable): the most values of a row that one
+                                // workgroup of vet_head_motion* takes (rounded down to a multiple of 1024, at least 1024; 0 = 16384);
+                                // longer rows run the chunked shape; read at every launch; the results do not depend on it
+                                // (test_head_motion_gpu.py)
     void from_environment();
 };
 
@@ -160,7 +167,7 @@ struct vet_ctx {
     double* d_log2 = nullptr;      // log2(k), k = 0..4096
     bool attrs_set = false;        // dynamic-LDS limits of the run kernels raised (first plan)
     // grow-only device staging buffers (no hipMalloc per call): 0-6 host-buffer entry points (the SLOT_* names of
-    // vet_hostapi.hip), (7 unused: batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list
+    // vet_hostapi.hip), 7 the still counts of vet_head_motion_host (batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list
     void* pool[12] = {};
     size_t pool_cap[12] = {};
     // descriptor blobs of the batch entry points: a ring of (pinned host, device) buffer pairs, each guarded by an event
@@ -422,6 +429,7 @@ int crowd_set_attrs(vet_ctx* c);
 int bootstrap_set_attrs(vet_ctx* c);
 int group_set_attrs(vet_ctx* c);
 int markov_set_attrs(vet_ctx* c);
+int motion_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -484,6 +492,11 @@ int window_tiles_lattice(vet_plan* pl, int k, const double* d_mu, const double* 
 // vet_markov.hip: what vet_transition_markov* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched
 int check_markov_args(const vet_plan* pl, int U, int T, int window, int stride, int lag, const void* stats, const void* matrix);
+
+// vet_motion.hip: what vet_head_motion* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched.  fractions [Q] and edges [B + 1] are host memory.
+int check_motion_args(const vet_plan* pl, int U, int T, int window, int stride, int lag, int per_user, const double* fractions, int Q,
+                      const double* edges, int B, const void* stats);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

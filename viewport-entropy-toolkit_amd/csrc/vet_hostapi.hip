@@ -1,6 +1,6 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous; staged_rows is the whole run of the nine row calls) and BlockDownload (heatmaps and
+// points in between, synchronous; staged_rows is the whole run of the ten row calls) and BlockDownload (heatmaps and
 // tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
 // device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
 // are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
@@ -18,7 +18,8 @@ using namespace vh;
 // vet_ctx::pool slots of the entropy host entries (8 and 9 belong to vet_transition.hip and vet_spatial.hip, vet_host.hpp):
 // the samples (h_mu or h_ids, h_mv), the entropies, output 0 (assignments / pairs), output 1 (weights / source counts), the
 // count per row (present / common / samples) and the two status words
-enum { SLOT_MU = 0, SLOT_IDS = 0, SLOT_MV = 1, SLOT_ENTROPY = 2, SLOT_OUT0 = 3, SLOT_OUT1 = 4, SLOT_COUNT = 5, SLOT_STATUS = 6 };
+enum { SLOT_MU = 0, SLOT_IDS = 0, SLOT_MV = 1, SLOT_ENTROPY = 2, SLOT_OUT0 = 3, SLOT_OUT1 = 4, SLOT_COUNT = 5, SLOT_STATUS = 6,
+       SLOT_STILL = 7 };    // 7: the second count per row of vet_head_motion_host
 #define POOL(slot, bytes, var) do { int rc_ = pooled(c, slot, bytes, (void**)&var); if (rc_) return rc_; } while (0)
 
 struct vet_result {
@@ -147,8 +148,8 @@ struct StagedRun {
     }
 };
 
-// The nine row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
-// / per-viewer transition entropy, the Markov transition statistics) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
+// The ten row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
+// / per-viewer transition entropy, the Markov transition statistics, the head-motion statistics) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
 // where the call has none) and the count per row; a null h = not wanted: no slot is taken, the launch gets nullptr and nothing
 // is downloaded — except the count, whose slot the device entries always write.  (vet_coverage_host has two primary outputs:
 // four entries, each on a slot of its own.)  launch(run, d) enqueues the call on the staged samples and the device outputs
@@ -709,6 +710,24 @@ int vet_transition_markov_host(vet_plan* pl, const double* h_mu, const double* h
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_transition_markov_ids, vet_transition_markov, pl, U, T, window, stride, lag, (double*)d[0],
                            (int32_t*)d[1], (int32_t*)d[2], run.status, run.s);
+    });
+}
+
+// Head-motion statistics with host buffers (include/vet.h): stats [4][Rows], and where wanted quantiles [Rows][Q], hist [Rows][B],
+// still [Rows] and samples [Rows]; Rows = vet_window_rows over the T - lag pairs, times n_users for the per-viewer layout.  Rows
+// without a sample are data: only VET_ERR_RANGE is decoded from the status words.
+int vet_head_motion_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window, int stride,
+                         int lag, int per_user, const double* h_fractions, int Q, const double* h_edges, int B, double* h_stats,
+                         double* h_quantiles, int32_t* h_hist, int32_t* h_still, int32_t* h_samples) {
+    int rc = check_host_args(pl, U, T, h_stats, h_mu, h_mv, h_ids);
+    if (!rc) rc = check_motion_args(pl, U, T, window, stride, lag, per_user, h_fractions, Q, h_edges, B, h_stats);
+    if (rc) return rc;
+    const size_t rows = (size_t)vet_window_rows(T - lag, window, stride) * (per_user ? (size_t)U : 1);
+    const RowOut outs[5] = {{h_stats, 4 * rows * 8, SLOT_ENTROPY}, {h_quantiles, rows * Q * 8, SLOT_OUT0}, {h_hist, rows * B * 4, SLOT_OUT1},
+                            {h_still, rows * 4, SLOT_STILL}, {h_samples, rows * 4, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_head_motion_ids, vet_head_motion, pl, U, T, window, stride, lag, per_user, h_fractions, Q, h_edges, B,
+                           (double*)d[0], (double*)d[1], (int32_t*)d[2], (int32_t*)d[3], (int32_t*)d[4], run.status, run.s);
     });
 }
 

@@ -50,6 +50,16 @@
 //                                                               one global integer atomicAdd per run into the row's dense matrix
 //                                              k_markov_cells   one workgroup per row: the dense matrix walked in index order -> the
 //                                                               same five statistics
+//   vet_motion.hip      (in the unit)          k_motion_angles  one FP64 angle per (frame pair, viewer): two unit vectors gathered from the
+//                                                               direction table, fused dot, clip, acos; +0.0 for the same Vector
+//                                              k_motion_wave    one wave per row of up to 64 angles: sums by wave_sum, the bit patterns
+//                                                               sorted across the lanes by shuffles
+//                                              k_motion_rows    one workgroup per row of up to 16384 angles: block-ordered sums, the bit
+//                                                               patterns sorted in LDS, quantiles between exact order statistics
+//                                              k_motion_chunk   longer rows: the same sums per chunk of 16384, and a pass of the
+//                                                               radix selection (the next 8-bit digit under the wanted prefixes)
+//                                              k_motion_select  one wave per row: partial sums in block order, each wanted rank
+//                                                               narrowed to its digit; after eight passes the exact values
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

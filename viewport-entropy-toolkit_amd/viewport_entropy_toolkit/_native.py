@@ -87,6 +87,7 @@ SIGNATURES = {
     "vet_test_group_chunk_rows": (_I, [_P, _I]),
     "vet_test_coverage_chunk_rows": (_I, [_P, _I]),
     "vet_test_markov_chunk_rows": (_I, [_P, _I]),
+    "vet_test_motion_lds_values": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -128,6 +129,9 @@ SIGNATURES = {
     "vet_transition_markov": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_markov_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vet_transition_markov_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vet_head_motion": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_head_motion_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_head_motion_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -410,6 +414,11 @@ class Engine:
         default budget); results do not depend on it (include/vet.h: vet_test_markov_chunk_rows)."""
         _check(self.lib, self.lib.vet_test_markov_chunk_rows(self.handle, int(rows)))
 
+    def test_motion_lds_values(self, n: int = 0):
+        """Test switch: one workgroup of the head-motion call takes rows of at most ``n`` values (a multiple of 1024; 0: the default,
+        16384), longer rows run the chunked shape; results do not depend on it (include/vet.h: vet_test_motion_lds_values)."""
+        _check(self.lib, self.lib.vet_test_motion_lds_values(self.handle, int(n)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -488,6 +497,17 @@ _ROW_CALLS = {
                             (("entropy", "UR", _F64, False), ("srccount", "URn", _I32, True), ("samples", "UR", _I32, False))),
     "transition_markov": ("vet_transition_markov", True, True, False,
                           (("stats", "5R", _F64, False), ("matrix", "Rnn", _I32, True), ("samples", "R", _I32, False))),
+}
+
+# The head-motion call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dims: Q
+# fractions, H histogram bins).  Its extra arguments are lag, per_user and the two host arrays with their lengths.
+_MOTION_CALLS = {
+    False: ("vet_head_motion", True, True, False,
+            (("stats", "4R", _F64, False), ("quantiles", "RQ", _F64, True), ("hist", "RH", _I32, True), ("still", "R", _I32, False),
+             ("samples", "R", _I32, False))),
+    True: ("vet_head_motion", True, True, False,
+           (("stats", "4UR", _F64, False), ("quantiles", "URQ", _F64, True), ("hist", "URH", _I32, True), ("still", "UR", _I32, False),
+            ("samples", "UR", _I32, False))),
 }
 
 
@@ -650,11 +670,12 @@ class Plan:
 
     def _row_host(self, call, mu, mv, ids, window, stride, want_optional, check, max_lag=None, extra=(), extra_dims=None,
                   pair_lag=1):
-        """The host wrapper of row call ``call`` (_ROW_CALLS): arguments, outputs, the ``_host`` entry, the result dict.
+        """The host wrapper of row call ``call`` (a name in _ROW_CALLS, or a descriptor of that form): arguments, outputs, the
+        ``_host`` entry, the result dict.
         ``want_optional``: one bool for every optional output, or the set of the wanted keys.  ``extra``: the call's scalars behind
         stride (after max_lag, where the call has one), passed as they are; ``extra_dims``: the output dimensions they define.
         ``pair_lag``: the frames between the two frames of a pair (a call over pairs has T - pair_lag of them)."""
-        stem, pairs, whole, empty_ok, outputs = _ROW_CALLS[call]
+        stem, pairs, whole, empty_ok, outputs = _ROW_CALLS[call] if isinstance(call, str) else call
         mu, mv, ids, (T, U) = self._samples(mu, mv, ids)
         n, unit, bound = (T - pair_lag, "frame pairs", f"n_frames - {pair_lag}") if pairs else (T, "frames", "n_frames")
         if window is None and not whole:
@@ -681,8 +702,9 @@ class Plan:
         return dict(out, code=rc)
 
     def _row_device(self, call, d_mu, d_mv, d_ids, n_users, n_frames, scalars, d_out, d_optional, stream):
-        """The device wrapper of row call ``call``: the ``_ids`` entry when ``d_ids`` is given, else the (mu, mv) entry."""
-        stem = _ROW_CALLS[call][0]
+        """The device wrapper of row call ``call`` (a name in _ROW_CALLS, or a descriptor of that form): the ``_ids`` entry when
+        ``d_ids`` is given, else the (mu, mv) entry."""
+        stem = (_ROW_CALLS[call] if isinstance(call, str) else call)[0]
         entry, samples = (getattr(self.lib, stem + "_ids"), (d_ids,)) if d_ids else (getattr(self.lib, stem), (d_mu, d_mv))
         _check(self.lib, entry(self.handle, *samples, n_users, n_frames, *(v if isinstance(v, float) else int(v) for v in scalars), d_out,
                                *(p or None for p in d_optional), _stream(stream)))
@@ -903,6 +925,53 @@ class Plan:
         return self._row_host("transition_markov", mu, mv, ids, window, stride, bool(want_matrix), check, extra=(lag,),
                               extra_dims={"5": 5}, pair_lag=lag)
 
+    @staticmethod
+    def _motion_arrays(quantiles, edges):
+        """(fractions float64 [Q] or None, edges float64 [B + 1] or None) as the C entry takes them; ``ValueError`` unless 0 <= Q <= 8
+        fractions in [0, 1], strictly increasing, and 1 <= B <= 64 bins between finite, strictly ascending edges."""
+        def array(values, what):
+            try:
+                a = np.ascontiguousarray(values, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what} must be a sequence of numbers (got {values!r})")
+            if a.ndim != 1:
+                raise ValueError(f"{what} must be a one-dimensional sequence (got shape {a.shape})")
+            return a
+        f = e = None
+        if quantiles is not None and len(quantiles):
+            f = array(quantiles, "quantiles")
+            if f.size > 8:
+                raise ValueError(f"need at most 8 quantiles (got {f.size})")
+            if not ((f >= 0.0) & (f <= 1.0)).all():
+                raise ValueError(f"quantiles must lie in [0, 1] (got {f.tolist()})")
+            if not (np.diff(f) > 0.0).all():
+                raise ValueError(f"quantiles must be strictly increasing (got {f.tolist()})")
+        if edges is not None:
+            e = array(edges, "edges")
+            if not 2 <= e.size <= 65:
+                raise ValueError(f"need 2 to 65 histogram edges, 1 to 64 bins (got {e.size})")
+            if not np.isfinite(e).all() or not (np.diff(e) > 0.0).all():
+                raise ValueError(f"edges must be finite and strictly ascending (got {e.tolist()})")
+        return f, e
+
+    def head_motion(self, mu=None, mv=None, ids=None, window=None, stride=1, lag=1, per_user=False, quantiles=(0.5, 0.9, 0.99),
+                    edges=None, check=True):
+        """How fast heads turn (include/vet.h: vet_head_motion): pair f is (frame f, frame f + lag); a (pair, viewer) present in both
+        frames is a sample, its angle (radians) the reference's ``vector_angle_distance`` of the two Vectors, +0.0 exactly where they
+        are the same Vector (still).  Row r pools the samples of pairs [r * stride, r * stride + window) over all viewers, or with
+        ``per_user`` row (u, r) holds viewer u's own (outputs user-major, a leading U axis).  ``window`` and ``stride`` count pairs;
+        ``window=None`` is all T - lag pairs.  Returns dict(stats[4,R] (mean, sd with ddof = 1, max, total), quantiles[R,Q]|None
+        (linear interpolation between exact order statistics), hist[R,B]|None (``edges``: B + 1 ascending values in radians, bins
+        half-open), still[R], samples[R], code), R = (T - lag - window) // stride + 1.  A row without a sample is NaN with ``samples``
+        0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        first = ids if ids is not None else mu
+        lag = self._pair_lag(lag, np.shape(first)[0] if np.ndim(first) == 2 else None)
+        f, e = self._motion_arrays(quantiles, edges)
+        Q, B = (0 if f is None else int(f.size)), (0 if e is None else int(e.size) - 1)
+        want = {key for key, a in (("quantiles", f), ("hist", e)) if a is not None}
+        return self._row_host(_MOTION_CALLS[bool(per_user)], mu, mv, ids, window, stride, want, check,
+                              extra=(lag, int(bool(per_user)), _ptr(f), Q, _ptr(e), B), extra_dims={"Q": Q, "H": B}, pair_lag=lag)
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1083,6 +1152,18 @@ class Plan:
         vet_transition_markov_ids)."""
         self._row_device("transition_markov", d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, lag), d_stats, (d_matrix, d_samples, d_status), stream)
+
+    def head_motion_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, lag: int, per_user: bool,
+                           quantiles, edges, d_stats: int, d_quantiles: int = 0, d_hist: int = 0, d_still: int = 0, d_samples: int = 0,
+                           d_status: int = 0, stream=None, d_ids: int = 0):
+        """``quantiles`` / ``edges``: the host sequences [Q] / [B + 1] (or None); d_stats f64 [4][Rows]; d_quantiles f64 [Rows][Q];
+        d_hist i32 [Rows][B]; d_still, d_samples i32 [Rows]; Rows = R, or U * R user-major with ``per_user`` (include/vet.h:
+        vet_head_motion; ``d_ids``: vet_head_motion_ids)."""
+        f, e = self._motion_arrays(quantiles, edges)
+        self._row_device(_MOTION_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, lag, int(bool(per_user)), f.ctypes.data if f is not None else 0, 0 if f is None else f.size,
+                          e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1), d_stats,
+                         (d_quantiles, d_hist, d_still, d_samples, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

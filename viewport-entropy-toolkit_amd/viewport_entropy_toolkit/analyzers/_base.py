@@ -517,5 +517,99 @@ class _EntropyAnalyzerBase:
             raise ValidationError("Normalized coordinates must be between 0 and 1")
         return self._group_frame(times, names, window, stride, code, labels, res, permutations, seed, confidence)
 
+    @staticmethod
+    def _motion_args(quantiles, bins_deg):
+        """(quantiles as a tuple of floats, bins_deg as a tuple of floats or None); ``ValueError`` unless there are at most 8
+        quantiles, each a number in [0, 1], strictly increasing, and 2 to 65 finite, strictly ascending bin edges in degrees."""
+        def numbers(values, what):
+            if values is None or isinstance(values, (str, bytes)) or not hasattr(values, "__len__"):
+                raise ValueError(f"{what} must be a sequence of numbers (got {values!r})")
+            vals = list(values)
+            for v in vals:
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                    raise ValueError(f"{what} must be finite numbers (got {v!r})")
+            return [float(v) for v in vals]
+        q = numbers(() if quantiles is None else quantiles, "quantiles")
+        if len(q) > 8:
+            raise ValueError(f"need at most 8 quantiles (got {len(q)})")
+        if any(not 0.0 <= v <= 1.0 for v in q):
+            raise ValueError(f"quantiles must be numbers in [0, 1] (got {q})")
+        if any(b <= a for a, b in zip(q, q[1:])):
+            raise ValueError(f"quantiles must be strictly increasing (got {q})")
+        if bins_deg is None:
+            return tuple(q), None
+        e = numbers(bins_deg, "bins_deg")
+        if not 2 <= len(e) <= 65:
+            raise ValueError(f"need 2 to 65 bin edges, 1 to 64 bins (got {len(e)})")
+        if any(b <= a for a, b in zip(e, e[1:])):
+            raise ValueError(f"bins_deg must be strictly ascending (got {e})")
+        return tuple(q), tuple(e)
+
+    @staticmethod
+    def _motion_frame(times, names, window: int, stride: int, lag: int, per_user: bool, res: dict, quantiles, bins_deg) -> pd.DataFrame:
+        """The head-motion statistics as a DataFrame in DEGREES, one row per window (``per_user``: per (user, window), user-major,
+        ``user`` first): the ``quantiles`` cell of a row is the [Q] view of its quantiles and, where ``res`` holds it, ``hist`` the
+        [B] view ``res["hist"][row]`` (no copy of the counts).  ``times``: every frame's time; a pair's time is its later frame's."""
+        times = np.asarray(times)
+        stats = np.degrees(np.asarray(res["stats"], dtype=np.float64)).reshape(4, -1)
+        samples, still = np.asarray(res["samples"]).reshape(-1), np.asarray(res["still"]).reshape(-1)
+        rows = len(samples)
+        R = rows // len(names) if per_user else rows
+        first = np.arange(R, dtype=np.int64) * stride
+        if per_user:
+            first = np.tile(first, len(names))
+        pair_time = times[lag:]
+        cols = {}
+        if per_user:
+            cols["user"] = np.repeat(np.asarray(list(names), dtype=object), R)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            share = np.where(samples > 0, still / np.maximum(samples, 1), np.nan)
+        cols.update(time=pair_time[first], time_end=pair_time[first + window - 1], samples=samples, still=still, still_share=share,
+                    mean=stats[0], sd=stats[1], max=stats[2], total=stats[3])
+        q_deg = np.degrees(res["quantiles"]).reshape(rows, -1) if res.get("quantiles") is not None else np.empty((rows, 0))
+        q_col = np.empty(rows, dtype=object)
+        for r in range(rows):
+            q_col[r] = q_deg[r]
+        cols["quantiles"] = q_col
+        if res.get("hist") is not None:
+            hist = np.asarray(res["hist"]).reshape(rows, -1)
+            h_col = np.empty(rows, dtype=object)
+            for r in range(rows):
+                h_col[r] = hist[r]
+            cols["hist"] = h_col
+        df = pd.DataFrame(cols)
+        steps = times[lag:] - times[:-lag]
+        df.attrs.update(lag=lag, lag_frames=lag, quantiles=tuple(quantiles), bins_deg=None if bins_deg is None else tuple(bins_deg),
+                        users=list(names), pair_seconds=float(np.median(steps)) if len(steps) else float("nan"))
+        return df
+
+    def compute_head_motion(self, window: Optional[int] = None, stride: int = 1, lag: int = 1, per_user: bool = False,
+                            quantiles=(0.5, 0.9, 0.99), bins_deg=None) -> pd.DataFrame:
+        """How fast heads turn: pair f is (frame f, frame f + lag); a (pair, viewer) with a sample in both frames is a sample, its
+        angle the great-circle angle between the two viewing directions (the reference's ``vector_angle_distance``; exactly 0 for
+        two samples with the same Vector, which count as ``still``).  Row r pools the samples of the pairs
+        [r * stride, r * stride + window) over all viewers, or with ``per_user`` each viewer's own.  ``window`` and ``stride``
+        count pairs; ``window=None`` is the whole video.  Independent of the tiling.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame in DEGREES (``compute_entropy``'s results are left
+        alone), one row per window — user-major with ``user`` first when ``per_user``: ``time`` / ``time_end`` (the later frame of
+        the row's first / last pair), ``samples``, ``still``, ``still_share``, ``mean``, ``sd`` (ddof = 1), ``max``, ``total`` (the
+        path travelled), ``quantiles`` (a [Q] view: linear interpolation between exact order statistics) and, with ``bins_deg``
+        (ascending edges in degrees, half-open bins), ``hist`` (a [B] view of counts).  ``attrs`` hold ``lag``, ``lag_frames``,
+        ``quantiles``, ``bins_deg``, ``users`` and ``pair_seconds`` (the median of time[f + lag] - time[f]): degrees per second is
+        one division.  A window without a sample is NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError``
+        before data is loaded and for samples outside [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` / ``lag`` /
+        ``quantiles`` / ``bins_deg``."""
+        times, names, call = self._row_call("head_motion")
+        lag = _native.Plan._pair_lag(lag, len(times))
+        n_pairs = len(times) - lag
+        window, stride = self._window_args(n_pairs if window is None else window, stride, n_pairs)
+        quantiles, bins_deg = self._motion_args(quantiles, bins_deg)
+        res = call(window=window, stride=stride, lag=lag, per_user=bool(per_user), quantiles=quantiles,
+                   edges=None if bins_deg is None else np.radians(bins_deg), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._motion_frame(times, names, window, stride, lag, bool(per_user), res, quantiles, bins_deg)
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError
