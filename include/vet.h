@@ -64,7 +64,9 @@ extern "C" {
                           then the vet_transition_markov* entry points (tile-to-tile transition counts per window: entropy rate,
                           stationary and destination entropy, mutual information at a lag, stay share), and then the
                           vet_head_motion* entry points (angular speed of the heads: moments, exact quantiles and a histogram of the
-                          angle between a viewer's directions `lag` frames apart, per window and per viewer) */
+                          angle between a viewer's directions `lag` frames apart, per window and per viewer), and then the
+                          vet_dispersion* entry points (audience dispersion: the angle between two viewers' directions in one
+                          frame over all pairs, per window and per viewer) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -146,6 +148,10 @@ int vet_test_markov_chunk_rows(vet_ctx *ctx, int rows);
  * n (rounded down to a multiple of 1024, at least 1024, at most 16384), so that small inputs reach the chunked shape; 0 restores the
  * default.  Read at every launch.  Results are bit-identical whatever the value. */
 int vet_test_motion_lds_values(vet_ctx *ctx, int n);
+/* Test switch, not a tuning knob: n > 0 lowers the most viewers of a frame that k_dispersion_pairs (vet_dispersion*) stages in LDS at
+ * a time from 1024 to n (at most 1024), so that a small audience runs several tiles; 0 restores the default.  Read at every launch.
+ * Results are bit-identical whatever the value. */
+int vet_test_dispersion_tile(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -1010,6 +1016,83 @@ int vet_head_motion_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n
 int vet_head_motion_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
                          int window, int stride, int lag, int per_user, const double *h_fractions, int Q, const double *h_edges, int B,
                          double *h_stats, double *h_quantiles, int32_t *h_hist, int32_t *h_still, int32_t *h_samples);
+
+/* ---- audience dispersion: pairwise viewer angles per window and per viewer --------------------------------
+ * Not in the reference, and independent of the lattices: only the plan's direction table is read.  vet_head_motion describes each
+ * head on its own; this call reports how tightly the audience looks together in a frame, and which viewers are off on their own.
+ * A viewer is PRESENT in frame f exactly as in vet_head_motion (a sample that is not NaN and lies in [0, 1]; a direction id >= 0
+ * below the table's size); a sample outside is absent and counted in status[0].  V_f = the viewers present in frame f.
+ * A PAIR SAMPLE is (f, {u, v}) with u < v and both present in frame f.  Its angle a(u, v), in radians, is vet_head_motion's angle of
+ * the two direction ids: with A and B the rows of the plan's unit table,
+ *   c = fma(A.z, B.z, fma(A.y, B.y, A.x * B.x)),   a = acos(min(max(c, -1), 1))   (ocml acos),
+ * and +0.0 exactly when the two Vectors are equal as numbers (SAME; whatever their direction ids).  A NaN angle (a zero-length
+ * Vector in an explicit table) is not a sample.  a(u, v) and a(v, u) have the same bits: the products commute and the fused dot
+ * adds them in one order; the kernel relies on it.  The PARTNERS of u in f are the v != u of V_f with a(u, v) not NaN.
+ * window and stride count frames; R = vet_window_rows(n_frames, window, stride); row r covers frames [r*stride, r*stride + window).
+ * Per (frame, viewer) with u in V_f:  s(f, u) = the sum of a(u, v) over u's partners in ASCENDING v (a sequential sum from +0.0),
+ * m(f, u) = the smallest, x(f, u) = the largest, k(f, u) = their number, z(f, u) = those with a == 0.
+ * Layouts:
+ *   per_user = 0  pooled, Rows = R.  Over the row's pair samples, N of them:
+ *                 mean = (sum of s(f, u) over the row) / (2 N): every pair sample enters the sum from both sides;
+ *                 max = the audience's angular diameter; same = #{a == 0}; hist[b] = #{e_b <= a < e_(b+1)} for the B + 1 host
+ *                 edges e in radians (vet_head_motion's d_hist rules: half-open bins, values outside [e_0, e_B) not counted);
+ *                 slots = #{(f, u): k(f, u) > 0}; nearest = (sum of m(f, u) over those) / slots, the mean nearest-neighbour
+ *                 angle: small for a clustered crowd even when `mean` is large because there are two clusters;
+ *                 present = sum_f |V_f|; centroid = the sum of the unit vectors of all present (f, u), lone viewers included (a
+ *                 NaN unit vector adds nothing).  |centroid| / present is the resultant length.
+ *   per_user = 1  Rows = n_users * R, row index u * R + r: the same from viewer u's side.  samples = sum_f k(f, u);
+ *                 mean = sum_f s(f, u) / samples; max = the farthest partner; slots = the frames in which u has a partner;
+ *                 nearest = sum_f m(f, u) / slots; same = sum_f z(f, u); present = the frames u is in; centroid = the sum of u's
+ *                 own unit vectors (|centroid| / present near 1: a viewer who stays put).  No histogram: per_user with B > 0 is
+ *                 VET_ERR_INVALID.  Summed over u, samples = 2 N and same = 2 * same of the pooled row (integers, exact).
+ * Outputs, each nullable:
+ *   d_stats    [3][Rows] f64, statistic-major: 0 mean, 1 max, 2 nearest
+ *   d_centroid [Rows][3] f64
+ *   d_hist     [Rows][B] i64
+ *   d_counts   [4][Rows] i64: 0 samples (N), 1 same, 2 slots, 3 present (i64: a pooled whole-video row of 1024 viewers x 30000
+ *              frames holds 1.57e10 pairs)
+ *   d_status   [2] i32 {bad, #rows with N = 0}; the call ADDS, the caller zeroes
+ * h_edges [B + 1] (0 <= B <= 64, finite, strictly ascending, radians) is a HOST array in every entry, consumed before the call
+ * returns.  B = 0 (or d_hist NULL) skips the histogram.
+ * A row with N = 0 (never two viewers in one frame; n_users = 1 is legal) has NaN mean / max / nearest, a zero histogram and
+ * samples = same = slots = 0: data, not an error.  Its present and centroid are still filled; a row with present = 0 has a +0.0
+ * centroid.
+ * FP sums follow one fixed order that depends on the row only.  Inside a frame: s(f, u) as above.  Over the row: vet_head_motion's
+ * rule on the row's POSITIONS — pooled: frame-major, viewer-minor, W = window * n_users (absent ones included); per viewer: W =
+ * window in frame order.  The positions are cut into blocks of 1024 from the row's start; in a block, thread t of 256 adds its
+ * positions t, t + 256, t + 512, t + 768 in that order (an absent position, or for s and m one without a partner, adds nothing),
+ * the 64 lanes of a wave combine by wave_sum's butterfly (offsets 32, 16, 8, 4, 2, 1), the four waves are added in order, and the
+ * blocks are added in ascending order.  Five sums go by this rule: s, m and the three centroid components.  Counts, the maximum
+ * and the histograms are integers or order-free.  A value's bits depend on the plan, window, the layout and the row's frames only —
+ * not on stride, the number of rows, the video's length, the entry point, which optional outputs were asked for, the edges, or
+ * vet_test_dispersion_tile.  No FP atomics.
+ * Stage 1, k_dispersion_pairs: workgroup = (frame, 256 viewers), thread = viewer u; the frame's samples are quantised and their unit
+ * vectors staged in LDS in tiles of 1024 viewers (32 B each); the thread walks the partners in ascending v (every lane reads the same
+ * LDS address: a broadcast) with s, m, x, k, z in registers and leaves them per (frame, viewer) — [T][U], or [U][T] for the per-viewer
+ * layout, so a row is a contiguous slice — with the frame's edge histogram (up to 8 bins: the counts of a >= e_k in registers,
+ * differenced; more: a private LDS column per thread; then integer adds).  It walks ALL ORDERED PAIRS, twice the acos, with no
+ * cross-lane step; walking the upper triangle and crediting the partner was NOT built and the two were not measured against each
+ * other.  Stage 2: k_dispersion_chunk (16 blocks of a row per workgroup: block totals, the row's integers by integer atomics),
+ * k_dispersion_finish (one wave per row: the blocks in order, the frames' histograms added and halved); rows in passes under a 256 MB
+ * workspace budget.  Overlapping windows never recompute a frame.
+ * Workspace: 36 B per (frame, viewer).  Not built: collapsing a frame to (direction, multiplicity) before the walk; the upper
+ * triangle; one wave per short row in stage 2 (a per-viewer row of 20 positions takes a workgroup).
+ * VET_ERR_INVALID (before anything is allocated or launched): window < 1, window > n_frames, stride < 1, B outside [0, 64], edges
+ * not finite and strictly ascending, per_user with B > 0.  VET_ERR_UNSUPPORTED: n_users > 65535 (a frame's pair count must fit 31
+ * bits); n_frames * ceil(n_users / 256) above 2^31 - 1.
+ * Profile ids: k_dispersion_pairs to k_spatial, stage 2 to k_transition.  Asynchronous on `stream`. */
+int vet_dispersion(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                   int per_user, const double *h_edges, int B, double *d_stats, double *d_centroid, int64_t *d_hist,
+                   int64_t *d_counts, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_dispersion_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int per_user,
+                       const double *h_edges, int B, double *d_stats, double *d_centroid, int64_t *d_hist, int64_t *d_counts,
+                       int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_dispersion_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                        int window, int stride, int per_user, const double *h_edges, int B, double *h_stats, double *h_centroid,
+                        int64_t *h_hist, int64_t *h_counts);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

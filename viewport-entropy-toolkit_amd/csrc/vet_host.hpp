@@ -19,6 +19,8 @@
 //   vet_motion.hip      the head-motion statistics (one angle per (frame pair, viewer) from the direction table; per row the moments,
 //                       exact order statistics — an LDS sort, or a radix selection over chunks — and an edge histogram of the
 //                       angles) and their launch logic
+//   vet_dispersion.hip  the audience dispersion (the angle between two viewers' directions in one frame over all pairs: per (frame,
+//                       viewer) partials from unit vectors staged in LDS, then per row the block-ordered sums) and its launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -150,6 +152,9 @@ struct Tuning {
                                 // workgroup of vet_head_motion* takes (rounded down to a multiple of 1024, at least 1024; 0 = 16384);
                                 // longer rows run the chunked shape; read at every launch; the results do not depend on it
                                 // (test_head_motion_gpu.py)
+    int dispersion_tile = 0;        // vet_test_dispersion_tile (no environment variable): the most viewers of a frame that
+                                // k_dispersion_pairs stages in LDS at a time (0 = 1024); read at every launch; the results do not
+                                // depend on it (test_dispersion_gpu.py)
     void from_environment();
 };
 
@@ -430,6 +435,7 @@ int bootstrap_set_attrs(vet_ctx* c);
 int group_set_attrs(vet_ctx* c);
 int markov_set_attrs(vet_ctx* c);
 int motion_set_attrs(vet_ctx* c);
+int dispersion_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -497,6 +503,10 @@ int check_markov_args(const vet_plan* pl, int U, int T, int window, int stride, 
 // staged, allocated or launched.  fractions [Q] and edges [B + 1] are host memory.
 int check_motion_args(const vet_plan* pl, int U, int T, int window, int stride, int lag, int per_user, const double* fractions, int Q,
                       const double* edges, int B, const void* stats);
+
+// vet_dispersion.hip: what vet_dispersion* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched.  edges [B + 1] is host memory.
+int check_dispersion_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, const double* edges, int B);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

@@ -1,6 +1,6 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous; staged_rows is the whole run of the ten row calls) and BlockDownload (heatmaps and
+// points in between, synchronous; staged_rows is the whole run of the eleven row calls) and BlockDownload (heatmaps and
 // tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
 // device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
 // are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
@@ -148,12 +148,12 @@ struct StagedRun {
     }
 };
 
-// The ten row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed
-// / per-viewer transition entropy, the Markov transition statistics, the head-motion statistics) after their refusals: one staged run.  outs = the primary output, the optional one (kNoOut
-// where the call has none) and the count per row; a null h = not wanted: no slot is taken, the launch gets nullptr and nothing
-// is downloaded — except the count, whose slot the device entries always write.  (vet_coverage_host has two primary outputs:
-// four entries, each on a slot of its own.)  launch(run, d) enqueues the call on the staged samples and the device outputs
-// d[]; empty_msg as StagedRun::decode, or kRowsAreData (finish_rows_are_data).
+// The eleven row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
+// per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion) after their
+// refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
+// null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
+// entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
+// the call on the staged samples and the device outputs d[]; empty_msg as StagedRun::decode, or kRowsAreData (finish_rows_are_data).
 struct RowOut { void* h; size_t bytes; int slot; };
 constexpr RowOut kNoOut = {nullptr, 0, SLOT_OUT1};
 constexpr const char* kRowsAreData = nullptr;
@@ -728,6 +728,25 @@ int vet_head_motion_host(vet_plan* pl, const double* h_mu, const double* h_mv, c
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_head_motion_ids, vet_head_motion, pl, U, T, window, stride, lag, per_user, h_fractions, Q, h_edges, B,
                            (double*)d[0], (double*)d[1], (int32_t*)d[2], (int32_t*)d[3], (int32_t*)d[4], run.status, run.s);
+    });
+}
+
+// Audience dispersion with host buffers (include/vet.h): where wanted stats [3][Rows], centroid [Rows][3], hist [Rows][B] and counts
+// [4][Rows]; Rows = vet_window_rows over the T frames, times n_users for the per-viewer layout.  Every output may be NULL.  Rows
+// without a pair are data: only VET_ERR_RANGE is decoded from the status words.
+int vet_dispersion_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window, int stride,
+                        int per_user, const double* h_edges, int B, double* h_stats, double* h_centroid, int64_t* h_hist,
+                        int64_t* h_counts) {
+    int rc = check_dispersion_args(pl, U, T, window, stride, per_user, h_edges, B);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t rows = (size_t)vet_window_rows(T, window, stride) * (per_user ? (size_t)U : 1);
+    const RowOut outs[4] = {{h_stats, 3 * rows * 8, SLOT_ENTROPY}, {h_centroid, 3 * rows * 8, SLOT_OUT0}, {h_hist, rows * B * 8, SLOT_OUT1},
+                            {h_counts, 4 * rows * 8, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_dispersion_ids, vet_dispersion, pl, U, T, window, stride, per_user, h_edges, B, (double*)d[0],
+                           (double*)d[1], (int64_t*)d[2], (int64_t*)d[3], run.status, run.s);
     });
 }
 

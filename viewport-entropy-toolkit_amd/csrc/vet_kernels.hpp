@@ -60,6 +60,13 @@
 //                                                               radix selection (the next 8-bit digit under the wanted prefixes)
 //                                              k_motion_select  one wave per row: partial sums in block order, each wanted rank
 //                                                               narrowed to its digit; after eight passes the exact values
+//   vet_dispersion.hip  (in the unit)          k_dispersion_pairs   workgroup = (frame, 256 viewers): the frame's unit vectors staged in LDS,
+//                                                               every thread walks its viewer's partners in ascending order (fused
+//                                                               dot, clip, acos; an LDS broadcast per partner): sum, nearest, farthest,
+//                                                               counts per (frame, viewer), the frame's edge histogram
+//                                              k_dispersion_chunk   16 blocks of 1024 positions of a row: block-ordered partial sums,
+//                                                               the row's integers by integer atomics
+//                                              k_dispersion_finish  one wave per row: the blocks in order, the frames' histograms added
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

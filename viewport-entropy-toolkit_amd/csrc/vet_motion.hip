@@ -24,6 +24,7 @@
 // No CPU compute path; nothing here reads the environment.
 #include "vet_host.hpp"
 #include "vet_common.hpp"
+#include "vet_angle.hpp"
 #include "vet_rank.hpp"
 
 #include <algorithm>
@@ -45,7 +46,7 @@ constexpr unsigned long long MO_ABSENT = ~0ull;
 // k_motion_angles — stage 1.  MODE 0: (mu, mv) quantised by sample_dir, 1: ids, both [T][U] -> angles [P][U]; 2: dirs [U][T]
 // (k_user_dirs) -> angles [U][P].  One thread per output in a grid-stride loop: consecutive threads read consecutive samples of
 // both frames and write consecutive angles.  The two unit vectors are gathered from the table (L2-resident at the reference grid);
-// ids that differ compare the raw Vectors only when the cosine is near 1.  status[0] counts a sample outside [0, 1] once: as the
+// ids that differ compare the raw Vectors only when the cosine is near 1 (motion_angle, vet_angle.hpp).  status[0] counts a sample outside [0, 1] once: as the
 // earlier frame of its pair, or as the later frame where it is the earlier frame of none.
 // ------------------------------------------------------------------------------------------
 struct MotionAnglesParams {
@@ -58,20 +59,6 @@ struct MotionAnglesParams {
     double* angles;
     int32_t* status;             // [2] or null
 };
-
-__device__ __forceinline__ double motion_angle(int ia, int ib, const double* unit, const double* raw) {
-    if (ia < 0 || ib < 0) return __builtin_nan("");
-    if (ia == ib) return 0.0;
-    const double* A = unit + 3L * ia;
-    const double* B = unit + 3L * ib;
-    const double c = fma(A[2], B[2], fma(A[1], B[1], A[0] * B[0]));
-    if (c > 0.999999) {          // the same Vector under another id (the pole rows of a grid): still
-        const double* ra = raw + 3L * ia;
-        const double* rb = raw + 3L * ib;
-        if (ra[0] == rb[0] && ra[1] == rb[1] && ra[2] == rb[2]) return 0.0;
-    }
-    return acos(clip_unit(c));
-}
 
 template <int MODE>
 __global__ __launch_bounds__(MO_THREADS) void k_motion_angles(const MotionAnglesParams p) {
@@ -124,20 +111,6 @@ __device__ __forceinline__ const double* mo_row(const MotionRows& g, long row) {
     }
     return g.angles + row * (long)g.stride * g.U;
 }
-
-// bin b with e[b] <= a < e[b + 1], -1 outside the edges
-__device__ __forceinline__ int mo_bin(const double* e, int B, double a) {
-    if (B <= 0 || !(a >= e[0]) || !(a < e[B])) return -1;
-    int lo = 0, hi = B;                                          // e[lo] <= a < e[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a >= e[mid]) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the four waves' sums of a block in order
-__device__ __forceinline__ double mo_block_total(const double* w) { return ((w[0] + w[1]) + w[2]) + w[3]; }
 
 // lerp_quantile's rule between two order statistics, as one explicit fma so that both shapes give the same bits
 __device__ __forceinline__ void mo_rank_of(double q, int N, double& pos, int& i) {

@@ -88,6 +88,7 @@ SIGNATURES = {
     "vet_test_coverage_chunk_rows": (_I, [_P, _I]),
     "vet_test_markov_chunk_rows": (_I, [_P, _I]),
     "vet_test_motion_lds_values": (_I, [_P, _I]),
+    "vet_test_dispersion_tile": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -132,6 +133,9 @@ SIGNATURES = {
     "vet_head_motion": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vet_head_motion_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vet_head_motion_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "vet_dispersion": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_dispersion_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_dispersion_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -419,6 +423,11 @@ class Engine:
         16384), longer rows run the chunked shape; results do not depend on it (include/vet.h: vet_test_motion_lds_values)."""
         _check(self.lib, self.lib.vet_test_motion_lds_values(self.handle, int(n)))
 
+    def test_dispersion_tile(self, n: int = 0):
+        """Test switch: the pair kernel of the dispersion call stages at most ``n`` viewers of a frame in LDS at a time (0: the
+        default, 1024); results do not depend on it (include/vet.h: vet_test_dispersion_tile)."""
+        _check(self.lib, self.lib.vet_test_dispersion_tile(self.handle, int(n)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -464,7 +473,7 @@ class DeviceResult:
             pass
 
 
-_F64, _I32 = np.float64, np.int32
+_F64, _I32, _NP_I64 = np.float64, np.int32, np.int64
 # The eleven row calls.  Plan method -> (C symbol stem: the (mu, mv) device entry, + "_ids", + "_host"; window and stride count
 # frame pairs, not frames (T - 1 of them, or T - lag for the call that takes a lag between the two frames of a pair); window=None is
 # all of them; VET_ERR_EMPTY is a result (check=False); outputs).  An output is
@@ -508,6 +517,16 @@ _MOTION_CALLS = {
     True: ("vet_head_motion", True, True, False,
            (("stats", "4UR", _F64, False), ("quantiles", "URQ", _F64, True), ("hist", "URH", _I32, True), ("still", "UR", _I32, False),
             ("samples", "UR", _I32, False))),
+}
+
+# The dispersion call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dim H:
+# histogram bins).  Rows count frames; its extra arguments are per_user and the host edges with their number of bins.
+_DISPERSION_CALLS = {
+    False: ("vet_dispersion", False, True, False,
+            (("stats", "3R", _F64, False), ("centroid", "R3", _F64, False), ("hist", "RH", _NP_I64, True), ("counts", "4R", _NP_I64, False))),
+    True: ("vet_dispersion", False, True, False,
+           (("stats", "3UR", _F64, False), ("centroid", "UR3", _F64, False), ("hist", "URH", _NP_I64, True),
+            ("counts", "4UR", _NP_I64, False))),
 }
 
 
@@ -972,6 +991,30 @@ class Plan:
         return self._row_host(_MOTION_CALLS[bool(per_user)], mu, mv, ids, window, stride, want, check,
                               extra=(lag, int(bool(per_user)), _ptr(f), Q, _ptr(e), B), extra_dims={"Q": Q, "H": B}, pair_lag=lag)
 
+    @staticmethod
+    def _dispersion_edges(edges, per_user=False):
+        """edges float64 [B + 1] or None, as the C entry takes them; ``ValueError`` unless there are 1 <= B <= 64 bins between finite,
+        strictly ascending edges, and none with ``per_user`` (the per-viewer layout has no histogram)."""
+        if edges is None:
+            return None
+        if per_user:
+            raise ValueError("edges: the per-viewer layout has no histogram (pass edges=None with per_user)")
+        return Plan._motion_arrays(None, edges)[1]
+
+    def dispersion(self, mu=None, mv=None, ids=None, window=1, stride=1, per_user=False, edges=None, check=True):
+        """How tightly the audience looks together (include/vet.h: vet_dispersion): a pair sample is two viewers present in the same
+        frame, its angle (radians) the great-circle angle between their directions — the reference's ``vector_angle_distance``, +0.0
+        exactly where the two Vectors are the same.  Row r pools the pair samples of frames [r * stride, r * stride + window), or
+        with ``per_user`` row (u, r) holds them from viewer u's side (outputs user-major, a leading U axis).  ``window=None`` is
+        the whole video.  Returns dict(stats[3,R] (mean, max, nearest: the mean angle to the nearest partner), centroid[R,3] (the
+        sum of the present viewers' unit vectors), hist[R,B]|None (``edges``: B + 1 ascending values in radians, bins half-open;
+        pooled only), counts[4,R] int64 (samples, same, slots, present), code), R = (T - window) // stride + 1.  A row that never
+        has two viewers in one frame is NaN with ``samples`` 0 — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        e = self._dispersion_edges(edges, per_user)
+        B = 0 if e is None else int(e.size) - 1
+        return self._row_host(_DISPERSION_CALLS[bool(per_user)], mu, mv, ids, window, stride, {"hist"} if e is not None else set(),
+                              check, extra=(int(bool(per_user)), _ptr(e), B), extra_dims={"H": B})
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1164,6 +1207,17 @@ class Plan:
                          (window, stride, lag, int(bool(per_user)), f.ctypes.data if f is not None else 0, 0 if f is None else f.size,
                           e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1), d_stats,
                          (d_quantiles, d_hist, d_still, d_samples, d_status), stream)
+
+    def dispersion_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, per_user: bool, edges,
+                          d_stats: int = 0, d_centroid: int = 0, d_hist: int = 0, d_counts: int = 0, d_status: int = 0, stream=None,
+                          d_ids: int = 0):
+        """``edges``: the host sequence [B + 1] in radians (or None); d_stats f64 [3][Rows]; d_centroid f64 [Rows][3]; d_hist i64
+        [Rows][B]; d_counts i64 [4][Rows]; Rows = R, or U * R user-major with ``per_user``; every output may be 0 (include/vet.h:
+        vet_dispersion; ``d_ids``: vet_dispersion_ids)."""
+        e = self._dispersion_edges(edges, per_user)
+        self._row_device(_DISPERSION_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, int(bool(per_user)), e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1),
+                         d_stats or None, (d_centroid, d_hist, d_counts, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

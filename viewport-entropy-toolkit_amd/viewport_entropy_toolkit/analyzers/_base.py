@@ -611,5 +611,71 @@ class _EntropyAnalyzerBase:
             raise ValidationError("Normalized coordinates must be between 0 and 1")
         return self._motion_frame(times, names, window, stride, lag, bool(per_user), res, quantiles, bins_deg)
 
+    @staticmethod
+    def _dispersion_frame(times, names, window: int, stride: int, per_user: bool, res: dict, bins_deg) -> pd.DataFrame:
+        """The dispersion statistics as a DataFrame in DEGREES, one row per window (``per_user``: per (user, window), user-major,
+        ``user`` first): ``center`` of a row is the [3] view of its mean direction (NaN where the centroid is zero) and, where
+        ``res`` holds it, ``hist`` the [B] view ``res["hist"][row]`` (no copy of the counts)."""
+        times = np.asarray(times)
+        stats = np.degrees(np.asarray(res["stats"], dtype=np.float64)).reshape(3, -1)
+        counts = np.asarray(res["counts"]).reshape(4, -1)
+        samples, same, present = counts[0], counts[1], counts[3]
+        centroid = np.asarray(res["centroid"], dtype=np.float64).reshape(-1, 3)
+        rows = len(samples)
+        R = rows // len(names) if per_user else rows
+        first = np.arange(R, dtype=np.int64) * stride
+        if per_user:
+            first = np.tile(first, len(names))
+        cols = {}
+        if per_user:
+            cols["user"] = np.repeat(np.asarray(list(names), dtype=object), R)
+        length = np.sqrt((centroid * centroid).sum(axis=1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            share = np.where(samples > 0, same / np.maximum(samples, 1), np.nan)
+            resultant = np.where(present > 0, np.minimum(length / np.maximum(present, 1), 1.0), np.nan)
+            center = np.where(length[:, None] > 0, centroid / length[:, None], np.nan)
+        c_col = np.empty(rows, dtype=object)
+        for r in range(rows):
+            c_col[r] = center[r]
+        cols.update(time=times[first], time_end=times[first + window - 1], samples=samples, same=same, same_share=share,
+                    mean=stats[0], max=stats[1], nearest=stats[2], present=present, resultant=resultant, center=c_col)
+        if res.get("hist") is not None:
+            hist = np.asarray(res["hist"]).reshape(rows, -1)
+            h_col = np.empty(rows, dtype=object)
+            for r in range(rows):
+                h_col[r] = hist[r]
+            cols["hist"] = h_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(bins_deg=None if bins_deg is None else tuple(bins_deg), users=list(names), window=window, stride=stride)
+        return df
+
+    def compute_dispersion(self, window: Optional[int] = 1, stride: int = 1, per_user: bool = False, bins_deg=None) -> pd.DataFrame:
+        """How tightly the audience looks together: a pair sample is two viewers present in the same frame, its angle the
+        great-circle angle between their viewing directions (the reference's ``vector_angle_distance``; exactly 0 for two samples
+        with the same Vector, which count as ``same``).  Row r pools the pair samples of the frames
+        [r * stride, r * stride + window), or with ``per_user`` holds them from each viewer's own side.  ``window`` and ``stride``
+        count frames; ``window=None`` is the whole video.  Independent of the tiling.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame in DEGREES (``compute_entropy``'s results are left
+        alone), one row per window — user-major with ``user`` first when ``per_user``: ``time`` / ``time_end`` (the first / last
+        frame of the row), ``samples`` (pairs; per viewer: partners), ``same``, ``same_share``, ``mean``, ``max`` (the audience's
+        angular diameter; per viewer: the farthest partner), ``nearest`` (the mean angle to the nearest partner: small for a
+        clustered crowd), ``present``, ``resultant`` (the length of the mean unit vector, in [0, 1]: 1 = everybody looks one way;
+        per viewer: the viewer stays put), ``center`` (a [3] unit-vector view of the mean direction, NaN where it is undefined)
+        and, with ``bins_deg`` (ascending edges in degrees, half-open bins; pooled only), ``hist`` (a [B] view of counts).
+        ``attrs`` hold ``bins_deg``, ``users``, ``window`` and ``stride``.  A window that never has two viewers in one frame is
+        NaN with ``samples`` 0 — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside
+        [0, 1], ``ValueError`` for an illegal ``window`` / ``stride`` / ``bins_deg`` and for ``per_user`` with ``bins_deg``."""
+        times, names, call = self._row_call("dispersion")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        _, bins_deg = self._motion_args((), bins_deg)
+        if per_user and bins_deg is not None:
+            raise ValueError("bins_deg: the per-viewer layout has no histogram (pass bins_deg=None with per_user)")
+        res = call(window=window, stride=stride, per_user=bool(per_user), edges=None if bins_deg is None else np.radians(bins_deg),
+                   check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._dispersion_frame(times, names, window, stride, bool(per_user), res, bins_deg)
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError
