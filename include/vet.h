@@ -284,6 +284,26 @@ int vet_plan_table_cap(const vet_plan *plan, int lattice, int64_t *overflow_rows
 int vet_plan_record_bytes(const vet_plan *plan);
 int vet_plan_read_records(vet_plan *plan, uint32_t *h_rec32);
 int vet_plan_last_formulation(const vet_plan *plan, int lattice);
+/* The table kernel (k_spatial_lut instantiation) and launch geometry of the plan's last table launch, as the launch decided
+ * them: read-only introspection for tests, 0 before any table launch (formulations `table` and `ftable`; the other
+ * formulations leave the word as it is).  Fields: */
+#define VET_TK_LAUNCHED  0x00000001u /* a table kernel has been launched */
+#define VET_TK_NB_SHIFT  1           /* bits 1..2: blocks of a capped row (1..3: the fixed-trip kernels), 0 = whole rows */
+#define VET_TK_NB_MASK   0x3u
+#define VET_TK_REC32     0x00000008u /* the 4-byte direction record (vet_plan_record_bytes) */
+#define VET_TK_BUCKETED  0x00000010u /* bucket-ordered row lists */
+#define VET_TK_DEDUP     0x00000020u /* the per-frame set of distinct rows */
+#define VET_TK_IL        0x00000040u /* class-dealt (interleaved) rows */
+#define VET_TK_OCC8      0x00000080u /* the instantiation bounded to 8 workgroups per CU */
+#define VET_TK_FP_TABLE  0x00000100u /* FP32 table (`ftable`) */
+#define VET_TK_FUSED     0x00000200u /* the plan's fused table: one row over all lattices */
+#define VET_TK_NARROW    0x00000400u /* fused only: the 8-lane kernel (32-entry blocks), else the 16-lane one */
+#define VET_TK_FROM_IDS  0x00000800u /* samples given as direction ids (vet_spatial_entropy_ids) */
+#define VET_TK_BATCH     0x00001000u /* one launch over the videos of a batch */
+#define VET_TK_CHUNKED   0x00002000u /* the users of a frame ran in more than one chunk (0 for a batch: per video there) */
+#define VET_TK_FPW_SHIFT 16          /* bits 16..23: frames per workgroup (0 for a batch: per video there) */
+#define VET_TK_FPW_MASK  0xFFu
+uint32_t vet_plan_last_table_kernel(const vet_plan *plan);
 int vet_plan_error_bounds(vet_plan *plan, int lattice, double *table_bound, double *sweep_bound);
 /* Parity hooks: read back the device-built tables (synchronous). */
 int vet_plan_read_dirs(vet_plan *plan, double *h_xyz /* [n_dirs*3] rounded Vector xyz */);

@@ -10,8 +10,8 @@ table's own histogram must be the same BYTES.
 
 What this file can and cannot tell.  record_bytes() and last_formulation() assert that the compact record's table kernel served
 a call; they are equally true of that kernel in arrival order, and since the two orders give the same bytes by design, NOTHING
-here can tell the bucket-ordered kernel from the arrival-ordered one: the library has no read-back of which of the two a launch
-took (its exported symbols and environment variables are pinned, tests/test_cabi_symbols.py).  By the launch rule (launch_lut:
+here can tell the bucket-ordered kernel from the arrival-ordered one (tests/test_row_cap_blocks.py does, through
+Plan.last_table_kernel(): it asserts which of the two each of its launches took).  By the launch rule (launch_lut:
 compact record, one frame per workgroup, users in one chunk) every single-video call below of at most 2 048 users — each has
 fewer than 4 * CUs frames, hence one frame per workgroup — runs the bucket-ordered kernel, and a wrong placement, count or scan
 there breaks the byte comparison; a regression of the rule itself back to the arrival order would pass.  Two-chunk frames

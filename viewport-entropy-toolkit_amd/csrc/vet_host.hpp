@@ -268,6 +268,8 @@ struct vet_plan {
     bool ultra = false;            // some lattice has ultra-tiny in-FoV weights: FP64 formulations only (plan-wide)
     bool fp64 = false;             // vet_plan_set_fp64: weighted Fibonacci lattices run `dtable` or `precise` only
     size_t exact_bytes = 0;        // device bytes of the exact weight rows of all lattices (one cap for the plan)
+    uint32_t last_table_kernel = 0;// the k_spatial_lut instantiation and geometry of the last table launch (launch_lut,
+                                   // launch_lut_fused; include/vet.h: VET_TK_*), 0 = none yet
 };
 
 namespace vh {

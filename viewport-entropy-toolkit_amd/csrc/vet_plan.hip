@@ -808,6 +808,8 @@ int vet_plan_last_formulation(const vet_plan* pl, int k) {
     return pl->lat[k].last_form;
 }
 
+uint32_t vet_plan_last_table_kernel(const vet_plan* pl) { return pl ? pl->last_table_kernel : 0; }
+
 int vet_plan_error_bounds(vet_plan* pl, int k, double* table_bound, double* sweep_bound) {
     if (!pl) return fail(VET_ERR_INVALID, "plan is NULL");
     if (k < 0 || k >= (int)pl->lat.size()) return fail(VET_ERR_INVALID, "lattice index %d out of range", k);

@@ -345,6 +345,16 @@ struct LutProbe {
 };
 #endif
 
+// vet_plan_last_table_kernel's word (include/vet.h: VET_TK_*) from the decisions of a launch as it made them.  fpw and chunked:
+// of a single video; a batch keeps them per video in its descriptors, the word has 0 there.
+uint32_t table_kernel_word(int nb, bool rec32, bool bucketed, bool dedup, bool il, bool occ8, bool fpt, bool fused, bool narrow,
+                           bool from_ids, bool batch, int fpw, bool chunked) {
+    return VET_TK_LAUNCHED | (uint32_t)nb << VET_TK_NB_SHIFT | (rec32 ? VET_TK_REC32 : 0) | (bucketed ? VET_TK_BUCKETED : 0) |
+           (dedup ? VET_TK_DEDUP : 0) | (il ? VET_TK_IL : 0) | (occ8 ? VET_TK_OCC8 : 0) | (fpt ? VET_TK_FP_TABLE : 0) |
+           (fused ? VET_TK_FUSED : 0) | (narrow ? VET_TK_NARROW : 0) | (from_ids ? VET_TK_FROM_IDS : 0) |
+           (batch ? VET_TK_BATCH : 0) | (batch ? 0 : (uint32_t)fpw << VET_TK_FPW_SHIFT) | (!batch && chunked ? VET_TK_CHUNKED : 0);
+}
+
 // one launch of the table kernel over lattices lat_idx[0..K) of the plan (single video or a batch)
 template <bool FROM_IDS>
 int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& src, int U, int T,
@@ -434,6 +444,8 @@ int launch_lut(vet_plan* pl, const int* lat_idx, int K, const vet::SampleSrc& sr
 #if VET_STAGE_CYCLES
     if (int rc = probe.report(s, rec32 ? "rec32" : nb ? "capped" : fpt ? "fp table" : "lattices", q.FPW, lds)) return rc;
 #endif
+    pl->last_table_kernel = table_kernel_word(nb, rec32, bucketed, dedup, il, occ8 && !fpt, fpt, false, false, FROM_IDS,
+                                              d_videos != nullptr, q.FPW, U > q.UC);
     *launched = true;
     return VET_OK;
 }
@@ -490,6 +502,8 @@ int launch_lut_fused(vet_plan* pl, const vet::SampleSrc& src, int U, int T, cons
 #if VET_STAGE_CYCLES
     if (int rc = probe.report(s, "fused", q.FPW, lds)) return rc;
 #endif
+    pl->last_table_kernel = table_kernel_word(0, false, false, dedup, F.interleaved, occ8, false, true, F.gs_log2 == 3, FROM_IDS,
+                                              d_videos != nullptr, q.FPW, U > q.UC);
     *launched = true;
     return VET_OK;
 }

@@ -108,6 +108,7 @@ SIGNATURES = {
     "vet_plan_record_bytes": (_I, [_P]),
     "vet_plan_read_records": (_I, [_P, _P]),
     "vet_plan_last_formulation": (_I, [_P, _I]),
+    "vet_plan_last_table_kernel": (C.c_uint32, [_P]),
     "vet_plan_error_bounds": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_D)]),
     "vet_plan_read_dirs": (_I, [_P, _P]),
     "vet_plan_read_nearest": (_I, [_P, _I, _P]),
@@ -639,6 +640,16 @@ class Plan:
     def last_formulation(self, lattice: int = 0) -> str:
         """'table' | 'sweep' | 'precise' | 'ftable' | 'dtable' of the last weighted call ('' before any)."""
         return FORMULATIONS.get(int(self.lib.vet_plan_last_formulation(self.handle, lattice)), "")
+
+    def last_table_kernel(self) -> dict:
+        """The table kernel and geometry of the plan's last table launch (include/vet.h: vet_plan_last_table_kernel, VET_TK_*);
+        {} before any.  ``fpw`` and ``chunked`` are per video in a batch launch and 0 / False there."""
+        w = int(self.lib.vet_plan_last_table_kernel(self.handle))
+        if not w & 1:
+            return {}
+        return dict(nb=(w >> 1) & 3, rec32=bool(w & 0x8), bucketed=bool(w & 0x10), dedup=bool(w & 0x20), il=bool(w & 0x40),
+                    occ8=bool(w & 0x80), fp_table=bool(w & 0x100), fused=bool(w & 0x200), narrow=bool(w & 0x400),
+                    from_ids=bool(w & 0x800), batch=bool(w & 0x1000), chunked=bool(w & 0x2000), fpw=(w >> 16) & 0xFF)
 
     def error_bounds(self, lattice: int = 0):
         """(table bound, sweep bound): proven worst-case relative entropy error of the integer formulations."""
