@@ -66,7 +66,9 @@ extern "C" {
                           vet_head_motion* entry points (angular speed of the heads: moments, exact quantiles and a histogram of the
                           angle between a viewer's directions `lag` frames apart, per window and per viewer), and then the
                           vet_dispersion* entry points (audience dispersion: the angle between two viewers' directions in one
-                          frame over all pairs, per window and per viewer) */
+                          frame over all pairs, per window and per viewer), and then the vet_saliency* entry points (saliency
+                          maps: the spherical kernel density of a window's viewing directions on an equirectangular map, with its
+                          mass, peak, entropy and effective area, per window and per viewer) and vet_test_saliency_tile */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -152,6 +154,9 @@ int vet_test_motion_lds_values(vet_ctx *ctx, int n);
  * a time from 1024 to n (at most 1024), so that a small audience runs several tiles; 0 restores the default.  Read at every launch.
  * Results are bit-identical whatever the value. */
 int vet_test_dispersion_tile(vet_ctx *ctx, int n);
+/* Test switch, not a tuning knob: n > 0 lowers the most list entries of a row that k_saliency_map (vet_saliency*) stages in LDS at
+ * a time (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
+int vet_test_saliency_tile(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -1113,6 +1118,78 @@ int vet_dispersion_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_
 int vet_dispersion_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
                         int window, int stride, int per_user, const double *h_edges, int B, double *h_stats, double *h_centroid,
                         int64_t *h_hist, int64_t *h_counts);
+
+/* ---- saliency maps: the spherical kernel density of attention per window and per viewer ------------------
+ * Not in the reference, and independent of the lattices: only the plan's direction table is read.  The continuous counterpart of
+ * the tile heatmaps: a smooth density of viewing directions on the sphere per segment of the video, comparable across tilings.
+ * PRESENCE, samples and direction ids exactly as in vet_head_motion / vet_dispersion: an absent sample, or one outside [0, 1] (an id
+ * at or beyond the table's size), is counted in status[0] and contributes nothing.
+ * MAP GRID: W x H cells, equirectangular, laid out as vet_heatmap_create lays out pixels: column c has lon = (c + 0.5) / W * 360 -
+ * 180, row y has lat = 90 - (y + 0.5) / H * 180 (row 0 is the top).  P(c, y) is the unrounded Vector.from_spherical(lon, lat) of the
+ * cell centre by the heatmap's arithmetic: theta = lon * (pi / 180), phi = (90 - lat) * (pi / 180), x = sin(phi) cos(theta),
+ * y = sin(phi) sin(theta), z = cos(phi), divided by sqrt(x*x + y*y + z*z) (no fused operation).  The W cosines and sines of theta and
+ * the H sines and cosines of phi are taken ONCE ON THE HOST (the C library's sin / cos) and the products, the root and the
+ * divisions on the device.  The cell's share of the sphere is a_y = (cos(pi*y/H) - cos(pi*(y+1)/H)) / (2*W), a host-built [H] FP64
+ * table (sum over the map: 1).
+ * KERNEL: kappa = 1 / sigma^2, sigma in radians, computed once on the host in FP64.  With A a row of the plan's unit table (as in
+ * vet_head_motion):  c = fma(P.z, A.z, fma(P.y, A.y, P.x * A.x)),  k(P, A) = exp(kappa * (c - 1))  (ocml exp; the product and the
+ * difference are not fused) — the von Mises-Fisher kernel, for small angles the Gaussian exp(-theta^2 / (2 sigma^2)).  Smooth over
+ * the whole sphere, no acos, NO TRUNCATION: a cut-off radius would make the value discontinuous in c.
+ * ROWS: R = vet_window_rows(n_frames, window, stride); row r covers frames [r*stride, r*stride + window).  per_user = 0: the row
+ * pools all viewers, Rows = R.  per_user = 1: Rows = n_users * R, row index u * R + r, viewer u's own samples.  The row's LIST is the
+ * distinct direction ids among its present samples in ASCENDING id, each with its multiplicity m (an integer).  Ids are collapsed by
+ * id, not by Vector equality: pole ids that share a Vector stay separate entries.  N = sum of m; distinct = the list's length.
+ * MAP VALUE: S(r, p) starts at +0.0; over the LIST in ascending id, S = fma((double)m, k(P_p, A_id), S) — one sequential sum per
+ * pixel.  M(r, p) = S * g_r: scale 0: g = 1 and the multiply is skipped; scale 1: g = 1 / (double)N; scale 2: g = C / (double)N with
+ * C = kappa / (2 pi (1 - exp(-2 kappa))), a host FP64 constant: a density per steradian whose integral is 1.  g is one division, the
+ * product one multiply.
+ * ROW STATISTICS, from M.  FP sums use vet_head_motion's rule with the map's pixels in row-major order as the positions: blocks of
+ * 1024, thread t of 256 adds t, t + 256, t + 512, t + 768 in that order, the lanes combine by wave_sum, then the four waves in
+ * order, then the blocks in ascending order.
+ *   mass       = sum_p M_p * a_y, the map's mean over the sphere (a_y is a share: the a_y of all cells add up to 1).  At scale 2,
+ *              a density per steradian, 4 pi * mass is the integral over the sphere: close to 1, mass close to 1 / (4 pi) =
+ *              0.0796, when the grid resolves sigma — the caller's resolution check
+ *   peak       = the largest M_p; peak_index = the smallest pixel index (y * W + c) that holds it
+ *   entropy    with w_p = M_p * a_y and Wsum = sum_p w_p (the rule; the same bits as mass): q_p = w_p / Wsum,
+ *              t_p = q_p * log2(q_p / a_y) (ocml log2), 0 where w_p == 0; entropy = -(sum_p t_p) by the rule.  Bits; <= 0 up to
+ *              rounding; 0 = uniform over the sphere
+ *   area       = exp2(entropy), the effective share of the sphere (per viewer: the exploration ratio)
+ * A row with N = 0 has a +0.0 map, NaN statistics, peak_index = -1, samples = distinct = 0: data, not an error; counted in status[1].
+ * A value's bits depend on the plan, W, H, sigma, scale, window, the layout and the row's frames only — not on stride, the number of
+ * rows, the video's length, the entry point, which optional outputs were asked for, the row chunk, or vet_test_saliency_tile.  No FP
+ * atomics.
+ * Outputs, each nullable:
+ *   d_map      [Rows][H][W] f64: M
+ *   d_stats    [4][Rows] f64, statistic-major: 0 mass, 1 peak, 2 entropy, 3 area
+ *   d_peak     [Rows] i32: peak_index
+ *   d_counts   [2][Rows] i64: 0 samples (N), 1 distinct
+ *   d_status   [2] i32 {bad, #rows with N = 0}; the call ADDS, the caller zeroes
+ * With d_map NULL nothing of [Rows][H][W] exists: the maps of a pass of rows live in the workspace, and a pass (its lists, and its
+ * maps when d_map is NULL) stays under a 256 MB budget.  With d_map, d_stats and d_peak all NULL no map is computed.
+ * Stages: the samples quantised once into direction ids ([T][U]; per viewer k_user_dirs' transposed [U][T], so a row is a contiguous
+ * slice in both); the lists — rows of up to 4096 positions by k_saliency_sort (one workgroup per row: LDS bitonic sort, run lengths),
+ * longer rows by integer atomics into a dense u32 [D] row (tables of up to 32768 directions: per workgroup in LDS first) and
+ * k_saliency_compact in ascending id; k_saliency_map — workgroup = (row,
+ * 256 pixels), thread = pixel with P in registers, the list staged in LDS in tiles of 1024 entries (32 B: unit vector and the
+ * multiplicity as a double; every lane reads the same address, a broadcast), S in a register across tiles: 69 VGPRs, no scratch,
+ * 32 KB LDS, 5 waves per SIMD (LDS-bound); k_saliency_rows — one workgroup per row.  Overlapping windows rebuild each row's list.
+ * Workspace: 4 B per sample + per row of a pass 8 B per list slot (min(positions, directions)), the dense counts on the long path.
+ * VET_ERR_INVALID (before anything is allocated or launched): window < 1, window > n_frames, stride < 1, sigma_rad not finite, <= 0
+ * or > pi, W outside [2, 4096], H outside [1, 2048], scale outside {0, 1, 2}.  VET_ERR_UNSUPPORTED: pooled, n_frames * n_users above
+ * 256 * (2^31 - 1) (one workgroup per 256 samples); per viewer, n_frames above 65535 * 64 (k_user_dirs' grid).
+ * Profile ids: k_saliency_map to k_spatial, the other stages to k_transition.  Asynchronous on `stream`. */
+int vet_saliency(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                 int per_user, double sigma_rad, int W, int H, int scale, double *d_map, double *d_stats, int32_t *d_peak,
+                 int64_t *d_counts, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_saliency_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int per_user,
+                     double sigma_rad, int W, int H, int scale, double *d_map, double *d_stats, int32_t *d_peak, int64_t *d_counts,
+                     int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_saliency_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                      int window, int stride, int per_user, double sigma_rad, int W, int H, int scale, double *h_map, double *h_stats,
+                      int32_t *h_peak, int64_t *h_counts);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

@@ -21,6 +21,9 @@
 //                       angles) and their launch logic
 //   vet_dispersion.hip  the audience dispersion (the angle between two viewers' directions in one frame over all pairs: per (frame,
 //                       viewer) partials from unit vectors staged in LDS, then per row the block-ordered sums) and its launch logic
+//   vet_saliency.hip    the saliency maps (the spherical kernel density of a row's viewing directions on an equirectangular map: the
+//                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics) and
+//                       their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -155,6 +158,9 @@ struct Tuning {
     int dispersion_tile = 0;        // vet_test_dispersion_tile (no environment variable): the most viewers of a frame that
                                 // k_dispersion_pairs stages in LDS at a time (0 = 1024); read at every launch; the results do not
                                 // depend on it (test_dispersion_gpu.py)
+    int saliency_tile = 0;          // vet_test_saliency_tile (no environment variable): the most list entries of a row that
+                                // k_saliency_map stages in LDS at a time (0 = 1024); read at every launch; the results do not
+                                // depend on it (test_saliency_gpu.py)
     void from_environment();
 };
 
@@ -438,6 +444,7 @@ int group_set_attrs(vet_ctx* c);
 int markov_set_attrs(vet_ctx* c);
 int motion_set_attrs(vet_ctx* c);
 int dispersion_set_attrs(vet_ctx* c);
+int saliency_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -509,6 +516,10 @@ int check_motion_args(const vet_plan* pl, int U, int T, int window, int stride, 
 // vet_dispersion.hip: what vet_dispersion* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched.  edges [B + 1] is host memory.
 int check_dispersion_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, const double* edges, int B);
+
+// vet_saliency.hip: what vet_saliency* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched.
+int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, double sigma, int W, int H, int scale);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

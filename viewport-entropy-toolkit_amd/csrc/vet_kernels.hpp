@@ -67,6 +67,14 @@
 //                                              k_dispersion_chunk   16 blocks of 1024 positions of a row: block-ordered partial sums,
 //                                                               the row's integers by integer atomics
 //                                              k_dispersion_finish  one wave per row: the blocks in order, the frames' histograms added
+//   vet_saliency.hip    (in the unit)          k_saliency_ids   the pooled layout's direction ids, frame-major (per viewer: k_user_dirs)
+//                                              k_saliency_sort  one workgroup per row of up to 4096 positions: LDS sort of the ids, the
+//                                                               distinct ids in ascending order with their run lengths
+//                                              k_saliency_count, k_saliency_compact   longer rows: dense integer counts per direction,
+//                                                               compacted in ascending id by one workgroup per row
+//                                              k_saliency_map   workgroup = (row, 256 pixels): the row's list staged in LDS in tiles of
+//                                                               1024 entries, S = fma(m, exp(kappa (c - 1)), S) per pixel in a register
+//                                              k_saliency_rows  one workgroup per row: mass, peak, entropy and area of the written map
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

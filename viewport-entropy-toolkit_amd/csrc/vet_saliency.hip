@@ -1,0 +1,543 @@
+// vet_saliency.hip — saliency maps behind vet_saliency* (include/vet.h): the spherical kernel density of the viewing directions of a
+// window of frames on a W x H equirectangular map, pooled or per viewer, and the row statistics taken from it (mass, peak,
+// differential entropy against the uniform sphere, effective area).  Lattice-independent: only the plan's direction table is read.
+// Stage 0, k_saliency_ids / k_user_dirs: every sample quantised once (sample_dir) into direction ids — frame-major [T][U] for the
+// pooled layout, transposed [U][T] for the per-viewer layout, so that a row's positions are a contiguous slice in both.
+// Stage 1, the row LISTS: the distinct ids of a row in ascending id with their multiplicities.  Rows of up to 4096 positions:
+// k_saliency_sort, one workgroup per row — lds_bitonic_sort of the ids (absent = the largest key), the heads of the runs compacted in
+// order, a head's multiplicity its run length.  Longer rows: k_saliency_count adds into a dense u32 [D] row of the workspace by
+// integer atomics (direction tables of up to 32768 entries: counted per workgroup in LDS first) and k_saliency_compact, one
+// workgroup per row, walks it in ascending id.
+// Stage 2, k_saliency_map: workgroup = (row, 256 pixels), thread = pixel with its direction P in registers.  The row's list is
+// staged in LDS in tiles of up to 1024 entries (32 B each: the unit vector and the multiplicity as a double); every lane reads the
+// same LDS address — a broadcast — and S = fma(m, exp(kappa * (c - 1)), S) stays in a register across the tiles.  P is built from
+// the host's per-column / per-row sines and cosines (five small tables in the workspace) by the heatmap's arithmetic.
+// Stage 3, k_saliency_rows: one workgroup per row over the written map: vet_head_motion's summation rule on the pixels in row-major
+// order (blocks of 1024; thread t adds t, t + 256, t + 512, t + 768; wave_sum; the four waves in order; the blocks ascending) for
+// the mass and the entropy, the peak as the largest (value bits, smallest index).  No FP atomics.  Rows run in passes under a 256 MB
+// workspace budget; with d_map NULL the maps of a pass live in the workspace only.
+// No CPU compute path; nothing here reads the environment.
+#include "vet_host.hpp"
+#include "vet_common.hpp"
+#include "vet_angle.hpp"
+#include "vet_rank.hpp"
+#include "vet_user_dirs.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace vet {
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_TILE = 1024;           // list entries per LDS tile (32 KB)
+constexpr int SM_BLOCK = 1024;          // positions of one block of the summation rule: four per thread
+constexpr int SM_SORT_MAX = 4096;       // positions of a row that k_saliency_sort takes (16 KB of keys)
+constexpr int SM_LDS_DIRS = 32768;      // direction tables up to this size are counted in LDS by k_saliency_count (128 KB)
+constexpr int SM_PART = 256;            // doubles of the host tables that one k_saliency_tables launch carries
+
+struct SalEntry {                       // one staged list entry
+    double x, y, z, m;
+};
+
+// the host tables, a launch argument at a time: ct [W], st [W] (cos / sin of the column's longitude), sp [H], cp [H] (sin / cos of
+// the row's polar angle), ay [H] (the cell's share of the sphere)
+struct SalTablePart {
+    double v[SM_PART];
+    double* dst;
+    int n;
+};
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_tables(const SalTablePart p) {
+    const int i = threadIdx.x;
+    if (i < p.n) p.dst[i] = p.v[i];
+}
+
+// k_saliency_ids — stage 0 of the pooled layout: ids [T][U], status[0] raised once per sample outside [0, 1].
+template <bool FROM_IDS>
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_ids(const SampleSrc src, const long n, int32_t* __restrict__ ids,
+                                                             int32_t* status) {
+    const long i = (long)blockIdx.x * SM_THREADS + threadIdx.x;
+    bool bad = false;
+    if (i < n) ids[i] = sample_dir<FROM_IDS>(src, i, bad);
+    if (status) {
+        const unsigned long long anybad = __ballot(bad);
+        if (anybad && lane_id() == 0) atomicAdd(&status[0], (int)__popcll(anybad));
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// stage 1: the lists
+// ------------------------------------------------------------------------------------------
+struct SalListParams {
+    const int32_t* ids;          // [T][U], or [U][T] per viewer
+    long R, Wpos, D, cap, r0;    // rows per viewer (or of the call), positions per row, directions, list slots per row, first row
+    int U, T, stride, per_user, P;
+    uint2* list;                 // [rows of the pass][cap]: (id, multiplicity) in ascending id
+    int32_t* nlist;              // [rows of the pass] distinct
+    unsigned long long* nsamp;   // [rows of the pass] N
+    unsigned* dense;             // [rows of the pass][D], zeroed by the host (the long-row path)
+};
+
+__device__ __forceinline__ long sal_row(const SalListParams& g, long row) {  // the row's first position in ids
+    if (g.per_user) {
+        const long u = row / g.R;
+        return u * g.T + (row - u * g.R) * g.stride;
+    }
+    return row * (long)g.stride * g.U;
+}
+
+// Where the flagged threads of this step write: base + the flagged threads of lower index.  Every thread of the workgroup calls
+// it; base advances by the step's flags.  s_wc: int [4] in LDS.
+__device__ __forceinline__ int sal_slot(bool flag, int& base, int* s_wc) {
+    const unsigned long long b = __ballot(flag);
+    const int wv = wave_id();
+    if (lane_id() == 0) s_wc[wv] = (int)__popcll(b);
+    __syncthreads();
+    int off = base + below(b), tot = 0;
+#pragma unroll
+    for (int w = 0; w < SM_THREADS / WAVE; ++w) {
+        const int c = s_wc[w];
+        off += w < wv ? c : 0;
+        tot += c;
+    }
+    __syncthreads();
+    base += tot;
+    return off;
+}
+
+// k_saliency_sort — one workgroup per row of up to 4096 positions.  P = the power of two (>= 2) that holds the positions.
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_sort(const SalListParams g) {
+    __shared__ unsigned keys[SM_SORT_MAX];
+    __shared__ int s_wc[SM_THREADS / WAVE];
+    __shared__ unsigned long long s_n[SM_THREADS / WAVE];
+    const int tid = threadIdx.x;
+    const long y = blockIdx.x;
+    const int32_t* src = g.ids + sal_row(g, g.r0 + y);
+    for (int i = tid; i < g.P; i += SM_THREADS) {
+        int id = -1;
+        if (i < g.Wpos) id = src[i];
+        keys[i] = id >= 0 ? (unsigned)id : EMPTY_KEY;
+    }
+    lds_bitonic_sort(keys, g.P);
+    uint2* out = g.list + y * g.cap;
+    int base = 0;
+    unsigned long long n = 0ull;
+    for (int i0 = 0; i0 < g.P; i0 += SM_THREADS) {
+        if (keys[i0] == EMPTY_KEY) break;                        // uniform: everything behind is absent
+        const int i = i0 + tid;
+        const unsigned key = i < g.P ? keys[i] : EMPTY_KEY;
+        const bool head = key != EMPTY_KEY && (i == 0 || keys[i - 1] != key);
+        n += key != EMPTY_KEY ? 1ull : 0ull;
+        const int off = sal_slot(head, base, s_wc);
+        if (head) {
+            unsigned m = 1u;
+            while (i + (int)m < g.P && keys[i + m] == key) ++m;
+            out[off] = make_uint2(key, m);
+        }
+    }
+    n = wave_sum(n);
+    if (lane_id() == 0) s_n[wave_id()] = n;
+    __syncthreads();
+    if (tid == 0) {
+        g.nlist[y] = base;
+        g.nsamp[y] = ((s_n[0] + s_n[1]) + s_n[2]) + s_n[3];
+    }
+}
+
+// k_saliency_count — the long-row path: workgroup (x, y) strides over the positions of row r0 + y.  LDS_HIST (direction tables of up
+// to 32768 entries; dynamic LDS u32 [D]): the workgroup counts in LDS and adds its non-zero counts to the row's dense counts, one
+// integer atomic per (workgroup, direction) instead of one per sample.  Integers: exact in any order.
+template <bool LDS_HIST>
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_count(const SalListParams g) {
+    extern __shared__ unsigned s_cnt[];
+    const long y = blockIdx.y;
+    const int32_t* src = g.ids + sal_row(g, g.r0 + y);
+    unsigned* cnt = g.dense + y * g.D;
+    if (LDS_HIST) {
+        for (int i = threadIdx.x; i < g.D; i += SM_THREADS) s_cnt[i] = 0u;
+        __syncthreads();
+    }
+    for (long q = (long)blockIdx.x * SM_THREADS + threadIdx.x; q < g.Wpos; q += (long)gridDim.x * SM_THREADS) {
+        const int id = src[q];
+        if (id >= 0) atomicAdd(LDS_HIST ? &s_cnt[id] : &cnt[id], 1u);
+    }
+    if (LDS_HIST) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < g.D; i += SM_THREADS) {
+            const unsigned c = s_cnt[i];
+            if (c) atomicAdd(&cnt[i], c);
+        }
+    }
+}
+
+// k_saliency_compact — one workgroup per row: the dense counts in ascending id.
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_compact(const SalListParams g) {
+    __shared__ int s_wc[SM_THREADS / WAVE];
+    __shared__ unsigned long long s_n[SM_THREADS / WAVE];
+    const int tid = threadIdx.x;
+    const long y = blockIdx.x;
+    const unsigned* cnt = g.dense + y * g.D;
+    uint2* out = g.list + y * g.cap;
+    int base = 0;
+    unsigned long long n = 0ull;
+    for (long i0 = 0; i0 < g.D; i0 += SM_THREADS) {
+        const long i = i0 + tid;
+        const unsigned c = i < g.D ? cnt[i] : 0u;
+        n += c;
+        const int off = sal_slot(c > 0u, base, s_wc);
+        if (c > 0u) out[off] = make_uint2((unsigned)i, c);
+    }
+    n = wave_sum(n);
+    if (lane_id() == 0) s_n[wave_id()] = n;
+    __syncthreads();
+    if (tid == 0) {
+        g.nlist[y] = base;
+        g.nsamp[y] = ((s_n[0] + s_n[1]) + s_n[2]) + s_n[3];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_saliency_map — stage 2.  grid (ceil(W * H / 256), rows of the pass); thread = pixel blockIdx.x * 256 + tid of row blockIdx.y.
+// LDS: SalEntry [1024] static (32 KB).  S is the sequential sum over the list in ascending id; M = S * g_r, the multiply skipped
+// at scale 0.  A row without a sample writes +0.0.
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 69 VGPRs, no scratch, 32 768 B LDS, 5 waves per SIMD (LDS-bound).
+// ------------------------------------------------------------------------------------------
+struct SalMapParams {
+    const uint2* list;
+    const int32_t* nlist;
+    const unsigned long long* nsamp;
+    const double* unit;          // [n_dirs][3]
+    const double* tab;           // ct [W] | st [W] | sp [H] | cp [H] | ay [H]
+    long cap, out_row0;
+    int W, H, tile, scale;
+    double kappa, C;
+    double* out;                 // row (out_row0 + y) of [..][H][W]
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_map(const SalMapParams p) {
+    __shared__ SalEntry s_tile[SM_TILE];
+    const int tid = threadIdx.x;
+    const long y = blockIdx.y;
+    const int npix = p.W * p.H, px = blockIdx.x * SM_THREADS + tid;
+    double Px = 0.0, Py = 0.0, Pz = 0.0;
+    if (px < npix) {                     // Vector.from_spherical of the cell centre, normalised: k_heatmap_map's arithmetic
+        const int r = px / p.W, c = px - r * p.W;
+        const double sp = p.tab[2 * p.W + r], cp = p.tab[2 * p.W + p.H + r];
+        const double x = sp * p.tab[c], yy = sp * p.tab[p.W + c], z = cp;
+        const double len = sqrt(x * x + yy * yy + z * z);
+        Px = x / len; Py = yy / len; Pz = z / len;
+    }
+    const int n = p.nlist[y];
+    const uint2* list = p.list + y * p.cap;
+    const double kappa = p.kappa;
+    double S = 0.0;
+    for (int e0 = 0; e0 < n; e0 += p.tile) {
+        const int cnt = min(p.tile, n - e0);
+        __syncthreads();                                         // the readers of the tile before
+        for (int i = tid; i < cnt; i += SM_THREADS) {
+            const uint2 e = list[e0 + i];
+            const double* A = p.unit + 3L * e.x;
+            s_tile[i] = SalEntry{A[0], A[1], A[2], (double)e.y};
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {                          // the same address in every lane: a broadcast
+            const SalEntry a = s_tile[j];
+            const double c = fma(Pz, a.z, fma(Py, a.y, Px * a.x));
+            S = fma(a.m, exp(kappa * (c - 1.0)), S);
+        }
+    }
+    if (px < npix) {
+        const unsigned long long N = p.nsamp[y];
+        double M = S;
+        if (N == 0ull) M = 0.0;
+        else if (p.scale == 1) M = S * (1.0 / (double)N);
+        else if (p.scale == 2) M = S * (p.C / (double)N);
+        p.out[(p.out_row0 + y) * (long)npix + px] = M;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_saliency_rows — stage 3, one workgroup per row of the pass.
+// ------------------------------------------------------------------------------------------
+struct SalRowParams {
+    const double* map;           // row (map_row0 + y), or null: only the counts are wanted
+    const double* ay;            // [H]
+    const int32_t* nlist;
+    const unsigned long long* nsamp;
+    long map_row0, r0, rows;
+    int W, H;
+    double* stats;               // [4][rows] or null
+    int32_t* peak;               // [rows] or null
+    long long* counts;           // [2][rows] or null
+    int32_t* status;             // [2] or null
+};
+
+// a block's total by the rule, in every thread
+__device__ __forceinline__ double sal_block_sum(double t, double* s_w) {
+    const double s = wave_sum(t);
+    if (lane_id() == 0) s_w[wave_id()] = s;
+    __syncthreads();
+    const double r = mo_block_total(s_w);
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_rows(const SalRowParams p) {
+    __shared__ double s_w[SM_THREADS / WAVE];
+    __shared__ unsigned long long s_bits[SM_THREADS / WAVE];
+    __shared__ int s_idx[SM_THREADS / WAVE];
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const long y = blockIdx.x, row = p.r0 + y;
+    const unsigned long long N = p.nsamp[y];
+    if (tid == 0) {
+        if (p.counts) { p.counts[row] = (long long)N; p.counts[p.rows + row] = (long long)p.nlist[y]; }
+        if (N == 0ull && p.status) atomicAdd(&p.status[1], 1);
+    }
+    if (!p.map || (!p.stats && !p.peak)) return;
+    if (N == 0ull) {                                             // uniform
+        const double nan = __builtin_nan("");
+        if (tid < 4 && p.stats) p.stats[tid * p.rows + row] = nan;
+        if (tid == 0 && p.peak) p.peak[row] = -1;
+        return;
+    }
+    const int npix = p.W * p.H;
+    const double* M = p.map + (p.map_row0 + y) * (long)npix;
+    double mass = 0.0;
+    unsigned long long bb = 0ull;
+    int bi = 0x7FFFFFFF;
+    for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < npix) {
+                const double m = M[q];
+                t += m * p.ay[q / p.W];
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(m);
+                if (bits > bb || (bits == bb && q < bi)) { bb = bits; bi = q; }
+            }
+        }
+        mass += sal_block_sum(t, s_w);
+    }
+    for (int o = 32; o > 0; o >>= 1) {                           // the largest value bits, the smallest index that holds them
+        const unsigned long long ob = (unsigned long long)__shfl_xor((long long)bb, o, WAVE);
+        const int oi = __shfl_xor(bi, o, WAVE);
+        if (ob > bb || (ob == bb && oi < bi)) { bb = ob; bi = oi; }
+    }
+    if (lane == 0) { s_bits[wv] = bb; s_idx[wv] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < SM_THREADS / WAVE; ++w)
+            if (s_bits[w] > bb || (s_bits[w] == bb && s_idx[w] < bi)) { bb = s_bits[w]; bi = s_idx[w]; }
+        if (p.peak) p.peak[row] = bi;
+        if (p.stats) { p.stats[row] = mass; p.stats[p.rows + row] = __longlong_as_double((long long)bb); }
+    }
+    if (!p.stats) return;
+    double ent = 0.0;                                            // Wsum is the mass: the same terms by the same rule
+    for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < npix) {
+                const double a = p.ay[q / p.W], w = M[q] * a;
+                if (w != 0.0) {
+                    const double qq = w / mass;
+                    t += qq * log2(qq / a);
+                }
+            }
+        }
+        ent += sal_block_sum(t, s_w);
+    }
+    if (tid == 0) {
+        p.stats[2 * p.rows + row] = -ent;
+        p.stats[3 * p.rows + row] = exp2(-ent);
+    }
+}
+
+}  // namespace vet
+
+namespace vh {
+
+// What vet_saliency* refuse about their arguments, before anything is staged, allocated or launched.
+int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, double sigma, int W, int H, int scale) {
+    if (!pl) return fail(VET_ERR_INVALID, "plan is NULL");
+    if (U <= 0 || T <= 0) return fail(VET_ERR_INVALID, "n_users and n_frames must be positive (got %d, %d)", U, T);
+    if (window < 1) return fail(VET_ERR_INVALID, "window must be at least 1 frame (got %d)", window);
+    if (stride < 1) return fail(VET_ERR_INVALID, "stride must be at least 1 frame (got %d)", stride);
+    if (window > T) return fail(VET_ERR_INVALID, "window of %d frames is longer than the video's %d frames", window, T);
+    if (!std::isfinite(sigma) || !(sigma > 0.0) || sigma > 3.141592653589793)
+        return fail(VET_ERR_INVALID, "sigma_rad must be finite, above 0 and at most pi (got %g)", sigma);
+    if (W < 2 || W > 4096) return fail(VET_ERR_INVALID, "the map needs 2 to 4096 columns (got %d)", W);
+    if (H < 1 || H > 2048) return fail(VET_ERR_INVALID, "the map needs 1 to 2048 rows (got %d)", H);
+    if (scale < 0 || scale > 2) return fail(VET_ERR_INVALID, "scale must be 0, 1 or 2 (got %d)", scale);
+    if (per_user) {
+        const int rc = check_user_dirs_frames(T, "saliency");
+        if (rc) return rc;
+    } else if (((int64_t)U * T + vet::SM_THREADS - 1) / vet::SM_THREADS > (int64_t)0x7FFFFFFF) {
+        return fail(VET_ERR_UNSUPPORTED, "saliency: %d frames of %d viewers in one call (at most 2^31 - 1 workgroups)", T, U);
+    }
+    return VET_OK;
+}
+
+namespace {
+
+constexpr size_t kSaliencyPassBudget = (size_t)256 << 20;     // bytes of per-row workspace a pass may take
+
+int launch_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
+                    int per_user, double sigma, int W, int H, int scale, double* d_map, double* d_stats, int32_t* d_peak,
+                    int64_t* d_counts, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const long R = (long)vet_window_rows(T, window, stride);
+    const long rows = per_user ? R * U : R, Wpos = per_user ? window : (long)window * U, D = (long)pl->n_dirs;
+    const long npix = (long)W * H, cap = std::min(Wpos, D);
+    const bool sorted = Wpos <= vet::SM_SORT_MAX;
+    const bool want_map = d_map || d_stats || d_peak;
+    int tile = vet::SM_TILE;
+    if (c->tune.saliency_tile > 0) tile = std::min(tile, c->tune.saliency_tile);
+    const size_t per_row = (size_t)cap * 8 + 16 + (sorted ? 0 : (size_t)D * 4) + (want_map && !d_map ? (size_t)npix * 8 : 0);
+    const long CR = std::max(1L, std::min({(long)(kSaliencyPassBudget / per_row), rows, 65535L}));
+    const size_t ntab = (size_t)2 * W + (size_t)3 * H;
+    // workspace: the ids | the host tables | of a pass: the lists, their lengths, N, the dense counts, the maps
+    WsLayout lay;
+    const size_t ids_o = lay.take<int32_t>((size_t)T * U), tab_o = lay.take<double>(ntab), list_o = lay.take<uint2>((size_t)CR * cap),
+                 nl_o = lay.take<int32_t>((size_t)CR), ns_o = lay.take<unsigned long long>((size_t)CR),
+                 dense_o = lay.take<uint32_t>(sorted ? 0 : (size_t)CR * D),
+                 map_o = lay.take<double>(want_map && !d_map ? (size_t)CR * npix : 0);
+    int rc = ensure_ws(c, lay.at);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    int32_t* ids = (int32_t*)(ws + ids_o);
+    double* tab = (double*)(ws + tab_o);
+    const double kappa = 1.0 / (sigma * sigma);
+    const double C = kappa / (2.0 * 3.141592653589793 * (1.0 - std::exp(-2.0 * kappa)));
+    {   // stage 0
+        ProfScope ps(c, s, KID_TRANSITION);
+        const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, D};
+        if (per_user) {
+            vet::UserDirsParams q{};
+            q.src = src; q.U = U; q.T = T; q.dirs = ids; q.status = d_status;
+            const dim3 grid((unsigned)((U + vet::UT - 1) / vet::UT), (unsigned)((T + vet::UT - 1) / vet::UT));
+            if (d_ids) hipLaunchKernelGGL(vet::k_user_dirs<true>, grid, dim3(256), 0, s, q);
+            else hipLaunchKernelGGL(vet::k_user_dirs<false>, grid, dim3(256), 0, s, q);
+        } else {
+            const long n = (long)T * U;
+            const dim3 grid((unsigned)((n + vet::SM_THREADS - 1) / vet::SM_THREADS));
+            if (d_ids) hipLaunchKernelGGL(vet::k_saliency_ids<true>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+            else hipLaunchKernelGGL(vet::k_saliency_ids<false>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (want_map) {  // the host tables: np.radians is x * (pi / 180)
+        ProfScope ps(c, s, KID_TRANSITION);
+        std::vector<double> h(ntab);
+        constexpr double kRad = 3.141592653589793 / 180.0, kPi = 3.141592653589793;
+        for (int x = 0; x < W; ++x) {
+            const double lon = ((double)x + 0.5) / (double)W * 360.0 - 180.0, theta = lon * kRad;
+            h[x] = std::cos(theta); h[(size_t)W + x] = std::sin(theta);
+        }
+        for (int y = 0; y < H; ++y) {
+            const double lat = 90.0 - ((double)y + 0.5) / (double)H * 180.0, phi = (90.0 - lat) * kRad;
+            h[(size_t)2 * W + y] = std::sin(phi); h[(size_t)2 * W + H + y] = std::cos(phi);
+            h[(size_t)2 * W + 2 * (size_t)H + y] =
+                (std::cos(kPi * (double)y / (double)H) - std::cos(kPi * (double)(y + 1) / (double)H)) / (2.0 * (double)W);
+        }
+        for (size_t o = 0; o < ntab; o += vet::SM_PART) {
+            vet::SalTablePart q;
+            q.n = (int)std::min((size_t)vet::SM_PART, ntab - o);
+            for (int i = 0; i < q.n; ++i) q.v[i] = h[o + i];
+            for (int i = q.n; i < vet::SM_PART; ++i) q.v[i] = 0.0;
+            q.dst = tab + o;
+            hipLaunchKernelGGL(vet::k_saliency_tables, dim3(1), dim3(vet::SM_THREADS), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    vet::SalListParams g{};
+    g.ids = ids; g.R = R; g.Wpos = Wpos; g.D = D; g.cap = cap;
+    g.U = U; g.T = T; g.stride = stride; g.per_user = per_user ? 1 : 0;
+    g.P = 2;
+    while (sorted && g.P < Wpos) g.P <<= 1;
+    g.list = (uint2*)(ws + list_o); g.nlist = (int32_t*)(ws + nl_o); g.nsamp = (unsigned long long*)(ws + ns_o);
+    g.dense = (unsigned*)(ws + dense_o);
+    vet::SalMapParams m{};
+    m.list = g.list; m.nlist = g.nlist; m.nsamp = g.nsamp; m.unit = pl->d_dir_unit; m.tab = tab; m.cap = cap;
+    m.W = W; m.H = H; m.tile = tile; m.scale = scale; m.kappa = kappa; m.C = C;
+    m.out = d_map ? d_map : (double*)(ws + map_o);
+    vet::SalRowParams q{};
+    q.map = want_map ? m.out : nullptr; q.ay = tab + (size_t)2 * W + 2 * (size_t)H; q.nlist = g.nlist; q.nsamp = g.nsamp; q.rows = rows;
+    q.W = W; q.H = H; q.stats = d_stats; q.peak = d_peak; q.counts = (long long*)d_counts; q.status = d_status;
+    const bool want_rows = d_stats || d_peak || d_counts || d_status;
+    for (long r0 = 0; r0 < rows; r0 += CR) {
+        const long cr = std::min(CR, rows - r0);
+        g.r0 = r0;
+        if (sorted) {
+            ProfScope ps(c, s, KID_TRANSITION);
+            hipLaunchKernelGGL(vet::k_saliency_sort, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+            HIP_TRY(hipGetLastError());
+        } else {
+            ProfScope ps(c, s, KID_TRANSITION);
+            HIP_TRY(hipMemsetAsync(g.dense, 0, (size_t)cr * D * 4, s));
+            if (D <= vet::SM_LDS_DIRS) {                         // 16384 positions or more per workgroup, at most 64 workgroups a row
+                const long gx = std::max(1L, std::min(Wpos / 16384, 64L));
+                hipLaunchKernelGGL(vet::k_saliency_count<true>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), (size_t)D * 4, s, g);
+            } else {
+                const long gx = std::min((Wpos + vet::SM_THREADS - 1) / vet::SM_THREADS, 4096L);
+                hipLaunchKernelGGL(vet::k_saliency_count<false>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+            }
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(vet::k_saliency_compact, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+            HIP_TRY(hipGetLastError());
+        }
+        if (want_map) {
+            m.out_row0 = d_map ? r0 : 0;
+            ProfScope pm(c, s, KID_SPATIAL);
+            const dim3 grid((unsigned)((npix + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr);
+            hipLaunchKernelGGL(vet::k_saliency_map, grid, dim3(vet::SM_THREADS), 0, s, m);
+            HIP_TRY(hipGetLastError());
+        }
+        if (want_rows) {
+            ProfScope ps(c, s, KID_TRANSITION);
+            q.map_row0 = m.out_row0; q.r0 = r0;
+            hipLaunchKernelGGL(vet::k_saliency_rows, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return VET_OK;
+}
+
+}  // namespace
+
+int saliency_set_attrs(vet_ctx*) {
+    HIP_TRY(hipFuncSetAttribute((const void*)vet::k_saliency_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                vet::SM_LDS_DIRS * 4));
+    return VET_OK;
+}
+
+}  // namespace vh
+
+using namespace vh;
+
+extern "C" {
+
+int vet_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, int per_user,
+                 double sigma_rad, int W, int H, int scale, double* d_map, double* d_stats, int32_t* d_peak, int64_t* d_counts,
+                 int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_saliency_args(pl, U, T, window, stride, per_user, sigma_rad, W, H, scale);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_saliency_ids", stream, &s);
+    return rc ? rc : launch_saliency(pl, d_mu, d_mv, nullptr, U, T, window, stride, per_user, sigma_rad, W, H, scale, d_map, d_stats,
+                                     d_peak, d_counts, d_status, s);
+}
+
+int vet_saliency_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, int per_user, double sigma_rad, int W,
+                     int H, int scale, double* d_map, double* d_stats, int32_t* d_peak, int64_t* d_counts, int32_t* d_status,
+                     void* stream) {
+    hipStream_t s;
+    int rc = check_saliency_args(pl, U, T, window, stride, per_user, sigma_rad, W, H, scale);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_saliency(pl, nullptr, nullptr, d_ids, U, T, window, stride, per_user, sigma_rad, W, H, scale, d_map,
+                                     d_stats, d_peak, d_counts, d_status, s);
+}
+
+}  // extern "C"

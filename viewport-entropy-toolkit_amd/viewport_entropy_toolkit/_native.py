@@ -89,6 +89,7 @@ SIGNATURES = {
     "vet_test_markov_chunk_rows": (_I, [_P, _I]),
     "vet_test_motion_lds_values": (_I, [_P, _I]),
     "vet_test_dispersion_tile": (_I, [_P, _I]),
+    "vet_test_saliency_tile": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -137,6 +138,9 @@ SIGNATURES = {
     "vet_dispersion": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vet_dispersion_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vet_dispersion_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "vet_saliency": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_saliency_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vet_saliency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -429,6 +433,11 @@ class Engine:
         default, 1024); results do not depend on it (include/vet.h: vet_test_dispersion_tile)."""
         _check(self.lib, self.lib.vet_test_dispersion_tile(self.handle, int(n)))
 
+    def test_saliency_tile(self, n: int = 0):
+        """Test switch: the map kernel of the saliency call stages at most ``n`` list entries of a row in LDS at a time (0: the
+        default, 1024); results do not depend on it (include/vet.h: vet_test_saliency_tile)."""
+        _check(self.lib, self.lib.vet_test_saliency_tile(self.handle, int(n)))
+
     def test_crowd_divergence_chunk_rows(self, rows: int = 0):
         """Test switch: the crowd divergence takes ``rows`` rows per chunk (0: the default budget); results do not depend on
         it (include/vet.h: vet_test_crowd_divergence_chunk_rows)."""
@@ -529,6 +538,16 @@ _DISPERSION_CALLS = {
            (("stats", "3UR", _F64, False), ("centroid", "UR3", _F64, False), ("hist", "URH", _NP_I64, True),
             ("counts", "4UR", _NP_I64, False))),
 }
+
+# The saliency call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dims Y, X: the
+# map's rows and columns).  Rows count frames; its extra arguments are per_user, sigma in radians, the map's size and the scale.
+_SALIENCY_CALLS = {
+    False: ("vet_saliency", False, True, False,
+            (("map", "RYX", _F64, True), ("stats", "4R", _F64, False), ("peak", "R", _I32, False), ("counts", "2R", _NP_I64, False))),
+    True: ("vet_saliency", False, True, False,
+           (("map", "URYX", _F64, True), ("stats", "4UR", _F64, False), ("peak", "UR", _I32, False), ("counts", "2UR", _NP_I64, False))),
+}
+SALIENCY_SCALES = {"none": 0, "mean": 1, "density": 2}
 
 
 class Plan:
@@ -1026,6 +1045,36 @@ class Plan:
         return self._row_host(_DISPERSION_CALLS[bool(per_user)], mu, mv, ids, window, stride, {"hist"} if e is not None else set(),
                               check, extra=(int(bool(per_user)), _ptr(e), B), extra_dims={"H": B})
 
+    @staticmethod
+    def _saliency_args(sigma_deg, width, height, scale):
+        """(sigma in radians, W, H, the C scale 0 / 1 / 2) as the C entry takes them; ``ValueError`` unless sigma_deg is a finite
+        number in (0, 180], 2 <= width <= 4096 and 1 <= height <= 2048 are integers and scale is "none", "mean" or "density"."""
+        if isinstance(sigma_deg, bool) or not isinstance(sigma_deg, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(sigma_deg) or not 0.0 < float(sigma_deg) <= 180.0:
+            raise ValueError(f"sigma_deg must be a finite number of degrees in (0, 180] (got {sigma_deg!r})")
+        for name, v, lo, hi in (("width", width, 2, 4096), ("height", height, 1, 2048)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (got {v!r})")
+        if not isinstance(scale, str) or scale not in SALIENCY_SCALES:
+            raise ValueError(f"scale must be one of {sorted(SALIENCY_SCALES)} (got {scale!r})")
+        return min(float(np.radians(float(sigma_deg))), float(np.pi)), int(width), int(height), SALIENCY_SCALES[scale]
+
+    def saliency(self, mu=None, mv=None, ids=None, window=1, stride=1, per_user=False, sigma_deg=5.0, width=180, height=90,
+                 scale="density", want_map=True, check=True):
+        """Saliency maps (include/vet.h: vet_saliency): the von Mises-Fisher kernel density, kappa = 1 / sigma^2, of the viewing
+        directions of frames [r * stride, r * stride + window) on a ``width`` x ``height`` equirectangular map (row 0 at the top,
+        laid out as the heatmaps), pooled over the viewers, or with ``per_user`` each viewer's own (outputs user-major, a leading
+        U axis).  ``window=None`` is the whole video.  ``sigma_deg = 5.0`` is a choice for head-direction data (about the spread
+        of gaze around the head direction), not taken from the reference, which has no such call.  ``scale``: "none" (the sum of
+        the kernels), "mean" (divided by the samples) or "density" (per steradian, integral 1).  Returns dict(map[R,H,W]|None
+        (``want_map``), stats[4,R] (mass = the map's mean over the sphere, 1 / (4 pi) for a resolved "density" map; peak; entropy in bits against the uniform sphere, area = 2 ** entropy: the effective
+        share of the sphere), peak[R] int32 (the peak's pixel index, -1 for a row without a sample), counts[2,R] int64 (samples,
+        distinct directions), code), R = (T - window) // stride + 1.  A row without a sample has a zero map and NaN statistics —
+        data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        sigma, W, H, sc = self._saliency_args(sigma_deg, width, height, scale)
+        return self._row_host(_SALIENCY_CALLS[bool(per_user)], mu, mv, ids, window, stride, {"map"} if want_map else set(), check,
+                              extra=(int(bool(per_user)), sigma, W, H, sc), extra_dims={"Y": H, "X": W, "2": 2})
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1229,6 +1278,17 @@ class Plan:
         self._row_device(_DISPERSION_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, int(bool(per_user)), e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1),
                          d_stats or None, (d_centroid, d_hist, d_counts, d_status), stream)
+
+    def saliency_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, per_user: bool,
+                        sigma_deg: float = 5.0, width: int = 180, height: int = 90, scale: str = "density", d_map: int = 0,
+                        d_stats: int = 0, d_peak: int = 0, d_counts: int = 0, d_status: int = 0, stream=None, d_ids: int = 0):
+        """d_map f64 [Rows][H][W]; d_stats f64 [4][Rows]; d_peak i32 [Rows]; d_counts i64 [2][Rows]; Rows = R, or U * R user-major
+        with ``per_user``; every output may be 0 — without d_map no map leaves the workspace (include/vet.h: vet_saliency;
+        ``d_ids``: vet_saliency_ids)."""
+        sigma, W, H, sc = self._saliency_args(sigma_deg, width, height, scale)
+        self._row_device(_SALIENCY_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, int(bool(per_user)), sigma, W, H, sc), d_map or None,
+                         (d_stats, d_peak, d_counts, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

@@ -677,5 +677,75 @@ class _EntropyAnalyzerBase:
             raise ValidationError("Normalized coordinates must be between 0 and 1")
         return self._dispersion_frame(times, names, window, stride, bool(per_user), res, bins_deg)
 
+    SALIENCY_MAP_LIMIT = 4 << 30     # bytes of maps that compute_saliency(keep_maps=True) hands back at most
+
+    @staticmethod
+    def _saliency_frame(times, names, window: int, stride: int, per_user: bool, res: dict, sigma_deg: float, width: int, height: int,
+                        normalize: str) -> pd.DataFrame:
+        """The saliency statistics as a DataFrame, one row per window (``per_user``: per (user, window), user-major, ``user``
+        first); where ``res`` holds the maps, ``map`` of a row is the [H, W] view of its map (no copy)."""
+        times = np.asarray(times)
+        stats = np.asarray(res["stats"], dtype=np.float64).reshape(4, -1)
+        counts = np.asarray(res["counts"]).reshape(2, -1)
+        peak = np.asarray(res["peak"]).reshape(-1)
+        rows = len(peak)
+        R = rows // len(names) if per_user else rows
+        first = np.arange(R, dtype=np.int64) * stride
+        if per_user:
+            first = np.tile(first, len(names))
+        cols = {}
+        if per_user:
+            cols["user"] = np.repeat(np.asarray(list(names), dtype=object), R)
+        has = peak >= 0
+        py, px = np.divmod(np.where(has, peak, 0), width)
+        cols.update(time=times[first], time_end=times[first + window - 1], samples=counts[0], distinct=counts[1], mass=stats[0],
+                    peak=stats[1], peak_lon=np.where(has, (px + 0.5) / width * 360.0 - 180.0, np.nan),
+                    peak_lat=np.where(has, 90.0 - (py + 0.5) / height * 180.0, np.nan), entropy=stats[2], area=stats[3])
+        if res.get("map") is not None:
+            maps = np.asarray(res["map"]).reshape(rows, height, width)
+            m_col = np.empty(rows, dtype=object)
+            for r in range(rows):
+                m_col[r] = maps[r]
+            cols["map"] = m_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(sigma_deg=float(sigma_deg), kappa=1.0 / min(float(np.radians(sigma_deg)), float(np.pi)) ** 2, width=width, height=height,
+                        normalize=normalize, window=window, stride=stride, users=list(names))
+        return df
+
+    def compute_saliency(self, window: Optional[int] = 1, stride: int = 1, sigma_deg: float = 5.0, width: int = 180, height: int = 90,
+                         per_user: bool = False, normalize: str = "density", keep_maps: bool = True) -> pd.DataFrame:
+        """Saliency maps: the continuous density of viewing directions on the sphere per window of frames — the von Mises-Fisher
+        kernel density (for small angles the Gaussian of width ``sigma_deg``) of the samples of frames
+        [r * stride, r * stride + window) on a ``width`` x ``height`` equirectangular map (row 0 at the top, as the heatmaps),
+        pooled over the viewers or with ``per_user`` each viewer's own.  ``window`` and ``stride`` count frames; ``window=None`` is
+        the whole video.  Independent of the tiling.  ``sigma_deg = 5.0`` is a choice for head-direction data, not taken from the
+        reference, which has no such call.  ``normalize``: "none" (the sum of the kernels), "mean" (divided by the samples) or
+        "density" (per steradian; the map integrates to 1 over the sphere).
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, one row per window — user-major with ``user`` first
+        when ``per_user``: ``time`` / ``time_end`` (the first / last frame of the row), ``samples``, ``distinct`` (directions),
+        ``mass`` (the map's mean over the sphere: 4 pi * mass is near 1 with "density" when the map resolves sigma), ``peak`` and its cell
+        centre ``peak_lon`` / ``peak_lat`` in degrees, ``entropy`` (bits, against the uniform sphere: 0 = uniform, negative =
+        concentrated), ``area`` (2 ** entropy: the effective share of the sphere looked at; per viewer the exploration ratio)
+        and, with ``keep_maps``, ``map`` (an [H, W] view into the one result array).  ``attrs`` hold ``sigma_deg``, ``kappa``,
+        ``width``, ``height``, ``normalize``, ``window``, ``stride`` and ``users``.  A window without a sample has a zero map and
+        NaN statistics — returned, never raised.  Raises ``ValidationError`` before data is loaded and for samples outside
+        [0, 1], ``ValueError`` for illegal arguments and, with ``keep_maps``, for maps beyond 4 GiB."""
+        times, names, call = self._row_call("saliency")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        if not isinstance(normalize, str) or normalize not in _native.SALIENCY_SCALES:
+            raise ValueError(f"normalize must be one of {sorted(_native.SALIENCY_SCALES)} (got {normalize!r})")
+        _native.Plan._saliency_args(sigma_deg, width, height, normalize)
+        rows = ((len(times) - window) // stride + 1) * (len(names) if per_user else 1)
+        if keep_maps and rows * int(width) * int(height) * 8 > self.SALIENCY_MAP_LIMIT:
+            raise ValueError(f"{rows} maps of {width} x {height} are {rows * int(width) * int(height) * 8 / 2 ** 30:.1f} GiB, beyond 4 GiB: "
+                             "use a larger stride, a coarser map (width, height), or keep_maps=False")
+        res = call(window=window, stride=stride, per_user=bool(per_user), sigma_deg=float(sigma_deg), width=int(width),
+                   height=int(height), scale=normalize, want_map=bool(keep_maps), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._saliency_frame(times, names, window, stride, bool(per_user), res, float(sigma_deg), int(width), int(height),
+                                    normalize)
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError
