@@ -68,7 +68,8 @@ extern "C" {
                           vet_dispersion* entry points (audience dispersion: the angle between two viewers' directions in one
                           frame over all pairs, per window and per viewer), and then the vet_saliency* entry points (saliency
                           maps: the spherical kernel density of a window's viewing directions on an equirectangular map, with its
-                          mass, peak, entropy and effective area, per window and per viewer) and vet_test_saliency_tile */
+                          mass, peak, entropy and effective area, per window and per viewer) and vet_test_saliency_tile, and then
+                          the vet_saliency_similarity* entry points (CC, SIM, JSD, KL and NSS between the maps of two audiences) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -154,8 +155,9 @@ int vet_test_motion_lds_values(vet_ctx *ctx, int n);
  * a time from 1024 to n (at most 1024), so that a small audience runs several tiles; 0 restores the default.  Read at every launch.
  * Results are bit-identical whatever the value. */
 int vet_test_dispersion_tile(vet_ctx *ctx, int n);
-/* Test switch, not a tuning knob: n > 0 lowers the most list entries of a row that k_saliency_map (vet_saliency*) stages in LDS at
- * a time (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
+/* Test switch, not a tuning knob: n > 0 lowers the most list entries of a row that k_saliency_map (vet_saliency*,
+ * vet_saliency_similarity*) and k_saliency_points (vet_saliency_similarity*: the other audience's list) stage in LDS at a time
+ * (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
 int vet_test_saliency_tile(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
@@ -1190,6 +1192,68 @@ int vet_saliency_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_fr
 int vet_saliency_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
                       int window, int stride, int per_user, double sigma_rad, int W, int H, int scale, double *h_map, double *h_stats,
                       int32_t *h_peak, int64_t *h_counts);
+
+/* ---- saliency similarity: CC, SIM, JSD, KL and NSS between the saliency maps of two audiences ------------------
+ * Not in the reference.  The two-audience question of vet_group_divergence asked of the tiling-free maps of vet_saliency: per
+ * window of frames, how alike are the densities of where audience A and audience B look.
+ * ROWS, PRESENCE, ids, MAP GRID, the KERNEL k(P, A), kappa, C and the summation RULE exactly as vet_saliency, pooled layout (the rule:
+ * blocks of 1024 positions, thread t of 256 adds t, t + 256, t + 512, t + 768, then wave_sum, the four waves in order, the blocks
+ * ascending).  There is no per_user and no scale: the maps are scale 2 (density); every value below is scale-free in exact arithmetic.
+ * AUDIENCES: groups is a HOST array [n_users] in every entry, read before the call returns: 0 = audience A, 1 = audience B, any
+ * other value = excluded.  Audience g of row r is the row's present samples of the viewers labelled g; its list, N_g, distinct_g and
+ * map M^g are vet_saliency's — the maps are bit for bit what vet_saliency_ids returns at scale 2 on ids in which every other viewer's
+ * samples are -1 — and mass_g is its mass (the same rule, the same bits).  status[0] counts the out-of-range samples of ALL viewers,
+ * the excluded ones too (stage 0 runs before the mask); status[1] counts the rows in which an audience is empty.
+ * PIXEL SUMS, each by the rule over the pixels in row-major order; a = M^A_p, b = M^B_p, ay the cell's share:
+ *   qa = (a*ay)/mass_a, qb = (b*ay)/mass_b;  da = a - mass_a, db = b - mass_b (the mass is the area-weighted mean: the shares add to 1)
+ *   va = sum ay*(da*da), vb = sum ay*(db*db), cov = sum ay*(da*db);  cc = cov / sqrt(va*vb)      Pearson's correlation
+ *   sim    = sum fmin(qa, qb)                                                                     histogram intersection, in [0, 1]
+ *   jsd    = 0.5 * sum (ta + tb), m = 0.5*(qa+qb), ta = qa != 0 ? qa*log2(qa/m) : 0, tb alike     bits, in [0, 1]
+ *   kl_ab  = sum (qa != 0 ? qa*log2(qa/qb) : 0); kl_ba the same expression with the roles exchanged (its own log2)
+ * Where A has weight on a cell whose B value underflowed to 0.0 the IEEE value of the expression is +inf and so is kl_ab: data, not
+ * an error (sigma below about 3 degrees, where 2 kappa exceeds 708).  The products are parenthesised as written: exchanging the two
+ * labels exchanges kl_ab <-> kl_ba, nss_ab <-> nss_ba, mass_a <-> mass_b and leaves cc, sim and jsd unchanged, byte for byte.
+ * NSS BY POINT EVALUATION (X evaluated on Y's density; nss_ab: X = A, Y = B) — the map is a kernel density, so it is evaluated AT a
+ * sample's direction; no sample is assigned to a pixel.  For entry i of X's list (ascending id, unit row A_i, multiplicity m_i):
+ * S_i starts at +0.0 and runs over Y's list in ascending id, S_i = fma((double)m_j, k(A_i, B_j), S_i) — the map's inner loop with the
+ * cell direction replaced by A_i;  v_i = (double)m_i * (S_i * g_Y), g_Y = C / (double)N_Y;  V = sum_i v_i by the rule over the list
+ * positions;  nss_xy = (V / (double)N_X - mass_Y) / sqrt(v_Y), v_Y being Y's va or vb.  Positive: X looks where Y's density is above
+ * its sphere average.
+ * A row with N_A = 0 or N_B = 0: the seven comparison values are NaN, mass_g is NaN for the empty audience and vet_saliency's value
+ * for the other, the counts are as they are.
+ * A value's bits depend on the plan, W, H, sigma, window and the row's frames and labels only — not on stride, the number of rows, the
+ * video's length, the entry point, which outputs were asked for, the pass a row falls into, vet_test_saliency_tile, the excluded
+ * viewers' samples or the order of the viewer columns (lists are in ascending id).  No FP atomics.
+ * Outputs, each nullable:
+ *   d_maps     [2][Rows][H][W] f64: M^A, then M^B
+ *   d_stats    [9][Rows] f64, statistic-major: cc, sim, jsd, kl_ab, kl_ba, nss_ab, nss_ba, mass_a, mass_b
+ *   d_counts   [4][Rows] i64: samples_a, samples_b, distinct_a, distinct_b
+ *   d_status   [2] i32 {bad, #rows with an empty audience}; the call ADDS, the caller zeroes
+ * With d_maps NULL nothing of [Rows][H][W] exists outside a pass: the maps of a pass of rows live in the workspace, and a pass (two
+ * lists, two maps when d_maps is NULL, the v_i of both directions per row) stays under the 256 MB budget.  With d_maps and d_stats
+ * both NULL no map is computed.
+ * Stages: the samples quantised once (k_saliency_ids); k_saliency_mask — one streaming pass writes the two masked [T][U] id arrays
+ * (8 B more workspace per sample; the list and map kernels of vet_saliency then run unchanged, for A and for B, per pass);
+ * k_saliency_points — workgroup = (row, 256 entries of X's list, direction), thread = entry with its unit vector in registers, Y's
+ * list staged in LDS in tiles as k_saliency_map stages it (a broadcast), v_i to the workspace: 75 VGPRs, no scratch, 32 KB LDS,
+ * 5 waves per SIMD (LDS-bound); k_saliency_compare — one workgroup per row: the two masses, one pass over both maps with the seven
+ * sums carried together (four log2 per pixel, LDS for the wave partials only), the v_i by the rule, the values, the counts and
+ * status[1]: 98 VGPRs, no scratch, 224 B LDS, 4 waves per SIMD; k_saliency_mask 14 VGPRs, no scratch.
+ * VET_ERR_INVALID (before anything is allocated or launched): everything vet_saliency refuses for the pooled layout, groups NULL, an
+ * audience without a viewer.  VET_ERR_UNSUPPORTED as vet_saliency, pooled.
+ * Profile ids: k_saliency_map and k_saliency_points to k_spatial, the other stages to k_transition.  Asynchronous on `stream`. */
+int vet_saliency_similarity(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                            const int8_t *groups, double sigma_rad, int W, int H, double *d_maps, double *d_stats, int64_t *d_counts,
+                            int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_saliency_similarity_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                                const int8_t *groups, double sigma_rad, int W, int H, double *d_maps, double *d_stats,
+                                int64_t *d_counts, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_saliency_similarity_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
+                                 int n_frames, int window, int stride, const int8_t *groups, double sigma_rad, int W, int H,
+                                 double *h_maps, double *h_stats, int64_t *h_counts);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

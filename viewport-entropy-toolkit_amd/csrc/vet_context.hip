@@ -303,7 +303,7 @@ int vet_test_dispersion_tile(vet_ctx* c, int n) {
 int vet_test_saliency_tile(vet_ctx* c, int n) {
     if (!c) return fail(VET_ERR_INVALID, "ctx is NULL");
     if (n < 0) return fail(VET_ERR_INVALID, "list entries per tile must be positive, or 0 for the default (got %d)", n);
-    c->tune.saliency_tile = n;                     // read by every vet_saliency* launch of this context's plans
+    c->tune.saliency_tile = n;                     // read by every vet_saliency* / vet_saliency_similarity* launch of this context's plans
     return VET_OK;
 }
 int vet_profile_enable(vet_ctx* c, int on) {

@@ -22,8 +22,8 @@
 //   vet_dispersion.hip  the audience dispersion (the angle between two viewers' directions in one frame over all pairs: per (frame,
 //                       viewer) partials from unit vectors staged in LDS, then per row the block-ordered sums) and its launch logic
 //   vet_saliency.hip    the saliency maps (the spherical kernel density of a row's viewing directions on an equirectangular map: the
-//                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics) and
-//                       their launch logic
+//                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics), the
+//                       saliency similarity of two audiences (their maps by the same kernels, compared row by row) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -159,8 +159,8 @@ struct Tuning {
                                 // k_dispersion_pairs stages in LDS at a time (0 = 1024); read at every launch; the results do not
                                 // depend on it (test_dispersion_gpu.py)
     int saliency_tile = 0;          // vet_test_saliency_tile (no environment variable): the most list entries of a row that
-                                // k_saliency_map stages in LDS at a time (0 = 1024); read at every launch; the results do not
-                                // depend on it (test_saliency_gpu.py)
+                                // k_saliency_map and k_saliency_points stage in LDS at a time (0 = 1024); read at every launch; the
+                                // results do not depend on it (test_saliency_gpu.py, test_saliency_similarity_gpu.py)
     void from_environment();
 };
 
@@ -520,6 +520,9 @@ int check_dispersion_args(const vet_plan* pl, int U, int T, int window, int stri
 // vet_saliency.hip: what vet_saliency* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched.
 int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, double sigma, int W, int H, int scale);
+// ... and what vet_saliency_similarity* refuse: the above for the pooled layout, groups NULL (host memory [U]), an audience without a
+// viewer.
+int check_similarity_args(const vet_plan* pl, int U, int T, int window, int stride, const int8_t* groups, double sigma, int W, int H);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

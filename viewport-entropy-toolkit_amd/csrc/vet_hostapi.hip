@@ -1,6 +1,6 @@
 // vet_hostapi.hip — host-buffer entry points of the C-ABI (include/vet.h).  Two file-local helpers carry them: StagedRun
 // (the entropy entries: samples and status words through the context's grow-only device buffers, the device-pointer entry
-// points in between, synchronous; staged_rows is the whole run of the twelve row calls) and BlockDownload (heatmaps and
+// points in between, synchronous; staged_rows is the whole run of the thirteen row calls) and BlockDownload (heatmaps and
 // tilings: frames rendered in blocks, the download of one block overlapping the render of the next).  Also here:
 // device-resident results (vet_result), heatmaps (vet_heatmap: the map, the palette and the uploads of a block; the kernels
 // are vet_heatmap.hip's) and tilings (vet_tiling: the cameras; the kernels are vet_tiling.hip's).  File-local types and
@@ -148,9 +148,9 @@ struct StagedRun {
     }
 };
 
-// The twelve row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
+// The thirteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
 // per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion, the saliency
-// maps) after their
+// maps, the saliency similarity) after their
 // refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
 // null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
 // entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
@@ -767,6 +767,25 @@ int vet_saliency_host(vet_plan* pl, const double* h_mu, const double* h_mv, cons
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_saliency_ids, vet_saliency, pl, U, T, window, stride, per_user, sigma_rad, W, H, scale, (double*)d[1],
                            (double*)d[0], (int32_t*)d[2], (int64_t*)d[3], run.status, run.s);
+    });
+}
+
+// Saliency similarity with host buffers (include/vet.h): where wanted maps [2][Rows][H][W], stats [9][Rows] and counts [4][Rows];
+// Rows = vet_window_rows over the T frames.  Every output may be NULL; groups [U] is host memory in every entry.  Rows with an empty
+// audience are data: only VET_ERR_RANGE is decoded from the status words.
+int vet_saliency_similarity_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                                 int stride, const int8_t* groups, double sigma_rad, int W, int H, double* h_maps, double* h_stats,
+                                 int64_t* h_counts) {
+    int rc = check_similarity_args(pl, U, T, window, stride, groups, sigma_rad, W, H);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t rows = (size_t)vet_window_rows(T, window, stride);
+    const RowOut outs[3] = {{h_stats, 9 * rows * 8, SLOT_ENTROPY}, {h_maps, 2 * rows * (size_t)W * H * 8, SLOT_OUT0},
+                            {h_counts, 4 * rows * 8, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_saliency_similarity_ids, vet_saliency_similarity, pl, U, T, window, stride, groups, sigma_rad, W, H,
+                           (double*)d[1], (double*)d[0], (int64_t*)d[2], run.status, run.s);
     });
 }
 

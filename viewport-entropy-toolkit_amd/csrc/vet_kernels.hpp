@@ -75,6 +75,11 @@
 //                                              k_saliency_map   workgroup = (row, 256 pixels): the row's list staged in LDS in tiles of
 //                                                               1024 entries, S = fma(m, exp(kappa (c - 1)), S) per pixel in a register
 //                                              k_saliency_rows  one workgroup per row: mass, peak, entropy and area of the written map
+//                                              k_saliency_mask  the similarity call: the ids once more per audience, the others' samples -1
+//                                              k_saliency_points  workgroup = (row, 256 entries of one audience's list, direction): the
+//                                                               other audience's density at the entries' directions, its list in LDS tiles
+//                                              k_saliency_compare  one workgroup per row: the masses, CC, SIM, JSD, both KL and both NSS
+//                                                               of the two audiences' maps by the block-ordered sums
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

@@ -16,6 +16,10 @@
 // order (blocks of 1024; thread t adds t, t + 256, t + 512, t + 768; wave_sum; the four waves in order; the blocks ascending) for
 // the mass and the entropy, the peak as the largest (value bits, smallest index).  No FP atomics.  Rows run in passes under a 256 MB
 // workspace budget; with d_map NULL the maps of a pass live in the workspace only.
+// Saliency similarity (vet_saliency_similarity*): stage 0 once, k_saliency_mask writes the ids once more per audience (every other
+// viewer's samples -1), stages 1 and 2 run unchanged for audience A and for audience B per pass, k_saliency_points evaluates each
+// audience's density at the other's list entries (NSS without a pixel decision) and k_saliency_compare, one workgroup per row, takes
+// the two masses, CC, SIM, JSD and both KL from one pass over the two maps and the NSS from the point values, all by the same rule.
 // No CPU compute path; nothing here reads the environment.
 #include "vet_host.hpp"
 #include "vet_common.hpp"
@@ -356,6 +360,208 @@ __global__ __launch_bounds__(SM_THREADS) void k_saliency_rows(const SalRowParams
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Saliency similarity (vet_saliency_similarity*): two audiences of one video, their maps compared row by row.
+// k_saliency_mask — after stage 0: the ids [T][U] once more per audience, every other viewer's samples -1.  The list and map kernels
+// above then run on each copy unchanged, so an audience's list and map are vet_saliency_ids' on the masked ids by construction.
+// Resources: 14 VGPRs, no scratch, no LDS, 8 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_mask(const int32_t* __restrict__ ids, const unsigned char* __restrict__ groups,
+                                                              const long n, const int U, int32_t* __restrict__ ids_a,
+                                                              int32_t* __restrict__ ids_b) {
+    const long i = (long)blockIdx.x * SM_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int id = ids[i];
+    const unsigned char g = groups[i % U];
+    ids_a[i] = g == 0 ? id : -1;
+    ids_b[i] = g == 1 ? id : -1;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_saliency_points — NSS by point evaluation.  grid (ceil(cap / 256), rows of the pass, 2); blockIdx.z = 0: X = A on Y = B's
+// density (nss_ab), 1: X = B on Y = A.  Thread = entry blockIdx.x * 256 + tid of X's list with its unit vector in registers; Y's list
+// staged in LDS in tiles as k_saliency_map stages it and read as a broadcast; S the same sequential sum with the cell direction
+// replaced by the entry's.  Writes v_i = m_i * (S_i * g_Y) to pts [2][CR][cap].  Rows with an empty audience write nothing.
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 75 VGPRs, no scratch, 32 768 B LDS, 5 waves per SIMD (LDS-bound).
+// ------------------------------------------------------------------------------------------
+struct SalPointParams {
+    const uint2* list[2];        // A, B: [rows of the pass][cap]
+    const int32_t* nlist[2];
+    const unsigned long long* nsamp[2];
+    const double* unit;          // [n_dirs][3]
+    long cap, CR;
+    int tile;
+    double kappa, C;
+    double* pts;                 // [2][CR][cap]
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_points(const SalPointParams p) {
+    __shared__ SalEntry s_tile[SM_TILE];
+    const int tid = threadIdx.x;
+    const long y = blockIdx.y;
+    const int dx = blockIdx.z, dy = dx ^ 1;
+    const int nx = p.nlist[dx][y], n = p.nlist[dy][y];
+    const int i = blockIdx.x * SM_THREADS + tid;
+    if ((int)blockIdx.x * SM_THREADS >= nx || n == 0) return;   // uniform
+    double Px = 0.0, Py = 0.0, Pz = 0.0, mi = 0.0;
+    if (i < nx) {
+        const uint2 e = p.list[dx][y * p.cap + i];
+        const double* A = p.unit + 3L * e.x;
+        Px = A[0]; Py = A[1]; Pz = A[2]; mi = (double)e.y;
+    }
+    const uint2* list = p.list[dy] + y * p.cap;
+    const double kappa = p.kappa;
+    double S = 0.0;
+    for (int e0 = 0; e0 < n; e0 += p.tile) {
+        const int cnt = min(p.tile, n - e0);
+        __syncthreads();                                         // the readers of the tile before
+        for (int j = tid; j < cnt; j += SM_THREADS) {
+            const uint2 e = list[e0 + j];
+            const double* A = p.unit + 3L * e.x;
+            s_tile[j] = SalEntry{A[0], A[1], A[2], (double)e.y};
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {                          // the same address in every lane: a broadcast
+            const SalEntry a = s_tile[j];
+            const double c = fma(Pz, a.z, fma(Py, a.y, Px * a.x));
+            S = fma(a.m, exp(kappa * (c - 1.0)), S);
+        }
+    }
+    if (i < nx) {
+        const double g = p.C / (double)p.nsamp[dy][y];
+        p.pts[((long)dx * p.CR + y) * p.cap + i] = mi * (S * g);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_saliency_compare — one workgroup per row of the pass: the two masses by the rule (k_saliency_rows' terms in its order: the same
+// bits), one pass over both maps with the seven pixel sums carried together through the rule's block step, the v_i of both
+// directions by the rule over the list positions, then the nine values, the counts and status[1].
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 98 VGPRs, no scratch, 224 B LDS, 4 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+constexpr int SC_SUMS = 7;              // va, vb, cov, sim, jsd, kl_ab, kl_ba
+struct SalCompareParams {
+    const double* map[2];        // row (map_row0 + y) of each audience's maps, or null: only the counts are wanted
+    const double* ay;            // [H]
+    const int32_t* nlist[2];
+    const unsigned long long* nsamp[2];
+    const double* pts;           // [2][CR][cap]
+    long cap, CR, map_row0, r0, rows;
+    int W, H;
+    double* stats;               // [9][rows] or null
+    long long* counts;           // [4][rows] or null
+    int32_t* status;             // [2] or null
+};
+
+// the rule's sum of M_p * a_y over a map, in every thread: k_saliency_rows' mass
+__device__ __forceinline__ double sal_mass(const double* M, const double* ay, int W, int npix, int tid, double* s_w) {
+    double mass = 0.0;
+    for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < npix) t += M[q] * ay[q / W];
+        }
+        mass += sal_block_sum(t, s_w);
+    }
+    return mass;
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_saliency_compare(const SalCompareParams p) {
+    __shared__ double s_w[SC_SUMS][SM_THREADS / WAVE];
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const long y = blockIdx.x, row = p.r0 + y;
+    const unsigned long long NA = p.nsamp[0][y], NB = p.nsamp[1][y];
+    const int na = p.nlist[0][y], nb = p.nlist[1][y];
+    const bool empty = NA == 0ull || NB == 0ull;
+    if (tid == 0) {
+        if (p.counts) {
+            p.counts[row] = (long long)NA; p.counts[p.rows + row] = (long long)NB;
+            p.counts[2 * p.rows + row] = (long long)na; p.counts[3 * p.rows + row] = (long long)nb;
+        }
+        if (empty && p.status) atomicAdd(&p.status[1], 1);
+    }
+    if (!p.stats) return;
+    const int npix = p.W * p.H;
+    const double* MA = p.map[0] + (p.map_row0 + y) * (long)npix;
+    const double* MB = p.map[1] + (p.map_row0 + y) * (long)npix;
+    const double nan = __builtin_nan("");
+    const double mass_a = NA ? sal_mass(MA, p.ay, p.W, npix, tid, s_w[0]) : nan;
+    const double mass_b = NB ? sal_mass(MB, p.ay, p.W, npix, tid, s_w[0]) : nan;
+    if (empty) {                                                 // uniform
+        if (tid < 7) p.stats[tid * p.rows + row] = nan;
+        if (tid == 0) { p.stats[7 * p.rows + row] = mass_a; p.stats[8 * p.rows + row] = mass_b; }
+        return;
+    }
+    double sum[SC_SUMS];
+#pragma unroll
+    for (int k = 0; k < SC_SUMS; ++k) sum[k] = 0.0;
+    for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+        double t[SC_SUMS];
+#pragma unroll
+        for (int k = 0; k < SC_SUMS; ++k) t[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < npix) {
+                const double a = MA[q], b = MB[q], ay = p.ay[q / p.W];
+                const double qa = (a * ay) / mass_a, qb = (b * ay) / mass_b;
+                const double da = a - mass_a, db = b - mass_b;
+                const double m = 0.5 * (qa + qb);
+                const double ta = qa != 0.0 ? qa * log2(qa / m) : 0.0;
+                const double tb = qb != 0.0 ? qb * log2(qb / m) : 0.0;
+                t[0] += ay * (da * da);
+                t[1] += ay * (db * db);
+                t[2] += ay * (da * db);
+                t[3] += fmin(qa, qb);
+                t[4] += ta + tb;
+                t[5] += qa != 0.0 ? qa * log2(qa / qb) : 0.0;
+                t[6] += qb != 0.0 ? qb * log2(qb / qa) : 0.0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < SC_SUMS; ++k) {                      // the rule's block step, the seven sums side by side
+            const double s = wave_sum(t[k]);
+            if (lane == 0) s_w[k][wv] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SC_SUMS; ++k) sum[k] += mo_block_total(s_w[k]);
+        __syncthreads();
+    }
+    double V[2];                                                 // the v_i of X = A, then of X = B, over the list positions
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const int nx = d ? nb : na;
+        const double* v = p.pts + ((long)d * p.CR + y) * p.cap;
+        double acc = 0.0;
+        for (int b0 = 0; b0 < nx; b0 += SM_BLOCK) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = b0 + k * SM_THREADS + tid;
+                if (q < nx) t += v[q];
+            }
+            acc += sal_block_sum(t, s_w[0]);
+        }
+        V[d] = acc;
+    }
+    if (tid == 0) {
+        const double va = sum[0], vb = sum[1];
+        p.stats[row] = sum[2] / sqrt(va * vb);
+        p.stats[p.rows + row] = sum[3];
+        p.stats[2 * p.rows + row] = 0.5 * sum[4];
+        p.stats[3 * p.rows + row] = sum[5];
+        p.stats[4 * p.rows + row] = sum[6];
+        p.stats[5 * p.rows + row] = (V[0] / (double)NA - mass_b) / sqrt(vb);
+        p.stats[6 * p.rows + row] = (V[1] / (double)NB - mass_a) / sqrt(va);
+        p.stats[7 * p.rows + row] = mass_a;
+        p.stats[8 * p.rows + row] = mass_b;
+    }
+}
+
 }  // namespace vet
 
 namespace vh {
@@ -384,6 +590,56 @@ int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride
 namespace {
 
 constexpr size_t kSaliencyPassBudget = (size_t)256 << 20;     // bytes of per-row workspace a pass may take
+
+// The host tables of a W x H map (ct | st | sp | cp | ay) written to tab on s: np.radians is x * (pi / 180).
+int saliency_tables(vet_ctx* c, int W, int H, double* tab, hipStream_t s) {
+    ProfScope ps(c, s, KID_TRANSITION);
+    const size_t ntab = (size_t)2 * W + (size_t)3 * H;
+    std::vector<double> h(ntab);
+    constexpr double kRad = 3.141592653589793 / 180.0, kPi = 3.141592653589793;
+    for (int x = 0; x < W; ++x) {
+        const double lon = ((double)x + 0.5) / (double)W * 360.0 - 180.0, theta = lon * kRad;
+        h[x] = std::cos(theta); h[(size_t)W + x] = std::sin(theta);
+    }
+    for (int y = 0; y < H; ++y) {
+        const double lat = 90.0 - ((double)y + 0.5) / (double)H * 180.0, phi = (90.0 - lat) * kRad;
+        h[(size_t)2 * W + y] = std::sin(phi); h[(size_t)2 * W + H + y] = std::cos(phi);
+        h[(size_t)2 * W + 2 * (size_t)H + y] =
+            (std::cos(kPi * (double)y / (double)H) - std::cos(kPi * (double)(y + 1) / (double)H)) / (2.0 * (double)W);
+    }
+    for (size_t o = 0; o < ntab; o += vet::SM_PART) {
+        vet::SalTablePart q;
+        q.n = (int)std::min((size_t)vet::SM_PART, ntab - o);
+        for (int i = 0; i < q.n; ++i) q.v[i] = h[o + i];
+        for (int i = q.n; i < vet::SM_PART; ++i) q.v[i] = 0.0;
+        q.dst = tab + o;
+        hipLaunchKernelGGL(vet::k_saliency_tables, dim3(1), dim3(vet::SM_THREADS), 0, s, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return VET_OK;
+}
+
+// The list stage of cr rows from g.r0: the LDS sort, or the dense counts and their compaction.
+int saliency_lists(vet_ctx* c, const vet::SalListParams& g, bool sorted, long cr, hipStream_t s) {
+    ProfScope ps(c, s, KID_TRANSITION);
+    if (sorted) {
+        hipLaunchKernelGGL(vet::k_saliency_sort, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+        HIP_TRY(hipGetLastError());
+        return VET_OK;
+    }
+    HIP_TRY(hipMemsetAsync(g.dense, 0, (size_t)cr * g.D * 4, s));
+    if (g.D <= vet::SM_LDS_DIRS) {                               // 16384 positions or more per workgroup, at most 64 workgroups a row
+        const long gx = std::max(1L, std::min(g.Wpos / 16384, 64L));
+        hipLaunchKernelGGL(vet::k_saliency_count<true>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), (size_t)g.D * 4, s, g);
+    } else {
+        const long gx = std::min((g.Wpos + vet::SM_THREADS - 1) / vet::SM_THREADS, 4096L);
+        hipLaunchKernelGGL(vet::k_saliency_count<false>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(vet::k_saliency_compact, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
+    HIP_TRY(hipGetLastError());
+    return VET_OK;
+}
 
 int launch_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
                     int per_user, double sigma, int W, int H, int scale, double* d_map, double* d_stats, int32_t* d_peak,
@@ -429,29 +685,9 @@ int launch_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, const 
         }
         HIP_TRY(hipGetLastError());
     }
-    if (want_map) {  // the host tables: np.radians is x * (pi / 180)
-        ProfScope ps(c, s, KID_TRANSITION);
-        std::vector<double> h(ntab);
-        constexpr double kRad = 3.141592653589793 / 180.0, kPi = 3.141592653589793;
-        for (int x = 0; x < W; ++x) {
-            const double lon = ((double)x + 0.5) / (double)W * 360.0 - 180.0, theta = lon * kRad;
-            h[x] = std::cos(theta); h[(size_t)W + x] = std::sin(theta);
-        }
-        for (int y = 0; y < H; ++y) {
-            const double lat = 90.0 - ((double)y + 0.5) / (double)H * 180.0, phi = (90.0 - lat) * kRad;
-            h[(size_t)2 * W + y] = std::sin(phi); h[(size_t)2 * W + H + y] = std::cos(phi);
-            h[(size_t)2 * W + 2 * (size_t)H + y] =
-                (std::cos(kPi * (double)y / (double)H) - std::cos(kPi * (double)(y + 1) / (double)H)) / (2.0 * (double)W);
-        }
-        for (size_t o = 0; o < ntab; o += vet::SM_PART) {
-            vet::SalTablePart q;
-            q.n = (int)std::min((size_t)vet::SM_PART, ntab - o);
-            for (int i = 0; i < q.n; ++i) q.v[i] = h[o + i];
-            for (int i = q.n; i < vet::SM_PART; ++i) q.v[i] = 0.0;
-            q.dst = tab + o;
-            hipLaunchKernelGGL(vet::k_saliency_tables, dim3(1), dim3(vet::SM_THREADS), 0, s, q);
-            HIP_TRY(hipGetLastError());
-        }
+    if (want_map) {
+        rc = saliency_tables(c, W, H, tab, s);
+        if (rc) return rc;
     }
     vet::SalListParams g{};
     g.ids = ids; g.R = R; g.Wpos = Wpos; g.D = D; g.cap = cap;
@@ -471,24 +707,8 @@ int launch_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, const 
     for (long r0 = 0; r0 < rows; r0 += CR) {
         const long cr = std::min(CR, rows - r0);
         g.r0 = r0;
-        if (sorted) {
-            ProfScope ps(c, s, KID_TRANSITION);
-            hipLaunchKernelGGL(vet::k_saliency_sort, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
-            HIP_TRY(hipGetLastError());
-        } else {
-            ProfScope ps(c, s, KID_TRANSITION);
-            HIP_TRY(hipMemsetAsync(g.dense, 0, (size_t)cr * D * 4, s));
-            if (D <= vet::SM_LDS_DIRS) {                         // 16384 positions or more per workgroup, at most 64 workgroups a row
-                const long gx = std::max(1L, std::min(Wpos / 16384, 64L));
-                hipLaunchKernelGGL(vet::k_saliency_count<true>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), (size_t)D * 4, s, g);
-            } else {
-                const long gx = std::min((Wpos + vet::SM_THREADS - 1) / vet::SM_THREADS, 4096L);
-                hipLaunchKernelGGL(vet::k_saliency_count<false>, dim3((unsigned)gx, (unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
-            }
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(vet::k_saliency_compact, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, g);
-            HIP_TRY(hipGetLastError());
-        }
+        rc = saliency_lists(c, g, sorted, cr, s);
+        if (rc) return rc;
         if (want_map) {
             m.out_row0 = d_map ? r0 : 0;
             ProfScope pm(c, s, KID_SPATIAL);
@@ -506,7 +726,128 @@ int launch_saliency(vet_plan* pl, const double* d_mu, const double* d_mv, const 
     return VET_OK;
 }
 
+// vet_saliency_similarity*: stage 0 on all viewers, the mask, then per pass of rows the lists and maps of A and of B by the kernels
+// of vet_saliency, the point evaluations and the comparison.  The dense counts of the long-row path serve A, then B.
+int launch_similarity(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
+                      const int8_t* groups, double sigma, int W, int H, double* d_maps, double* d_stats, int64_t* d_counts,
+                      int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const long R = (long)vet_window_rows(T, window, stride);
+    const long Wpos = (long)window * U, D = (long)pl->n_dirs, n = (long)T * U;
+    const long npix = (long)W * H, cap = std::min(Wpos, D);
+    const bool sorted = Wpos <= vet::SM_SORT_MAX;
+    const bool want_map = d_maps || d_stats;
+    int tile = vet::SM_TILE;
+    if (c->tune.saliency_tile > 0) tile = std::min(tile, c->tune.saliency_tile);
+    // per row of a pass: two lists with their lengths and N, the dense counts, two maps when they stay here, the v_i of both directions
+    const size_t per_row = (size_t)2 * cap * 8 + 32 + (sorted ? 0 : (size_t)D * 4) + (want_map && !d_maps ? (size_t)2 * npix * 8 : 0) +
+                           (d_stats ? (size_t)2 * cap * 8 : 0);
+    const long CR = std::max(1L, std::min({(long)(kSaliencyPassBudget / per_row), R, 65535L}));
+    const size_t ntab = (size_t)2 * W + (size_t)3 * H;
+    WsLayout lay;
+    const size_t ids_o = lay.take<int32_t>((size_t)n), ida_o = lay.take<int32_t>((size_t)n), idb_o = lay.take<int32_t>((size_t)n),
+                 tab_o = lay.take<double>(ntab), list_o = lay.take<uint2>((size_t)2 * CR * cap), nl_o = lay.take<int32_t>((size_t)2 * CR),
+                 ns_o = lay.take<unsigned long long>((size_t)2 * CR), dense_o = lay.take<uint32_t>(sorted ? 0 : (size_t)CR * D),
+                 map_o = lay.take<double>(want_map && !d_maps ? (size_t)2 * CR * npix : 0),
+                 pts_o = lay.take<double>(d_stats ? (size_t)2 * CR * cap : 0);
+    int rc = ensure_ws(c, lay.at);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    int32_t* ids = (int32_t*)(ws + ids_o);
+    int32_t* ids_g[2] = {(int32_t*)(ws + ida_o), (int32_t*)(ws + idb_o)};
+    double* tab = (double*)(ws + tab_o);
+    const double kappa = 1.0 / (sigma * sigma);
+    const double C = kappa / (2.0 * 3.141592653589793 * (1.0 - std::exp(-2.0 * kappa)));
+    BatchBlob blob;                                              // the labels as bytes; the host array is read before the call returns
+    rc = blob.acquire(c, pad16((size_t)U));
+    if (rc) return rc;
+    for (int u = 0; u < U; ++u) ((unsigned char*)blob.host())[u] = (unsigned char)groups[u];
+    rc = blob.upload(s);
+    if (rc) return rc;
+    {   // stage 0 on every viewer (status[0] counts the excluded viewers' samples too), then the mask
+        ProfScope ps(c, s, KID_TRANSITION);
+        const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, D};
+        const dim3 grid((unsigned)((n + vet::SM_THREADS - 1) / vet::SM_THREADS));
+        if (d_ids) hipLaunchKernelGGL(vet::k_saliency_ids<true>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+        else hipLaunchKernelGGL(vet::k_saliency_ids<false>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(vet::k_saliency_mask, grid, dim3(vet::SM_THREADS), 0, s, ids, (const unsigned char*)blob.dev(), n, U, ids_g[0],
+                           ids_g[1]);
+        HIP_TRY(hipGetLastError());
+    }
+    if (want_map) {
+        rc = saliency_tables(c, W, H, tab, s);
+        if (rc) return rc;
+    }
+    vet::SalListParams g[2];
+    vet::SalMapParams m[2];
+    vet::SalPointParams pt{};
+    vet::SalCompareParams q{};
+    for (int a = 0; a < 2; ++a) {
+        g[a] = vet::SalListParams{};
+        g[a].ids = ids_g[a]; g[a].R = R; g[a].Wpos = Wpos; g[a].D = D; g[a].cap = cap;
+        g[a].U = U; g[a].T = T; g[a].stride = stride; g[a].per_user = 0;
+        g[a].P = 2;
+        while (sorted && g[a].P < Wpos) g[a].P <<= 1;
+        g[a].list = (uint2*)(ws + list_o) + (size_t)a * CR * cap; g[a].nlist = (int32_t*)(ws + nl_o) + (size_t)a * CR;
+        g[a].nsamp = (unsigned long long*)(ws + ns_o) + (size_t)a * CR;
+        g[a].dense = (unsigned*)(ws + dense_o);
+        m[a] = vet::SalMapParams{};
+        m[a].list = g[a].list; m[a].nlist = g[a].nlist; m[a].nsamp = g[a].nsamp; m[a].unit = pl->d_dir_unit; m[a].tab = tab; m[a].cap = cap;
+        m[a].W = W; m[a].H = H; m[a].tile = tile; m[a].scale = 2; m[a].kappa = kappa; m[a].C = C;
+        m[a].out = d_maps ? d_maps + (size_t)a * R * npix : (double*)(ws + map_o) + (size_t)a * CR * npix;
+        pt.list[a] = g[a].list; pt.nlist[a] = g[a].nlist; pt.nsamp[a] = g[a].nsamp;
+        q.map[a] = want_map ? m[a].out : nullptr; q.nlist[a] = g[a].nlist; q.nsamp[a] = g[a].nsamp;
+    }
+    pt.unit = pl->d_dir_unit; pt.cap = cap; pt.CR = CR; pt.tile = tile; pt.kappa = kappa; pt.C = C; pt.pts = (double*)(ws + pts_o);
+    q.ay = tab + (size_t)2 * W + 2 * (size_t)H; q.pts = pt.pts; q.cap = cap; q.CR = CR; q.rows = R; q.W = W; q.H = H;
+    q.stats = d_stats; q.counts = (long long*)d_counts; q.status = d_status;
+    const bool want_rows = d_stats || d_counts || d_status;
+    for (long r0 = 0; r0 < R; r0 += CR) {
+        const long cr = std::min(CR, R - r0);
+        for (int a = 0; a < 2; ++a) {
+            g[a].r0 = r0;
+            rc = saliency_lists(c, g[a], sorted, cr, s);
+            if (rc) return rc;
+            if (want_map) {
+                m[a].out_row0 = d_maps ? r0 : 0;
+                ProfScope pm(c, s, KID_SPATIAL);
+                const dim3 grid((unsigned)((npix + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr);
+                hipLaunchKernelGGL(vet::k_saliency_map, grid, dim3(vet::SM_THREADS), 0, s, m[a]);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (d_stats) {
+            ProfScope pp(c, s, KID_SPATIAL);
+            const dim3 grid((unsigned)((cap + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr, 2);
+            hipLaunchKernelGGL(vet::k_saliency_points, grid, dim3(vet::SM_THREADS), 0, s, pt);
+            HIP_TRY(hipGetLastError());
+        }
+        if (want_rows) {
+            ProfScope ps(c, s, KID_TRANSITION);
+            q.map_row0 = d_maps ? r0 : 0; q.r0 = r0;
+            hipLaunchKernelGGL(vet::k_saliency_compare, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return VET_OK;
+}
+
 }  // namespace
+
+// What vet_saliency_similarity* refuse: check_saliency_args for the pooled layout at scale 2, groups NULL, an audience without a viewer.
+int check_similarity_args(const vet_plan* pl, int U, int T, int window, int stride, const int8_t* groups, double sigma, int W, int H) {
+    int rc = check_saliency_args(pl, U, T, window, stride, 0, sigma, W, H, 2);
+    if (rc) return rc;
+    if (!groups) return fail(VET_ERR_INVALID, "groups is NULL");
+    int na = 0, nb = 0;
+    for (int u = 0; u < U; ++u) {
+        na += groups[u] == 0;
+        nb += groups[u] == 1;
+    }
+    if (na < 1 || nb < 1) return fail(VET_ERR_INVALID, "both audiences need a viewer (got %d in A, %d in B)", na, nb);
+    return VET_OK;
+}
 
 int saliency_set_attrs(vet_ctx*) {
     HIP_TRY(hipFuncSetAttribute((const void*)vet::k_saliency_count<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -538,6 +879,26 @@ int vet_saliency_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int windo
     if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
     return rc ? rc : launch_saliency(pl, nullptr, nullptr, d_ids, U, T, window, stride, per_user, sigma_rad, W, H, scale, d_map,
                                      d_stats, d_peak, d_counts, d_status, s);
+}
+
+int vet_saliency_similarity(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride,
+                            const int8_t* groups, double sigma_rad, int W, int H, double* d_maps, double* d_stats, int64_t* d_counts,
+                            int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_similarity_args(pl, U, T, window, stride, groups, sigma_rad, W, H);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_saliency_similarity_ids", stream, &s);
+    return rc ? rc : launch_similarity(pl, d_mu, d_mv, nullptr, U, T, window, stride, groups, sigma_rad, W, H, d_maps, d_stats, d_counts,
+                                       d_status, s);
+}
+
+int vet_saliency_similarity_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, const int8_t* groups,
+                                double sigma_rad, int W, int H, double* d_maps, double* d_stats, int64_t* d_counts, int32_t* d_status,
+                                void* stream) {
+    hipStream_t s;
+    int rc = check_similarity_args(pl, U, T, window, stride, groups, sigma_rad, W, H);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_similarity(pl, nullptr, nullptr, d_ids, U, T, window, stride, groups, sigma_rad, W, H, d_maps, d_stats,
+                                       d_counts, d_status, s);
 }
 
 }  // extern "C"

@@ -141,6 +141,9 @@ SIGNATURES = {
     "vet_saliency": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P]),
+    "vet_saliency_similarity": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_saliency_similarity_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_saliency_similarity_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -548,6 +551,13 @@ _SALIENCY_CALLS = {
            (("map", "URYX", _F64, True), ("stats", "4UR", _F64, False), ("peak", "UR", _I32, False), ("counts", "2UR", _NP_I64, False))),
 }
 SALIENCY_SCALES = {"none": 0, "mean": 1, "density": 2}
+
+# The saliency similarity call, in a table of its own: one descriptor of the same form (dims Y, X: the map's rows and columns; 9
+# statistics: cc, sim, jsd, kl_ab, kl_ba, nss_ab, nss_ba, mass_a, mass_b; 4 counts: samples_a, samples_b, distinct_a, distinct_b).
+# Rows count frames; its extra arguments are the host array groups, sigma in radians and the map's size.
+_SALIENCY_SIMILARITY_CALL = ("vet_saliency_similarity", False, True, False,
+                             (("maps", "2RYX", _F64, True), ("stats", "9R", _F64, False), ("counts", "4R", _NP_I64, False)))
+SALIENCY_SIMILARITY_STATS = ("cc", "sim", "jsd", "kl_ab", "kl_ba", "nss_ab", "nss_ba", "mass_a", "mass_b")
 
 
 class Plan:
@@ -1075,6 +1085,22 @@ class Plan:
         return self._row_host(_SALIENCY_CALLS[bool(per_user)], mu, mv, ids, window, stride, {"map"} if want_map else set(), check,
                               extra=(int(bool(per_user)), sigma, W, H, sc), extra_dims={"Y": H, "X": W, "2": 2})
 
+    def saliency_similarity(self, mu=None, mv=None, ids=None, groups=None, window=1, stride=1, sigma_deg=5.0, width=180, height=90,
+                            want_maps=False, check=True):
+        """Saliency similarity of two audiences (include/vet.h: vet_saliency_similarity): ``groups`` [U] is 0 (audience A), 1
+        (audience B) or -1 (excluded); for every row of ``saliency`` (frames [r * stride, r * stride + window), ``window=None`` the
+        whole video) the density maps of the two audiences' samples are compared.  Returns dict(maps[2,R,H,W]|None
+        (``want_maps``: A's maps, then B's), stats[9,R] (cc = Pearson's correlation, sim = histogram intersection, jsd and kl_ab /
+        kl_ba in bits, nss_ab / nss_ba = A's samples on B's standardised density and the reverse, by evaluating the density at the
+        samples' directions, mass_a, mass_b), counts[4,R] int64 (samples_a, samples_b, distinct_a, distinct_b), code),
+        R = (T - window) // stride + 1.  A row in which an audience has no sample is NaN — data, never an error; kl is +inf where
+        one audience has weight on a cell in which the other's density underflowed to zero; ``code`` is VET_OK or VET_ERR_RANGE."""
+        sigma, W, H, _ = self._saliency_args(sigma_deg, width, height, "density")
+        first = ids if ids is not None else mu
+        g = self._group_array(groups, np.shape(first)[1] if np.ndim(first) == 2 else None)
+        return self._row_host(_SALIENCY_SIMILARITY_CALL, mu, mv, ids, window, stride, {"maps"} if want_maps else set(), check,
+                              extra=(_ptr(g), sigma, W, H), extra_dims={"Y": H, "X": W, "2": 2, "9": 9})
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1289,6 +1315,17 @@ class Plan:
         self._row_device(_SALIENCY_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, int(bool(per_user)), sigma, W, H, sc), d_map or None,
                          (d_stats, d_peak, d_counts, d_status), stream)
+
+    def saliency_similarity_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, groups,
+                                   sigma_deg: float = 5.0, width: int = 180, height: int = 90, d_maps: int = 0, d_stats: int = 0,
+                                   d_counts: int = 0, d_status: int = 0, stream=None, d_ids: int = 0):
+        """``groups``: the host array [U]; d_maps f64 [2][R][H][W]; d_stats f64 [9][R]; d_counts i64 [4][R]; every output may be 0 —
+        without d_maps no map leaves the workspace (include/vet.h: vet_saliency_similarity; ``d_ids``:
+        vet_saliency_similarity_ids)."""
+        sigma, W, H, _ = self._saliency_args(sigma_deg, width, height, "density")
+        g = self._group_array(groups, n_users)
+        self._row_device(_SALIENCY_SIMILARITY_CALL, d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, g.ctypes.data, sigma, W, H), d_maps or None, (d_stats, d_counts, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

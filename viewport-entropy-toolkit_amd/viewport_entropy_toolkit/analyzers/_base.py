@@ -747,5 +747,72 @@ class _EntropyAnalyzerBase:
         return self._saliency_frame(times, names, window, stride, bool(per_user), res, float(sigma_deg), int(width), int(height),
                                     normalize)
 
+    @staticmethod
+    def _saliency_similarity_frame(times, names, window: int, stride: int, code, labels, res: dict, sigma_deg: float, width: int,
+                                   height: int) -> pd.DataFrame:
+        """The saliency similarity as a DataFrame, one row per window; where ``res`` holds the maps, ``map_a`` / ``map_b`` of a row
+        are the [H, W] views of its two maps in the one [2][R][H][W] array (no copy)."""
+        times = np.asarray(times)
+        stats = np.asarray(res["stats"], dtype=np.float64).reshape(9, -1)
+        counts = np.asarray(res["counts"]).reshape(4, -1)
+        R = stats.shape[1]
+        first = np.arange(R, dtype=np.int64) * stride
+        cols = dict(time=times[first], time_end=times[first + window - 1], samples_a=counts[0], samples_b=counts[1],
+                    distinct_a=counts[2], distinct_b=counts[3])
+        cols.update(zip(_native.SALIENCY_SIMILARITY_STATS, stats))
+        if res.get("maps") is not None:
+            maps = np.asarray(res["maps"]).reshape(2, R, height, width)
+            for g, name in enumerate(("map_a", "map_b")):
+                m_col = np.empty(R, dtype=object)
+                for r in range(R):
+                    m_col[r] = maps[g, r]
+                cols[name] = m_col
+        df = pd.DataFrame(cols)
+        names = list(names)
+        df.attrs.update(groups=labels, sizes=(int((code == 0).sum()), int((code == 1).sum())),
+                        users=([n for n, c in zip(names, code) if c == 0], [n for n, c in zip(names, code) if c == 1]),
+                        sigma_deg=float(sigma_deg), kappa=1.0 / min(float(np.radians(sigma_deg)), float(np.pi)) ** 2, width=width,
+                        height=height, window=window, stride=stride)
+        return df
+
+    def compute_saliency_similarity(self, groups, window: Optional[int] = 1, stride: int = 1, sigma_deg: float = 5.0, width: int = 180,
+                                    height: int = 90, keep_maps: bool = False) -> pd.DataFrame:
+        """How alike two audiences look at the video, on the tiling-free saliency maps: per window of frames
+        [r * stride, r * stride + window) (``window=None``: the whole video) the density maps of ``compute_saliency``
+        ("density", the same ``sigma_deg``, ``width``, ``height``) of audience A's and of audience B's samples, and the metrics
+        saliency benchmarks report between two maps.
+
+        ``groups`` is ``compute_group_divergence``'s argument: a sequence aligned with the analyzer's user order, or a mapping from
+        user name to label; exactly two distinct labels, the first in sorted order is audience A; ``None`` / NaN (and users a
+        mapping does not name) are excluded.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, one row per window: ``time`` / ``time_end``,
+        ``samples_a`` / ``samples_b``, ``distinct_a`` / ``distinct_b`` (directions), ``cc`` (Pearson's correlation of the two maps,
+        area-weighted), ``sim`` (histogram intersection of the maps as distributions over the sphere, 1 = the same), ``jsd``
+        (Jensen-Shannon divergence, bits, 0 .. 1), ``kl_ab`` / ``kl_ba`` (Kullback-Leibler divergence of A from B and of B from
+        A, bits; +inf where one audience has weight on a cell in which the other's density underflowed to zero — small
+        ``sigma_deg``), ``nss_ab`` / ``nss_ba`` (normalised scanpath saliency: B's standardised density at A's samples and the
+        reverse, the density evaluated at the samples' directions; positive = they look where the other audience's density is
+        above its sphere average), ``mass_a`` / ``mass_b`` (each map's mean over the sphere, 4 pi * mass near 1 when the map
+        resolves sigma) and, with ``keep_maps``, ``map_a`` / ``map_b`` ([H, W] views into one result array).  ``attrs`` hold
+        ``groups`` (the two labels), ``sizes``, ``users``, ``sigma_deg``, ``kappa``, ``width``, ``height``, ``window`` and
+        ``stride``.  A window in which an audience has no sample has NaN metrics — returned, never raised.  Raises
+        ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for illegal arguments and, with
+        ``keep_maps``, for maps beyond 4 GiB."""
+        times, names, call = self._row_call("saliency_similarity")
+        code, labels = self._group_labels(groups, names)
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        _native.Plan._saliency_args(sigma_deg, width, height, "density")
+        rows = 2 * ((len(times) - window) // stride + 1)
+        if keep_maps and rows * int(width) * int(height) * 8 > self.SALIENCY_MAP_LIMIT:
+            raise ValueError(f"{rows} maps of {width} x {height} are {rows * int(width) * int(height) * 8 / 2 ** 30:.1f} GiB, beyond 4 GiB: "
+                             "use a larger stride, a coarser map (width, height), or keep_maps=False")
+        res = call(groups=code, window=window, stride=stride, sigma_deg=float(sigma_deg), width=int(width), height=int(height),
+                   want_maps=bool(keep_maps), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._saliency_similarity_frame(times, names, window, stride, code, labels, res, float(sigma_deg), int(width),
+                                               int(height))
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError
