@@ -69,7 +69,8 @@ extern "C" {
                           frame over all pairs, per window and per viewer), and then the vet_saliency* entry points (saliency
                           maps: the spherical kernel density of a window's viewing directions on an equirectangular map, with its
                           mass, peak, entropy and effective area, per window and per viewer) and vet_test_saliency_tile, and then
-                          the vet_saliency_similarity* entry points (CC, SIM, JSD, KL and NSS between the maps of two audiences) */
+                          the vet_saliency_similarity* entry points (CC, SIM, JSD, KL and NSS between the maps of two audiences), and
+                          then the vet_congruency* entry points (each viewer's leave-one-out saliency score per window) */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -156,8 +157,8 @@ int vet_test_motion_lds_values(vet_ctx *ctx, int n);
  * Results are bit-identical whatever the value. */
 int vet_test_dispersion_tile(vet_ctx *ctx, int n);
 /* Test switch, not a tuning knob: n > 0 lowers the most list entries of a row that k_saliency_map (vet_saliency*,
- * vet_saliency_similarity*) and k_saliency_points (vet_saliency_similarity*: the other audience's list) stage in LDS at a time
- * (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
+ * vet_saliency_similarity*), k_saliency_points (vet_saliency_similarity*: the other audience's list) and k_congruency_points
+ * (vet_congruency*: the pooled list) stage in LDS at a time (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
 int vet_test_saliency_tile(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
@@ -1254,6 +1255,72 @@ int vet_saliency_similarity_ids(vet_plan *plan, const int32_t *d_ids, int n_user
 int vet_saliency_similarity_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                                  int n_frames, int window, int stride, const int8_t *groups, double sigma_rad, int W, int H,
                                  double *h_maps, double *h_stats, int64_t *h_counts);
+
+/* ---- viewer congruency: the leave-one-out saliency score of every viewer per window ------------------
+ * Not in the reference.  Inter-observer congruency: how well the REST of the audience predicts where viewer u looks, per window of
+ * frames — the noise ceiling of a saliency model, the outlier detector for viewers, the lattice-free counterpart of
+ * vet_crowd_divergence.  No map is built: the others' kernel density is evaluated AT the viewer's own directions, and the mean and
+ * variance of that density over the sphere are closed forms of the vMF kernel.
+ * ROWS, PRESENCE, ids, the KERNEL k(P, A) = exp(kappa * (c - 1)) with its fused dot c, kappa = 1 / sigma^2, C = kappa / (2 pi (1 -
+ * exp(-2 kappa))) and the summation RULE exactly as vet_saliency (the rule: blocks of 1024 positions, thread t of 256 adds t, t + 256,
+ * t + 512, t + 768 to +0.0 in that order, then wave_sum, the four waves in order, the blocks ascending).  R = vet_window_rows(n_frames,
+ * window, stride); row r covers frames [r*stride, r*stride + window).
+ * LISTS of row r: the POOLED list is vet_saliency's (per_user = 0): the distinct ids d_j in ascending id with multiplicities m_j,
+ * N = sum m_j.  Viewer u's OWN list is vet_saliency's per-viewer list of the same row: multiplicities a_j, n_u = sum a_j, distinct_u
+ * entries.  The OTHERS: N' = N - n_u, w_j = m_j - a_j (a_j = 0 where u does not hold d_j), an integer >= 0, taken as integers.
+ * DENSITY OF THE OTHERS at own entry i (unit row A_i): S_i starts at +0.0 and runs over the POOLED list in ascending id,
+ * S_i = fma((double)w_j, k(A_i, A_j), S_i); f_i = S_i * g with g = C / (double)N'.  An entry with w_j = 0 adds exactly nothing, so S_i
+ * has the bits k_saliency_points produces on the list of everyone but u; no difference of two densities is taken anywhere.
+ * OVERLAP of two kernels, G(c) = the integral over the sphere of k(., A_i) k(., A_j):  r = sqrt(fmax(0, fma(2, c, 2))), x = kappa * r;
+ * x < 1e-4 (antipodal directions): G = g0 * (1 + (x*x) / 6) with the host constant g0 = 4 pi exp(-2 kappa); otherwise
+ * G = ((2 pi * exp(kappa * (r - 2))) * (-expm1(-2 * x))) / x  (ocml sqrt, exp, expm1).  With want_nss the same walk carries, per own
+ * entry i,  T_i = fma((double)m_j, G_ij, T_i) over the whole pooled list  and  O_i = fma((double)a_j, G_ij, O_i) over the entries the
+ * viewer holds, both from +0.0 in ascending id.  T_i depends on the direction alone: every viewer that holds it has the same bits.
+ * PER (u, r), sums over the own entries by the rule with the own-list positions as the positions:
+ *   F = sum (double)a_i * f_i;  L = sum (double)a_i * log2(4 pi * f_i)  (ocml log2; 4 pi = 4 * 3.141592653589793);
+ *   B_u = sum (double)a_i * T_i;  A_u = sum (double)a_i * O_i
+ *   lift      = (4 pi * F) / (double)n_u       the others' density at the viewer's samples relative to the uniform sphere (1 = chance)
+ *   info_gain = L / (double)n_u                bits over the uniform baseline; -inf where an S_i underflowed to 0.0: data, not an error
+ *   nss       = (F / (double)n_u - mu) / sqrt(v),  mu = 1 / (4 pi),  v = ((g*g) * Q_u) / (4 pi) - mu*mu,  Q_u = (Q - 2 * B_u) + A_u
+ *               with Q = sum_j (double)m_j * T_j by the rule over the POOLED list's positions (Q = sum_ij m_i m_j G_ij, so Q_u =
+ *               sum_ij w_i w_j G_ij is of Q's size and the subtraction is benign).  v <= 0 or not finite: NaN.
+ * A viewer without a sample in the row (n_u = 0) or alone in it (N' = 0) is NOT SCORED: NaN statistics, the counts as they are — data,
+ * not an error.
+ * PER ROW, by the rule with the viewer index as the position (a viewer that is not scored adds nothing): scored = the scored viewers,
+ * and the means lift, info_gain and nss = sum / scored with IEEE propagation (-inf and NaN carry; scored = 0 gives NaN) — the segment's
+ * inter-observer congruency.
+ * A value's bits depend on the plan, sigma, window and the row's frames only — not on stride, the number of rows, the video's length,
+ * the pass a row falls into, vet_test_saliency_tile, the entry point or the outputs asked for; a viewer's own values do not depend on
+ * the order of the other viewers' columns (every sum behind them runs over a list in ascending id), the row means do (the rule over
+ * the viewer index).  With want_nss = 0 the nss outputs (stats 2, rows 3) are NaN and every other output keeps its bytes.  No FP atomics.
+ * Outputs, each nullable (a NULL output is not written):
+ *   d_stats    [3][n_users][R] f64, statistic-major, then user-major: 0 lift, 1 info_gain, 2 nss
+ *   d_counts   [3][n_users][R] i64: 0 samples (n_u), 1 distinct (distinct_u), 2 others (N')
+ *   d_rows     [4][R] f64: 0 scored, 1 mean lift, 2 mean info_gain, 3 mean nss
+ *   d_status   [2] i32 {bad, #rows without a scored viewer}; the call ADDS, the caller zeroes
+ * Stages: the samples quantised once per layout (k_saliency_ids [T][U], k_user_dirs [U][T]); per pass of rows the pooled lists and
+ * every viewer's own lists by vet_saliency's list kernels; k_congruency_points — workgroup = (row, 256 queries), a query = (viewer,
+ * one entry of the viewer's own list) on a dense [U][min(window, directions)] grid (a workgroup without an active query returns, a
+ * wave without one skips the walk), the pooled list staged in LDS in tiles of 1024 entries of 32 B (unit vector, id, multiplicity;
+ * a broadcast), the leave-one-out weight one integer compare per step against the viewer's next own id: 64 VGPRs (96 with want_nss),
+ * no scratch, 32 KB LDS, 5 waves per SIMD (LDS-bound); k_congruency_users — one wave per (row, viewer) playing the rule's four waves
+ * in turn; k_congruency_rows — one workgroup per row.  With d_stats and d_rows both NULL no density is evaluated.
+ * Workspace: 8 B per sample + per row of a pass 8 B per list slot (pooled: min(window * n_users, directions); per viewer: n_users *
+ * min(window, directions)), 8 B (24 B with want_nss) per query slot, the dense counts on the long-row path (up to half the budget);
+ * a pass stays under vet_saliency's 256 MB budget.
+ * VET_ERR_INVALID (before anything is allocated or launched): window < 1, window > n_frames, stride < 1, sigma_rad not finite, <= 0
+ * or > pi, n_users < 2.  VET_ERR_UNSUPPORTED as vet_saliency for both layouts.
+ * Profile ids: k_congruency_points to k_spatial, the other stages to k_transition.  Asynchronous on `stream`. */
+int vet_congruency(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                   double sigma_rad, int want_nss, double *d_stats, int64_t *d_counts, double *d_rows, int32_t *d_status,
+                   void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_congruency_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, double sigma_rad,
+                       int want_nss, double *d_stats, int64_t *d_counts, double *d_rows, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_congruency_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                        int window, int stride, double sigma_rad, int want_nss, double *h_stats, int64_t *h_counts, double *h_rows);
 
 /* ---- hot path: TransitionEntropyAnalyzer.compute_entropy ------------------
  * (analyzers/transition_entropy.py:107-175 -> entropy_utils.py:213-332)

@@ -159,8 +159,9 @@ struct Tuning {
                                 // k_dispersion_pairs stages in LDS at a time (0 = 1024); read at every launch; the results do not
                                 // depend on it (test_dispersion_gpu.py)
     int saliency_tile = 0;          // vet_test_saliency_tile (no environment variable): the most list entries of a row that
-                                // k_saliency_map and k_saliency_points stage in LDS at a time (0 = 1024); read at every launch; the
-                                // results do not depend on it (test_saliency_gpu.py, test_saliency_similarity_gpu.py)
+                                // k_saliency_map, k_saliency_points and k_congruency_points stage in LDS at a time (0 = 1024); read at
+                                // every launch; the results do not depend on it (test_saliency_gpu.py,
+                                // test_saliency_similarity_gpu.py, test_congruency_gpu.py)
     void from_environment();
 };
 
@@ -523,6 +524,8 @@ int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride
 // ... and what vet_saliency_similarity* refuse: the above for the pooled layout, groups NULL (host memory [U]), an audience without a
 // viewer.
 int check_similarity_args(const vet_plan* pl, int U, int T, int window, int stride, const int8_t* groups, double sigma, int W, int H);
+// ... and what vet_congruency* refuse: check_saliency_args' sigma, window and stride for both layouts, fewer than two viewers.
+int check_congruency_args(const vet_plan* pl, int U, int T, int window, int stride, double sigma);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

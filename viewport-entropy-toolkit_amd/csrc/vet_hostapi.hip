@@ -148,9 +148,9 @@ struct StagedRun {
     }
 };
 
-// The thirteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
+// The fourteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
 // per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion, the saliency
-// maps, the saliency similarity) after their
+// maps, the saliency similarity, the viewer congruency) after their
 // refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
 // null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
 // entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
@@ -786,6 +786,23 @@ int vet_saliency_similarity_host(vet_plan* pl, const double* h_mu, const double*
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_saliency_similarity_ids, vet_saliency_similarity, pl, U, T, window, stride, groups, sigma_rad, W, H,
                            (double*)d[1], (double*)d[0], (int64_t*)d[2], run.status, run.s);
+    });
+}
+
+// Viewer congruency with host buffers (include/vet.h): where wanted stats [3][U][R], counts [3][U][R] and rows [4][R]; R =
+// vet_window_rows over the T frames.  Every output may be NULL.  Viewers without a sample or without company in a row are data: only
+// VET_ERR_RANGE is decoded from the status words.
+int vet_congruency_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window, int stride,
+                        double sigma_rad, int want_nss, double* h_stats, int64_t* h_counts, double* h_rows) {
+    int rc = check_congruency_args(pl, U, T, window, stride, sigma_rad);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t R = (size_t)vet_window_rows(T, window, stride);
+    const RowOut outs[3] = {{h_stats, 3 * R * U * 8, SLOT_ENTROPY}, {h_rows, 4 * R * 8, SLOT_OUT0}, {h_counts, 3 * R * U * 8, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_congruency_ids, vet_congruency, pl, U, T, window, stride, sigma_rad, want_nss, (double*)d[0],
+                           (int64_t*)d[2], (double*)d[1], run.status, run.s);
     });
 }
 

@@ -80,6 +80,12 @@
 //                                                               other audience's density at the entries' directions, its list in LDS tiles
 //                                              k_saliency_compare  one workgroup per row: the masses, CC, SIM, JSD, both KL and both NSS
 //                                                               of the two audiences' maps by the block-ordered sums
+//                                              k_congruency_points  the congruency call: workgroup = (row, 256 queries), a query = one entry
+//                                                               of one viewer's own list; the pooled list in LDS tiles with its ids, the
+//                                                               viewer's own multiplicity taken off on an id match (leave-one-out)
+//                                              k_congruency_users  one wave per (row, viewer): the own-entry sums by the block-ordered rule
+//                                              k_congruency_rows  one workgroup per row: Q, every viewer's lift, information gain and NSS,
+//                                                               the row's means over the scored viewers
 //   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave

@@ -20,6 +20,9 @@
 // viewer's samples -1), stages 1 and 2 run unchanged for audience A and for audience B per pass, k_saliency_points evaluates each
 // audience's density at the other's list entries (NSS without a pixel decision) and k_saliency_compare, one workgroup per row, takes
 // the two masses, CC, SIM, JSD and both KL from one pass over the two maps and the NSS from the point values, all by the same rule.
+// Viewer congruency (vet_congruency*): stage 0 for both layouts, stage 1 pooled and per viewer per pass, k_congruency_points walks the
+// pooled list once per entry of every viewer's own list with the viewer's own multiplicities taken off (the leave-one-out density of
+// the others at the viewer's directions; no map), k_congruency_users and k_congruency_rows take the sums by the same rule.
 // No CPU compute path; nothing here reads the environment.
 #include "vet_host.hpp"
 #include "vet_common.hpp"
@@ -562,6 +565,296 @@ __global__ __launch_bounds__(SM_THREADS) void k_saliency_compare(const SalCompar
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Viewer congruency (vet_congruency*): how well the rest of the audience predicts where a viewer looks — the leave-one-out density
+// of the others at the viewer's own directions, without a map.  Stage 0 runs for both layouts, the list stage once pooled and once
+// per viewer per pass of rows (the kernels above, unchanged).
+// k_congruency_points<NSS> — grid (ceil(U * cap_u / 256), rows of the pass); thread = query q = u * cap_u + slot: entry `slot` of
+// viewer u's own list of the row, its unit vector in registers.  The row's pooled list is staged in LDS in tiles as
+// k_saliency_points stages it, the entry's id packed next to its multiplicity (32 B an entry still), and read as a broadcast.  Both
+// lists ascend in id: the thread holds the id and multiplicity of its viewer's NEXT own entry and, on a match, takes that
+// multiplicity off the step's weight and moves on in the own list (global memory, cache-resident) — one integer compare per step,
+// w = m - a an integer, no difference of densities.  NSS: the step also adds m * G into T and, on a match, a * G into O (one sqrt,
+// exp, expm1 and division more per pair), and the query that sits on its own direction notes the pooled position, where it leaves T
+// for the row's Q (every viewer that holds the direction writes the same bits).  A workgroup without an active query returns; a wave
+// without one skips the walk, not the barriers of the staging.
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): <false> 64 VGPRs, <true> 96 VGPRs; neither uses scratch;
+// 32 768 B LDS (the workgroup's "any query" flag lives in the tile before the first staging); 5 waves per SIMD (LDS-bound).
+// ------------------------------------------------------------------------------------------
+struct CgEntry {                        // one staged pooled entry
+    double x, y, z;
+    unsigned id, m;
+};
+
+struct CgPointParams {
+    const uint2* plist;          // pooled [rows of the pass][cap_p]
+    const int32_t* pn;
+    const uint2* ulist;          // per viewer [U][rows of the pass][cap_u]
+    const int32_t* un;
+    const double* unit;          // [n_dirs][3]
+    long cap_p, cap_u, cr, plane;
+    int U, tile;
+    double kappa, g0;            // g0 = 4 pi exp(-2 kappa)
+    double* qs;                  // S [CR][U][cap_u]; NSS: T and O behind it, `plane` doubles apart
+    double* tp;                  // NSS: T at the pooled positions [CR][cap_p]
+};
+
+constexpr double CG_TWOPI = 2.0 * 3.141592653589793, CG_FOURPI = 4.0 * 3.141592653589793;
+
+// the integral of two kernels' product over the sphere, from the cosine between their centres
+__device__ __forceinline__ double cg_overlap(double c, double kappa, double g0) {
+    const double r = sqrt(fmax(0.0, fma(2.0, c, 2.0)));
+    const double x = kappa * r;
+    if (x < 1e-4) return g0 * (1.0 + (x * x) / 6.0);
+    return ((CG_TWOPI * exp(kappa * (r - 2.0))) * (-expm1(-2.0 * x))) / x;
+}
+
+template <bool NSS>
+__global__ __launch_bounds__(SM_THREADS) void k_congruency_points(const CgPointParams p) {
+    __shared__ CgEntry s_tile[SM_TILE];
+    int& s_any = *(int*)s_tile;                                  // read by all before the first staging barrier
+    const int tid = threadIdx.x;
+    const long y = blockIdx.y;
+    const long q = (long)blockIdx.x * SM_THREADS + tid;
+    int u = 0, slot = 0, nown = 0;
+    if (q < (long)p.U * p.cap_u) {
+        u = (int)(q / p.cap_u);
+        slot = (int)(q - (long)u * p.cap_u);
+        nown = p.un[(long)u * p.cr + y];
+    }
+    const bool active = slot < nown;
+    if (tid == 0) s_any = 0;
+    __syncthreads();
+    if (active) s_any = 1;
+    __syncthreads();
+    if (!s_any) return;                                          // uniform
+    const uint2* own = p.ulist + ((long)u * p.cr + y) * p.cap_u;
+    double Px = 0.0, Py = 0.0, Pz = 0.0;
+    unsigned nid = EMPTY_KEY, na = 0u;                           // the viewer's next own entry
+    int ptr = 0, jpos = 0;
+    if (active) {
+        const double* A = p.unit + 3L * own[slot].x;
+        Px = A[0]; Py = A[1]; Pz = A[2];
+        const uint2 e = own[0];
+        nid = e.x; na = e.y;
+    }
+    const bool wave_on = __ballot(active) != 0ull;
+    const int n = p.pn[y];
+    const uint2* list = p.plist + y * p.cap_p;
+    const double kappa = p.kappa, g0 = p.g0;
+    double S = 0.0, T = 0.0, O = 0.0;
+    for (int e0 = 0; e0 < n; e0 += p.tile) {
+        const int cnt = min(p.tile, n - e0);
+        __syncthreads();                                         // the readers of the tile before
+        for (int j = tid; j < cnt; j += SM_THREADS) {
+            const uint2 e = list[e0 + j];
+            const double* A = p.unit + 3L * e.x;
+            s_tile[j] = CgEntry{A[0], A[1], A[2], e.x, e.y};
+        }
+        __syncthreads();
+        if (!wave_on) continue;
+#pragma unroll 2
+        for (int j = 0; j < cnt; ++j) {                          // the same address in every lane: a broadcast
+            const CgEntry a = s_tile[j];
+            const double c = fma(Pz, a.z, fma(Py, a.y, Px * a.x));
+            const double k = exp(kappa * (c - 1.0));
+            double G = 0.0;
+            if (NSS) {
+                G = cg_overlap(c, kappa, g0);
+                T = fma((double)a.m, G, T);
+            }
+            unsigned w = a.m;
+            if (a.id == nid) {
+                w -= na;
+                if (NSS) {
+                    O = fma((double)na, G, O);
+                    if (ptr == slot) jpos = e0 + j;
+                }
+                ++ptr;
+                nid = EMPTY_KEY;
+                if (ptr < nown) {
+                    const uint2 e = own[ptr];
+                    nid = e.x; na = e.y;
+                }
+            }
+            S = fma((double)w, k, S);
+        }
+    }
+    if (active) {
+        const long o = (y * p.U + u) * p.cap_u + slot;
+        p.qs[o] = S;
+        if (NSS) {
+            p.qs[p.plane + o] = T;
+            p.qs[2 * p.plane + o] = O;
+            p.tp[y * p.cap_p + jpos] = T;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_congruency_users — one wave per (row, viewer), four to a workgroup: the own-entry sums F = sum a_i f_i, L = sum a_i log2(4 pi f_i)
+// and, with NSS, B = sum a_i T_i and A = sum a_i O_i by the rule over the own-list positions.  The wave plays the rule's four waves
+// in turn (lane l as thread l, 64 + l, 128 + l, 192 + l), so the bits are those of a 256-thread workgroup; no LDS, no barrier.
+// Resources: 94 VGPRs, no scratch, no LDS, 5 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+struct CgUserParams {
+    const uint2* ulist;
+    const int32_t* un;
+    const unsigned long long* uns;   // n_u [U][rows of the pass]
+    const unsigned long long* pns;   // N [rows of the pass]
+    const double* qs;
+    long cap_u, cr, plane;
+    int U, nss;
+    double C;
+    double* sums;                // [rows of the pass][U][4]: F, L, B, A
+};
+
+template <class Term>
+__device__ __forceinline__ double cg_wave_rule(int n, Term term) {
+    const int lane = lane_id();
+    double acc = 0.0;
+    for (int b0 = 0; b0 < n; b0 += SM_BLOCK) {
+        double s[SM_THREADS / WAVE];
+#pragma unroll
+        for (int w = 0; w < SM_THREADS / WAVE; ++w) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = b0 + k * SM_THREADS + w * WAVE + lane;
+                if (q < n) t += term(q);
+            }
+            s[w] = wave_sum(t);
+        }
+        acc += mo_block_total(s);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(SM_THREADS) void k_congruency_users(const CgUserParams p) {
+    const long pair = (long)blockIdx.x * (SM_THREADS / WAVE) + wave_id();
+    if (pair >= p.cr * p.U) return;                              // uniform in the wave
+    const long y = pair / p.U;
+    const int u = (int)(pair - y * p.U);
+    const long ur = (long)u * p.cr + y;
+    const unsigned long long nu = p.uns[ur], N = p.pns[y];
+    double F = 0.0, L = 0.0, B = 0.0, A = 0.0;
+    if (nu > 0ull && N > nu) {
+        const int n = p.un[ur];
+        const uint2* own = p.ulist + ur * p.cap_u;
+        const double* S = p.qs + (y * p.U + u) * p.cap_u;
+        const double g = p.C / (double)(N - nu);
+        F = cg_wave_rule(n, [&](int i) { return (double)own[i].y * (S[i] * g); });
+        L = cg_wave_rule(n, [&](int i) { return (double)own[i].y * log2(CG_FOURPI * (S[i] * g)); });
+        if (p.nss) {
+            B = cg_wave_rule(n, [&](int i) { return (double)own[i].y * S[p.plane + i]; });
+            A = cg_wave_rule(n, [&](int i) { return (double)own[i].y * S[2 * p.plane + i]; });
+        }
+    }
+    if (lane_id() == 0) {
+        double* o = p.sums + pair * 4;
+        o[0] = F; o[1] = L; o[2] = B; o[3] = A;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_congruency_rows — one workgroup per row of the pass: Q = sum_j m_j T_j by the rule over the pooled list's positions, then by the
+// rule over the viewer index the three statistics of every viewer (written on the way), the scored viewers and their sums.
+// Resources: 122 VGPRs, no scratch, 32 B LDS, 4 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+struct CgRowParams {
+    const uint2* plist;
+    const int32_t* pn;
+    const unsigned long long* pns;
+    const int32_t* un;
+    const unsigned long long* uns;
+    const double* tp;
+    const double* sums;          // null: only the counts are wanted
+    long cap_p, cr, r0, rows;
+    int U, nss;
+    double C;
+    double* stats;               // [3][U][rows] or null
+    long long* counts;           // [3][U][rows] or null
+    double* out_rows;            // [4][rows] or null
+    int32_t* status;             // [2] or null
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_congruency_rows(const CgRowParams p) {
+    __shared__ double s_w[SM_THREADS / WAVE];
+    const int tid = threadIdx.x;
+    const long y = blockIdx.x, row = p.r0 + y;
+    const unsigned long long N = p.pns[y];
+    const double nan = __builtin_nan("");
+    double Q = 0.0;
+    if (p.sums && p.nss) {
+        const int n = p.pn[y];
+        const uint2* list = p.plist + y * p.cap_p;
+        const double* T = p.tp + y * p.cap_p;
+        for (int b0 = 0; b0 < n; b0 += SM_BLOCK) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = b0 + k * SM_THREADS + tid;
+                if (q < n) t += (double)list[q].y * T[q];
+            }
+            Q += sal_block_sum(t, s_w);
+        }
+    }
+    const double mu = 1.0 / CG_FOURPI;
+    double sl = 0.0, si = 0.0, sn = 0.0, sc = 0.0;
+    for (int b0 = 0; b0 < p.U; b0 += SM_BLOCK) {
+        double tl = 0.0, ti = 0.0, tn = 0.0, tc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int u = b0 + k * SM_THREADS + tid;
+            if (u < p.U) {
+                const long ur = (long)u * p.cr + y, o = (long)u * p.rows + row, plane = (long)p.U * p.rows;
+                const unsigned long long nu = p.uns[ur];
+                if (p.counts) {
+                    p.counts[o] = (long long)nu;
+                    p.counts[plane + o] = (long long)p.un[ur];
+                    p.counts[2 * plane + o] = (long long)(N - nu);
+                }
+                const bool scored = nu > 0ull && N > nu;
+                tc += scored ? 1.0 : 0.0;
+                if (p.sums) {
+                    double lift = nan, gain = nan, nss = nan;
+                    if (scored) {
+                        const double* s = p.sums + (y * p.U + u) * 4;
+                        const double F = s[0];
+                        lift = (CG_FOURPI * F) / (double)nu;
+                        gain = s[1] / (double)nu;
+                        if (p.nss) {
+                            const double g = p.C / (double)(N - nu);
+                            const double Qu = (Q - 2.0 * s[2]) + s[3];
+                            const double v = ((g * g) * Qu) / CG_FOURPI - mu * mu;
+                            if (v > 0.0 && v < __builtin_inf()) nss = (F / (double)nu - mu) / sqrt(v);
+                        }
+                        tl += lift; ti += gain; tn += nss;
+                    }
+                    if (p.stats) {
+                        p.stats[o] = lift;
+                        p.stats[plane + o] = gain;
+                        p.stats[2 * plane + o] = nss;
+                    }
+                }
+            }
+        }
+        sl += sal_block_sum(tl, s_w);
+        si += sal_block_sum(ti, s_w);
+        sn += sal_block_sum(tn, s_w);
+        sc += sal_block_sum(tc, s_w);
+    }
+    if (tid == 0 && p.sums) {
+        if (p.out_rows) {
+            p.out_rows[row] = sc;
+            p.out_rows[p.rows + row] = sl / sc;
+            p.out_rows[2 * p.rows + row] = si / sc;
+            p.out_rows[3 * p.rows + row] = sn / sc;
+        }
+    }
+    if (tid == 0 && p.status && sc == 0.0) atomicAdd(&p.status[1], 1);   // fewer than two viewers present
+}
+
 }  // namespace vet
 
 namespace vh {
@@ -833,7 +1126,128 @@ int launch_similarity(vet_plan* pl, const double* d_mu, const double* d_mv, cons
     return VET_OK;
 }
 
+// vet_congruency*: stage 0 for both layouts, then per pass of rows the pooled lists, every viewer's own lists of the same rows, the
+// point walk, the own-entry sums and the rows.  The list kernels index a per-viewer row as u * R + r: a pass hands them R = the rows
+// of the pass and the ids from the pass's first frame on, so the own lists of a pass are [U][rows of the pass].  The dense counts of
+// the long-row path serve the pooled lists, then the viewers' in chunks of the rows they hold.
+int launch_congruency(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
+                      double sigma, int want_nss, double* d_stats, int64_t* d_counts, double* d_rows, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const long R = (long)vet_window_rows(T, window, stride);
+    const long Wp = (long)window * U, Wu = window, D = (long)pl->n_dirs, n = (long)T * U;
+    const long cap_p = std::min(Wp, D), cap_u = std::min(Wu, D);
+    const bool sorted_p = Wp <= vet::SM_SORT_MAX, sorted_u = Wu <= vet::SM_SORT_MAX;
+    const bool want_vals = d_stats || d_rows, nss = want_vals && want_nss;
+    int tile = vet::SM_TILE;
+    if (c->tune.saliency_tile > 0) tile = std::min(tile, c->tune.saliency_tile);
+    // the dense counts take up to half the budget (at least a row), the rows of a pass the rest
+    const long dense_rows = sorted_p ? 0 : std::max(1L, std::min((long)(kSaliencyPassBudget / 2 / ((size_t)D * 4)), 65535L));
+    const size_t per_row = (size_t)cap_p * 8 + 16 + (size_t)U * ((size_t)cap_u * 8 + 16) +
+                           (want_vals ? (size_t)U * cap_u * (nss ? 24 : 8) + (size_t)U * 32 + (nss ? (size_t)cap_p * 8 : 0) : 0);
+    long CR = std::max(1L, std::min({(long)((sorted_p ? kSaliencyPassBudget : kSaliencyPassBudget / 2) / per_row), R, 65535L,
+                                     (long)0x7FFFFFFF / U}));
+    if (!sorted_p) CR = std::min(CR, dense_rows);
+    const size_t plane = (size_t)CR * U * cap_u;
+    WsLayout lay;
+    const size_t idp_o = lay.take<int32_t>((size_t)n), idu_o = lay.take<int32_t>((size_t)n),
+                 pl_o = lay.take<uint2>((size_t)CR * cap_p), pn_o = lay.take<int32_t>((size_t)CR),
+                 ps_o = lay.take<unsigned long long>((size_t)CR), ul_o = lay.take<uint2>((size_t)CR * U * cap_u),
+                 un_o = lay.take<int32_t>((size_t)CR * U), us_o = lay.take<unsigned long long>((size_t)CR * U),
+                 dense_o = lay.take<uint32_t>((size_t)dense_rows * D), qs_o = lay.take<double>(want_vals ? plane * (nss ? 3 : 1) : 0),
+                 tp_o = lay.take<double>(nss ? (size_t)CR * cap_p : 0), sum_o = lay.take<double>(want_vals ? (size_t)CR * U * 4 : 0);
+    int rc = ensure_ws(c, lay.at);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    int32_t* ids_p = (int32_t*)(ws + idp_o);
+    int32_t* ids_u = (int32_t*)(ws + idu_o);
+    const double kappa = 1.0 / (sigma * sigma);
+    const double C = kappa / (2.0 * 3.141592653589793 * (1.0 - std::exp(-2.0 * kappa)));
+    {   // stage 0, both layouts; status[0] is raised by the pooled one alone
+        ProfScope ps(c, s, KID_TRANSITION);
+        const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, D};
+        const dim3 grid((unsigned)((n + vet::SM_THREADS - 1) / vet::SM_THREADS));
+        if (d_ids) hipLaunchKernelGGL(vet::k_saliency_ids<true>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids_p, d_status);
+        else hipLaunchKernelGGL(vet::k_saliency_ids<false>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids_p, d_status);
+        HIP_TRY(hipGetLastError());
+        vet::UserDirsParams q{};
+        q.src = src; q.U = U; q.T = T; q.dirs = ids_u; q.status = nullptr;
+        const dim3 gu((unsigned)((U + vet::UT - 1) / vet::UT), (unsigned)((T + vet::UT - 1) / vet::UT));
+        if (d_ids) hipLaunchKernelGGL(vet::k_user_dirs<true>, gu, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL(vet::k_user_dirs<false>, gu, dim3(256), 0, s, q);
+        HIP_TRY(hipGetLastError());
+    }
+    vet::SalListParams gp{}, gu{};
+    gp.ids = ids_p; gp.R = R; gp.Wpos = Wp; gp.D = D; gp.cap = cap_p; gp.U = U; gp.T = T; gp.stride = stride; gp.per_user = 0;
+    gp.P = 2;
+    while (sorted_p && gp.P < Wp) gp.P <<= 1;
+    gp.list = (uint2*)(ws + pl_o); gp.nlist = (int32_t*)(ws + pn_o); gp.nsamp = (unsigned long long*)(ws + ps_o);
+    gp.dense = (unsigned*)(ws + dense_o);
+    gu.Wpos = Wu; gu.D = D; gu.cap = cap_u; gu.U = U; gu.T = T; gu.stride = stride; gu.per_user = 1;
+    gu.P = 2;
+    while (sorted_u && gu.P < Wu) gu.P <<= 1;
+    gu.dense = gp.dense;
+    uint2* ulist = (uint2*)(ws + ul_o);
+    int32_t* un = (int32_t*)(ws + un_o);
+    unsigned long long* uns = (unsigned long long*)(ws + us_o);
+    vet::CgPointParams pt{};
+    pt.plist = gp.list; pt.pn = gp.nlist; pt.ulist = ulist; pt.un = un; pt.unit = pl->d_dir_unit; pt.cap_p = cap_p; pt.cap_u = cap_u;
+    pt.plane = (long)plane; pt.U = U; pt.tile = tile; pt.kappa = kappa; pt.g0 = 4.0 * 3.141592653589793 * std::exp(-2.0 * kappa);
+    pt.qs = (double*)(ws + qs_o); pt.tp = (double*)(ws + tp_o);
+    vet::CgUserParams us{};
+    us.ulist = ulist; us.un = un; us.uns = uns; us.pns = gp.nsamp; us.qs = pt.qs; us.cap_u = cap_u; us.plane = (long)plane; us.U = U;
+    us.nss = nss ? 1 : 0; us.C = C; us.sums = (double*)(ws + sum_o);
+    vet::CgRowParams q{};
+    q.plist = gp.list; q.pn = gp.nlist; q.pns = gp.nsamp; q.un = un; q.uns = uns; q.tp = pt.tp; q.sums = want_vals ? us.sums : nullptr;
+    q.cap_p = cap_p; q.rows = R; q.U = U; q.nss = us.nss; q.C = C; q.stats = d_stats; q.counts = (long long*)d_counts; q.out_rows = d_rows;
+    q.status = d_status;
+    for (long r0 = 0; r0 < R; r0 += CR) {
+        const long cr = std::min(CR, R - r0);
+        gp.r0 = r0;
+        rc = saliency_lists(c, gp, sorted_p, cr, s);
+        if (rc) return rc;
+        gu.ids = ids_u + r0 * stride; gu.R = cr;
+        const long urows = cr * U, chunk = sorted_u ? urows : dense_rows;
+        for (long c0 = 0; c0 < urows; c0 += chunk) {
+            gu.r0 = c0; gu.list = ulist + c0 * cap_u; gu.nlist = un + c0; gu.nsamp = uns + c0;
+            rc = saliency_lists(c, gu, sorted_u, std::min(chunk, urows - c0), s);
+            if (rc) return rc;
+        }
+        if (want_vals) {
+            {
+                ProfScope pp(c, s, KID_SPATIAL);
+                pt.cr = cr;
+                const dim3 grid((unsigned)(((long)U * cap_u + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr);
+                if (nss) hipLaunchKernelGGL(vet::k_congruency_points<true>, grid, dim3(vet::SM_THREADS), 0, s, pt);
+                else hipLaunchKernelGGL(vet::k_congruency_points<false>, grid, dim3(vet::SM_THREADS), 0, s, pt);
+                HIP_TRY(hipGetLastError());
+            }
+            ProfScope pu(c, s, KID_TRANSITION);
+            us.cr = cr;
+            constexpr long per_wg = vet::SM_THREADS / vet::WAVE;
+            hipLaunchKernelGGL(vet::k_congruency_users, dim3((unsigned)((urows + per_wg - 1) / per_wg)), dim3(vet::SM_THREADS), 0, s, us);
+            HIP_TRY(hipGetLastError());
+        }
+        if (d_stats || d_rows || d_counts || d_status) {
+            ProfScope ps(c, s, KID_TRANSITION);
+            q.cr = cr; q.r0 = r0;
+            hipLaunchKernelGGL(vet::k_congruency_rows, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return VET_OK;
+}
+
 }  // namespace
+
+// What vet_congruency* refuse: check_saliency_args for both layouts (sigma, window, stride, the frames a per-viewer call takes), and
+// fewer than two viewers.
+int check_congruency_args(const vet_plan* pl, int U, int T, int window, int stride, double sigma) {
+    int rc = check_saliency_args(pl, U, T, window, stride, 0, sigma, 2, 1, 0);
+    if (!rc) rc = check_saliency_args(pl, U, T, window, stride, 1, sigma, 2, 1, 0);
+    if (rc) return rc;
+    if (U < 2) return fail(VET_ERR_INVALID, "congruency needs at least two viewers (got %d)", U);
+    return VET_OK;
+}
 
 // What vet_saliency_similarity* refuse: check_saliency_args for the pooled layout at scale 2, groups NULL, an audience without a viewer.
 int check_similarity_args(const vet_plan* pl, int U, int T, int window, int stride, const int8_t* groups, double sigma, int W, int H) {
@@ -899,6 +1313,24 @@ int vet_saliency_similarity_ids(vet_plan* pl, const int32_t* d_ids, int U, int T
     if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
     return rc ? rc : launch_similarity(pl, nullptr, nullptr, d_ids, U, T, window, stride, groups, sigma_rad, W, H, d_maps, d_stats,
                                        d_counts, d_status, s);
+}
+
+int vet_congruency(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, double sigma_rad,
+                   int want_nss, double* d_stats, int64_t* d_counts, double* d_rows, int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_congruency_args(pl, U, T, window, stride, sigma_rad);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_congruency_ids", stream, &s);
+    return rc ? rc : launch_congruency(pl, d_mu, d_mv, nullptr, U, T, window, stride, sigma_rad, want_nss, d_stats, d_counts, d_rows,
+                                       d_status, s);
+}
+
+int vet_congruency_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double sigma_rad, int want_nss,
+                       double* d_stats, int64_t* d_counts, double* d_rows, int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_congruency_args(pl, U, T, window, stride, sigma_rad);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_congruency(pl, nullptr, nullptr, d_ids, U, T, window, stride, sigma_rad, want_nss, d_stats, d_counts, d_rows,
+                                       d_status, s);
 }
 
 }  // extern "C"

@@ -144,6 +144,9 @@ SIGNATURES = {
     "vet_saliency_similarity": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
     "vet_saliency_similarity_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
     "vet_saliency_similarity_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P]),
+    "vet_congruency": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P]),
+    "vet_congruency_ids": (_I, [_P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P]),
+    "vet_congruency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P]),
     "vet_user_divergence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vet_user_divergence_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -558,6 +561,13 @@ SALIENCY_SCALES = {"none": 0, "mean": 1, "density": 2}
 _SALIENCY_SIMILARITY_CALL = ("vet_saliency_similarity", False, True, False,
                              (("maps", "2RYX", _F64, True), ("stats", "9R", _F64, False), ("counts", "4R", _NP_I64, False)))
 SALIENCY_SIMILARITY_STATS = ("cc", "sim", "jsd", "kl_ab", "kl_ba", "nss_ab", "nss_ba", "mass_a", "mass_b")
+
+# The congruency call, in a table of its own: one descriptor of the same form (3 statistics per viewer and row: lift, info_gain,
+# nss; 3 counts: samples, distinct, others; 4 values per row: scored, mean lift, mean info_gain, mean nss).  Rows count frames; its
+# extra arguments are sigma in radians and want_nss.
+_CONGRUENCY_CALL = ("vet_congruency", False, True, False,
+                    (("stats", "3UR", _F64, False), ("counts", "3UR", _NP_I64, False), ("rows", "4R", _F64, False)))
+CONGRUENCY_STATS = ("lift", "info_gain", "nss")
 
 
 class Plan:
@@ -1101,6 +1111,18 @@ class Plan:
         return self._row_host(_SALIENCY_SIMILARITY_CALL, mu, mv, ids, window, stride, {"maps"} if want_maps else set(), check,
                               extra=(_ptr(g), sigma, W, H), extra_dims={"Y": H, "X": W, "2": 2, "9": 9})
 
+    def congruency(self, mu=None, mv=None, ids=None, window=None, stride=1, sigma_deg=5.0, nss=True, check=True):
+        """Viewer congruency (include/vet.h: vet_congruency): for every viewer and every row of ``saliency`` (frames
+        [r * stride, r * stride + window), ``window=None`` the whole video) the kernel density of everyone else's samples, evaluated
+        at the viewer's own directions — no map.  Returns dict(stats[3,U,R] (lift = the others' density at the viewer's samples over
+        the uniform sphere's, info_gain = the mean log2 of that ratio in bits, nss = the density standardised by its closed-form
+        mean and variance over the sphere; NaN without ``nss``), counts[3,U,R] int64 (samples, distinct directions, the others'
+        samples), rows[4,R] (scored viewers, mean lift, mean info_gain, mean nss over them), code), R = (T - window) // stride + 1.
+        A viewer without a sample in a row, or alone in it, is NaN — data, never an error; info_gain is -inf where the others'
+        density underflowed to zero at a sample; ``code`` is VET_OK or VET_ERR_RANGE."""
+        sigma, _, _, _ = self._saliency_args(sigma_deg, 2, 1, "density")
+        return self._row_host(_CONGRUENCY_CALL, mu, mv, ids, window, stride, set(), check, extra=(sigma, int(bool(nss))))
+
     def transition_per_user(self, mu=None, mv=None, ids=None, window=None, stride=1, want_srccount=False, check=True):
         """Each user's own tile moves over time (include/vet.h: vet_user_transition_entropy): row (u, r) pools user u's
         transitions of pairs [r * stride, r * stride + window), pair f = (frame f, frame f + 1), into one call of the
@@ -1326,6 +1348,15 @@ class Plan:
         g = self._group_array(groups, n_users)
         self._row_device(_SALIENCY_SIMILARITY_CALL, d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, g.ctypes.data, sigma, W, H), d_maps or None, (d_stats, d_counts, d_status), stream)
+
+    def congruency_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, sigma_deg: float = 5.0,
+                          nss: bool = True, d_stats: int = 0, d_counts: int = 0, d_rows: int = 0, d_status: int = 0, stream=None,
+                          d_ids: int = 0):
+        """d_stats f64 [3][U][R]; d_counts i64 [3][U][R]; d_rows f64 [4][R]; every output may be 0 (include/vet.h: vet_congruency;
+        ``d_ids``: vet_congruency_ids)."""
+        sigma, _, _, _ = self._saliency_args(sigma_deg, 2, 1, "density")
+        self._row_device(_CONGRUENCY_CALL, d_mu, d_mv, d_ids, n_users, n_frames, (window, stride, sigma, int(bool(nss))),
+                         d_stats or None, (d_counts, d_rows, d_status), stream)
 
     def transition_per_user_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int,
                                    d_entropy: int, d_srccount: int = 0, d_samples: int = 0, d_status: int = 0, stream=None):

@@ -814,5 +814,52 @@ class _EntropyAnalyzerBase:
         return self._saliency_similarity_frame(times, names, window, stride, code, labels, res, float(sigma_deg), int(width),
                                                int(height))
 
+    @staticmethod
+    def _congruency_frame(times, names, window: int, stride: int, res: dict, sigma_deg: float) -> pd.DataFrame:
+        """The viewer congruency as a DataFrame, user-major; ``attrs["rows"]`` is the per-window frame."""
+        times = np.asarray(times)
+        names = list(names)
+        U = len(names)
+        stats = np.asarray(res["stats"], dtype=np.float64).reshape(3, U, -1)
+        counts = np.asarray(res["counts"]).reshape(3, U, -1)
+        per_row = np.asarray(res["rows"], dtype=np.float64).reshape(4, -1)
+        R = stats.shape[2]
+        first = np.arange(R, dtype=np.int64) * stride
+        df = pd.DataFrame(dict(user=np.repeat(np.asarray(names, dtype=object), R), time=np.tile(times[first], U),
+                               time_end=np.tile(times[first + window - 1], U), samples=counts[0].reshape(-1),
+                               distinct=counts[1].reshape(-1), others=counts[2].reshape(-1),
+                               **{k: stats[i].reshape(-1) for i, k in enumerate(_native.CONGRUENCY_STATS)}))
+        rows = pd.DataFrame(dict(time=times[first], time_end=times[first + window - 1], scored=per_row[0].astype(np.int64),
+                                 **{k: per_row[1 + i] for i, k in enumerate(_native.CONGRUENCY_STATS)}))
+        df.attrs.update(rows=rows, users=names, sigma_deg=float(sigma_deg),
+                        kappa=1.0 / min(float(np.radians(sigma_deg)), float(np.pi)) ** 2, window=window, stride=stride)
+        return df
+
+    def compute_congruency(self, window: Optional[int] = None, stride: int = 1, sigma_deg: float = 5.0, nss: bool = True) -> pd.DataFrame:
+        """Inter-observer congruency: how well the rest of the audience predicts where each viewer looks, per window of frames
+        [r * stride, r * stride + window) (``window=None``: the whole video).  The kernel density of ``compute_saliency``
+        (``sigma_deg``) of everyone else's samples is evaluated at the viewer's own directions — leave-one-out, no map, independent
+        of the tiling.  The noise ceiling for a saliency model, and an outlier detector for viewers.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, user-major: ``user``, ``time`` / ``time_end`` (the
+        first / last frame of the row), ``samples`` and ``distinct`` (the viewer's own), ``others`` (everyone else's samples),
+        ``lift`` (the others' density at the viewer's samples relative to the uniform sphere: 1 = chance), ``info_gain`` (the mean
+        log2 of that ratio, bits; -inf where the others' density underflowed to zero at a sample — small ``sigma_deg``) and
+        ``nss`` (the density at the samples, standardised by its mean and variance over the sphere in closed form; NaN with
+        ``nss=False``, which spares its arithmetic).  ``attrs["rows"]`` is the per-window frame — ``time``, ``time_end``,
+        ``scored`` (viewers with a sample and company) and the means ``lift``, ``info_gain``, ``nss`` over them: the segment's
+        congruency; ``attrs`` also hold ``users``, ``sigma_deg``, ``kappa``, ``window`` and ``stride``.  A viewer without a sample
+        in a window, or alone in it, is NaN — returned, never raised.  Raises ``ValidationError`` before data is loaded and for
+        samples outside [0, 1], ``ValueError`` for illegal arguments and fewer than two viewers."""
+        times, names, call = self._row_call("congruency")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        _native.Plan._saliency_args(sigma_deg, 2, 1, "density")
+        if len(names) < 2:
+            raise ValueError(f"congruency needs at least two viewers (got {len(names)})")
+        res = call(window=window, stride=stride, sigma_deg=float(sigma_deg), nss=bool(nss), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._congruency_frame(times, names, window, stride, res, float(sigma_deg))
+
     def compute_entropy(self) -> pd.DataFrame:  # pragma: no cover - overridden
         raise NotImplementedError
