@@ -70,7 +70,9 @@ extern "C" {
                           maps: the spherical kernel density of a window's viewing directions on an equirectangular map, with its
                           mass, peak, entropy and effective area, per window and per viewer) and vet_test_saliency_tile, and then
                           the vet_saliency_similarity* entry points (CC, SIM, JSD, KL and NSS between the maps of two audiences), and
-                          then the vet_congruency* entry points (each viewer's leave-one-out saliency score per window) */
+                          then the vet_congruency* entry points (each viewer's leave-one-out saliency score per window); the
+                          vet_saliency_score* entry points (AUC, NSS, information gain, CC, SIM, JSD and KL of a predicted map)
+                          were added under the same number */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -1255,6 +1257,82 @@ int vet_saliency_similarity_ids(vet_plan *plan, const int32_t *d_ids, int n_user
 int vet_saliency_similarity_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users,
                                  int n_frames, int window, int stride, const int8_t *groups, double sigma_rad, int W, int H,
                                  double *h_maps, double *h_stats, int64_t *h_counts);
+
+/* ---- saliency scoring: AUC, NSS, IG, CC, SIM, KL of a predicted map against where the audience looked ------------------
+ * Not in the reference.  The question a saliency toolkit is asked most: here is a map from elsewhere — a model's prediction, another
+ * dataset's ground truth, a centre or equator bias, last segment's map — how well does it predict where THIS audience looked, per
+ * window of frames.  Pooled layout only.
+ * ROWS, PRESENCE, ids, MAP GRID, a_y, the KERNEL k(P, A), kappa, C, the LIST of a row (distinct ids d_i ascending, multiplicities m_i,
+ * N = sum m_i) and the summation RULE exactly as vet_saliency, pooled layout (the rule: blocks of 1024 positions, thread t of 256 adds
+ * t, t + 256, t + 512, t + 768 to +0.0 in that order, then wave_sum, the four waves in order, the blocks ascending).
+ * PREDICTED MAP: pred is [n_pred][H][W] f64, laid out exactly as vet_saliency's maps (row 0 at the top, column c centred at lon
+ * (c + 0.5) / W * 360 - 180); n_pred = 1: one static map scores every row; n_pred = R: row r is scored by map r.  PRECONDITION of the
+ * device entries: every value finite and non-negative, in any scale (-0.0 is taken as +0.0); the entries read it in place and do not
+ * check it.  P is the row's map, P_p a cell, a_p = a_y its share of the sphere.
+ * SAMPLING: v_i is P at direction d_i by BILINEAR interpolation on the cell-centre grid.  With (x, y, z) the unit row of the plan's
+ * table (as in vet_head_motion) and pi = 3.141592653589793:
+ *   lon = (x == 0 && y == 0) ? 0 : atan2(y, x);  fx = (lon + pi) / (2 * pi) * W - 0.5;  c0 = floor(fx), tx = fx - c0;
+ *   c0 and c1 = c0 + 1 wrap modulo W;
+ *   fy = clamp(acos(clamp(z, -1, 1)) / pi * H - 0.5, 0, H - 1);  y0 = floor(fy), y1 = min(y0 + 1, H - 1), ty = fy - y0;
+ *   top = P[y0][c0] + tx * (P[y0][c1] - P[y0][c0]), bot likewise on y1;  v = top + ty * (bot - top)
+ * (ocml atan2 and acos; no fused operation).  The a + t * (b - a) form is required: four equal corners return exactly their value, so
+ * the AUC's ties on constant regions of a map (zeros above all) are exact.  Interpolation, not "the pixel the sample falls in": on
+ * a 100 x 200 sample grid and a 180 x 90 map every tenth longitude lies exactly on a cell border, where a floor is decided by the
+ * last bit of atan2; the interpolated value is continuous there.
+ * LOCATION METRICS (no audience map is built for them):
+ *   mass_pred = sum_p a_p * P_p by the rule over the pixels in row-major order (vet_saliency's mass terms)
+ *   var_pred  = sum_p a_p * ((P_p - mass_pred) * (P_p - mass_pred)) by the rule
+ *   nss       = (sum_i (double)m_i * v_i / (double)N - mass_pred) / sqrt(var_pred)
+ *   info_gain = sum_i (double)m_i * log2(v_i / mass_pred) / (double)N      bits over the uniform sphere (ocml log2); -inf where the map
+ *               is 0.0 at a sample: data, not an error
+ *   auc       = sum_i (double)m_i * u_i / (double)N,  u_i = L(v_i) + 0.5 * E(v_i),
+ *               L(v) = sum_y a_y * #{x : P[y][x] < v},  E(v) = sum_y a_y * #{x : P[y][x] == v}
+ * The y sums of L and E run in ascending y as acc = acc + a_y * (double)count from +0.0 (integer counts); the three sums over i run
+ * by the rule over the list positions.  STATED DEPARTURE: this AUC is the Mann-Whitney form of AUC-Judd with the WHOLE SPHERE as
+ * the negatives and every cell weighted by its area — the probability that a sample's value exceeds that of a uniformly drawn point
+ * of the sphere, ties counting a half.  It is not the thresholded trapezoid over unfixated pixels, and it is 0.5 for a constant map.
+ * DISTRIBUTION METRICS (want_dist != 0): the audience's density map M is vet_saliency's at scale 2, bit for bit (k_saliency_map,
+ * unchanged), mass its mass.  cc, sim, jsd and kl are vet_saliency_similarity's PIXEL SUMS with a = M_p, b = P_p, mass_a = mass,
+ * mass_b = mass_pred: cc = cov / sqrt(va*vb), sim = sum fmin(qa, qb), jsd = 0.5 * sum (ta + tb), kl = kl_ab = sum (qa != 0 ?
+ * qa*log2(qa/qb) : 0) — the audience from the prediction; +inf where the audience has weight on a cell with P = 0.0.
+ * NaN RULES: a row with N = 0 has NaN in the first eight statistics and mass_pred is still the map's; it is counted in status[1].
+ * With want_dist = 0, cc, sim, jsd, kl and mass are NaN and no density is evaluated (sigma_rad is still validated).  Beyond that
+ * nothing is special-cased: an all-zero or a constant map gives what IEEE gives for the expressions above.
+ * A value's bits depend on the plan, the row's predicted map, sigma, window and the row's frames only — not on stride, the number of
+ * rows, the video's length, the entry point, which outputs were asked for, want_dist (the location metrics), n_pred (a static map
+ * against R copies of it), the pass a row falls into, vet_test_saliency_tile or the order of the viewer columns.  No FP atomics.
+ * Outputs, each nullable:
+ *   d_map      [R][H][W] f64: M, the audience's map (built whenever d_map is given, also with want_dist = 0)
+ *   d_stats    [9][R] f64, statistic-major: auc, nss, info_gain, cc, sim, jsd, kl, mass, mass_pred
+ *   d_counts   [2][R] i64: 0 samples (N), 1 distinct
+ *   d_status   [2] i32 {bad, #rows with N = 0}; the call ADDS, the caller zeroes
+ * Stages: the samples quantised once (k_saliency_ids) and the lists by vet_saliency's list kernels; k_score_sort — workgroup = (map
+ * row, map): the row's W bit patterns sorted in LDS by lds_bitonic_sort (non-negative doubles order as their bits, so W <= 4096,
+ * 32 KB of keys, needs no second path), a sorted copy [H][W] in the workspace; a static map is sorted once per call;
+ * k_score_points — workgroup = (row, 256 list entries), thread = entry: v_i by four loads, then the sorted map rows staged in LDS in
+ * tiles of whole map rows (at most 32 KB) and one lower- and one upper-bound binary search per map row, L and E in registers
+ * (about H * 2 * log2 W LDS reads per entry instead of W * H compares): 28 VGPRs, no scratch, 32 KB LDS, 5 waves per SIMD
+ * (LDS-bound); k_score_rows — one workgroup per row: mass_pred, var_pred, the list sums, with want_dist the audience's mass and the
+ * five pixel sums carried together, the values, the counts and status[1]: 94 VGPRs, no scratch, 160 B LDS, 5 waves per SIMD;
+ * k_score_sort 10 VGPRs, no scratch, 32 KB LDS, 5 waves per SIMD (LDS-bound).  k_saliency_map runs only with want_dist (and d_stats) or d_map.
+ * Workspace: 4 B per sample, the sorted copy of a static map, + per row of a pass 8 B per list slot, 16 B per list slot for v_i and
+ * u_i, W*H*8 B for the sorted copy when n_pred = R and for M when d_map is NULL; a pass stays under vet_saliency's 256 MB budget.
+ * VET_ERR_INVALID (before anything is allocated or launched): everything vet_saliency refuses for the pooled layout, pred NULL,
+ * n_pred other than 1 or R.  VET_ERR_UNSUPPORTED as vet_saliency, pooled.
+ * Profile ids: k_saliency_map and k_score_points to k_spatial, the other stages to k_transition.  Asynchronous on `stream`. */
+int vet_saliency_score(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                       double sigma_rad, int W, int H, const double *d_pred, int n_pred, int want_dist, double *d_map,
+                       double *d_stats, int64_t *d_counts, int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_saliency_score_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, double sigma_rad,
+                           int W, int H, const double *d_pred, int n_pred, int want_dist, double *d_map, double *d_stats,
+                           int64_t *d_counts, int32_t *d_status, void *stream);
+/* Host buffers: H2D (h_pred [n_pred][H][W] is HOST memory here, uploaded with the samples), run, D2H, synchronous; VET_ERR_RANGE when
+ * a sample is outside [0, 1] (outputs are still written); never VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice
+ * versa. */
+int vet_saliency_score_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                            int window, int stride, double sigma_rad, int W, int H, const double *h_pred, int n_pred, int want_dist,
+                            double *h_map, double *h_stats, int64_t *h_counts);
 
 /* ---- viewer congruency: the leave-one-out saliency score of every viewer per window ------------------
  * Not in the reference.  Inter-observer congruency: how well the REST of the audience predicts where viewer u looks, per window of

@@ -23,7 +23,9 @@
 //                       viewer) partials from unit vectors staged in LDS, then per row the block-ordered sums) and its launch logic
 //   vet_saliency.hip    the saliency maps (the spherical kernel density of a row's viewing directions on an equirectangular map: the
 //                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics), the
-//                       saliency similarity of two audiences (their maps by the same kernels, compared row by row) and their launch logic
+//                       saliency similarity of two audiences (their maps by the same kernels, compared row by row), the viewer
+//                       congruency, the saliency scoring of a predicted map (its rows sorted in LDS, sampled and ranked at the list
+//                       entries' directions) and their launch logic
 //   vet_crowd.hip       the viewer-to-crowd divergence kernels (each viewer's KL from the pooled row histogram) and their launch logic
 //   vet_bootstrap.hip   the bootstrap kernels (viewers resampled with replacement: an FP64 MFMA contraction of resample counts with
 //                       the per-viewer histograms, the entropy epilogue, the per-row summary) and their launch logic
@@ -526,6 +528,9 @@ int check_saliency_args(const vet_plan* pl, int U, int T, int window, int stride
 int check_similarity_args(const vet_plan* pl, int U, int T, int window, int stride, const int8_t* groups, double sigma, int W, int H);
 // ... and what vet_congruency* refuse: check_saliency_args' sigma, window and stride for both layouts, fewer than two viewers.
 int check_congruency_args(const vet_plan* pl, int U, int T, int window, int stride, double sigma);
+// ... and what vet_saliency_score* refuse: check_saliency_args for the pooled layout, pred NULL, n_pred other than 1 or the rows.
+int check_score_args(const vet_plan* pl, int U, int T, int window, int stride, double sigma, int W, int H, const double* pred,
+                     int n_pred);
 
 // vet_coverage.hip: what vet_coverage* refuse about their own arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched — after check_window_args.  R = the rows of the call; fractions is host memory [Q].

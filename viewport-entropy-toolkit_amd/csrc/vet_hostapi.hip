@@ -19,7 +19,7 @@ using namespace vh;
 // the samples (h_mu or h_ids, h_mv), the entropies, output 0 (assignments / pairs), output 1 (weights / source counts), the
 // count per row (present / common / samples) and the two status words
 enum { SLOT_MU = 0, SLOT_IDS = 0, SLOT_MV = 1, SLOT_ENTROPY = 2, SLOT_OUT0 = 3, SLOT_OUT1 = 4, SLOT_COUNT = 5, SLOT_STATUS = 6,
-       SLOT_STILL = 7 };    // 7: the second count per row of vet_head_motion_host
+       SLOT_STILL = 7 };    // 7: the second count per row of vet_head_motion_host; the predicted maps of vet_saliency_score_host
 #define POOL(slot, bytes, var) do { int rc_ = pooled(c, slot, bytes, (void**)&var); if (rc_) return rc_; } while (0)
 
 struct vet_result {
@@ -150,7 +150,7 @@ struct StagedRun {
 
 // The fourteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
 // per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion, the saliency
-// maps, the saliency similarity, the viewer congruency) after their
+// maps, the saliency similarity, the viewer congruency; and the saliency scoring, a fifteenth) after their
 // refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
 // null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
 // entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
@@ -803,6 +803,29 @@ int vet_congruency_host(vet_plan* pl, const double* h_mu, const double* h_mv, co
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_congruency_ids, vet_congruency, pl, U, T, window, stride, sigma_rad, want_nss, (double*)d[0],
                            (int64_t*)d[2], (double*)d[1], run.status, run.s);
+    });
+}
+
+// Saliency scoring with host buffers (include/vet.h): h_pred [n_pred][H][W] is uploaded to a pool slot behind the samples; where
+// wanted map [R][H][W], stats [9][R] and counts [2][R]; R = vet_window_rows over the T frames.  Every output may be NULL.  Rows
+// without a sample are data: only VET_ERR_RANGE is decoded from the status words.
+int vet_saliency_score_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                            int stride, double sigma_rad, int W, int H, const double* h_pred, int n_pred, int want_dist, double* h_map,
+                            double* h_stats, int64_t* h_counts) {
+    int rc = check_score_args(pl, U, T, window, stride, sigma_rad, W, H, h_pred, n_pred);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t rows = (size_t)vet_window_rows(T, window, stride), pred_bytes = (size_t)n_pred * W * H * 8;
+    const RowOut outs[3] = {{h_stats, 9 * rows * 8, SLOT_ENTROPY}, {h_map, rows * (size_t)W * H * 8, SLOT_OUT0},
+                            {h_counts, 2 * rows * 8, SLOT_COUNT}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        vet_ctx* c = run.c;
+        double* d_pred = nullptr;
+        POOL(SLOT_STILL, pred_bytes, d_pred);
+        HIP_TRY(hipMemcpyAsync(d_pred, h_pred, pred_bytes, hipMemcpyHostToDevice, run.s));
+        return launch_rows(run, vet_saliency_score_ids, vet_saliency_score, pl, U, T, window, stride, sigma_rad, W, H,
+                           (const double*)d_pred, n_pred, want_dist, (double*)d[1], (double*)d[0], (int64_t*)d[2], run.status, run.s);
     });
 }
 

@@ -86,7 +86,13 @@
 //                                              k_congruency_users  one wave per (row, viewer): the own-entry sums by the block-ordered rule
 //                                              k_congruency_rows  one workgroup per row: Q, every viewer's lift, information gain and NSS,
 //                                                               the row's means over the scored viewers
-//   vet_crowd.hip       (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
+//                                              k_score_sort     the scoring call: workgroup = (map row, predicted map): the row's W bit patterns
+//                                                               sorted in LDS (non-negative doubles order as their bits), a sorted copy
+//                                              k_score_points   workgroup = (row, 256 list entries): the predicted map at the entry's direction
+//                                                               (bilinear), its rank in every sorted map row by two binary searches in LDS
+//                                              k_score_rows     one workgroup per row: mass and variance of the prediction, AUC, NSS and
+//                                                               information gain from the list sums, CC, SIM, JSD, KL against the audience's map
+//   vet_crowd.hip      (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave
 //                                              k_crowd_rows     one wave per row: pooled, within and between

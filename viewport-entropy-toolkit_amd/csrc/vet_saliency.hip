@@ -23,6 +23,11 @@
 // Viewer congruency (vet_congruency*): stage 0 for both layouts, stage 1 pooled and per viewer per pass, k_congruency_points walks the
 // pooled list once per entry of every viewer's own list with the viewer's own multiplicities taken off (the leave-one-out density of
 // the others at the viewer's directions; no map), k_congruency_users and k_congruency_rows take the sums by the same rule.
+// Saliency scoring (vet_saliency_score*): a predicted map from elsewhere against the pooled audience.  k_score_sort sorts every row
+// of the predicted map in LDS (once for a static map), k_score_points samples the map at each list entry's direction (bilinear) and
+// takes the entry's area-weighted rank in the map by two binary searches per sorted map row (AUC), k_score_rows takes mass_pred,
+// var_pred, the list sums (AUC, NSS, information gain) and, when the distribution metrics are wanted, the audience's map by
+// k_saliency_map unchanged and k_saliency_compare's pixel sums against the prediction (CC, SIM, JSD, KL).
 // No CPU compute path; nothing here reads the environment.
 #include "vet_host.hpp"
 #include "vet_common.hpp"
@@ -855,6 +860,245 @@ __global__ __launch_bounds__(SM_THREADS) void k_congruency_rows(const CgRowParam
     if (tid == 0 && p.status && sc == 0.0) atomicAdd(&p.status[1], 1);   // fewer than two viewers present
 }
 
+// ------------------------------------------------------------------------------------------
+// Saliency scoring (vet_saliency_score*): how well a map from elsewhere predicts where the audience looked.  The row's list is
+// the pooled list of the kernels above; the audience's own map (k_saliency_map, scale 2) is built only for the distribution metrics.
+// k_score_sort — workgroup = (map row y, map of the launch): the row's W values as u64 bit patterns in LDS (non-negative doubles order
+// as their bits; -0.0 enters as +0.0), padded to the power of two P with all-ones, lds_bitonic_sort, the first W written to
+// sorted [maps][H][W].  A static map is sorted once per call, per-row maps once per pass.
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 10 VGPRs, no scratch, 32 768 B LDS, 5 waves per SIMD (LDS-bound).
+// ------------------------------------------------------------------------------------------
+constexpr int SS_SORT_MAX = 4096;       // the widest map row k_score_sort takes (32 KB of keys): vet_saliency's limit on W
+constexpr int SS_TILE = 4096;           // sorted values of one LDS tile of k_score_points (32 KB), filled in whole map rows
+
+struct ScoreSortParams {
+    const double* pred;          // [maps][H][W]
+    unsigned long long* sorted;  // [maps of the launch][H][W]
+    long map0;                   // the launch's first map in pred
+    int W, P;
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_score_sort(const ScoreSortParams p) {
+    __shared__ unsigned long long keys[SS_SORT_MAX];
+    const int tid = threadIdx.x;
+    const long H = gridDim.x;
+    const double* src = p.pred + ((p.map0 + blockIdx.y) * H + blockIdx.x) * p.W;
+    for (int i = tid; i < p.P; i += SM_THREADS)
+        keys[i] = i < p.W ? (unsigned long long)__double_as_longlong(src[i] + 0.0) : ~0ull;
+    lds_bitonic_sort(keys, p.P);
+    unsigned long long* out = p.sorted + ((long)blockIdx.y * H + blockIdx.x) * p.W;
+    for (int i = tid; i < p.W; i += SM_THREADS) out[i] = keys[i];
+}
+
+// The map P [H][W] at the unit vector (x, y, z) by bilinear interpolation on the cell-centre grid: the columns wrap, the rows clamp.
+// a + t * (b - a): four equal corners return their value exactly.  Every index is brought into the map whatever the vector holds.
+__device__ __forceinline__ double score_sample(const double* __restrict__ P, int W, int H, double x, double y, double z) {
+    constexpr double kPi = 3.141592653589793;
+    const double lon = (x == 0.0 && y == 0.0) ? 0.0 : atan2(y, x);
+    const double fx = (lon + kPi) / (2.0 * kPi) * (double)W - 0.5;
+    const double flx = floor(fx), tx = fx - flx;
+    int c0 = (int)flx % W;
+    if (c0 < 0) c0 += W;
+    const int c1 = c0 + 1 == W ? 0 : c0 + 1;
+    const double fy = fmin(fmax(acos(fmin(fmax(z, -1.0), 1.0)) / kPi * (double)H - 0.5, 0.0), (double)(H - 1));
+    const double fly = floor(fy), ty = fy - fly;
+    const int y0 = min(max((int)fly, 0), H - 1), y1 = min(y0 + 1, H - 1);
+    const double* r0 = P + (long)y0 * W;
+    const double* r1 = P + (long)y1 * W;
+    const double top = r0[c0] + tx * (r0[c1] - r0[c0]);
+    const double bot = r1[c0] + tx * (r1[c1] - r1[c0]);
+    return top + ty * (bot - top);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_score_points — grid (ceil(cap / 256), rows of the pass); thread = entry blockIdx.x * 256 + tid of the row's list.  v_i = the
+// row's predicted map at the entry's direction (four loads).  The sorted map rows are staged in LDS in tiles of whole map rows (at
+// most 4096 values); per map row one lower- and one upper-bound binary search of W values (the same trip count in every lane)
+// gives the integer counts #{P < v} and #{P <= v}; L and E stay in registers, added in ascending y.  Writes v_i and
+// u_i = L + 0.5 * E to pts [2][CR][cap].  A workgroup beyond the list returns.
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 28 VGPRs, no scratch, 32 768 B LDS, 5 waves per SIMD (LDS-bound).
+// ------------------------------------------------------------------------------------------
+struct ScorePointParams {
+    const uint2* list;           // [rows of the pass][cap]
+    const int32_t* nlist;
+    const double* unit;          // [n_dirs][3]
+    const double* pred;          // the map of row y: pred + (r0 + y) * pred_stride (0: one static map)
+    const double* sorted;        // its sorted rows: sorted + y * sorted_stride
+    const double* ay;            // [H]
+    long cap, CR, r0, pred_stride, sorted_stride;
+    int W, H, tile_rows;
+    double* pts;                 // [2][CR][cap]
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_score_points(const ScorePointParams p) {
+    __shared__ double s_tile[SS_TILE];
+    const int tid = threadIdx.x, W = p.W;
+    const long y = blockIdx.y;
+    const int n = p.nlist[y];
+    if ((int)blockIdx.x * SM_THREADS >= n) return;               // uniform
+    const int i = blockIdx.x * SM_THREADS + tid;
+    const double* S = p.sorted + y * p.sorted_stride;
+    double v = 0.0;
+    if (i < n) {
+        const double* A = p.unit + 3L * p.list[y * p.cap + i].x;
+        v = score_sample(p.pred + (p.r0 + y) * p.pred_stride, W, p.H, A[0], A[1], A[2]);
+    }
+    double L = 0.0, E = 0.0;
+    for (int y0 = 0; y0 < p.H; y0 += p.tile_rows) {
+        const int nr = min(p.tile_rows, p.H - y0), cnt = nr * W;
+        __syncthreads();                                         // the readers of the tile before
+        for (int j = tid; j < cnt; j += SM_THREADS) s_tile[j] = S[(long)y0 * W + j];
+        __syncthreads();
+        for (int r = 0; r < nr; ++r) {
+            const double* row = s_tile + r * W;
+            int lo = 0, hi = 0, len = W;
+            while (len > 1) {                                    // uniform: the trip count depends on W alone
+                const int half = len >> 1;
+                lo += row[lo + half - 1] < v ? half : 0;
+                hi += row[hi + half - 1] <= v ? half : 0;
+                len -= half;
+            }
+            lo += row[lo] < v ? 1 : 0;
+            hi += row[hi] <= v ? 1 : 0;
+            const double a = p.ay[y0 + r];
+            L = L + a * (double)lo;
+            E = E + a * (double)(hi - lo);
+        }
+    }
+    if (i < n) {
+        p.pts[y * p.cap + i] = v;
+        p.pts[(p.CR + y) * p.cap + i] = L + 0.5 * E;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_score_rows — one workgroup per row of the pass: mass_pred and var_pred by the rule (k_saliency_rows' mass terms, k_saliency_compare's
+// variance terms), the three list sums by the rule over the list positions, with the audience's map its mass and the five pixel
+// sums of k_saliency_compare (a = the audience, b = the prediction) carried together through the rule's block step; then the nine
+// values, the counts and status[1].
+// Resources (hipcc, gfx950, -Rpass-analysis=kernel-resource-usage): 94 VGPRs, no scratch, 160 B LDS, 5 waves per SIMD.
+// ------------------------------------------------------------------------------------------
+constexpr int SR_SUMS = 5;              // va, cov, sim, jsd, kl
+struct ScoreRowParams {
+    const double* pred;          // the map of row r: pred + r * pred_stride (0: one static map)
+    const double* map;           // row (map_row0 + y) of the audience's maps, or null: no distribution metrics
+    const double* ay;            // [H]
+    const uint2* list;
+    const int32_t* nlist;
+    const unsigned long long* nsamp;
+    const double* pts;           // [2][CR][cap]
+    long cap, CR, pred_stride, map_row0, r0, rows;
+    int W, H;
+    double* stats;               // [9][rows] or null
+    long long* counts;           // [2][rows] or null
+    int32_t* status;             // [2] or null
+};
+
+__global__ __launch_bounds__(SM_THREADS) void k_score_rows(const ScoreRowParams p) {
+    __shared__ double s_w[SR_SUMS][SM_THREADS / WAVE];
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const long y = blockIdx.x, row = p.r0 + y;
+    const unsigned long long N = p.nsamp[y];
+    const int n = p.nlist[y];
+    if (tid == 0) {
+        if (p.counts) { p.counts[row] = (long long)N; p.counts[p.rows + row] = (long long)n; }
+        if (N == 0ull && p.status) atomicAdd(&p.status[1], 1);
+    }
+    if (!p.stats) return;
+    const int npix = p.W * p.H;
+    const double* P = p.pred + row * p.pred_stride;
+    const double nan = __builtin_nan("");
+    const double mass_p = sal_mass(P, p.ay, p.W, npix, tid, s_w[0]);
+    double var_p = 0.0;
+    for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < npix) {
+                const double db = P[q] - mass_p;
+                t += p.ay[q / p.W] * (db * db);
+            }
+        }
+        var_p += sal_block_sum(t, s_w[0]);
+    }
+    if (N == 0ull) {                                             // uniform
+        if (tid < 8) p.stats[tid * p.rows + row] = nan;
+        if (tid == 0) p.stats[8 * p.rows + row] = mass_p;
+        return;
+    }
+    const uint2* list = p.list + y * p.cap;
+    const double* pv = p.pts + y * p.cap;
+    const double* pu = p.pts + (p.CR + y) * p.cap;
+    double SV = 0.0, SG = 0.0, SU = 0.0;                         // sum m v, sum m log2(v / mass_pred), sum m u
+    for (int b0 = 0; b0 < n; b0 += SM_BLOCK) {
+        double tv = 0.0, tg = 0.0, tu = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = b0 + k * SM_THREADS + tid;
+            if (q < n) {
+                const double m = (double)list[q].y, v = pv[q];
+                tv += m * v;
+                tg += m * log2(v / mass_p);
+                tu += m * pu[q];
+            }
+        }
+        SV += sal_block_sum(tv, s_w[0]);
+        SG += sal_block_sum(tg, s_w[0]);
+        SU += sal_block_sum(tu, s_w[0]);
+    }
+    double mass_a = nan, sum[SR_SUMS];
+#pragma unroll
+    for (int k = 0; k < SR_SUMS; ++k) sum[k] = 0.0;
+    if (p.map) {                                                 // uniform
+        const double* M = p.map + (p.map_row0 + y) * (long)npix;
+        mass_a = sal_mass(M, p.ay, p.W, npix, tid, s_w[0]);
+        for (int b0 = 0; b0 < npix; b0 += SM_BLOCK) {
+            double t[SR_SUMS];
+#pragma unroll
+            for (int k = 0; k < SR_SUMS; ++k) t[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = b0 + k * SM_THREADS + tid;
+                if (q < npix) {
+                    const double a = M[q], b = P[q], ay = p.ay[q / p.W];
+                    const double qa = (a * ay) / mass_a, qb = (b * ay) / mass_p;
+                    const double da = a - mass_a, db = b - mass_p;
+                    const double m = 0.5 * (qa + qb);
+                    const double ta = qa != 0.0 ? qa * log2(qa / m) : 0.0;
+                    const double tb = qb != 0.0 ? qb * log2(qb / m) : 0.0;
+                    t[0] += ay * (da * da);
+                    t[1] += ay * (da * db);
+                    t[2] += fmin(qa, qb);
+                    t[3] += ta + tb;
+                    t[4] += qa != 0.0 ? qa * log2(qa / qb) : 0.0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < SR_SUMS; ++k) {                  // the rule's block step, the five sums side by side
+                const double s = wave_sum(t[k]);
+                if (lane == 0) s_w[k][wv] = s;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < SR_SUMS; ++k) sum[k] += mo_block_total(s_w[k]);
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        const double Nd = (double)N;
+        p.stats[row] = SU / Nd;
+        p.stats[p.rows + row] = (SV / Nd - mass_p) / sqrt(var_p);
+        p.stats[2 * p.rows + row] = SG / Nd;
+        p.stats[3 * p.rows + row] = p.map ? sum[1] / sqrt(sum[0] * var_p) : nan;
+        p.stats[4 * p.rows + row] = p.map ? sum[2] : nan;
+        p.stats[5 * p.rows + row] = p.map ? 0.5 * sum[3] : nan;
+        p.stats[6 * p.rows + row] = p.map ? sum[4] : nan;
+        p.stats[7 * p.rows + row] = mass_a;
+        p.stats[8 * p.rows + row] = mass_p;
+    }
+}
+
 }  // namespace vet
 
 namespace vh {
@@ -1237,7 +1481,129 @@ int launch_congruency(vet_plan* pl, const double* d_mu, const double* d_mv, cons
     return VET_OK;
 }
 
+// vet_saliency_score*: stage 0, the tables, a static map's sorted rows once, then per pass of rows the lists, the audience's maps
+// (only for the distribution metrics or d_map), the sorted rows of the pass's own predicted maps, the point walk and the rows.
+int launch_score(vet_plan* pl, const double* d_mu, const double* d_mv, const int32_t* d_ids, int U, int T, int window, int stride,
+                 double sigma, int W, int H, const double* d_pred, int n_pred, int want_dist, double* d_map, double* d_stats,
+                 int64_t* d_counts, int32_t* d_status, hipStream_t s) {
+    vet_ctx* c = pl->ctx;
+    const long R = (long)vet_window_rows(T, window, stride);
+    const long Wpos = (long)window * U, D = (long)pl->n_dirs, n = (long)T * U;
+    const long npix = (long)W * H, cap = std::min(Wpos, D);
+    const bool sorted = Wpos <= vet::SM_SORT_MAX;
+    const bool is_static = n_pred == 1;
+    const bool want_map = d_map || (d_stats && want_dist);
+    int tile = vet::SM_TILE;
+    if (c->tune.saliency_tile > 0) tile = std::min(tile, c->tune.saliency_tile);
+    // per row of a pass: the list with its length and N, the dense counts, the audience's map when it stays here, the sorted copy of
+    // the row's own predicted map, v_i and u_i
+    const size_t per_row = (size_t)cap * 8 + 16 + (sorted ? 0 : (size_t)D * 4) + (want_map && !d_map ? (size_t)npix * 8 : 0) +
+                           (d_stats ? (is_static ? 0 : (size_t)npix * 8) + (size_t)2 * cap * 8 : 0);
+    const long CR = std::max(1L, std::min({(long)(kSaliencyPassBudget / per_row), R, 65535L}));
+    const size_t ntab = (size_t)2 * W + (size_t)3 * H;
+    WsLayout lay;
+    const size_t ids_o = lay.take<int32_t>((size_t)n), tab_o = lay.take<double>(ntab), list_o = lay.take<uint2>((size_t)CR * cap),
+                 nl_o = lay.take<int32_t>((size_t)CR), ns_o = lay.take<unsigned long long>((size_t)CR),
+                 dense_o = lay.take<uint32_t>(sorted ? 0 : (size_t)CR * D),
+                 map_o = lay.take<double>(want_map && !d_map ? (size_t)CR * npix : 0),
+                 srt_o = lay.take<double>(d_stats ? (size_t)(is_static ? 1 : CR) * npix : 0),
+                 pts_o = lay.take<double>(d_stats ? (size_t)2 * CR * cap : 0);
+    int rc = ensure_ws(c, lay.at);
+    if (rc) return rc;
+    char* ws = (char*)c->ws;
+    int32_t* ids = (int32_t*)(ws + ids_o);
+    double* tab = (double*)(ws + tab_o);
+    const double kappa = 1.0 / (sigma * sigma);
+    const double C = kappa / (2.0 * 3.141592653589793 * (1.0 - std::exp(-2.0 * kappa)));
+    {   // stage 0
+        ProfScope ps(c, s, KID_TRANSITION);
+        const vet::SampleSrc src{d_mu, d_mv, d_ids, pl->W, pl->H, D};
+        const dim3 grid((unsigned)((n + vet::SM_THREADS - 1) / vet::SM_THREADS));
+        if (d_ids) hipLaunchKernelGGL(vet::k_saliency_ids<true>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+        else hipLaunchKernelGGL(vet::k_saliency_ids<false>, grid, dim3(vet::SM_THREADS), 0, s, src, n, ids, d_status);
+        HIP_TRY(hipGetLastError());
+    }
+    if (want_map || d_stats) {
+        rc = saliency_tables(c, W, H, tab, s);
+        if (rc) return rc;
+    }
+    vet::SalListParams g{};
+    g.ids = ids; g.R = R; g.Wpos = Wpos; g.D = D; g.cap = cap; g.U = U; g.T = T; g.stride = stride; g.per_user = 0;
+    g.P = 2;
+    while (sorted && g.P < Wpos) g.P <<= 1;
+    g.list = (uint2*)(ws + list_o); g.nlist = (int32_t*)(ws + nl_o); g.nsamp = (unsigned long long*)(ws + ns_o);
+    g.dense = (unsigned*)(ws + dense_o);
+    vet::SalMapParams m{};
+    m.list = g.list; m.nlist = g.nlist; m.nsamp = g.nsamp; m.unit = pl->d_dir_unit; m.tab = tab; m.cap = cap;
+    m.W = W; m.H = H; m.tile = tile; m.scale = 2; m.kappa = kappa; m.C = C;
+    m.out = d_map ? d_map : (double*)(ws + map_o);
+    vet::ScoreSortParams so{};
+    so.pred = d_pred; so.sorted = (unsigned long long*)(ws + srt_o); so.W = W;
+    so.P = 2;
+    while (so.P < W) so.P <<= 1;
+    vet::ScorePointParams pt{};
+    pt.list = g.list; pt.nlist = g.nlist; pt.unit = pl->d_dir_unit; pt.pred = d_pred; pt.sorted = (const double*)(ws + srt_o);
+    pt.ay = tab + (size_t)2 * W + 2 * (size_t)H; pt.cap = cap; pt.CR = CR; pt.pred_stride = is_static ? 0 : npix;
+    pt.sorted_stride = pt.pred_stride; pt.W = W; pt.H = H; pt.tile_rows = std::max(1, vet::SS_TILE / W); pt.pts = (double*)(ws + pts_o);
+    vet::ScoreRowParams q{};
+    q.pred = d_pred; q.map = d_stats && want_dist ? m.out : nullptr; q.ay = pt.ay; q.list = g.list; q.nlist = g.nlist; q.nsamp = g.nsamp;
+    q.pts = pt.pts; q.cap = cap; q.CR = CR; q.pred_stride = pt.pred_stride; q.rows = R; q.W = W; q.H = H;
+    q.stats = d_stats; q.counts = (long long*)d_counts; q.status = d_status;
+    if (d_stats && is_static) {
+        ProfScope ps(c, s, KID_TRANSITION);
+        so.map0 = 0;
+        hipLaunchKernelGGL(vet::k_score_sort, dim3((unsigned)H, 1), dim3(vet::SM_THREADS), 0, s, so);
+        HIP_TRY(hipGetLastError());
+    }
+    const bool want_rows = d_stats || d_counts || d_status;
+    for (long r0 = 0; r0 < R; r0 += CR) {
+        const long cr = std::min(CR, R - r0);
+        g.r0 = r0;
+        rc = saliency_lists(c, g, sorted, cr, s);
+        if (rc) return rc;
+        if (want_map) {
+            m.out_row0 = d_map ? r0 : 0;
+            ProfScope pm(c, s, KID_SPATIAL);
+            const dim3 grid((unsigned)((npix + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr);
+            hipLaunchKernelGGL(vet::k_saliency_map, grid, dim3(vet::SM_THREADS), 0, s, m);
+            HIP_TRY(hipGetLastError());
+        }
+        if (d_stats) {
+            if (!is_static) {
+                ProfScope ps(c, s, KID_TRANSITION);
+                so.map0 = r0;
+                hipLaunchKernelGGL(vet::k_score_sort, dim3((unsigned)H, (unsigned)cr), dim3(vet::SM_THREADS), 0, s, so);
+                HIP_TRY(hipGetLastError());
+            }
+            ProfScope pp(c, s, KID_SPATIAL);
+            pt.r0 = r0;
+            const dim3 grid((unsigned)((cap + vet::SM_THREADS - 1) / vet::SM_THREADS), (unsigned)cr);
+            hipLaunchKernelGGL(vet::k_score_points, grid, dim3(vet::SM_THREADS), 0, s, pt);
+            HIP_TRY(hipGetLastError());
+        }
+        if (want_rows) {
+            ProfScope ps(c, s, KID_TRANSITION);
+            q.map_row0 = d_map ? r0 : 0; q.r0 = r0;
+            hipLaunchKernelGGL(vet::k_score_rows, dim3((unsigned)cr), dim3(vet::SM_THREADS), 0, s, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return VET_OK;
+}
+
 }  // namespace
+
+// What vet_saliency_score* refuse: check_saliency_args for the pooled layout at scale 2, pred NULL, n_pred other than 1 or the rows.
+int check_score_args(const vet_plan* pl, int U, int T, int window, int stride, double sigma, int W, int H, const double* pred,
+                     int n_pred) {
+    int rc = check_saliency_args(pl, U, T, window, stride, 0, sigma, W, H, 2);
+    if (rc) return rc;
+    if (!pred) return fail(VET_ERR_INVALID, "pred is NULL");
+    const int64_t R = vet_window_rows(T, window, stride);
+    if (n_pred != 1 && (int64_t)n_pred != R)
+        return fail(VET_ERR_INVALID, "n_pred must be 1 (a static map) or the %lld rows of the call (got %d)", (long long)R, n_pred);
+    return VET_OK;
+}
 
 // What vet_congruency* refuse: check_saliency_args for both layouts (sigma, window, stride, the frames a per-viewer call takes), and
 // fewer than two viewers.
@@ -1313,6 +1679,26 @@ int vet_saliency_similarity_ids(vet_plan* pl, const int32_t* d_ids, int U, int T
     if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
     return rc ? rc : launch_similarity(pl, nullptr, nullptr, d_ids, U, T, window, stride, groups, sigma_rad, W, H, d_maps, d_stats,
                                        d_counts, d_status, s);
+}
+
+int vet_saliency_score(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, double sigma_rad,
+                       int W, int H, const double* d_pred, int n_pred, int want_dist, double* d_map, double* d_stats, int64_t* d_counts,
+                       int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_score_args(pl, U, T, window, stride, sigma_rad, W, H, d_pred, n_pred);
+    if (!rc) rc = entry_samples(pl, d_mu, d_mv, nullptr, "vet_saliency_score_ids", stream, &s);
+    return rc ? rc : launch_score(pl, d_mu, d_mv, nullptr, U, T, window, stride, sigma_rad, W, H, d_pred, n_pred, want_dist, d_map,
+                                  d_stats, d_counts, d_status, s);
+}
+
+int vet_saliency_score_ids(vet_plan* pl, const int32_t* d_ids, int U, int T, int window, int stride, double sigma_rad, int W, int H,
+                           const double* d_pred, int n_pred, int want_dist, double* d_map, double* d_stats, int64_t* d_counts,
+                           int32_t* d_status, void* stream) {
+    hipStream_t s;
+    int rc = check_score_args(pl, U, T, window, stride, sigma_rad, W, H, d_pred, n_pred);
+    if (!rc) rc = entry_samples(pl, nullptr, nullptr, d_ids, nullptr, stream, &s);
+    return rc ? rc : launch_score(pl, nullptr, nullptr, d_ids, U, T, window, stride, sigma_rad, W, H, d_pred, n_pred, want_dist, d_map,
+                                  d_stats, d_counts, d_status, s);
 }
 
 int vet_congruency(vet_plan* pl, const double* d_mu, const double* d_mv, int U, int T, int window, int stride, double sigma_rad,

@@ -144,6 +144,9 @@ SIGNATURES = {
     "vet_saliency_similarity": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
     "vet_saliency_similarity_ids": (_I, [_P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P, _P]),
     "vet_saliency_similarity_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P]),
+    "vet_saliency_score": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_saliency_score_ids": (_I, [_P, _P, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "vet_saliency_score_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I, _P, _P, _P]),
     "vet_congruency": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P]),
     "vet_congruency_ids": (_I, [_P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P]),
     "vet_congruency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _I, _P, _P, _P]),
@@ -561,6 +564,13 @@ SALIENCY_SCALES = {"none": 0, "mean": 1, "density": 2}
 _SALIENCY_SIMILARITY_CALL = ("vet_saliency_similarity", False, True, False,
                              (("maps", "2RYX", _F64, True), ("stats", "9R", _F64, False), ("counts", "4R", _NP_I64, False)))
 SALIENCY_SIMILARITY_STATS = ("cc", "sim", "jsd", "kl_ab", "kl_ba", "nss_ab", "nss_ba", "mass_a", "mass_b")
+
+# The saliency scoring call, in a table of its own: one descriptor of the same form (dims Y, X: the map's rows and columns; 9
+# statistics: auc, nss, info_gain, cc, sim, jsd, kl, mass, mass_pred; 2 counts: samples, distinct).  Rows count frames; its extra
+# arguments are sigma in radians, the map's size, the predicted maps with their number and want_dist.
+_SALIENCY_SCORE_CALL = ("vet_saliency_score", False, True, False,
+                        (("map", "RYX", _F64, True), ("stats", "9R", _F64, False), ("counts", "2R", _NP_I64, False)))
+SALIENCY_SCORE_STATS = ("auc", "nss", "info_gain", "cc", "sim", "jsd", "kl", "mass", "mass_pred")
 
 # The congruency call, in a table of its own: one descriptor of the same form (3 statistics per viewer and row: lift, info_gain,
 # nss; 3 counts: samples, distinct, others; 4 values per row: scored, mean lift, mean info_gain, mean nss).  Rows count frames; its
@@ -1111,6 +1121,44 @@ class Plan:
         return self._row_host(_SALIENCY_SIMILARITY_CALL, mu, mv, ids, window, stride, {"maps"} if want_maps else set(), check,
                               extra=(_ptr(g), sigma, W, H), extra_dims={"Y": H, "X": W, "2": 2, "9": 9})
 
+    @staticmethod
+    def _score_maps(maps, rows, check):
+        """The predicted maps as the C entry takes them: (contiguous float64 array, n_pred, W, H).  ``ValueError`` unless ``maps``
+        is a float64 array [H, W] (one static map) or [rows, H, W] (``rows``: the rows of the call, None where the window is refused
+        later) and, with ``check``, finite and non-negative."""
+        if not isinstance(maps, np.ndarray) or maps.dtype != np.float64:
+            raise ValueError(f"maps must be a float64 array [H, W] or [rows, H, W] (got {type(maps).__name__}"
+                             f"{' of ' + str(maps.dtype) if isinstance(maps, np.ndarray) else ''})")
+        if maps.ndim not in (2, 3):
+            raise ValueError(f"maps must be [H, W] (one static map) or [rows, H, W] (got {maps.ndim} dimensions)")
+        if maps.ndim == 3 and rows is not None and maps.shape[0] != rows:
+            raise ValueError(f"maps holds {maps.shape[0]} maps for {rows} rows: pass one map per row, or one [H, W] map for all")
+        if check and (not np.isfinite(maps).all() or (maps < 0).any()):
+            raise ValueError("maps must be finite and non-negative")
+        return np.ascontiguousarray(maps), (1 if maps.ndim == 2 else int(maps.shape[0])), int(maps.shape[-1]), int(maps.shape[-2])
+
+    def saliency_score(self, mu=None, mv=None, ids=None, maps=None, window=1, stride=1, sigma_deg=5.0, distribution=True,
+                       want_map=False, check=True):
+        """Saliency scoring (include/vet.h: vet_saliency_score): how well the predicted ``maps`` — float64 [H, W], one static map
+        for every row, or [R, H, W], one per row; finite, non-negative, any scale, laid out as ``saliency``'s maps — predict where the
+        audience looked in frames [r * stride, r * stride + window) (``window=None``: the whole video).  Returns dict(map[R,H,W]|None
+        (``want_map``: the audience's own density map), stats[9,R] (auc = the area-weighted Mann-Whitney AUC of the map's values at
+        the samples against the whole sphere, nss, info_gain in bits over the uniform sphere — the map sampled at the samples'
+        directions by bilinear interpolation — and, with ``distribution``, cc, sim, jsd, kl of the audience's density map
+        (``sigma_deg``) against the prediction and mass, the audience map's; mass_pred), counts[2,R] int64 (samples, distinct
+        directions), code), R = (T - window) // stride + 1.  A row without a sample is NaN but for mass_pred — data, never an error;
+        info_gain is -inf where the map is 0.0 at a sample, kl +inf where the audience has weight on a cell the map holds 0.0 in;
+        without ``distribution`` cc .. mass are NaN and no density is evaluated.  ``check`` also refuses a negative or non-finite
+        map value.  ``code`` is VET_OK or VET_ERR_RANGE."""
+        first = ids if ids is not None else mu
+        T = np.shape(first)[0] if np.ndim(first) == 2 else None
+        w = T if window is None else window
+        ok = T is not None and isinstance(w, (int, np.integer)) and isinstance(stride, (int, np.integer)) and 1 <= w <= T and stride >= 1
+        pred, n_pred, W, H = self._score_maps(maps, (T - int(w)) // int(stride) + 1 if ok else None, check)
+        sigma, W, H, _ = self._saliency_args(sigma_deg, W, H, "density")
+        return self._row_host(_SALIENCY_SCORE_CALL, mu, mv, ids, window, stride, {"map"} if want_map else set(), check,
+                              extra=(sigma, W, H, _ptr(pred), n_pred, int(bool(distribution))), extra_dims={"Y": H, "X": W, "2": 2, "9": 9})
+
     def congruency(self, mu=None, mv=None, ids=None, window=None, stride=1, sigma_deg=5.0, nss=True, check=True):
         """Viewer congruency (include/vet.h: vet_congruency): for every viewer and every row of ``saliency`` (frames
         [r * stride, r * stride + window), ``window=None`` the whole video) the kernel density of everyone else's samples, evaluated
@@ -1348,6 +1396,17 @@ class Plan:
         g = self._group_array(groups, n_users)
         self._row_device(_SALIENCY_SIMILARITY_CALL, d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, g.ctypes.data, sigma, W, H), d_maps or None, (d_stats, d_counts, d_status), stream)
+
+    def saliency_score_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, d_pred: int,
+                              n_pred: int, width: int, height: int, sigma_deg: float = 5.0, distribution: bool = True, d_map: int = 0,
+                              d_stats: int = 0, d_counts: int = 0, d_status: int = 0, stream=None, d_ids: int = 0):
+        """d_pred f64 [n_pred][H][W] on the device, read in place (finite and non-negative: a precondition, not checked); n_pred 1 or
+        R; d_map f64 [R][H][W]; d_stats f64 [9][R]; d_counts i64 [2][R]; every output may be 0 (include/vet.h: vet_saliency_score;
+        ``d_ids``: vet_saliency_score_ids)."""
+        sigma, W, H, _ = self._saliency_args(sigma_deg, width, height, "density")
+        self._row_device(_SALIENCY_SCORE_CALL, d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, sigma, W, H, int(d_pred), int(n_pred), int(bool(distribution))), d_map or None,
+                         (d_stats, d_counts, d_status), stream)
 
     def congruency_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, sigma_deg: float = 5.0,
                           nss: bool = True, d_stats: int = 0, d_counts: int = 0, d_rows: int = 0, d_status: int = 0, stream=None,

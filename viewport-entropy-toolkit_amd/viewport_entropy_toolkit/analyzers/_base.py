@@ -815,6 +815,68 @@ class _EntropyAnalyzerBase:
                                                int(height))
 
     @staticmethod
+    def _saliency_score_frame(times, names, window: int, stride: int, res: dict, sigma_deg: float, width: int, height: int,
+                              static: bool, distribution: bool) -> pd.DataFrame:
+        """The saliency scores as a DataFrame, one row per window; where ``res`` holds the audience's maps, ``map`` of a row is the
+        [H, W] view of its map in the one [R][H][W] array (no copy)."""
+        times = np.asarray(times)
+        stats = np.asarray(res["stats"], dtype=np.float64).reshape(9, -1)
+        counts = np.asarray(res["counts"]).reshape(2, -1)
+        R = stats.shape[1]
+        first = np.arange(R, dtype=np.int64) * stride
+        cols = dict(time=times[first], time_end=times[first + window - 1], samples=counts[0], distinct=counts[1])
+        cols.update(zip(_native.SALIENCY_SCORE_STATS, stats))
+        if res.get("map") is not None:
+            maps = np.asarray(res["map"]).reshape(R, height, width)
+            m_col = np.empty(R, dtype=object)
+            for r in range(R):
+                m_col[r] = maps[r]
+            cols["map"] = m_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(sigma_deg=float(sigma_deg), kappa=1.0 / min(float(np.radians(sigma_deg)), float(np.pi)) ** 2, width=width,
+                        height=height, window=window, stride=stride, users=list(names), static=bool(static),
+                        distribution=bool(distribution))
+        return df
+
+    def compute_saliency_score(self, maps, window: Optional[int] = 1, stride: int = 1, sigma_deg: float = 5.0,
+                               distribution: bool = True, keep_maps: bool = False) -> pd.DataFrame:
+        """How well a saliency map from elsewhere — a model's prediction, another dataset's ground truth, a centre or equator bias,
+        last segment's map — predicts where this audience looked, per window of frames [r * stride, r * stride + window)
+        (``window=None``: the whole video).  ``maps`` is a float64 array, finite and non-negative in any scale, laid out as
+        ``compute_saliency``'s maps (row 0 at the top, column c centred at lon (c + 0.5) / W * 360 - 180): [H, W], one static map
+        for every window, or [R, H, W], one per window.  The map's size is taken from its shape.  Independent of the tiling.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, one row per window: ``time`` / ``time_end``,
+        ``samples``, ``distinct`` (directions); the location metrics, from the map sampled at the samples' directions by bilinear
+        interpolation — ``auc`` (the probability that the map is higher at a sample than at a uniformly drawn point of the sphere,
+        ties a half: the Mann-Whitney form of AUC-Judd with the whole sphere as negatives, area-weighted; 0.5 = chance), ``nss``
+        (the map standardised by its area-weighted mean and variance, averaged over the samples), ``info_gain`` (mean log2 of the
+        map at a sample over the map's sphere mean, bits; -inf where the map is 0 at a sample); with ``distribution`` the
+        distribution metrics of the audience's own density map (``compute_saliency``, "density", ``sigma_deg``) against the
+        prediction — ``cc``, ``sim``, ``jsd``, ``kl`` (the audience from the prediction, bits; +inf where the audience has weight on
+        a cell the map holds 0 in) and ``mass`` (the audience map's) — NaN without it, and no density is evaluated then;
+        ``mass_pred`` (the predicted map's mean over the sphere) and, with ``keep_maps``, ``map`` (the audience's map, an [H, W]
+        view into one result array).  ``attrs`` hold ``sigma_deg``, ``kappa``, ``width``, ``height``, ``window``, ``stride``,
+        ``users``, ``static`` and ``distribution``.  A window without a sample is NaN but for ``mass_pred`` — returned, never
+        raised.  Raises ``ValidationError`` before data is loaded and for samples outside [0, 1], ``ValueError`` for illegal
+        arguments, a map of the wrong rank, dtype or number, a negative or non-finite map value and, with ``keep_maps``, for maps
+        beyond 4 GiB."""
+        times, names, call = self._row_call("saliency_score")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        R = (len(times) - window) // stride + 1
+        pred, _, width, height = _native.Plan._score_maps(maps, R, True)
+        _native.Plan._saliency_args(sigma_deg, width, height, "density")
+        if keep_maps and R * width * height * 8 > self.SALIENCY_MAP_LIMIT:
+            raise ValueError(f"{R} maps of {width} x {height} are {R * width * height * 8 / 2 ** 30:.1f} GiB, beyond 4 GiB: "
+                             "use a larger stride, a coarser map (width, height), or keep_maps=False")
+        res = call(maps=pred, window=window, stride=stride, sigma_deg=float(sigma_deg), distribution=bool(distribution),
+                   want_map=bool(keep_maps), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._saliency_score_frame(times, names, window, stride, res, float(sigma_deg), width, height, pred.ndim == 2,
+                                          bool(distribution))
+
+    @staticmethod
     def _congruency_frame(times, names, window: int, stride: int, res: dict, sigma_deg: float) -> pd.DataFrame:
         """The viewer congruency as a DataFrame, user-major; ``attrs["rows"]`` is the per-window frame."""
         times = np.asarray(times)
