@@ -1238,10 +1238,10 @@ int vet_saliency_host(vet_plan *plan, const double *h_mu, const double *h_mv, co
  * Stages: the samples quantised once (k_saliency_ids); k_saliency_mask — one streaming pass writes the two masked [T][U] id arrays
  * (8 B more workspace per sample; the list and map kernels of vet_saliency then run unchanged, for A and for B, per pass);
  * k_saliency_points — workgroup = (row, 256 entries of X's list, direction), thread = entry with its unit vector in registers, Y's
- * list staged in LDS in tiles as k_saliency_map stages it (a broadcast), v_i to the workspace: 75 VGPRs, no scratch, 32 KB LDS,
+ * list staged in LDS in tiles as k_saliency_map stages it (a broadcast), v_i to the workspace: 77 VGPRs, no scratch, 32 KB LDS,
  * 5 waves per SIMD (LDS-bound); k_saliency_compare — one workgroup per row: the two masses, one pass over both maps with the seven
  * sums carried together (four log2 per pixel, LDS for the wave partials only), the v_i by the rule, the values, the counts and
- * status[1]: 98 VGPRs, no scratch, 224 B LDS, 4 waves per SIMD; k_saliency_mask 14 VGPRs, no scratch.
+ * status[1]: 97 VGPRs, no scratch, 224 B LDS, 4 waves per SIMD; k_saliency_mask 14 VGPRs, no scratch.
  * VET_ERR_INVALID (before anything is allocated or launched): everything vet_saliency refuses for the pooled layout, groups NULL, an
  * audience without a viewer.  VET_ERR_UNSUPPORTED as vet_saliency, pooled.
  * Profile ids: k_saliency_map and k_saliency_points to k_spatial, the other stages to k_transition.  Asynchronous on `stream`. */
@@ -1313,7 +1313,7 @@ int vet_saliency_similarity_host(vet_plan *plan, const double *h_mu, const doubl
  * tiles of whole map rows (at most 32 KB) and one lower- and one upper-bound binary search per map row, L and E in registers
  * (about H * 2 * log2 W LDS reads per entry instead of W * H compares): 28 VGPRs, no scratch, 32 KB LDS, 5 waves per SIMD
  * (LDS-bound); k_score_rows — one workgroup per row: mass_pred, var_pred, the list sums, with want_dist the audience's mass and the
- * five pixel sums carried together, the values, the counts and status[1]: 94 VGPRs, no scratch, 160 B LDS, 5 waves per SIMD;
+ * five pixel sums carried together, the values, the counts and status[1]: 93 VGPRs, no scratch, 160 B LDS, 5 waves per SIMD;
  * k_score_sort 10 VGPRs, no scratch, 32 KB LDS, 5 waves per SIMD (LDS-bound).  k_saliency_map runs only with want_dist (and d_stats) or d_map.
  * Workspace: 4 B per sample, the sorted copy of a static map, + per row of a pass 8 B per list slot, 16 B per list slot for v_i and
  * u_i, W*H*8 B for the sorted copy when n_pred = R and for M when d_map is NULL; a pass stays under vet_saliency's 256 MB budget.

@@ -15,10 +15,20 @@ per-viewer transition's own refusal together with missing samples (which one win
 outputs are compared.  The Plan wrappers: their ValueErrors, the optional output not wanted, the *_device wrappers (with d_ids
 where they take it).  The analyzers' twelve row methods on a 12 x 3 video: their frames, a sample of 1.5, a window without a
 sample.
+The saliency family is what a refactor of vet_saliency.hip must keep: the eight device entries (vet_saliency, _similarity, _score,
+vet_congruency, each with (mu, mv) and with ids) on the same video and the 100 x 200 grid plan.  Maps of 37 x 19 (703 pixels: one
+partial block of the summation rule, a partial last workgroup) and 64 x 33 (2 112: three blocks, the last partial), sigma 5 and 1
+degrees; windows 1, 20 and 150 at stride 7 and window 20 at stride 1 (65 and 1 300 positions: the LDS sort, the latter at 2 048 keys
+with lists beyond one LDS tile and one rule block; 9 750: counted, in LDS).  vet_saliency pooled and per viewer, scales 0 to 2, each
+optional output present and absent, vet_test_saliency_tile 0, 4 and 1; the similarity with viewer u in audience A, B or neither by
+u mod 3, with and without d_maps, tile 0 and 4; the congruency with and without NSS and d_rows, tile 0 and 4; the scoring of a seeded
+noise map, static and one per row, with and without the distribution metrics and d_map.  One vet_saliency_ids case on a 300 x 200
+grid plan (60 501 directions, past the LDS counts) with rows of 4 550 positions.  The refusals: window 0 and T + 1, stride 0, sigma
+0, W 1 and 4 097, H 2 049, scale 3, groups NULL, an audience without a viewer, pred NULL, n_pred 2, one viewer for the congruency.
 One line per case; exit status 1 on any difference.  A refusal's line holds the exception's type name or the code before the
 message, so the lines of profiles/refactor/row_calls_ab_bits.txt (message only) do not compare with today's.
-usage: python tools/ab_bits.py libA.so libB.so
-       python tools/ab_bits.py --dump LIB      the case lines of one library with the Python layer of this checkout, to diff
+usage: python tools/ab_bits.py libA.so libB.so [rows|saliency|all]      (the family; default all)
+       python tools/ab_bits.py --dump LIB [family]   the case lines of one library with the Python layer of this checkout, to diff
                                                against the same from another checkout"""
 import hashlib
 import json
@@ -32,10 +42,11 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'viewport-entrop
 VW, VH = 100, 200
 U, T = 65, 150
 WINDOWS, STRIDES = (20, 100, 150), (7, 1)
+FAMILIES = ("rows", "saliency", "all")
 CHUNKS = (0, 1, 7)                              # forced rows per chunk of the divergence calls (0: sized by the budget)
 
 
-def child():
+def child(family):
     import numpy as np
     import torch
     from viewport_entropy_toolkit import NaiveSpatialEntropyAnalyzer, _native, _quantiser, _synthetic
@@ -240,7 +251,7 @@ def child():
              ("w_1000", lambda: _native.Plan(eng, lattice([1000]), 120.0, 2.0, True, VW, VH)),
              ("u_50", lambda: _native.Plan(eng, lattice([50]), 120.0, 2.0, False, VW, VH)),
              ("naive_10x20", naive._naive_plan)]
-    for pname, make in plans:
+    for pname, make in plans if family != "saliency" else []:
         plan = make()
         n0 = plan.n_tiles[0]
         for window in WINDOWS:
@@ -287,10 +298,118 @@ def child():
         if pname != "naive_10x20":
             plan.close()
 
+    def saliency_family():
+        """The eight device entries of vet_saliency.hip (module docstring), called through ctypes on the 100 x 200 grid plan."""
+        plan = _native.Plan(eng, lattice([50]), 120.0, 2.0, True, VW, VH)
+        rad = lambda deg: deg * (np.pi / 180.0)
+        groups = (np.arange(U) % 3).astype(np.int8)
+        groups[groups == 2] = -1
+        SHAPES = ((37, 19), (64, 33))                           # 703 pixels: one partial rule block; 2 112: three, the last partial
+        SIGMAS = (5.0, 1.0)
+        WS = ((1, 7), (20, 7), (150, 7), (20, 1))               # 65 and 1 300 positions: sorted; 9 750: counted in LDS
+        corners = ((SHAPES[0], SIGMAS[0]), (SHAPES[1], SIGMAS[1]))
 
-def run_child(lib):
+        def call(case, stem, args, shapes, samples=None, u=U, hold=()):
+            """args: what follows (U, T) up to the outputs; shapes: (name, shape or None = not wanted, dtype) in the entry's order;
+            hold: arrays the arguments point to"""
+            for src, ptrs in (("mu_mv", (d_mu.data_ptr(), d_mv.data_ptr())), ("ids", (d_ids.data_ptr(),))) if samples is None else samples:
+                outs = [None if shape is None else torch.full(shape, -7, dtype=dtype, device=dev) for _, shape, dtype in shapes]
+                status.zero_()
+                torch.cuda.synchronize()
+                rc = getattr(lib, stem + ("_ids" if len(ptrs) == 1 else ""))(
+                    plan.handle, *ptrs, u, T, *args, *(None if o is None else o.data_ptr() for o in outs), status.data_ptr(), None)
+                eng.synchronize()
+                if rc:
+                    res = {"error": f"{rc}: {(lib.vet_last_error() or b'').decode()}"}
+                else:
+                    res = {name: digest(o.cpu().numpy()) for (name, _, _), o in zip(shapes, outs) if o is not None}
+                    res["status"] = digest(status.cpu().numpy())
+                emit(f"{case} device {src}", res)
+
+        i64 = torch.int64
+        for window, stride in WS:
+            R = (T - window) // stride + 1
+            for (W, H), sigma in [(wh, sg) for wh in SHAPES for sg in SIGMAS]:
+                tag = f"w{window} s{stride} {W}x{H} sigma{sigma:g}"
+                corner = ((W, H), sigma) in corners
+                # vet_saliency: the base case everywhere; scales, absent outputs and tiles at the two corners
+                variants = [(2, "mspc", 0)]
+                if corner:
+                    variants += [(0, "mspc", 0), (1, "mspc", 0), (2, "mspc", 4), (2, "mspc", 1)]
+                if corner and sigma == SIGMAS[0]:
+                    variants += [(2, "spc", 0), (2, "mc", 0), (2, "msp", 0), (2, "c", 0)]
+                for per_user in (0, 1):
+                    rows = R * U if per_user else R
+                    for scale, want, tile in variants:
+                        eng.test_saliency_tile(tile)
+                        call(f"saliency {tag} {'viewer' if per_user else 'pooled'} scale{scale} outs={want} tile{tile}", "vet_saliency",
+                             (window, stride, per_user, rad(sigma), W, H, scale),
+                             [("map", (rows, H, W) if "m" in want else None, f64), ("stats", (4, rows) if "s" in want else None, f64),
+                              ("peak", (rows,) if "p" in want else None, i32), ("counts", (2, rows) if "c" in want else None, i64)])
+                for tile in (0, 4):
+                    eng.test_saliency_tile(tile)
+                    for maps in (True, False):
+                        call(f"similarity {tag} maps={int(maps)} tile{tile}", "vet_saliency_similarity",
+                             (window, stride, groups.ctypes.data, rad(sigma), W, H),
+                             [("maps", (2, R, H, W) if maps else None, f64), ("stats", (9, R), f64), ("counts", (4, R), i64)], hold=(groups,))
+                eng.test_saliency_tile(0)
+                noise = torch.from_numpy(np.random.default_rng(11).random((R, H, W))).to(dev)
+                for n_pred in sorted({1, R}):
+                    for dist in (0, 1):
+                        for own in (True, False):
+                            call(f"score {tag} n_pred={'1' if n_pred == 1 else 'R'} dist{dist} map={int(own)}", "vet_saliency_score",
+                                 (window, stride, rad(sigma), W, H, noise.data_ptr(), n_pred, dist),
+                                 [("map", (R, H, W) if own else None, f64), ("stats", (9, R), f64), ("counts", (2, R), i64)], hold=(noise,))
+            for sigma in SIGMAS:
+                for tile in (0, 4):
+                    eng.test_saliency_tile(tile)
+                    for nss in (0, 1):
+                        for rows in (True, False):
+                            call(f"congruency w{window} s{stride} sigma{sigma:g} nss{nss} rows={int(rows)} tile{tile}", "vet_congruency",
+                                 (window, stride, rad(sigma), nss),
+                                 [("stats", (3, U, R), f64), ("counts", (3, U, R), i64), ("rows", (4, R) if rows else None, f64)])
+                eng.test_saliency_tile(0)
+
+        # the refusals: every output NULL, so a call that is not refused writes nothing
+        none = lambda names: [(n, None, f64) for n in names]
+        pred = torch.zeros((19, 37), dtype=f64, device=dev)
+        sal = lambda window=20, stride=7, sigma=rad(5.0), W=37, H=19, scale=2: (window, stride, 0, sigma, W, H, scale)
+        sim = lambda g=groups, window=20, stride=7, sigma=rad(5.0), W=37, H=19: (window, stride, None if g is None else g.ctypes.data,
+                                                                                   sigma, W, H)
+        sco = lambda p=pred, n_pred=1, window=20, stride=7, sigma=rad(5.0), W=37, H=19: (window, stride, sigma, W, H,
+                                                                                       None if p is None else p.data_ptr(), n_pred, 1)
+        only_a = np.zeros(U, dtype=np.int8)
+        common = [("window0", dict(window=0)), ("window_long", dict(window=T + 1)), ("stride0", dict(stride=0)), ("sigma0", dict(sigma=0.0))]
+        mapped = common + [("W1", dict(W=1)), ("W4097", dict(W=4097)), ("H2049", dict(H=2049))]
+        for what, kw in mapped + [("scale3", dict(scale=3))]:
+            call(f"refusal saliency {what}", "vet_saliency", sal(**kw), none(("map", "stats", "peak", "counts")))
+        for what, kw in mapped + [("groups_null", dict(g=None)), ("empty_audience", dict(g=only_a))]:
+            call(f"refusal similarity {what}", "vet_saliency_similarity", sim(**kw), none(("maps", "stats", "counts")), hold=(only_a,))
+        for what, kw in mapped + [("pred_null", dict(p=None)), ("n_pred2", dict(n_pred=2))]:
+            call(f"refusal score {what}", "vet_saliency_score", sco(**kw), none(("map", "stats", "counts")))
+        for what, kw in common:
+            a = dict(window=20, stride=7, sigma=rad(5.0)); a.update(kw)
+            call(f"refusal congruency {what}", "vet_congruency", (a["window"], a["stride"], a["sigma"], 1), none(("stats", "counts", "rows")))
+        call("refusal congruency U1", "vet_congruency", (20, 7, rad(5.0), 1), none(("stats", "counts", "rows")), u=1)
+        plan.close()
+
+        # a direction table beyond the LDS counts: a 300 x 200 pixel grid (60 501 directions), rows of 70 frames (4 550 positions)
+        plan = _native.Plan(eng, lattice([50]), 120.0, 2.0, True, 300, 200)
+        big_ids = np.where(absent, -1, (np.nan_to_num(mv) * 200).astype(np.int64) * 301 + (np.nan_to_num(mu) * 300).astype(np.int64))
+        d_big = torch.from_numpy(big_ids.astype(np.int32)).to(dev)
+        R = (T - 70) // 40 + 1
+        call("saliency big_table w70 s40 12x6 sigma10", "vet_saliency", (70, 40, 0, rad(10.0), 12, 6, 2),
+             [("map", (R, 6, 12), f64), ("stats", (4, R), f64), ("peak", (R,), i32), ("counts", (2, R), i64)],
+             samples=(("ids", (d_big.data_ptr(),)),), hold=(d_big,))
+        plan.close()
+
+    if family != "rows":
+        saliency_family()
+
+
+def run_child(lib, family):
     env = dict(os.environ, VET_HIP_LIBRARY=os.path.abspath(lib))
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, stdout=subprocess.PIPE, text=True)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", family], env=env, stdout=subprocess.PIPE, text=True)
     cases = {}
     for line in p.stdout.splitlines():
         if line.startswith("{"):
@@ -299,8 +418,11 @@ def run_child(lib):
     return p.returncode, cases
 
 
-def main(lib_a, lib_b):
-    (rc_a, a), (rc_b, b) = run_child(lib_a), run_child(lib_b)
+def main(lib_a, lib_b, family):
+    rc_a, a = run_child(lib_a, family)
+    if rc_a:                                                     # nothing more is started on a GPU that a run may have faulted
+        sys.exit(f"the run of A ({lib_a}) ended with status {rc_a} after {len(a)} cases; B was not run")
+    rc_b, b = run_child(lib_b, family)
     bad = 0
     for case in sorted(set(a) | set(b), key=lambda c: (list(a).index(c) if c in a else len(a), c)):
         same = case in a and case in b and a[case] == b[case]
@@ -312,8 +434,8 @@ def main(lib_a, lib_b):
     return 1 if bad or rc_a or rc_b or not a else 0
 
 
-def dump(lib):
-    rc, cases = run_child(lib)
+def dump(lib, family):
+    rc, cases = run_child(lib, family)
     for case, outputs in cases.items():
         print(f"{case}  {json.dumps(outputs, sort_keys=True)}")
     print(f"{len(cases)} cases (exit {rc})")
@@ -321,11 +443,13 @@ def dump(lib):
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--child"]:
-        child()
-    elif len(sys.argv) == 3 and sys.argv[1] == "--dump":
-        sys.exit(dump(sys.argv[2]))
-    elif len(sys.argv) == 3:
-        sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = sys.argv[1:]
+    family = args.pop() if args and args[-1] in FAMILIES else "all"
+    if args == ["--child"]:
+        child(family)
+    elif len(args) == 2 and args[0] == "--dump":
+        sys.exit(dump(args[1], family))
+    elif len(args) == 2:
+        sys.exit(main(args[0], args[1], family))
     else:
         sys.exit(__doc__)

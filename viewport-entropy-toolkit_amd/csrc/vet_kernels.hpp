@@ -68,18 +68,21 @@
 //                                                               the row's integers by integer atomics
 //                                              k_dispersion_finish  one wave per row: the blocks in order, the frames' histograms added
 //   vet_saliency.hip    (in the unit)          k_saliency_ids   the pooled layout's direction ids, frame-major (per viewer: k_user_dirs)
+//                                              (shared by the kernels below, written once: sal_walk — the density of a list at a
+//                                                               direction; sal_rule — the block-ordered summation rule of a workgroup, and
+//                                                               cg_wave_rule, the same by one wave; sal_pixel_terms — the comparison terms)
 //                                              k_saliency_sort  one workgroup per row of up to 4096 positions: LDS sort of the ids, the
 //                                                               distinct ids in ascending order with their run lengths
 //                                              k_saliency_count, k_saliency_compact   longer rows: dense integer counts per direction,
 //                                                               compacted in ascending id by one workgroup per row
 //                                              k_saliency_map   workgroup = (row, 256 pixels): the row's list staged in LDS in tiles of
-//                                                               1024 entries, S = fma(m, exp(kappa (c - 1)), S) per pixel in a register
+//                                                               1024 entries, S = fma(m, exp(kappa (c - 1)), S) per pixel in a register (sal_walk)
 //                                              k_saliency_rows  one workgroup per row: mass, peak, entropy and area of the written map
 //                                              k_saliency_mask  the similarity call: the ids once more per audience, the others' samples -1
 //                                              k_saliency_points  workgroup = (row, 256 entries of one audience's list, direction): the
-//                                                               other audience's density at the entries' directions, its list in LDS tiles
+//                                                               other audience's density at the entries' directions by sal_walk
 //                                              k_saliency_compare  one workgroup per row: the masses, CC, SIM, JSD, both KL and both NSS
-//                                                               of the two audiences' maps by the block-ordered sums
+//                                                               of the two audiences' maps by sal_rule over sal_pixel_terms
 //                                              k_congruency_points  the congruency call: workgroup = (row, 256 queries), a query = one entry
 //                                                               of one viewer's own list; the pooled list in LDS tiles with its ids, the
 //                                                               viewer's own multiplicity taken off on an id match (leave-one-out)
@@ -91,7 +94,7 @@
 //                                              k_score_points   workgroup = (row, 256 list entries): the predicted map at the entry's direction
 //                                                               (bilinear), its rank in every sorted map row by two binary searches in LDS
 //                                              k_score_rows     one workgroup per row: mass and variance of the prediction, AUC, NSS and
-//                                                               information gain from the list sums, CC, SIM, JSD, KL against the audience's map
+//                                                               information gain from the list sums, CC, SIM, JSD, KL against the audience's map (sal_pixel_terms)
 //   vet_crowd.hip      (in the unit)          k_crowd_logp     log2 of the pooled proportions of a chunk's rows, once per row and tile
 //                                              k_crowd_w, k_crowd_c   one workgroup per (row, viewer): k_user_entropy_w/_c's walk in LDS, then
 //                                                               W_u, S(h_u) and the viewer's KL divergence from the pooled row in one wave
