@@ -72,7 +72,9 @@ extern "C" {
                           the vet_saliency_similarity* entry points (CC, SIM, JSD, KL and NSS between the maps of two audiences), and
                           then the vet_congruency* entry points (each viewer's leave-one-out saliency score per window); the
                           vet_saliency_score* entry points (AUC, NSS, information gain, CC, SIM, JSD and KL of a predicted map)
-                          were added under the same number */
+                          were added under the same number, and so were the vet_viewer_clusters* entry points (the connected
+                          components of the viewers linked by the angle between their directions, per window) and
+                          vet_test_cluster_tile */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -162,6 +164,11 @@ int vet_test_dispersion_tile(vet_ctx *ctx, int n);
  * vet_saliency_similarity*), k_saliency_points (vet_saliency_similarity*: the other audience's list) and k_congruency_points
  * (vet_congruency*: the pooled list) stage in LDS at a time (default and upper limit 1024; 0 restores the default).  Read at every launch; results do not depend on it. */
 int vet_test_saliency_tile(vet_ctx *ctx, int n);
+/* Test switch, not a tuning knob: rows > 0 makes vet_viewer_clusters* take at most `rows` rows per pass instead of as many as its
+ * 256 MB budget of link words holds, and tile > 0 lowers the most partners of one workgroup of k_cluster_links from 128 to `tile`,
+ * so that a small input runs several passes and several partner tiles; 0 restores a default.  Read at every launch, nowhere from
+ * the environment.  Results are bit-identical whatever the values. */
+int vet_test_cluster_tile(vet_ctx *ctx, int rows, int tile);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -1123,6 +1130,90 @@ int vet_dispersion_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_
 int vet_dispersion_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
                         int window, int stride, int per_user, const double *h_edges, int B, double *h_stats, double *h_centroid,
                         int64_t *h_hist, int64_t *h_counts);
+
+/* ---- viewer clusters: who looks together, per window -------------------------------------------------------
+ * Not in the reference, and independent of the lattices: only the plan's direction table is read.  vet_dispersion says how far apart
+ * the viewers are; this call names the groups: which viewers could share one viewport stream in a segment, how many streams the
+ * audience needs, and which viewers belong to none.  It is the clustering of viewers by the geodesic distance of their viewport
+ * centres of the 360-degree streaming literature; the threshold is the caller's (the Python layer's default of 30 degrees is a
+ * choice for head-direction data, not taken from the reference, which has no such call).
+ * PRESENCE, samples, direction ids and rows exactly as in vet_dispersion: an absent or out-of-range sample is absent and counted in
+ * status[0]; R = vet_window_rows(n_frames, window, stride); row r covers frames [r*stride, r*stride + window).
+ * NEAR.  In frame f two present viewers u != v are NEAR if their direction ids are equal, or vet_dispersion's SAME rule applies (the
+ * two Vectors are equal as numbers, whatever their ids), or c >= cos_threshold with, A and B the rows of the plan's unit table,
+ *   c = fma(A.z, B.z, fma(A.y, B.y, A.x * B.x)).
+ * There is no acos.  A NaN c is not near.  NEAR is symmetric bit for bit: the products commute and the fused dot adds them in one
+ * order.  cos_threshold is a double in [-1, 1]: the caller takes the cosine of its angle once (Python: math.cos(math.radians(
+ * threshold_deg)), reported in attrs["cos_threshold"]), so no two libms decide one link.
+ * LINKED.  For row r and a pair {u, v}: co = the number of the row's frames in which both are present, near = the number of those in
+ * which they are NEAR; they are LINKED iff co >= 1 and (double)near >= min_share * (double)co, 0 < min_share <= 1 — one IEEE
+ * multiply and one compare.  window = 1: NEAR in that frame.  min_share = 1: within the threshold whenever both are there, the
+ * segment rule of the clustering literature.
+ * CLUSTERS.  The viewers of a row are those present in at least one of its frames, P of them.  Its clusters are the connected
+ * components of the LINKED graph on them; a viewer without a link is a cluster of one (a singleton); a viewer never present has
+ * label -1.  Clusters are numbered 0, 1, ... in ascending order of their smallest member's index, K of them: the labels are a
+ * function of the row alone.
+ * Outputs, each nullable:
+ *   d_labels    [R][U] i32
+ *   d_sizes     [R][U] i32: the members of cluster k, zero beyond K
+ *   d_counts    [5][R] i64, count-major: 0 viewers (P), 1 clusters (K), 2 the largest cluster's size, 3 singletons, 4 links (unordered
+ *               LINKED pairs)
+ *   d_top       [R][Q] i32: the smallest number of clusters, largest first and equal sizes by label, whose sizes sum to s with
+ *               (double)s >= fractions[i] * (double)P — how many viewport streams serve that share of the row's audience (vet_coverage's
+ *               `tiles`, over viewers instead of tiles); 0 for P = 0.  0 <= Q <= 16; h_fractions [Q], each in (0, 1], is a HOST array
+ *               in every entry, consumed before the call returns.  Q = 0 (or d_top NULL) skips it.
+ *   d_stats     [3][R] f64: 0 the partition entropy H = log2 P - (sum_k s_k log2 s_k) / P in bits (ocml log2), the sum by
+ *               vet_head_motion's summation rule with the cluster labels k = 0 .. K - 1 as the positions (blocks of 1024 from 0; in a
+ *               block thread t of 256 adds positions t, t + 256, t + 512, t + 768, the 64 lanes of a wave combine by wave_sum's
+ *               butterfly, the four waves are added in order, the blocks ascending); 1 H / log2 P (NaN for P <= 1); 2 largest / P
+ *   d_centroids [R][U][3] f64: for cluster k the sum of the unit vectors of its members' present samples in the row, frame-major then
+ *               viewer ascending, a sequential sum from +0.0; entries beyond K are zero; a NaN unit vector adds nothing.  Divide by
+ *               the norm for the direction the cluster looks in.
+ *   d_links     [R][U][ceil(U / 64)] u64: bit v mod 64 of word v / 64 of row u is LINKED(u, v); the diagonal is zero, the matrix is
+ *               symmetric, the bits at and beyond U are zero
+ *   d_status    [2] i32 {bad, #rows with P = 0}; the call ADDS, the caller zeroes
+ * A row with P = 0 has labels -1, zero counts, sizes and centroids and NaN stats: data, not an error.
+ * A value's bits depend on the plan, window, cos_threshold, min_share and the row's frames only — not on stride, the number of rows,
+ * the video's length, the entry point, which optional outputs were asked for, the other fractions, or vet_test_cluster_tile.
+ * Stage 0, k_cluster_ids: the samples quantised to direction ids [T][U] once.  Stage 1, k_cluster_links: workgroup = (row, 256
+ * viewers u, a tile of up to 128 partners v — fewer, a multiple of 8, where a pass has few rows), lane = viewer u, a wave = 64 consecutive u; the partners' records (unit vector and id,
+ * 32 B) of a chunk of the row's frames are staged in LDS one per thread (8 partners x 32 frames of a long window; up to 256 / window
+ * partners of a window of at most 32 frames), the lane walks the frames with (co, near) of 8 partners in registers (every lane reads
+ * the same LDS address: a broadcast), decides LINKED, and one __ballot of the wave is the word links[v][u / 64], stored by one lane.
+ * No atomics, no scratch, 8 KB of LDS, no acos.  It walks ALL ORDERED PAIRS; walking the upper triangle and mirroring the words was
+ * NOT built and the two were not measured against each other.  Stage 2, k_cluster_components: one 256-thread workgroup per row, the
+ * labels in LDS (12 B per viewer, rounded up to a power of two: 96 KB at 8192 viewers): label propagation over the set bits of the
+ * link words with pointer jumping until a sweep changes nothing (the fixpoint is each component's smallest member whatever the
+ * schedule), the roots ranked by a block prefix sum, sizes by integer LDS atomics, the (size descending, label ascending) records
+ * sorted in LDS, the entropy sum by the rule above, and — only when d_centroids is given — a thread per cluster over the row's
+ * positions.  Rows run in passes under a 256 MB budget of link words (n_users * ceil(n_users / 64) * 8 B per row; written straight
+ * into d_links when that is given).  Workspace besides: 4 B per (frame, viewer).
+ * Not built: complete-linkage or clique clusters; a lag band of partition agreement between windows; clusters carried across
+ * overlapping windows (every row is clustered on its own, and overlapping windows recompute their shared frames); more than 8192
+ * viewers.
+ * VET_ERR_INVALID (before anything is allocated or launched): window < 1, window > n_frames, stride < 1, Q outside [0, 16], a
+ * fraction outside (0, 1] or NaN, min_share outside (0, 1] or NaN, cos_threshold outside [-1, 1] or NaN.  VET_ERR_UNSUPPORTED:
+ * n_users > 8192 (the labels of a row live in LDS); n_frames * ceil(n_users / 256) above 2^31 - 1.
+ * Profile ids: k_cluster_ids to k_spatial, k_cluster_links to k_transition, k_cluster_components to k_finalize.  Asynchronous on
+ * `stream`. */
+int vet_viewer_clusters(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride,
+                        double cos_threshold, double min_share, const double *h_fractions, int Q, int32_t *d_labels, int32_t *d_sizes,
+                        int64_t *d_counts, int32_t *d_top, double *d_stats, double *d_centroids, uint64_t *d_links, int32_t *d_status,
+                        void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_viewer_clusters_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride,
+                            double cos_threshold, double min_share, const double *h_fractions, int Q, int32_t *d_labels,
+                            int32_t *d_sizes, int64_t *d_counts, int32_t *d_top, double *d_stats, double *d_centroids,
+                            uint64_t *d_links, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa. */
+int vet_viewer_clusters_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                             int window, int stride, double cos_threshold, double min_share, const double *h_fractions, int Q,
+                             int32_t *h_labels, int32_t *h_sizes, int64_t *h_counts, int32_t *h_top, double *h_stats,
+                             double *h_centroids, uint64_t *h_links);
+/* Diagnostic: h_sweeps [2] = the most label-propagation sweeps a row of the plan's context's last vet_viewer_clusters* call took,
+ * and their sum over its rows (zeros before any call).  Synchronises the device. */
+int vet_viewer_clusters_sweeps(vet_plan *plan, int64_t *h_sweeps);
 
 /* ---- saliency maps: the spherical kernel density of attention per window and per viewer ------------------
  * Not in the reference, and independent of the lattices: only the plan's direction table is read.  The continuous counterpart of

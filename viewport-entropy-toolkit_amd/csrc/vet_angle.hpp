@@ -23,6 +23,21 @@ __device__ __forceinline__ double unit_angle(int ia, int ib, double ax, double a
     return acos(clip_unit(c));
 }
 
+// Whether the two directions are within a cone given by its cosine (vet_viewer_clusters*): the same id, the same Vector under
+// another id (unit_angle's rule), or c >= cos_thr for unit_angle's fused dot c.  No acos; a NaN c is not near.  Symmetric in (a, b).
+__device__ __forceinline__ bool unit_near(int ia, int ib, double ax, double ay, double az, double bx, double by, double bz,
+                                          double cos_thr, const double* raw) {
+    if (ia == ib) return true;
+    const double c = fma(az, bz, fma(ay, by, ax * bx));
+    if (c >= cos_thr) return true;
+    if (c > 0.999999) {          // only a threshold above that leaves the same Vector to be found
+        const double* ra = raw + 3L * ia;
+        const double* rb = raw + 3L * ib;
+        return ra[0] == rb[0] && ra[1] == rb[1] && ra[2] == rb[2];
+    }
+    return false;
+}
+
 // the same of two direction ids, the unit vectors gathered from the table; NaN where either is absent
 __device__ __forceinline__ double motion_angle(int ia, int ib, const double* unit, const double* raw) {
     if (ia < 0 || ib < 0) return __builtin_nan("");

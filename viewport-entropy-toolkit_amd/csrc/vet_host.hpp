@@ -21,6 +21,9 @@
 //                       angles) and their launch logic
 //   vet_dispersion.hip  the audience dispersion (the angle between two viewers' directions in one frame over all pairs: per (frame,
 //                       viewer) partials from unit vectors staged in LDS, then per row the block-ordered sums) and its launch logic
+//   vet_cluster.hip     the viewer clusters (per row the LINKED pairs of viewers as bit words from a pair walk over the direction
+//                       table, then the connected components by label propagation in LDS, their sizes, entropy and centroids) and
+//                       their launch logic
 //   vet_saliency.hip    the saliency maps (the spherical kernel density of a row's viewing directions on an equirectangular map: the
 //                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics), the
 //                       saliency similarity of two audiences (their maps by the same kernels, compared row by row), the viewer
@@ -164,6 +167,10 @@ struct Tuning {
                                 // k_saliency_map, k_saliency_points and k_congruency_points stage in LDS at a time (0 = 1024); read at
                                 // every launch; the results do not depend on it (test_saliency_gpu.py,
                                 // test_saliency_similarity_gpu.py, test_congruency_gpu.py)
+    int cluster_rows = 0;           // vet_test_cluster_tile (no environment variable): the most rows of a pass of vet_viewer_clusters*
+                                // (0 = sized by the workspace budget) ...
+    int cluster_tile = 0;           // ... and the most partners of one workgroup of k_cluster_links (0 = 128); read at every launch;
+                                // the results do not depend on them (test_viewer_clusters_gpu.py)
     void from_environment();
 };
 
@@ -181,9 +188,10 @@ struct vet_ctx {
     double* d_log2 = nullptr;      // log2(k), k = 0..4096
     bool attrs_set = false;        // dynamic-LDS limits of the run kernels raised (first plan)
     // grow-only device staging buffers (no hipMalloc per call): 0-6 host-buffer entry points (the SLOT_* names of
-    // vet_hostapi.hip), 7 the still counts of vet_head_motion_host (batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list
-    void* pool[12] = {};
-    size_t pool_cap[12] = {};
+    // vet_hostapi.hip), 7 the still counts of vet_head_motion_host (batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list,
+    // 10-11 the centroids and link words of vet_viewer_clusters_host, 12 the sweep counts of vet_viewer_clusters*
+    void* pool[14] = {};
+    size_t pool_cap[14] = {};
     // descriptor blobs of the batch entry points: a ring of (pinned host, device) buffer pairs, each guarded by an event
     // recorded behind the last launch that reads it (vh::BatchBlob) — the calls only enqueue work, so neither the host
     // copy nor the device copy of one batch may be reused while an earlier batch (possibly on another stream) is pending
@@ -448,6 +456,7 @@ int markov_set_attrs(vet_ctx* c);
 int motion_set_attrs(vet_ctx* c);
 int dispersion_set_attrs(vet_ctx* c);
 int saliency_set_attrs(vet_ctx* c);
+int cluster_set_attrs(vet_ctx* c);
 
 // vet_window.hip, shared with vet_window_divergence.hip: what the windowed spatial calls refuse about their arguments, and their
 // stage 1.  window_frames_layout places, behind head_bytes of the caller's own, present[T] and per lattice the per-frame array
@@ -519,6 +528,11 @@ int check_motion_args(const vet_plan* pl, int U, int T, int window, int stride, 
 // vet_dispersion.hip: what vet_dispersion* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched.  edges [B + 1] is host memory.
 int check_dispersion_args(const vet_plan* pl, int U, int T, int window, int stride, int per_user, const double* edges, int B);
+
+// vet_cluster.hip: what vet_viewer_clusters* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched.  fractions [Q] is host memory.
+int check_cluster_args(const vet_plan* pl, int U, int T, int window, int stride, double cos_threshold, double min_share,
+                       const double* fractions, int Q);
 
 // vet_saliency.hip: what vet_saliency* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched.

@@ -150,7 +150,7 @@ struct StagedRun {
 
 // The fourteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
 // per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion, the saliency
-// maps, the saliency similarity, the viewer congruency; and the saliency scoring, a fifteenth) after their
+// maps, the saliency similarity, the viewer congruency; and the saliency scoring and the viewer clusters, a fifteenth and a sixteenth) after their
 // refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
 // null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
 // entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
@@ -748,6 +748,30 @@ int vet_dispersion_host(vet_plan* pl, const double* h_mu, const double* h_mv, co
     return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
         return launch_rows(run, vet_dispersion_ids, vet_dispersion, pl, U, T, window, stride, per_user, h_edges, B, (double*)d[0],
                            (double*)d[1], (int64_t*)d[2], (int64_t*)d[3], run.status, run.s);
+    });
+}
+
+// Viewer clusters with host buffers (include/vet.h): where wanted labels [R][U], sizes [R][U], counts [5][R], top [R][Q], stats [3][R],
+// centroids [R][U][3] and links [R][U][ceil(U / 64)]; R = vet_window_rows over the T frames.  Every output may be NULL.  Rows without
+// a viewer are data: only VET_ERR_RANGE is decoded from the status words.
+int vet_viewer_clusters_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window,
+                             int stride, double cos_threshold, double min_share, const double* h_fractions, int Q, int32_t* h_labels,
+                             int32_t* h_sizes, int64_t* h_counts, int32_t* h_top, double* h_stats, double* h_centroids,
+                             uint64_t* h_links) {
+    enum { SLOT_CENTROIDS = 10, SLOT_LINKS = 11 };
+    int rc = check_cluster_args(pl, U, T, window, stride, cos_threshold, min_share, h_fractions, Q);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t rows = (size_t)vet_window_rows(T, window, stride), words = ((size_t)U + 63) / 64;
+    if (!Q) h_top = nullptr;
+    const RowOut outs[7] = {{h_labels, rows * U * 4, SLOT_OUT0}, {h_sizes, rows * U * 4, SLOT_OUT1}, {h_counts, 5 * rows * 8, SLOT_COUNT},
+                            {h_top, rows * Q * 4, SLOT_STILL}, {h_stats, 3 * rows * 8, SLOT_ENTROPY},
+                            {h_centroids, rows * U * 24, SLOT_CENTROIDS}, {h_links, rows * U * words * 8, SLOT_LINKS}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_viewer_clusters_ids, vet_viewer_clusters, pl, U, T, window, stride, cos_threshold, min_share,
+                           h_fractions, Q, (int32_t*)d[0], (int32_t*)d[1], (int64_t*)d[2], (int32_t*)d[3], (double*)d[4], (double*)d[5],
+                           (uint64_t*)d[6], run.status, run.s);
     });
 }
 

@@ -67,6 +67,15 @@
 //                                              k_dispersion_chunk   16 blocks of 1024 positions of a row: block-ordered partial sums,
 //                                                               the row's integers by integer atomics
 //                                              k_dispersion_finish  one wave per row: the blocks in order, the frames' histograms added
+//   vet_cluster.hip     (in the unit)          k_cluster_ids    the direction ids of the samples, frame-major
+//                                              k_cluster_links  workgroup = (row, 256 viewers, a tile of partners): the partners' unit
+//                                                               vectors of a chunk of frames staged in LDS, every lane counts for 8
+//                                                               partners the frames both are in and those in which they are near
+//                                                               (fused dot against a cosine; no acos), one ballot per partner = a
+//                                                               64-bit word of the row's LINKED matrix
+//                                              k_cluster_components  one workgroup per row: label propagation over the link bits with
+//                                                               pointer jumping in LDS, the roots ranked, sizes, the sorted
+//                                                               (size, label) records, the partition entropy, the centroids
 //   vet_saliency.hip    (in the unit)          k_saliency_ids   the pooled layout's direction ids, frame-major (per viewer: k_user_dirs)
 //                                              (shared by the kernels below, written once: sal_walk — the density of a list at a
 //                                                               direction; sal_rule — the block-ordered summation rule of a workgroup, and

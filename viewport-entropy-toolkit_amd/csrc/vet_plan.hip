@@ -638,6 +638,7 @@ int vet_plan_create(vet_ctx* c, const vet_plan_desc* d, vet_plan** out) {
         if (!rc) rc = motion_set_attrs(c);
         if (!rc) rc = dispersion_set_attrs(c);
         if (!rc) rc = saliency_set_attrs(c);
+        if (!rc) rc = cluster_set_attrs(c);
         if (rc) return cleanup(rc);
         c->attrs_set = true;
     }

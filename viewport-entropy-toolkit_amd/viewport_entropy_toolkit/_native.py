@@ -8,6 +8,7 @@ point raises ``NativeUnavailable`` with the reason.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from pathlib import Path
@@ -90,6 +91,7 @@ SIGNATURES = {
     "vet_test_motion_lds_values": (_I, [_P, _I]),
     "vet_test_dispersion_tile": (_I, [_P, _I]),
     "vet_test_saliency_tile": (_I, [_P, _I]),
+    "vet_test_cluster_tile": (_I, [_P, _I, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -138,6 +140,10 @@ SIGNATURES = {
     "vet_dispersion": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vet_dispersion_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vet_dispersion_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "vet_viewer_clusters": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_viewer_clusters_ids": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_viewer_clusters_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_viewer_clusters_sweeps": (_I, [_P, _P]),
     "vet_saliency": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P]),
@@ -442,6 +448,12 @@ class Engine:
         default, 1024); results do not depend on it (include/vet.h: vet_test_dispersion_tile)."""
         _check(self.lib, self.lib.vet_test_dispersion_tile(self.handle, int(n)))
 
+    def test_cluster_tile(self, rows: int = 0, tile: int = 0):
+        """Test switch: the viewer-clusters call takes at most ``rows`` rows per pass (0: the default budget) and its link kernel at
+        most ``tile`` partners per workgroup (0: the default, 128); results do not depend on them (include/vet.h:
+        vet_test_cluster_tile)."""
+        _check(self.lib, self.lib.vet_test_cluster_tile(self.handle, int(rows), int(tile)))
+
     def test_saliency_tile(self, n: int = 0):
         """Test switch: the map kernel of the saliency call stages at most ``n`` list entries of a row in LDS at a time (0: the
         default, 1024); results do not depend on it (include/vet.h: vet_test_saliency_tile)."""
@@ -547,6 +559,12 @@ _DISPERSION_CALLS = {
            (("stats", "3UR", _F64, False), ("centroid", "UR3", _F64, False), ("hist", "URH", _NP_I64, True),
             ("counts", "4UR", _NP_I64, False))),
 }
+
+# The viewer-clusters call, in a table of its own: one descriptor of the same form (dims Q: fractions, W: the 64-bit words of a row
+# of link bits).  Rows count frames; its extra arguments are cos_threshold, min_share and the host fractions with their number.
+_CLUSTERS_CALL = ("vet_viewer_clusters", False, True, False,
+                  (("labels", "RU", _I32, True), ("sizes", "RU", _I32, True), ("counts", "5R", _NP_I64, False), ("top", "RQ", _I32, True),
+                   ("stats", "3R", _F64, False), ("centroids", "RU3", _F64, True), ("links", "RUW", np.uint64, True)))
 
 # The saliency call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dims Y, X: the
 # map's rows and columns).  Rows count frames; its extra arguments are per_user, sigma in radians, the map's size and the scale.
@@ -1076,6 +1094,63 @@ class Plan:
                               check, extra=(int(bool(per_user)), _ptr(e), B), extra_dims={"H": B})
 
     @staticmethod
+    def _cluster_args(threshold_deg, min_share, fractions):
+        """(cos_threshold, min_share, fractions float64 [Q] or None) as the C entry takes them; ``ValueError`` unless threshold_deg
+        is a finite number of degrees in [0, 180], 0 < min_share <= 1 and there are at most 16 fractions, each in (0, 1]."""
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if not number(threshold_deg) or not 0.0 <= float(threshold_deg) <= 180.0:
+            raise ValueError(f"threshold_deg must be a finite number of degrees in [0, 180] (got {threshold_deg!r})")
+        if not number(min_share) or not 0.0 < float(min_share) <= 1.0:
+            raise ValueError(f"min_share must be a number in (0, 1] (got {min_share!r})")
+        f = None
+        if fractions is not None and len(fractions):
+            try:
+                f = np.ascontiguousarray(fractions, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"fractions must be a sequence of numbers (got {fractions!r})")
+            if f.ndim != 1 or f.size > 16:
+                raise ValueError(f"need at most 16 fractions in a one-dimensional sequence (got shape {f.shape})")
+            if not ((f > 0.0) & (f <= 1.0)).all():
+                raise ValueError(f"fractions must lie in (0, 1] (got {f.tolist()})")
+        cos_threshold = min(1.0, max(-1.0, math.cos(math.radians(float(threshold_deg)))))
+        return cos_threshold, float(min_share), f
+
+    def viewer_clusters(self, mu=None, mv=None, ids=None, window=1, stride=1, threshold_deg=30.0, min_share=1.0,
+                        fractions=(0.5, 0.8, 0.95), want_labels=True, want_centroids=False, want_links=False, cos_threshold=None,
+                        check=True):
+        """Who looks together (include/vet.h: vet_viewer_clusters): in a frame two present viewers are NEAR when the angle between
+        their directions is at most ``threshold_deg`` (decided on the cosine, ``math.cos(math.radians(threshold_deg))``, or
+        ``cos_threshold`` itself where that is given; the same Vector is always near); in row r — frames
+        [r * stride, r * stride + window), ``window=None`` the whole video — a pair is LINKED when it is NEAR in at least
+        ``min_share`` of the frames both are in, and the row's clusters are the connected components of the LINKED graph, numbered
+        by their smallest member.  ``threshold_deg = 30`` is a choice for head-direction data, not taken from the reference, which
+        has no such call.  Returns dict(labels[R,U]|None (-1: not in the row), sizes[R,U]|None (both ``want_labels``),
+        counts[5,R] int64 (viewers, clusters, largest, singletons, links), top[R,Q]|None (the fewest clusters, largest first, that
+        hold ``fractions[i]`` of the row's viewers), stats[3,R] (partition entropy in bits, the same over log2 viewers, largest /
+        viewers), centroids[R,U,3]|None (``want_centroids``: per cluster the sum of its members' unit vectors), links[R,U,ceil(U /
+        64)] uint64|None (``want_links``: bit v of row u), cos_threshold, code), R = (T - window) // stride + 1.  A row without a
+        viewer has labels -1, zero counts and NaN stats — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        c, share, f = self._cluster_args(threshold_deg, min_share, fractions)
+        if cos_threshold is not None:
+            c = float(cos_threshold)
+        Q = 0 if f is None else int(f.size)
+        first = ids if ids is not None else mu
+        U = int(np.shape(first)[1]) if np.ndim(first) == 2 else 0
+        want = {key for key, on in (("labels", want_labels), ("sizes", want_labels), ("top", Q > 0), ("centroids", want_centroids),
+                                    ("links", want_links)) if on}
+        res = self._row_host(_CLUSTERS_CALL, mu, mv, ids, window, stride, want, check, extra=(c, share, _ptr(f), Q),
+                             extra_dims={"Q": Q, "5": 5, "W": (U + 63) // 64})
+        return dict(res, cos_threshold=c)
+
+    def viewer_clusters_sweeps(self):
+        """(most, total): the label-propagation sweeps of the rows of the last viewer-clusters call on this plan's engine
+        (include/vet.h: vet_viewer_clusters_sweeps)."""
+        out = np.zeros(2, dtype=np.int64)
+        _check(self.lib, self.lib.vet_viewer_clusters_sweeps(self.handle, _ptr(out)))
+        return int(out[0]), int(out[1])
+
+    @staticmethod
     def _saliency_args(sigma_deg, width, height, scale):
         """(sigma in radians, W, H, the C scale 0 / 1 / 2) as the C entry takes them; ``ValueError`` unless sigma_deg is a finite
         number in (0, 180], 2 <= width <= 4096 and 1 <= height <= 2048 are integers and scale is "none", "mean" or "density"."""
@@ -1374,6 +1449,19 @@ class Plan:
         self._row_device(_DISPERSION_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
                          (window, stride, int(bool(per_user)), e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1),
                          d_stats or None, (d_centroid, d_hist, d_counts, d_status), stream)
+
+    def viewer_clusters_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, cos_threshold: float,
+                               min_share: float, fractions, d_labels: int = 0, d_sizes: int = 0, d_counts: int = 0, d_top: int = 0,
+                               d_stats: int = 0, d_centroids: int = 0, d_links: int = 0, d_status: int = 0, stream=None,
+                               d_ids: int = 0):
+        """``fractions``: the host sequence [Q] (or None); d_labels, d_sizes i32 [R][U]; d_counts i64 [5][R]; d_top i32 [R][Q];
+        d_stats f64 [3][R]; d_centroids f64 [R][U][3]; d_links u64 [R][U][ceil(U / 64)]; every output may be 0 (include/vet.h:
+        vet_viewer_clusters; ``d_ids``: vet_viewer_clusters_ids).  The C entry checks cos_threshold, min_share and the fractions."""
+        f = None if fractions is None or not len(fractions) else np.ascontiguousarray(fractions, dtype=np.float64)
+        self._row_device(_CLUSTERS_CALL, d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, float(cos_threshold), float(min_share), f.ctypes.data if f is not None else 0,
+                          0 if f is None else f.size), d_labels or None,
+                         (d_sizes, d_counts, d_top, d_stats, d_centroids, d_links, d_status), stream)
 
     def saliency_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, per_user: bool,
                         sigma_deg: float = 5.0, width: int = 180, height: int = 90, scale: str = "density", d_map: int = 0,

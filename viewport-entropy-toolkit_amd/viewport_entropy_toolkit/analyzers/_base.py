@@ -677,6 +677,81 @@ class _EntropyAnalyzerBase:
             raise ValidationError("Normalized coordinates must be between 0 and 1")
         return self._dispersion_frame(times, names, window, stride, bool(per_user), res, bins_deg)
 
+    CLUSTER_KEEP_LIMIT = 4 << 30     # bytes of per-viewer arrays that compute_viewer_clusters(keep_*=True) hands back at most
+
+    @staticmethod
+    def _clusters_frame(times, names, window: int, stride: int, res: dict, threshold_deg: float, min_share: float,
+                        fractions) -> pd.DataFrame:
+        """The viewer clusters as a DataFrame, one row per window; ``streams``, ``labels``, ``sizes``, ``centroids`` and
+        ``links_bits`` of a row are views into the result arrays (no copy)."""
+        times = np.asarray(times)
+        counts = np.asarray(res["counts"]).reshape(5, -1)
+        stats = np.asarray(res["stats"], dtype=np.float64).reshape(3, -1)
+        R, U = counts.shape[1], len(names)
+        first = np.arange(R, dtype=np.int64) * stride
+
+        def views(a, shape):
+            a = np.asarray(a).reshape((R,) + shape)
+            col = np.empty(R, dtype=object)
+            for r in range(R):
+                col[r] = a[r]
+            return col
+        cols = dict(time=times[first], time_end=times[first + window - 1], viewers=counts[0], clusters=counts[1], largest=counts[2],
+                    largest_share=stats[2], singletons=counts[3], links=counts[4], entropy=stats[0], entropy_norm=stats[1])
+        top = res.get("top")
+        cols["streams"] = views(top if top is not None else np.empty((R, 0), dtype=np.int32), (len(fractions),))
+        if res.get("labels") is not None:
+            cols["labels"] = views(res["labels"], (U,))
+            cols["sizes"] = views(res["sizes"], (U,))
+        if res.get("centroids") is not None:
+            cols["centroids"] = views(res["centroids"], (U, 3))
+        if res.get("links") is not None:
+            cols["links_bits"] = views(res["links"], (U, (U + 63) // 64))
+        df = pd.DataFrame(cols)
+        df.attrs.update(threshold_deg=float(threshold_deg), cos_threshold=float(res["cos_threshold"]), min_share=float(min_share),
+                        fractions=tuple(fractions), window=window, stride=stride, users=list(names))
+        return df
+
+    def compute_viewer_clusters(self, window: Optional[int] = 1, stride: int = 1, threshold_deg: float = 30.0, min_share: float = 1.0,
+                                fractions=(0.5, 0.8, 0.95), keep_labels: bool = True, keep_centroids: bool = False,
+                                keep_links: bool = False) -> pd.DataFrame:
+        """Who looks together: in a frame two present viewers are near when the great-circle angle between their viewing directions
+        is at most ``threshold_deg``; in the window of frames [r * stride, r * stride + window) two viewers are linked when they
+        are near in at least ``min_share`` of the frames both are in (1.0: whenever both are there, the segment rule of the
+        clustering literature), and the window's clusters are the connected components of the linked viewers: the groups that
+        could share one viewport stream.  A viewer without a link is a cluster of one.  ``window`` and ``stride`` count frames;
+        ``window=None`` is the whole video.  Independent of the tiling.  ``threshold_deg = 30.0`` is a choice for head-direction
+        data, not taken from the reference, which has no such call.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame, one row per window: ``time`` / ``time_end`` (the
+        first / last frame of the row), ``viewers`` (present in at least one frame), ``clusters``, ``largest``,
+        ``largest_share``, ``singletons``, ``links`` (linked pairs), ``entropy`` (of the partition, bits), ``entropy_norm``
+        (over log2 viewers), ``streams`` (a [Q] view: the fewest clusters, largest first, that hold ``fractions[i]`` of the
+        viewers) and, with ``keep_labels``, ``labels`` (a [U] view in the analyzer's user order: clusters are numbered by their
+        first member, -1 = not in the window) and ``sizes`` (a [U] view: the members of cluster k); with ``keep_centroids``,
+        ``centroids`` (a [U, 3] view: the sum of the members' unit vectors per cluster; divide by its norm for the direction);
+        with ``keep_links``, ``links_bits`` (a [U, ceil(U / 64)] uint64 view: bit v of row u).  ``attrs`` hold ``threshold_deg``,
+        ``cos_threshold`` (what decided the links), ``min_share``, ``fractions``, ``window``, ``stride`` and ``users``.  A window
+        without a viewer has labels -1, zero counts and NaN statistics — returned, never raised.  Raises ``ValidationError``
+        before data is loaded and for samples outside [0, 1], ``ValueError`` for illegal arguments and for kept arrays beyond
+        4 GiB; more than 8192 viewers are refused by the engine (``NativeError``, VET_ERR_UNSUPPORTED)."""
+        times, names, call = self._row_call("viewer_clusters")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        if fractions is None or isinstance(fractions, (str, bytes)) or not hasattr(fractions, "__len__"):
+            raise ValueError(f"fractions must be a sequence of numbers in (0, 1] (got {fractions!r})")
+        fractions = tuple(fractions)
+        _native.Plan._cluster_args(threshold_deg, min_share, fractions)
+        U, R = len(names), (len(times) - window) // stride + 1
+        kept = R * U * ((8 if keep_labels else 0) + (24 if keep_centroids else 0) + (((U + 63) // 64) * 8 if keep_links else 0))
+        if kept > self.CLUSTER_KEEP_LIMIT:
+            raise ValueError(f"{R} rows of {U} viewers keep {kept / 2 ** 30:.1f} GiB of labels, centroids and link bits, beyond 4 GiB: "
+                             "use a larger stride, or keep_labels=False, keep_centroids=False, keep_links=False")
+        res = call(window=window, stride=stride, threshold_deg=float(threshold_deg), min_share=float(min_share), fractions=fractions,
+                   want_labels=bool(keep_labels), want_centroids=bool(keep_centroids), want_links=bool(keep_links), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._clusters_frame(times, names, window, stride, res, float(threshold_deg), float(min_share), fractions)
+
     SALIENCY_MAP_LIMIT = 4 << 30     # bytes of maps that compute_saliency(keep_maps=True) hands back at most
 
     @staticmethod
