@@ -74,7 +74,9 @@ extern "C" {
                           vet_saliency_score* entry points (AUC, NSS, information gain, CC, SIM, JSD and KL of a predicted map)
                           were added under the same number, and so were the vet_viewer_clusters* entry points (the connected
                           components of the viewers linked by the angle between their directions, per window) and
-                          vet_test_cluster_tile */
+                          vet_test_cluster_tile, and the vet_fixations* entry points (fixation and tile-dwell events: per
+                          viewer the maximal runs of frames with a steady viewport, per window and per viewer) and
+                          vet_test_fixation_chunk */
 #define VET_STREAM_LEGACY ((void *)1) /* == hipStreamLegacy: the null stream with legacy ordering */
 /* Policy 0 of vet_plan_set_table_policy: a weighted call gathers from the direction weight table iff it holds at least this
  * many samples per direction of the plan's direction table.  Measured (profiles/r06/first_call.txt, grid_sensitivity.txt):
@@ -169,6 +171,11 @@ int vet_test_saliency_tile(vet_ctx *ctx, int n);
  * so that a small input runs several passes and several partner tiles; 0 restores a default.  Read at every launch, nowhere from
  * the environment.  Results are bit-identical whatever the values. */
 int vet_test_cluster_tile(vet_ctx *ctx, int rows, int tile);
+/* Test switch, not a tuning knob: n > 0 lowers the frames of one chunk of the walk of vet_fixations* over a viewer's frames from 1024
+ * to n (a multiple of 4, the frames of one thread; at most 1024), so that the seams between chunks, and between the waves of a
+ * chunk, show on videos of a few dozen frames; 0 restores the default.  Read at every launch, nowhere from the environment.
+ * Results are bit-identical whatever the value. */
+int vet_test_fixation_chunk(vet_ctx *ctx, int n);
 int vet_profile_reset(vet_ctx *ctx);
 /* kernel ids: 0 k_grid_dirs, 1 k_nearest_lut, 2 k_spatial (any variant), 3 k_transition,
  *             4 k_finalize, 5 k_wtab (direction weight table build),
@@ -1214,6 +1221,85 @@ int vet_viewer_clusters_host(vet_plan *plan, const double *h_mu, const double *h
 /* Diagnostic: h_sweeps [2] = the most label-propagation sweeps a row of the plan's context's last vet_viewer_clusters* call took,
  * and their sum over its rows (zeros before any call).  Synchronises the device. */
 int vet_viewer_clusters_sweeps(vet_plan *plan, int64_t *h_sweeps);
+
+/* ---- fixation and tile-dwell events: per-viewer runs of a steady viewport ---------------------------------
+ * Not in the reference.  The calls above describe where attention sits and how fast heads turn; this one segments each viewer's
+ * trajectory in time: when a viewer holds still and for how long (fixations, the velocity-threshold rule I-VT), or how long a viewer
+ * stays on one tile (tile dwell).
+ * Parameters: mode, cos_threshold, min_frames >= 1, window, stride, per_user.
+ * PRESENCE, samples and direction ids exactly as in vet_head_motion.
+ * HOLD.  The pair (f, f + 1) of viewer u HOLDS when u is present in both frames and
+ *   mode 0 (fixations)  the two directions are NEAR as in vet_viewer_clusters: the same direction id, the same Vector under another
+ *                       id, or c = fma(A.z, B.z, fma(A.y, B.y, A.x * B.x)) >= cos_threshold for their rows A, B of the plan's unit
+ *                       table.  No acos: cos_threshold = cos of the largest step between two frames, taken once by the caller.
+ *   mode 1 (tile dwell) the two samples have the same nearest tile t of lattice 0 (the plan's nearest-tile table, as the per-viewer
+ *                       counts read it), t < n_0.  cos_threshold is ignored.
+ * RUN.  A run of viewer u is a maximal interval of frames [s, e] in which u is present throughout and every pair inside holds.
+ * Every present frame lies in exactly one run; L = e - s + 1.  With n_frames = 1 there is no pair and a present frame is a run of 1.
+ * EVENT.  A run with L >= min_frames is an event: a fixation, or a dwell.  Runs are never cut at row boundaries: an event belongs
+ * to the row that contains its START frame, with its full length.
+ * Layouts:
+ *   per_user = 0  pooled: row r takes frames [r*stride, r*stride + window) of all viewers.  R = vet_window_rows(n_frames, window,
+ *                 stride), Rows = R; window = n_frames is the whole video.
+ *   per_user = 1  row (u, r) holds viewer u's own frames.  Outputs are user-major, Rows = n_users * R, row index u * R + r.
+ * Outputs, every one nullable:
+ *   d_counts    [5][Rows] i64, statistic-major: 0 samples: the present (viewer, frame) positions of the row; 1 fix_frames: those
+ *               positions that lie in an event, wherever the event started; 2 events: the events that start in the row; 3 sum_len:
+ *               the sum of their L; 4 max_len: the largest L, 0 when there is none
+ *   d_hist      [Rows][B] i32: bin b counts the row's events with e_b <= L < e_(b+1).  h_edges [B + 1] is a HOST i32 array in
+ *               every entry, consumed before the call returns: 0 <= B <= 64, edges >= 1 and strictly ascending.  B = 0 skips it
+ *   d_labels    [n_users][n_frames] i32: L of the event the sample lies in; 0 where the sample is present but its run is shorter
+ *               than min_frames; -1 where it is absent.  Independent of window, stride and the layout
+ *   d_offsets   [n_users + 1] i64: the exclusive prefix of the viewers' event counts over the whole video; offsets[n_users] is
+ *               the number of events
+ *   d_events    [max_events][4] i32: (viewer, start, L, the direction id of the sample at frame start + (L - 1) / 2), ordered by
+ *               viewer, then start.  Only the first max_events events are written; d_offsets[n_users] always says how many there are
+ *   d_centroids [max_events][3] f64, needs d_events: per listed event the sum of the unit vectors of its frames in ascending frame
+ *               order, one accumulator per component from +0.0, plain adds
+ *   d_status    [2]   {bad, #rows without a sample}; the call ADDS, the caller zeroes
+ * A row without a sample has zero counts and a zero histogram: data, not an error.  No NaN exists in this call.
+ * Everything is an integer except the centroids, and a centroid's bits depend on the plan and the event's own frames only.  No
+ * output depends on stride, the number of rows, the layout, the entry point, which optional outputs were asked for, the order of
+ * the viewer columns, or vet_test_fixation_chunk: under a permutation of the viewer columns the pooled rows are equal and the
+ * per-viewer rows, labels and events permute.  Integer atomics only; no FP atomics.
+ * Stage 1, k_user_dirs: the direction ids transposed to [U][T], for both layouts.  k_fix_runs: one 256-thread workgroup per viewer,
+ * persistent over the viewers, walks the viewer's frames in chunks of 1024, four consecutive frames per thread; the start of a
+ * frame's run is an inclusive max-scan of "f where a run starts at f" — inside the thread, across the lanes by shuffles, across the
+ * four waves through LDS words, the carry into the next chunk in a register, so a run may span any number of chunks; the thread
+ * that holds a run's END writes L at the run's start (4 B per sample of workspace).  k_fix_offsets: the exclusive prefix of the
+ * viewers' event counts.  k_fix_labels: the same walk, scan and carry give every sample its label, and a sum-scan of the qualifying
+ * starts an event's rank inside its viewer, hence its slot in the list.  k_fix_centroids: one thread per listed event.  Rows:
+ * per viewer a wave (windows of up to 512 frames) or a workgroup per row sums the row's labels and lengths, the histogram in LDS;
+ * pooled, k_fix_frames (workgroup = 256 frames x 64 viewers, lane = frame) adds each frame's totals by integer atomics, the histogram
+ * by one integer atomic per (event, row that holds its start), and the same row kernel sums a row's frames.  Workspace: 12 B per
+ * sample (8 B with d_labels), 24 B per frame of the pooled layout.
+ * Not built: dispersion-threshold (I-DT) fixations; a velocity estimate over a lag of more than one frame; saccade amplitudes
+ * between consecutive events; merging events across short absences; dwell on lattices other than the first; quantiles of the
+ * durations (the histogram is exact; quantiles would need a sort per row); a decoupled look-back scan for audiences of fewer viewers
+ * than the device has CUs (one workgroup walks one viewer); several short rows per wave; a per-workgroup LDS histogram in front of
+ * the pooled layout's histogram atomics (the whole video as one pooled row is the slow shape: README.md).
+ * VET_ERR_INVALID (before anything is allocated or launched): window < 1, window > n_frames, stride < 1, min_frames < 1, mode not 0
+ * or 1, cos_threshold NaN, B outside [0, 64], an edge below 1 or edges not strictly ascending, max_events < 0, d_centroids without
+ * d_events.  VET_ERR_UNSUPPORTED: window * n_users above 2^31 - 1; more than 65535 * 64 frames; mode 1 on a plan whose lattice 0
+ * the per-viewer count path does not take (4 n_0 bytes beyond the LDS).
+ * Profile ids: k_user_dirs to k_spatial, the walks, the prefix and the centroids to k_transition, the frame totals and the rows to
+ * k_finalize.  Asynchronous on `stream`. */
+int vet_fixations(vet_plan *plan, const double *d_mu, const double *d_mv, int n_users, int n_frames, int window, int stride, int mode,
+                  double cos_threshold, int min_frames, int per_user, const int32_t *h_edges, int B, int64_t max_events,
+                  int64_t *d_counts, int32_t *d_hist, int32_t *d_labels, int64_t *d_offsets, int32_t *d_events, double *d_centroids,
+                  int32_t *d_status, void *stream);
+/* Same, samples given as direction ids into the plan's direction table (-1 absent). */
+int vet_fixations_ids(vet_plan *plan, const int32_t *d_ids, int n_users, int n_frames, int window, int stride, int mode,
+                      double cos_threshold, int min_frames, int per_user, const int32_t *h_edges, int B, int64_t max_events,
+                      int64_t *d_counts, int32_t *d_hist, int32_t *d_labels, int64_t *d_offsets, int32_t *d_events,
+                      double *d_centroids, int32_t *d_status, void *stream);
+/* Host buffers: H2D, run, D2H, synchronous; VET_ERR_RANGE when a sample is outside [0, 1] (outputs are still written); never
+ * VET_ERR_EMPTY.  h_mu / h_mv may be NULL when h_ids is given and vice versa.  The event outputs take a second call: a first call
+ * with max_events = 0 and h_offsets gives their number. */
+int vet_fixations_host(vet_plan *plan, const double *h_mu, const double *h_mv, const int32_t *h_ids, int n_users, int n_frames,
+                       int window, int stride, int mode, double cos_threshold, int min_frames, int per_user, const int32_t *h_edges,
+                       int B, int64_t max_events, int64_t *h_counts, int32_t *h_hist, int32_t *h_labels, int64_t *h_offsets,
+                       int32_t *h_events, double *h_centroids);
 
 /* ---- saliency maps: the spherical kernel density of attention per window and per viewer ------------------
  * Not in the reference, and independent of the lattices: only the plan's direction table is read.  The continuous counterpart of

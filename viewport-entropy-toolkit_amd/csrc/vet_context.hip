@@ -40,7 +40,7 @@ void Tuning::from_environment() {
     // (vet_test_crowd_divergence_chunk_rows), bootstrap_chunk_rows (vet_test_bootstrap_chunk_rows) and group_chunk_rows
     // (vet_test_group_chunk_rows) and coverage_chunk_rows (vet_test_coverage_chunk_rows) and markov_chunk_rows
     // (vet_test_markov_chunk_rows) and motion_lds_values (vet_test_motion_lds_values) and dispersion_tile (vet_test_dispersion_tile)
-    // and saliency_tile (vet_test_saliency_tile) and cluster_rows / cluster_tile (vet_test_cluster_tile) are the switches that are not read here: the set of environment variables the library reads is pinned, so vet_test_no_row_cap /
+    // and saliency_tile (vet_test_saliency_tile) and cluster_rows / cluster_tile (vet_test_cluster_tile) and fixation_chunk (vet_test_fixation_chunk) are the switches that are not read here: the set of environment variables the library reads is pinned, so vet_test_no_row_cap /
     // vet_test_rec8 / vet_test_user_transition_hash / vet_test_divergence_chunk_rows / vet_test_window_divergence_chunk_rows set them
     // on a context.  Test switches, not tuning knobs: the uncapped row layout, cap = stride, next to the capped one, the 8-byte
     // direction record next to the 4-byte one, the hash kernel of the per-viewer transition rows next to the wave kernel, and several
@@ -306,6 +306,12 @@ int vet_test_cluster_tile(vet_ctx* c, int rows, int tile) {
         return fail(VET_ERR_INVALID, "rows per pass and partners per workgroup must be positive, or 0 for the default (got %d, %d)", rows, tile);
     c->tune.cluster_rows = rows;                   // read by every vet_viewer_clusters* launch of this context's plans
     c->tune.cluster_tile = tile;
+    return VET_OK;
+}
+int vet_test_fixation_chunk(vet_ctx* c, int n) {
+    if (!c) return fail(VET_ERR_INVALID, "ctx is NULL");
+    if (n < 0 || n % 4) return fail(VET_ERR_INVALID, "frames per chunk must be a positive multiple of 4, or 0 for the default (got %d)", n);
+    c->tune.fixation_chunk = n;                    // read by every vet_fixations* launch of this context's plans
     return VET_OK;
 }
 int vet_test_saliency_tile(vet_ctx* c, int n) {

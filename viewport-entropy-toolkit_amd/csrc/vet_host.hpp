@@ -24,6 +24,9 @@
 //   vet_cluster.hip     the viewer clusters (per row the LINKED pairs of viewers as bit words from a pair walk over the direction
 //                       table, then the connected components by label propagation in LDS, their sizes, entropy and centroids) and
 //                       their launch logic
+//   vet_fixation.hip    the fixation and tile-dwell events (per viewer the maximal runs of frames whose consecutive directions stay within
+//                       a cone, or on one tile: a segmented max-scan over the viewer's frames in order with a carry between chunks; the
+//                       events per row, their histogram, labels, list and centroids) and their launch logic
 //   vet_saliency.hip    the saliency maps (the spherical kernel density of a row's viewing directions on an equirectangular map: the
 //                       row's distinct directions and multiplicities, the map from the list staged in LDS, the row statistics), the
 //                       saliency similarity of two audiences (their maps by the same kernels, compared row by row), the viewer
@@ -171,6 +174,9 @@ struct Tuning {
                                 // (0 = sized by the workspace budget) ...
     int cluster_tile = 0;           // ... and the most partners of one workgroup of k_cluster_links (0 = 128); read at every launch;
                                 // the results do not depend on them (test_viewer_clusters_gpu.py)
+    int fixation_chunk = 0;         // vet_test_fixation_chunk (no environment variable): the frames of one chunk of the walk of
+                                // vet_fixations* (a multiple of 4, at most 1024; 0 = 1024); read at every launch; the results do not
+                                // depend on it (test_fixations_gpu.py)
     void from_environment();
 };
 
@@ -189,7 +195,7 @@ struct vet_ctx {
     bool attrs_set = false;        // dynamic-LDS limits of the run kernels raised (first plan)
     // grow-only device staging buffers (no hipMalloc per call): 0-6 host-buffer entry points (the SLOT_* names of
     // vet_hostapi.hip), 7 the still counts of vet_head_motion_host (batch descriptors live in the blob ring below), 8 transition scratch, 9 resolve list,
-    // 10-11 the centroids and link words of vet_viewer_clusters_host, 12 the sweep counts of vet_viewer_clusters*
+    // 10-11 the centroids and link words of vet_viewer_clusters_host (the events and centroids of vet_fixations_host), 12 the sweep counts of vet_viewer_clusters*
     void* pool[14] = {};
     size_t pool_cap[14] = {};
     // descriptor blobs of the batch entry points: a ring of (pinned host, device) buffer pairs, each guarded by an event
@@ -533,6 +539,11 @@ int check_dispersion_args(const vet_plan* pl, int U, int T, int window, int stri
 // staged, allocated or launched.  fractions [Q] is host memory.
 int check_cluster_args(const vet_plan* pl, int U, int T, int window, int stride, double cos_threshold, double min_share,
                        const double* fractions, int Q);
+
+// vet_fixation.hip: what vet_fixations* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
+// staged, allocated or launched.  edges [B + 1] is host memory; events and centroids are the outputs of those names (or NULL).
+int check_fixation_args(const vet_plan* pl, int U, int T, int window, int stride, int mode, double cos_threshold, int min_frames,
+                        const int32_t* edges, int B, int64_t max_events, const void* events, const void* centroids);
 
 // vet_saliency.hip: what vet_saliency* refuse about their arguments (VET_ERR_INVALID / VET_ERR_UNSUPPORTED), before anything is
 // staged, allocated or launched.

@@ -150,7 +150,7 @@ struct StagedRun {
 
 // The fourteen row-call host entries (windowed / per-viewer spatial entropy, viewer / crowd / window divergence, coverage, windowed /
 // per-viewer transition entropy, the Markov transition statistics, the head-motion statistics, the audience dispersion, the saliency
-// maps, the saliency similarity, the viewer congruency; and the saliency scoring and the viewer clusters, a fifteenth and a sixteenth) after their
+// maps, the saliency similarity, the viewer congruency; and the saliency scoring, the viewer clusters and the fixation events, a fifteenth to a seventeenth) after their
 // refusals: one staged run.  outs = the primary output, the optional one (kNoOut where the call has none) and the count per row; a
 // null h = not wanted: no slot is taken, the launch gets nullptr and nothing is downloaded — except the count, whose slot the device
 // entries always write.  (vet_coverage_host has two primary outputs: four entries, each on a slot of its own.)  launch(run, d) enqueues
@@ -772,6 +772,33 @@ int vet_viewer_clusters_host(vet_plan* pl, const double* h_mu, const double* h_m
         return launch_rows(run, vet_viewer_clusters_ids, vet_viewer_clusters, pl, U, T, window, stride, cos_threshold, min_share,
                            h_fractions, Q, (int32_t*)d[0], (int32_t*)d[1], (int64_t*)d[2], (int32_t*)d[3], (double*)d[4], (double*)d[5],
                            (uint64_t*)d[6], run.status, run.s);
+    });
+}
+
+// Fixation and tile-dwell events with host buffers (include/vet.h): where wanted counts [5][Rows], hist [Rows][B], labels [U][T],
+// offsets [U + 1], events [max_events][4] and centroids [max_events][3]; Rows = vet_window_rows over the T frames, times n_users for
+// the per-viewer layout.  Every output may be NULL.  Rows without a sample are data: only VET_ERR_RANGE is decoded from the status
+// words.  The event outputs take a second call: the first, with max_events = 0 and h_offsets, gives their number, offsets[U].
+int vet_fixations_host(vet_plan* pl, const double* h_mu, const double* h_mv, const int32_t* h_ids, int U, int T, int window, int stride,
+                       int mode, double cos_threshold, int min_frames, int per_user, const int32_t* h_edges, int B, int64_t max_events,
+                       int64_t* h_counts, int32_t* h_hist, int32_t* h_labels, int64_t* h_offsets, int32_t* h_events,
+                       double* h_centroids) {
+    enum { SLOT_EVENTS = 10, SLOT_CENTROIDS = 11 };
+    int rc = check_fixation_args(pl, U, T, window, stride, mode, cos_threshold, min_frames, h_edges, B, max_events, h_events,
+                                 h_centroids);
+    if (rc) return rc;
+    if (!h_ids && (!h_mu || !h_mv)) return fail(VET_ERR_INVALID, "need h_mu and h_mv, or h_ids");       // no output is required
+    if (!h_ids && !pl->grid) return fail(VET_ERR_INVALID, "plan has no pixel grid; pass h_ids");
+    const size_t rows = (size_t)vet_window_rows(T, window, stride) * (per_user ? (size_t)U : 1), E = (size_t)max_events;
+    if (!B) h_hist = nullptr;
+    if (!E) h_events = nullptr, h_centroids = nullptr;
+    const RowOut outs[6] = {{h_counts, 5 * rows * 8, SLOT_COUNT}, {h_hist, rows * B * 4, SLOT_OUT1}, {h_labels, (size_t)U * T * 4, SLOT_OUT0},
+                            {h_offsets, ((size_t)U + 1) * 8, SLOT_ENTROPY}, {h_events, E * 16, SLOT_EVENTS},
+                            {h_centroids, E * 24, SLOT_CENTROIDS}};
+    return staged_rows(pl, h_mu, h_mv, h_ids, U, T, outs, kRowsAreData, [&](const StagedRun& run, void* const* d) {
+        return launch_rows(run, vet_fixations_ids, vet_fixations, pl, U, T, window, stride, mode, cos_threshold, min_frames, per_user,
+                           h_edges, B, max_events, (int64_t*)d[0], (int32_t*)d[1], (int32_t*)d[2], (int64_t*)d[3], (int32_t*)d[4],
+                           (double*)d[5], run.status, run.s);
     });
 }
 

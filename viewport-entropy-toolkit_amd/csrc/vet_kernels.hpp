@@ -76,6 +76,14 @@
 //                                              k_cluster_components  one workgroup per row: label propagation over the link bits with
 //                                                               pointer jumping in LDS, the roots ranked, sizes, the sorted
 //                                                               (size, label) records, the partition entropy, the centroids
+//   vet_fixation.hip    (in the unit)          k_fix_runs       one workgroup per viewer walks the frames in order in chunks of 1024: run
+//                                                               starts by a max-scan (lanes, waves, a carry between chunks), the
+//                                                               length of every run written at its start
+//                                              k_fix_offsets    the exclusive prefix of the viewers' event counts
+//                                              k_fix_labels     the same walk: every sample's label, the event list by a sum-scan
+//                                              k_fix_frames     pooled layout: a frame's totals over 64 viewers, integer atomics
+//                                              k_fix_rows       a wave or a workgroup per row sums the row's frames
+//                                              k_fix_centroids  one thread per listed event: its unit vectors in frame order
 //   vet_saliency.hip    (in the unit)          k_saliency_ids   the pooled layout's direction ids, frame-major (per viewer: k_user_dirs)
 //                                              (shared by the kernels below, written once: sal_walk — the density of a list at a
 //                                                               direction; sal_rule — the block-ordered summation rule of a workgroup, and

@@ -92,6 +92,7 @@ SIGNATURES = {
     "vet_test_dispersion_tile": (_I, [_P, _I]),
     "vet_test_saliency_tile": (_I, [_P, _I]),
     "vet_test_cluster_tile": (_I, [_P, _I, _I]),
+    "vet_test_fixation_chunk": (_I, [_P, _I]),
     "vet_profile_reset": (_I, [_P]),
     "vet_profile_get": (_I, [_P, _I, C.POINTER(_D), C.POINTER(_I64)]),
     "vet_kernel_name": (C.c_char_p, [_I]),
@@ -144,6 +145,9 @@ SIGNATURES = {
     "vet_viewer_clusters_ids": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vet_viewer_clusters_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "vet_viewer_clusters_sweeps": (_I, [_P, _P]),
+    "vet_fixations": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_fixations_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vet_fixations_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _P, _I, _I64, _P, _P, _P, _P, _P, _P]),
     "vet_saliency": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_ids": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vet_saliency_host": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P]),
@@ -454,6 +458,11 @@ class Engine:
         vet_test_cluster_tile)."""
         _check(self.lib, self.lib.vet_test_cluster_tile(self.handle, int(rows), int(tile)))
 
+    def test_fixation_chunk(self, n: int = 0):
+        """Test switch: the walk of the fixations call over a viewer's frames takes chunks of ``n`` frames (a multiple of 4; 0: the
+        default, 1024); results do not depend on it (include/vet.h: vet_test_fixation_chunk)."""
+        _check(self.lib, self.lib.vet_test_fixation_chunk(self.handle, int(n)))
+
     def test_saliency_tile(self, n: int = 0):
         """Test switch: the map kernel of the saliency call stages at most ``n`` list entries of a row in LDS at a time (0: the
         default, 1024); results do not depend on it (include/vet.h: vet_test_saliency_tile)."""
@@ -565,6 +574,20 @@ _DISPERSION_CALLS = {
 _CLUSTERS_CALL = ("vet_viewer_clusters", False, True, False,
                   (("labels", "RU", _I32, True), ("sizes", "RU", _I32, True), ("counts", "5R", _NP_I64, False), ("top", "RQ", _I32, True),
                    ("stats", "3R", _F64, False), ("centroids", "RU3", _F64, True), ("links", "RUW", np.uint64, True)))
+
+# The fixations call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dims H: histogram
+# bins, T: frames, V: viewers + 1, E: the listed events).  Rows count frames; its extra arguments are the mode, cos_threshold,
+# min_frames, per_user, the host edges with their number of bins and max_events.
+_FIXATION_CALLS = {
+    False: ("vet_fixations", False, True, False,
+            (("counts", "5R", _NP_I64, False), ("hist", "RH", _I32, True), ("labels", "UT", _I32, True), ("offsets", "V", _NP_I64, True),
+             ("events", "E4", _I32, True), ("centroids", "E3", _F64, True))),
+    True: ("vet_fixations", False, True, False,
+           (("counts", "5UR", _NP_I64, False), ("hist", "URH", _I32, True), ("labels", "UT", _I32, True), ("offsets", "V", _NP_I64, True),
+            ("events", "E4", _I32, True), ("centroids", "E3", _F64, True))),
+}
+FIXATION_MODES = {"angle": 0, "tile": 1}
+FIXATION_COUNTS = ("samples", "fix_frames", "events", "sum_len", "max_len")
 
 # The saliency call, in a table of its own: a descriptor of the same form for each layout (per_user False / True; dims Y, X: the
 # map's rows and columns).  Rows count frames; its extra arguments are per_user, sigma in radians, the map's size and the scale.
@@ -1143,6 +1166,83 @@ class Plan:
                              extra_dims={"Q": Q, "5": 5, "W": (U + 63) // 64})
         return dict(res, cos_threshold=c)
 
+    @staticmethod
+    def _fixation_args(max_step_deg, min_frames, edges):
+        """(cos_threshold, min_frames, edges int32 [B + 1] or None) as the C entry takes them; ``ValueError`` unless max_step_deg is
+        a finite number of degrees in [0, 180], min_frames an integer >= 1, and the edges (where given) 2 to 65 integers >= 1,
+        strictly ascending."""
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not number(max_step_deg) or not 0.0 <= float(max_step_deg) <= 180.0:
+            raise ValueError(f"max_step_deg must be a finite number of degrees in [0, 180] (got {max_step_deg!r})")
+        if not integer(min_frames) or int(min_frames) < 1:
+            raise ValueError(f"min_frames must be an integer number of frames, at least 1 (got {min_frames!r})")
+        e = None
+        if edges is not None:
+            if isinstance(edges, (str, bytes)) or not hasattr(edges, "__len__"):
+                raise ValueError(f"edges must be a sequence of integers (got {edges!r})")
+            vals = list(edges)
+            if not all(integer(v) for v in vals):
+                raise ValueError(f"edges must be integer numbers of frames (got {vals!r})")
+            if not 2 <= len(vals) <= 65:
+                raise ValueError(f"need 2 to 65 edges, 1 to 64 bins (got {len(vals)})")
+            if any(not 1 <= int(v) <= 2 ** 31 - 1 for v in vals) or any(int(b) <= int(a) for a, b in zip(vals, vals[1:])):
+                raise ValueError(f"edges must be at least 1 frame and strictly ascending (got {vals!r})")
+            e = np.ascontiguousarray(vals, dtype=np.int32)
+        cos_threshold = min(1.0, max(-1.0, math.cos(math.radians(float(max_step_deg)))))
+        return cos_threshold, int(min_frames), e
+
+    @staticmethod
+    def _fixation_mode(by):
+        if by not in FIXATION_MODES:
+            raise ValueError(f"by must be one of {sorted(FIXATION_MODES)} (got {by!r})")
+        return FIXATION_MODES[by]
+
+    def fixations(self, mu=None, mv=None, ids=None, window=None, stride=1, by="angle", max_step_deg=2.0, min_frames=5, per_user=False,
+                  edges=None, keep_labels=False, keep_events=False, keep_centroids=False, check=True):
+        """When a viewer holds still, or stays on one tile, and for how long (include/vet.h: vet_fixations).  The pair (f, f + 1) of
+        a viewer HOLDS when the viewer is present in both frames and, ``by="angle"``, the angle between the two directions is at
+        most ``max_step_deg`` (decided on the cosine, ``math.cos(math.radians(max_step_deg))``; the same Vector always holds) or,
+        ``by="tile"``, both samples have the same nearest tile of lattice 0.  A run is a maximal stretch of present frames whose
+        pairs all hold; a run of at least ``min_frames`` frames is an event (a fixation, or a dwell) and belongs to the row that
+        holds its first frame, with its full length L.  Row r takes frames [r * stride, r * stride + window) of all viewers, or
+        with ``per_user`` row (u, r) viewer u's own (outputs user-major, a leading U axis); ``window=None`` is the whole video.
+        ``max_step_deg = 2`` and ``min_frames = 5`` are choices for head-direction data on the default grid, not taken from the
+        reference, which has no such call.  Returns dict(counts[5,R] int64 (samples, fix_frames: the samples that lie in an event,
+        events, sum_len, max_len), hist[R,B]|None (``edges``: B + 1 ascending integers >= 1, bins half-open, of L), labels[U,T]|None
+        (``keep_labels``: L of the sample's event, 0 outside an event, -1 absent), offsets[U+1] int64|None, events[N,4]|None
+        (``keep_events``: viewer, start, L, the direction id of the middle sample; by viewer, then start), centroids[N,3]|None
+        (``keep_centroids``, with ``keep_events``: the sum of the event's unit vectors), cos_threshold, code), R = (T - window) //
+        stride + 1.  With ``keep_events`` the engine is called twice: the first call gives N = offsets[U].  A row without a sample
+        has zero counts — data, never an error; ``code`` is VET_OK or VET_ERR_RANGE."""
+        mode = self._fixation_mode(by)
+        c, m, e = self._fixation_args(max_step_deg, min_frames, edges)
+        if keep_centroids and not keep_events:
+            raise ValueError("keep_centroids needs keep_events (the centroids are those of the listed events)")
+        B = 0 if e is None else int(e.size) - 1
+        first = ids if ids is not None else mu
+        T = int(np.shape(first)[0]) if np.ndim(first) == 2 else 0
+        U = int(np.shape(first)[1]) if np.ndim(first) == 2 else 0
+        call = _FIXATION_CALLS[bool(per_user)]
+
+        def run(want, max_events):
+            return self._row_host(call, mu, mv, ids, window, stride, want, check,
+                                  extra=(mode, c, m, int(bool(per_user)), _ptr(e), B, int(max_events)),
+                                  extra_dims={"5": 5, "H": B, "T": T, "V": U + 1, "E": int(max_events)})
+        want = {key for key, on in (("hist", e is not None), ("labels", keep_labels), ("offsets", keep_events)) if on}
+        res = run(want, 0)
+        if keep_events:
+            n = int(res["offsets"][U])
+            if n:
+                second = run({"events"} | ({"centroids"} if keep_centroids else set()), n)
+                res.update(events=second["events"], centroids=second["centroids"], code=res["code"] or second["code"])
+            else:
+                res.update(events=np.empty((0, 4), dtype=np.int32), centroids=np.empty((0, 3)) if keep_centroids else None)
+        return dict(res, cos_threshold=c)
+
     def viewer_clusters_sweeps(self):
         """(most, total): the label-propagation sweeps of the rows of the last viewer-clusters call on this plan's engine
         (include/vet.h: vet_viewer_clusters_sweeps)."""
@@ -1462,6 +1562,20 @@ class Plan:
                          (window, stride, float(cos_threshold), float(min_share), f.ctypes.data if f is not None else 0,
                           0 if f is None else f.size), d_labels or None,
                          (d_sizes, d_counts, d_top, d_stats, d_centroids, d_links, d_status), stream)
+
+    def fixations_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, by: str,
+                         cos_threshold: float, min_frames: int, per_user: bool, edges=None, max_events: int = 0, d_counts: int = 0,
+                         d_hist: int = 0, d_labels: int = 0, d_offsets: int = 0, d_events: int = 0, d_centroids: int = 0,
+                         d_status: int = 0, stream=None, d_ids: int = 0):
+        """``edges``: the host sequence [B + 1] of integers (or None); d_counts i64 [5][Rows]; d_hist i32 [Rows][B]; d_labels i32
+        [U][T]; d_offsets i64 [U + 1]; d_events i32 [max_events][4]; d_centroids f64 [max_events][3]; Rows = R, or U * R user-major
+        with ``per_user``; every output may be 0 (include/vet.h: vet_fixations; ``d_ids``: vet_fixations_ids).  The C entry checks
+        cos_threshold, min_frames, the edges and max_events."""
+        e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+        self._row_device(_FIXATION_CALLS[bool(per_user)], d_mu, d_mv, d_ids, n_users, n_frames,
+                         (window, stride, self._fixation_mode(by), float(cos_threshold), int(min_frames), int(bool(per_user)),
+                          e.ctypes.data if e is not None else 0, 0 if e is None else e.size - 1, int(max_events)), d_counts or None,
+                         (d_hist, d_labels, d_offsets, d_events, d_centroids, d_status), stream)
 
     def saliency_device(self, d_mu: int, d_mv: int, n_users: int, n_frames: int, window: int, stride: int, per_user: bool,
                         sigma_deg: float = 5.0, width: int = 180, height: int = 90, scale: str = "density", d_map: int = 0,

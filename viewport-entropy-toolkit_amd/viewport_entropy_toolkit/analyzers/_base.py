@@ -752,6 +752,141 @@ class _EntropyAnalyzerBase:
             raise ValidationError("Normalized coordinates must be between 0 and 1")
         return self._clusters_frame(times, names, window, stride, res, float(threshold_deg), float(min_share), fractions)
 
+    FIXATION_MAX_STEP_DEG = 2.0      # the defaults of compute_fixations: choices for head-direction data on the default grid
+    FIXATION_MIN_FRAMES = 5
+
+    @staticmethod
+    def _fixation_step_args(max_step_deg, velocity_deg_s, min_frames, min_seconds, frame_seconds: float):
+        """(max_step_deg, min_frames) as the engine takes them.  ``velocity_deg_s`` replaces ``max_step_deg`` (step = velocity *
+        frame_seconds) and ``min_seconds`` replaces ``min_frames`` (max(1, ceil(min_seconds / frame_seconds))); ``ValueError`` when
+        both of a pair are given (the frame-based one moved off its default), for a value that is not a finite number >= 0 (seconds:
+        > 0) and for a seconds-based value on data without a frame period."""
+        def number(v, what, positive):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or \
+                    (positive and v <= 0):
+                raise ValueError(f"{what} must be a finite number {'above' if positive else 'of at least'} 0 (got {v!r})")
+            return float(v)
+
+        def period(what):
+            if not np.isfinite(frame_seconds) or frame_seconds <= 0:
+                raise ValueError(f"{what} needs frame times that advance (the median frame period is {frame_seconds!r})")
+        base = _EntropyAnalyzerBase
+        if velocity_deg_s is not None:
+            if max_step_deg is not None and max_step_deg != base.FIXATION_MAX_STEP_DEG:
+                raise ValueError("give max_step_deg or velocity_deg_s, not both")
+            period("velocity_deg_s")
+            max_step_deg = number(velocity_deg_s, "velocity_deg_s", False) * float(frame_seconds)
+        if min_seconds is not None:
+            if min_frames is not None and min_frames != base.FIXATION_MIN_FRAMES:
+                raise ValueError("give min_frames or min_seconds, not both")
+            period("min_seconds")
+            min_frames = max(1, int(np.ceil(number(min_seconds, "min_seconds", True) / float(frame_seconds))))
+        return max_step_deg, min_frames
+
+    @staticmethod
+    def _fixation_bins(bins_frames):
+        """bins_frames as a tuple of ints or None; ``ValueError`` unless they are 2 to 65 integers >= 1, strictly ascending."""
+        if bins_frames is None:
+            return None
+        e = _native.Plan._fixation_args(0.0, 1, bins_frames)[2]
+        return tuple(int(v) for v in e)
+
+    @staticmethod
+    def _fixation_frame(times, names, window: int, stride: int, per_user: bool, res: dict, by: str, max_step_deg: float,
+                        min_frames: int, bins_frames) -> pd.DataFrame:
+        """The fixation (or dwell) statistics as a DataFrame, one row per window (``per_user``: per (user, window), user-major,
+        ``user`` first); where ``res`` holds them, ``hist`` of a row is the [B] view ``res["hist"][row]``, ``attrs["labels"]`` the
+        [T, U] transposed view of the labels and ``attrs["events"]`` the event list as a DataFrame (no copy of the arrays)."""
+        times = np.asarray(times, dtype=np.float64)
+        counts = np.asarray(res["counts"]).reshape(5, -1)
+        samples, fix, events, sum_len, max_len = counts
+        rows = counts.shape[1]
+        R = rows // len(names) if per_user else rows
+        first = np.arange(R, dtype=np.int64) * stride
+        if per_user:
+            first = np.tile(first, len(names))
+        steps = np.diff(times)
+        frame_seconds = float(np.median(steps)) if len(steps) else float("nan")
+        cols = {}
+        if per_user:
+            cols["user"] = np.repeat(np.asarray(list(names), dtype=object), R)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            share = np.where(samples > 0, fix / np.maximum(samples, 1), np.nan)
+            mean = np.where(events > 0, sum_len / np.maximum(events, 1), np.nan)
+        cols.update(time=times[first], time_end=times[first + window - 1], samples=samples, fix_frames=fix, fix_share=share,
+                    events=events, mean_frames=mean, max_frames=max_len, mean_seconds=mean * frame_seconds)
+        if res.get("hist") is not None:
+            hist = np.asarray(res["hist"]).reshape(rows, -1)
+            h_col = np.empty(rows, dtype=object)
+            for r in range(rows):
+                h_col[r] = hist[r]
+            cols["hist"] = h_col
+        df = pd.DataFrame(cols)
+        df.attrs.update(by=by, max_step_deg=float(max_step_deg), cos_threshold=float(res["cos_threshold"]), min_frames=int(min_frames),
+                        frame_seconds=frame_seconds, users=list(names), window=window, stride=stride,
+                        bins_frames=None if bins_frames is None else tuple(bins_frames))
+        if res.get("labels") is not None:
+            df.attrs["labels"] = np.asarray(res["labels"]).T
+        if res.get("events") is not None:
+            ev = np.asarray(res["events"]).reshape(-1, 4)
+            start, frames = ev[:, 1].astype(np.int64), ev[:, 2].astype(np.int64)
+            ecols = dict(user=np.asarray(list(names), dtype=object)[ev[:, 0]] if len(ev) else np.empty(0, dtype=object), frame=ev[:, 1],
+                         time=times[start], time_end=times[start + frames - 1] if len(ev) else times[:0], frames=ev[:, 2],
+                         seconds=frames * frame_seconds)
+            if res.get("centroids") is not None:
+                c = np.asarray(res["centroids"], dtype=np.float64).reshape(-1, 3)
+                length = np.sqrt((c * c).sum(axis=1))
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    ok = length > 0
+                    ecols["lon"] = np.where(ok, np.degrees(np.arctan2(c[:, 1], c[:, 0])), np.nan)
+                    ecols["lat"] = np.where(ok, np.degrees(np.arcsin(np.clip(c[:, 2] / np.where(ok, length, 1.0), -1.0, 1.0))), np.nan)
+            ecols["dir"] = ev[:, 3]
+            df.attrs["events"] = pd.DataFrame(ecols)
+        return df
+
+    def compute_fixations(self, window: Optional[int] = None, stride: int = 1, by: str = "angle", max_step_deg: float = 2.0,
+                          velocity_deg_s: Optional[float] = None, min_frames: int = 5, min_seconds: Optional[float] = None,
+                          per_user: bool = False, bins_frames=None, keep_labels: bool = False, keep_events: bool = False) -> pd.DataFrame:
+        """When a viewer holds still, and for how long — or, with ``by="tile"``, how long a viewer stays on one tile.  Two
+        consecutive frames of a viewer HOLD when the viewer has a sample in both and the great-circle angle between the two viewing
+        directions is at most ``max_step_deg`` (``by="angle"``: the velocity-threshold rule, I-VT; the same Vector always holds), or
+        both samples have the same nearest tile of the first tile count (``by="tile"``: tile dwell).  A run is a maximal stretch of
+        frames whose pairs all hold; a run of at least ``min_frames`` frames is an event — a fixation, or a dwell — and belongs to
+        the window that holds its first frame, with its full length (runs are never cut at window boundaries).
+        ``velocity_deg_s`` (degrees per second) and ``min_seconds`` are exclusive alternatives to ``max_step_deg`` and
+        ``min_frames``, converted with ``frame_seconds``, the median of ``diff(times)``: step = velocity * frame_seconds,
+        ``min_frames = max(1, ceil(min_seconds / frame_seconds))``; leave the frame-based one at its default then.
+        ``max_step_deg = 2`` and ``min_frames = 5`` are choices for head-direction data on the default grid, not taken from the
+        reference, which has no such call.  ``window`` and ``stride`` count frames; ``window=None`` is the whole video.
+
+        Uses the data ``process_directory`` cached.  Returns a new DataFrame (``compute_entropy``'s results are left alone), one row
+        per window — user-major with ``user`` first when ``per_user``: ``time`` / ``time_end`` (the first / last frame of the row),
+        ``samples``, ``fix_frames`` (the samples that lie in an event, wherever it started), ``fix_share``, ``events`` (that start
+        in the row), ``mean_frames``, ``max_frames``, ``mean_seconds`` and, with ``bins_frames`` (ascending integer edges >= 1 in
+        frames, half-open bins of the events' lengths), ``hist`` (a [B] view of counts).  Ratios are NaN where the denominator is 0.
+        ``attrs`` hold ``by``, ``max_step_deg``, ``cos_threshold`` (what decided the holds), ``min_frames``, ``frame_seconds``,
+        ``users``, ``window``, ``stride``; with ``keep_labels``, ``labels`` ([T, U], aligned with the cached samples: the length of
+        the sample's event, 0 outside an event, -1 absent — ``labels > 0`` masks the fixation samples for ``compute_saliency`` and
+        its scores); with ``keep_events``, ``events``: a DataFrame of ``user``, ``frame``, ``time``, ``time_end``, ``frames``,
+        ``seconds``, ``lon``, ``lat`` (degrees, of the mean direction; NaN for a zero sum) and ``dir`` (the direction id of the
+        middle sample).  A window without a sample has zero counts — returned, never raised.  Raises ``ValidationError`` before data
+        is loaded and for samples outside [0, 1], ``ValueError`` for illegal arguments."""
+        times, names, call = self._row_call("fixations")
+        window, stride = self._window_args(len(times) if window is None else window, stride, len(times))
+        _native.Plan._fixation_mode(by)
+        steps = np.diff(np.asarray(times, dtype=np.float64))
+        frame_seconds = float(np.median(steps)) if len(steps) else float("nan")
+        max_step_deg, min_frames = self._fixation_step_args(max_step_deg, velocity_deg_s, min_frames, min_seconds, frame_seconds)
+        bins_frames = self._fixation_bins(bins_frames)
+        _native.Plan._fixation_args(max_step_deg, min_frames, bins_frames)
+        res = call(window=window, stride=stride, by=by, max_step_deg=float(max_step_deg), min_frames=int(min_frames),
+                   per_user=bool(per_user), edges=bins_frames, keep_labels=bool(keep_labels), keep_events=bool(keep_events),
+                   keep_centroids=bool(keep_events), check=False)
+        if res["code"] == _native.VET_ERR_RANGE:
+            raise ValidationError("Normalized coordinates must be between 0 and 1")
+        return self._fixation_frame(times, names, window, stride, bool(per_user), res, by, float(max_step_deg), int(min_frames),
+                                    bins_frames)
+
     SALIENCY_MAP_LIMIT = 4 << 30     # bytes of maps that compute_saliency(keep_maps=True) hands back at most
 
     @staticmethod
